@@ -3,7 +3,12 @@
 on a synthetic 512^3 grid (BASELINE config 3), data resident in HBM, on N GPUs of one node.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--size 512] [--method neargrid]
-                    [--refine changed:2] [--cpu-size 320] [--no-cpu]
+                    [--refine changed:2] [--dump-outputs DIR] [--full [--cpu-size 320] [--no-cpu] ...]
+
+A plain run sets up, runs W warm-up steps and K timed steps, and prints the headline.  --full adds everything else that
+is measured or checked: the map check, the per-kernel and roofline figures, the sustained leg, config 5, the odd grid,
+the batch, user and drop-in legs, and the CPU baselines with their comparisons against the GPU map.
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float64), for comparing two builds.
 
 A "step" is one full pass of the hot path over the grid: volumes_init (label reset) -> bader_calc
 -> refine, exactly the call sequence of Bader.__call__ (interface.py:406-409).  N > 1: one rank per
@@ -301,6 +306,28 @@ def dropin_leg(ctx, size=256, k=6, reps=3):
             'trapping_boxes': {'count': int(stats[0]), 'voxel_fraction': stats[1] / float(size) ** 3}}
 
 
+DUMP_SAMPLE = 1 << 21          # --dump-outputs: voxels of the label map written (all of them on a grid of at most this many)
+DUMP_SEED = 20261016
+
+
+def dump_outputs(dirname, ctx, n_basins, log):
+    """--dump-outputs: what the last timed step hands its caller, as float64 .npy files (about 32 MB at most): the maxima
+    (voxel coordinates in basin order), the refinement log ((edges, changed) per iteration), the voxel count of every basin
+    over the whole label map, and the labels of a fixed, seeded sample of voxels with their C-order indices."""
+    os.makedirs(dirname, exist_ok=True)
+    labels = ctx.download_labels(np.int32).reshape(-1)
+    if labels.size <= DUMP_SAMPLE:
+        idx = np.arange(labels.size, dtype=np.int64)
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, labels.size, DUMP_SAMPLE))
+    if labels.size and (labels.min() < 0 or labels.max() >= n_basins):
+        raise SystemExit(f'--dump-outputs: labels outside [0, {n_basins}): {labels.min()} .. {labels.max()}')
+    arrays = {'maxima': ctx.maxima(), 'refine_log': np.array(log, np.int64).reshape(-1, 2),
+              'basin_voxels': np.bincount(labels, minlength=n_basins), 'labels_sample_index': idx, 'labels_sample': labels[idx]}
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + '.npy'), a.astype(np.float64))
+
+
 def spawn_ranks(n):
     """`python bench.py --gpus N` outside a launcher: start N rank processes of this script (fresh interpreters
     that have not touched the GPU; this parent never does), wait, relay rank 0's output.  Returns the exit code."""
@@ -343,6 +370,10 @@ def main():
     ap.add_argument('--size', type=int, default=512)
     ap.add_argument('--method', default='neargrid', choices=['neargrid', 'ongrid'])
     ap.add_argument('--refine', default='changed:2')
+    ap.add_argument('--full', action='store_true',
+                    help='also run every leg, check and figure beyond the headline (the --no-* switches below act on these)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed as DIR/<name>.npy (float64; one GPU)')
     ap.add_argument('--cpu-size', type=int, default=320)
     ap.add_argument('--no-cpu', action='store_true')
     ap.add_argument('--no-config5', action='store_true', help='skip the ongrid configuration timed after the headline one')
@@ -359,6 +390,10 @@ def main():
     ap.add_argument('--table-margin', type=int, default=None,
                     help='planes of gradient-field table each side of a slab (N > 1; default max(32, nx / 16))')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if args.dump_outputs and (args.gpus > 1 or int(os.environ.get('WORLD_SIZE', '1')) > 1):
+        ap.error('--dump-outputs needs a one-GPU run (the label map of a slab run is spread over its ranks)')
     mode, iters = args.refine.split(':')
     iters = int(iters)
 
@@ -455,77 +490,12 @@ def main():
     fence()
     dt = comm.max_float(time.perf_counter() - t0)       # max over ranks
     host_waits = (ctx.host_waits() - waits0 - 2) / args.steps   # waits of this rank for its card inside library calls (less the fence's two)
-
-    # The same step back to back for a few seconds (outside the timed region): the timed K steps above are tens of milliseconds, which
-    # a once-a-second activity sampler never sees; this gives it something to see and shows what the step costs when sustained.
-    sustained = None
-    if not args.no_sustained:
-        n_sus = max(args.steps, min(4000, int(args.sustain_s / max(dt / args.steps, 1e-5))))
-        n_sus = int(comm.max_float(float(n_sus)))       # the same count on every rank
-        fence()
-        ts = time.perf_counter()
-        for _ in range(n_sus):
-            step()
-        fence()
-        dts = comm.max_float(time.perf_counter() - ts)
-        sustained = {'steps': n_sus, 'seconds': dts, 'ms_per_step': dts / n_sus * 1e3}
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, ctx, n_basins, log)
 
     nvox = float(np.prod(shape))
-    # N > 1: where a slab step spends its time, from two EXTRA steps with a device sync around every scheduler phase
-    # (the timed steps above run without those syncs)
-    phase_ms = None
-    if world > 1:
-        runner.timing = {}
-        for _ in range(2):
-            step()
-        fence()
-        phase_ms = {k: v / 2 * 1e3 for k, v in runner.timing.items()}
-        runner.timing = None
-    # outside the timed region: every voxel carries exactly one basin of the merged numbering, over all ranks together (a wrong
-    # multi-rank map must be loud, not fast)
-    _, vols = ctx.charge_sum(1.0, n_basins)
-    vols = [int(v) for v in vols]
-    if world > 1:
-        vols = comm.sum(*vols)
-    if sum(vols) != int(nvox) or (vols and min(vols) <= 0):
-        raise SystemExit(f'map check failed: basin volumes {vols[:16]}... sum {sum(vols)} of {int(nvox)} voxels')
     ms_per_step = dt / args.steps * 1e3
-    # HIP-event timings on the library's own stream (xb_kernel_time): the dominant kernel from the timed region itself, the
-    # other stages from three extra steps with every timer on
-    stage_names = ['assign_after_masks(walk_list+k_brick_records+k_ng_trace)', 'k_og_masks', 'edge_find', 'k_refine_trace',
-                   'masks+trapping_regions', 'k_brick_masks', 'k_ng_trace', 'k_brick_records']   # (6: whichever trace kernel ran)
-    dom_time = ctx.kernel_time(dom_timer)
-    ctx.enable_timing(True)
-    ctx.kernel_time_reset()
-    for _ in range(0 if args.no_stage_steps else 3):
-        step()
-    fence()
-    tm = {name: ctx.kernel_time(i) for i, name in enumerate(stage_names)}
-    tm[stage_names[dom_timer]] = dom_time
-    ctx.enable_timing(only=[dom_timer])
-    avg = {k: (ms / n if n else 0.0) for k, (ms, n) in tm.items()}
-    own_frac = (runner.x_range[1] - runner.x_range[0]) / shape[0]
-    # SURVEY.md 8(d): roofline.achieved is the WHOLE PATH -- 25 algorithmic bytes per voxel (assign 12 + first refine sweep
-    # 13) over the step time; the single kernels (HIP events around each launch alone) sit under roofline.kernels with the
-    # stage's own algorithmic bytes (12 B per voxel this rank labels for an assignment kernel, 13 for the refinement's)
     step_s = dt / args.steps
-    achieved = BYTES_PATH * nvox / step_s / 1e9
-    kernels = {}
-    for name, bytes_per_voxel in (('k_brick_masks', BYTES_ASSIGN), ('k_ng_trace', BYTES_ASSIGN), ('k_brick_records', BYTES_ASSIGN),
-                                  ('k_og_masks', BYTES_ASSIGN), ('edge_find', 13), ('k_refine_trace', 13)):
-        if avg[name] > 0:
-            gbs = bytes_per_voxel * nvox * own_frac / (avg[name] * 1e-3) / 1e9
-            kernels[name] = {'ms_avg': avg[name], 'launches': int(tm[name][1]), 'algorithmic_bytes_per_voxel': bytes_per_voxel,
-                             'achieved': gbs, 'frac': gbs / HBM_PEAK_GBS}
-    dom = max(kernels, key=lambda k: kernels[k]['ms_avg']) if kernels else None
-    # HBM bytes of one step (FETCH_SIZE + WRITE_SIZE over every kernel of a one-step run) from the committed summary of the
-    # rocprofv3 --pmc passes of this very command, dropped when that summary was taken from other kernel sources
-    traffic, traffic_src = None, 'only recorded for the 512^3 one-GPU configuration'
-    if args.size == 512 and world == 1:
-        traffic, traffic_src = traffic_from_profile(None, args.method)
-        if dom and dom != 'edge_find':
-            kernels[dom]['traffic'], _ = traffic_from_profile({'k_ng_trace': 'k_ng_trace_g'}.get(dom, dom), args.method)
-
     out = {
         'metric': f'Mvoxels/s {args.method} assign+refine on {args.size}^3 grid',
         'value': nvox / (dt / args.steps) / 1e6,
@@ -548,19 +518,95 @@ def main():
                    'host_waits_per_step': host_waits, 'device_driven_slab_step': bool(runner.n_device_steps),
                    'basins': int(n_basins), 'refine_log': log,
                    'trapping_boxes': {'count': ctx.box_stats()[0], 'voxel_fraction': ctx.box_stats()[1] / nvox}},
-        'roofline': {'bound': 'hbm', 'achieved': achieved, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s', 'frac': achieved / HBM_PEAK_GBS,
-                     'traffic': traffic,
-                     'hbm_moved_gbs': (traffic / step_s / 1e9) if traffic else None,   # what the memory system actually moves per second (quoted traffic / measured step time)
-                     'traffic_note': 'NOT measured in this run: quoted from the committed PMC summary ' + str(traffic_src) +
-                                     ' -- HBM bytes of ONE steady-state step = (FETCH_SIZE + WRITE_SIZE) x 1024 summed over its kernels, '
-                                     'separate rocprofv3 --pmc passes of this command with the same kernel sources (hash checked; other '
-                                     'sources: null); 8 B/lane row loads, 32 B gathers and record stores, so the gfx950 x2 rule for '
-                                     '16 B/lane streams does not apply',
-                     'algorithmic_bytes_per_voxel': BYTES_PATH, 'ms_per_step': ms_per_step,
-                     'dominant_kernel': dom, 'kernels': kernels,
-                     'kernel_timing': f'HIP events on the library stream: {stage_names[dom_timer]} inside the timed region (the only timer on there); the other stages in 3 extra steps with every timer on',
-                     'stage_ms_avg': avg},
     }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out))
+        if store is not None:
+            comm.barrier()
+            ctx.close()
+            store.close()
+        return
+
+    # The same step back to back for a few seconds (outside the timed region): the timed K steps above are tens of milliseconds, which
+    # a once-a-second activity sampler never sees; this gives it something to see and shows what the step costs when sustained.
+    sustained = None
+    if not args.no_sustained:
+        n_sus = max(args.steps, min(4000, int(args.sustain_s / max(dt / args.steps, 1e-5))))
+        n_sus = int(comm.max_float(float(n_sus)))       # the same count on every rank
+        fence()
+        ts = time.perf_counter()
+        for _ in range(n_sus):
+            step()
+        fence()
+        dts = comm.max_float(time.perf_counter() - ts)
+        sustained = {'steps': n_sus, 'seconds': dts, 'ms_per_step': dts / n_sus * 1e3}
+
+    # N > 1: where a slab step spends its time, from two EXTRA steps with a device sync around every scheduler phase
+    # (the timed steps above run without those syncs)
+    phase_ms = None
+    if world > 1:
+        runner.timing = {}
+        for _ in range(2):
+            step()
+        fence()
+        phase_ms = {k: v / 2 * 1e3 for k, v in runner.timing.items()}
+        runner.timing = None
+    # outside the timed region: every voxel carries exactly one basin of the merged numbering, over all ranks together (a wrong
+    # multi-rank map must be loud, not fast)
+    _, vols = ctx.charge_sum(1.0, n_basins)
+    vols = [int(v) for v in vols]
+    if world > 1:
+        vols = comm.sum(*vols)
+    if sum(vols) != int(nvox) or (vols and min(vols) <= 0):
+        raise SystemExit(f'map check failed: basin volumes {vols[:16]}... sum {sum(vols)} of {int(nvox)} voxels')
+    # HIP-event timings on the library's own stream (xb_kernel_time): the dominant kernel from the timed region itself, the
+    # other stages from three extra steps with every timer on
+    stage_names = ['assign_after_masks(walk_list+k_brick_records+k_ng_trace)', 'k_og_masks', 'edge_find', 'k_refine_trace',
+                   'masks+trapping_regions', 'k_brick_masks', 'k_ng_trace', 'k_brick_records']   # (6: whichever trace kernel ran)
+    dom_time = ctx.kernel_time(dom_timer)
+    ctx.enable_timing(True)
+    ctx.kernel_time_reset()
+    for _ in range(0 if args.no_stage_steps else 3):
+        step()
+    fence()
+    tm = {name: ctx.kernel_time(i) for i, name in enumerate(stage_names)}
+    tm[stage_names[dom_timer]] = dom_time
+    ctx.enable_timing(only=[dom_timer])
+    avg = {k: (ms / n if n else 0.0) for k, (ms, n) in tm.items()}
+    own_frac = (runner.x_range[1] - runner.x_range[0]) / shape[0]
+    # SURVEY.md 8(d): roofline.achieved is the WHOLE PATH -- 25 algorithmic bytes per voxel (assign 12 + first refine sweep
+    # 13) over the step time; the single kernels (HIP events around each launch alone) sit under roofline.kernels with the
+    # stage's own algorithmic bytes (12 B per voxel this rank labels for an assignment kernel, 13 for the refinement's)
+    achieved = BYTES_PATH * nvox / step_s / 1e9
+    kernels = {}
+    for name, bytes_per_voxel in (('k_brick_masks', BYTES_ASSIGN), ('k_ng_trace', BYTES_ASSIGN), ('k_brick_records', BYTES_ASSIGN),
+                                  ('k_og_masks', BYTES_ASSIGN), ('edge_find', 13), ('k_refine_trace', 13)):
+        if avg[name] > 0:
+            gbs = bytes_per_voxel * nvox * own_frac / (avg[name] * 1e-3) / 1e9
+            kernels[name] = {'ms_avg': avg[name], 'launches': int(tm[name][1]), 'algorithmic_bytes_per_voxel': bytes_per_voxel,
+                             'achieved': gbs, 'frac': gbs / HBM_PEAK_GBS}
+    dom = max(kernels, key=lambda k: kernels[k]['ms_avg']) if kernels else None
+    # HBM bytes of one step (FETCH_SIZE + WRITE_SIZE over every kernel of a one-step run) from the committed summary of the
+    # rocprofv3 --pmc passes of this very command, dropped when that summary was taken from other kernel sources
+    traffic, traffic_src = None, 'only recorded for the 512^3 one-GPU configuration'
+    if args.size == 512 and world == 1:
+        traffic, traffic_src = traffic_from_profile(None, args.method)
+        if dom and dom != 'edge_find':
+            kernels[dom]['traffic'], _ = traffic_from_profile({'k_ng_trace': 'k_ng_trace_g'}.get(dom, dom), args.method)
+
+    out['roofline'] = {'bound': 'hbm', 'achieved': achieved, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s', 'frac': achieved / HBM_PEAK_GBS,
+                       'traffic': traffic,
+                       'hbm_moved_gbs': (traffic / step_s / 1e9) if traffic else None,   # what the memory system actually moves per second (quoted traffic / measured step time)
+                       'traffic_note': 'NOT measured in this run: quoted from the committed PMC summary ' + str(traffic_src) +
+                                       ' -- HBM bytes of ONE steady-state step = (FETCH_SIZE + WRITE_SIZE) x 1024 summed over its kernels, '
+                                       'separate rocprofv3 --pmc passes of this command with the same kernel sources (hash checked; other '
+                                       'sources: null); 8 B/lane row loads, 32 B gathers and record stores, so the gfx950 x2 rule for '
+                                       '16 B/lane streams does not apply',
+                       'algorithmic_bytes_per_voxel': BYTES_PATH, 'ms_per_step': ms_per_step,
+                       'dominant_kernel': dom, 'kernels': kernels,
+                       'kernel_timing': f'HIP events on the library stream: {stage_names[dom_timer]} inside the timed region (the only timer on there); the other stages in 3 extra steps with every timer on',
+                       'stage_ms_avg': avg}
 
     out['sustained'] = sustained
     cpu_tasks = []     # every CPU-oracle leg runs after the last GPU leg: the card's work stays in one stretch of the run

@@ -416,7 +416,7 @@ def test_bench_two_ranks_on_one_gpu(tmp_path):
     outs = []
     for n in (1, 2):
         p = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', str(n), '--size', '128', '--steps', '2',
-                            '--warmup', '1', '--no-cpu'], capture_output=True, timeout=600)
+                            '--warmup', '1', '--full', '--no-cpu'], capture_output=True, timeout=600)
         assert p.returncode == 0, p.stderr.decode()[-2000:]
         lines = [l for l in p.stdout.decode().splitlines() if l.strip()]
         assert len(lines) == 1 and lines[0].startswith('{'), lines[:3]   # ONE JSON line on stdout (librccl's greeting goes to stderr)

@@ -1,5 +1,5 @@
 #!/bin/bash
-# copies what tools/final_profiles.sh <tag> (+ tools/ec_probe.sh, + a full `python bench.py > gpurun_out/<tag>_final_bench_512.json`) left under
+# copies what tools/final_profiles.sh <tag> (+ tools/ec_probe.sh, + the line of `python bench.py --full` saved as <tag>_final_bench_512.json) left under
 # gpurun_out/ into profiles/<tag>_final_*  (run here, after the gpurun calls)
 set -e
 T=${1:-r5}
