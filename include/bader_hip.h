@@ -66,6 +66,33 @@ int xb_download_density(xb_ctx *c, double *rho_host);
  * exact fast path go through strtod on the host (n_host of them).  SURVEY.md 8(f) rank 4. */
 int xb_parse_density_text(xb_ctx *c, const char *text, int64_t nbytes, double divisor, int64_t *n_tokens,
                           int64_t *n_host);
+/* ---- density -> text (CHGCAR / cube writers) ------------------------------------------------------------------------
+ * io/vasp.py:167-250 (vasp.write) and io/cube.py:186-240 (cube.write) format the density with utils.python_format
+ * (' {:.11E}' per value, utils.py:85-94) or utils.fortran_format (utils.py:40-82), one value at a time in Python.  Here the
+ * values are formatted on the device, byte for byte as those functions do (csrc/fmt_core.h), and handed out as chunks of
+ * whole lines.  The caller's array gets a device buffer of its own: the resident density and labels are left alone.
+ *   xb_format_begin          values[x][y][z] float64 times `scale` (one IEEE multiply: `density *= lattice_vol`,
+ *                            `charge *= bohr_to_ang**3`), in the file order of `layout`; style XB_STYLE_*, `prec` digits
+ *                            after the point (11 CHGCAR, 5 cube); pow10[k - pow10_lo] = np.power(10.0, k) (the Fortran
+ *                            style divides by numpy's powers).  n_host: values the device leaves to the host (nan, inf,
+ *                            subnormals, magnitudes outside its exact range, uncertain floor(log10) in the Fortran style).
+ *   xb_format_host_values    those values (already scaled) and their file-order indices, ascending
+ *   xb_format_set_host_text  their text as the reference writes it: value i is text[offsets[i] .. offsets[i+1])
+ *   xb_format_next           the next chunk (a pointer into a pinned buffer of the context, valid until the following
+ *                            call); nbytes == 0 at the end.  The next chunk is formatted while the caller writes this one.
+ *   xb_format_times          device time of the formatting kernels and of the chunk copies so far (ms)
+ *   xb_format_end            frees the writer's buffers (also done by the next xb_format_begin and by xb_destroy) */
+enum { XB_STYLE_E = 0 /* python_format */, XB_STYLE_E_SPACE = 1 /* python_format(a, p, ' ') */,
+       XB_STYLE_F = 2 /* fortran_format */ };
+enum { XB_TEXT_CHGCAR = 0 /* Fortran order (x fastest), 5 per line, a partial last line */,
+       XB_TEXT_CUBE = 1 /* C order, every (x, y) record of nz values in lines of 6, a partial last line each */ };
+int xb_format_begin(xb_ctx *c, const double *values, const int64_t shape[3], int layout, double scale, int style, int prec,
+                    const double *pow10, int64_t pow10_lo, int64_t pow10_n, int64_t *n_host);
+int xb_format_host_values(xb_ctx *c, int64_t *idx, double *vals);
+int xb_format_set_host_text(xb_ctx *c, const int64_t *offsets, const char *text);
+int xb_format_next(xb_ctx *c, void **data, int64_t *nbytes);
+int xb_format_times(xb_ctx *c, double *format_ms, double *copy_ms);
+int xb_format_end(xb_ctx *c);
 /* labels: host <-> device with widening/narrowing on the device (utils.dtype_change, utils.py:255-259) */
 int xb_upload_labels(xb_ctx *c, const void *labels_host, int dtype);
 int xb_download_labels(xb_ctx *c, void *labels_host, int dtype);

@@ -28,6 +28,12 @@ SYMBOLS = {
     'xb_synth_density': (_int, [_vp, _pdbl, _pdbl, _i64, _dbl]),
     'xb_parse_density_text': (_int, [_vp, _vp, _i64, _dbl, _pi64, _pi64]),
     'xb_download_density': (_int, [_vp, _vp]),
+    'xb_format_begin': (_int, [_vp, _vp, _pi64, _int, _dbl, _int, _int, _vp, _i64, _i64, _pi64]),
+    'xb_format_host_values': (_int, [_vp, _vp, _vp]),
+    'xb_format_set_host_text': (_int, [_vp, _vp, _vp]),
+    'xb_format_next': (_int, [_vp, C.POINTER(_vp), _pi64]),
+    'xb_format_times': (_int, [_vp, _pdbl, _pdbl]),
+    'xb_format_end': (_int, [_vp]),
     'xb_upload_labels': (_int, [_vp, _vp, _int]),
     'xb_download_labels': (_int, [_vp, _vp, _int]),
     'xb_upload_known': (_int, [_vp, _vp]),
@@ -459,6 +465,46 @@ class Context:
         self.resident_density = None            # also when the parse fails midway: rho is partly rewritten
         check(self.lib.xb_parse_density_text(self.h, _ptr(buf), buf.size, float(divisor), C.byref(a), C.byref(b)))
         return a.value, b.value
+
+    def format_density_text(self, values, scale, style, prec, layout):
+        """The text of a density block as the reference's writers produce it (utils.python_format / fortran_format,
+        io/vasp.py write, io/cube.py write), formatted on the device: `values` [x][y][z] float64 times `scale`, style
+        'E' | 'E_space' | 'F', `prec` digits, layout 'chgcar' | 'cube'.  A generator of (chunk, n_host): `chunk` is a
+        memoryview of whole lines valid until the next step, n_host the number of values the host formatted.  The
+        resident density and labels are not touched."""
+        from . import textfmt
+        a = _f64(values)
+        if a.ndim != 3:
+            raise ValueError('format_density_text: a 3-d array is required')
+        shape = np.array(a.shape, dtype=np.int64)
+        p10 = textfmt.pow10_table()
+        nh = C.c_int64()
+        check(self.lib.xb_format_begin(self.h, _ptr(a), shape.ctypes.data_as(_pi64), textfmt.LAYOUTS[layout], float(scale),
+                                       textfmt.STYLES[style], int(prec), _ptr(p10), textfmt.POW10_LO, textfmt.POW10_N,
+                                       C.byref(nh)))
+        try:
+            n_host = nh.value
+            idx = np.zeros(n_host, np.int64)
+            vals = np.zeros(n_host, np.float64)
+            check(self.lib.xb_format_host_values(self.h, _ptr(idx), _ptr(vals)))
+            strings = textfmt.host_strings(vals, style, prec, p10) if n_host else []
+            text = ''.join(strings).encode('ascii')
+            off = np.zeros(n_host + 1, np.int64)
+            off[1:] = np.cumsum([len(t) for t in strings], dtype=np.int64)
+            buf = np.frombuffer(text + b'\0', dtype=np.uint8)
+            check(self.lib.xb_format_set_host_text(self.h, _ptr(off), _ptr(buf)))
+            self.format_host = (idx, vals)
+            ptr, nb = C.c_void_p(), C.c_int64()
+            while True:
+                check(self.lib.xb_format_next(self.h, C.byref(ptr), C.byref(nb)))
+                if nb.value == 0:
+                    break
+                yield memoryview((C.c_char * nb.value).from_address(ptr.value)).cast('B'), n_host
+            fm, cm = C.c_double(), C.c_double()
+            check(self.lib.xb_format_times(self.h, C.byref(fm), C.byref(cm)))
+            self.format_times = (fm.value, cm.value)
+        finally:
+            self.lib.xb_format_end(self.h)
 
     def escaped_paths(self, max_len=1 << 15):
         """(starts, offsets, voxels, complete): for every parked (known == -6) voxel of the owned slab its start

@@ -1,5 +1,5 @@
 // bader_hip.hip -- libbader_hip.so: HIP kernels + C ABI (include/bader_hip.h) for gfx950.  ONE translation unit:
-//   kernels    k_common.h k_masks.h k_fused.h k_trace.h k_ongrid.h k_edges.h k_sums.h k_text.h
+//   kernels    k_common.h k_masks.h k_fused.h k_trace.h k_ongrid.h k_edges.h k_sums.h k_text.h k_format.h (fmt_core.h)
 //   host side  this file (context struct, options, statistics, timing) + host_context.h (life cycle, transfers)
 //              + host_assign.h (the table outside an assignment, the assignments) + host_refine.h + host_sums.h + host_slab_table.h (host-driven slab calls) + comm.h (RCCL through the ABI)
 //              + slab_step.h (the slab step with its control flow on the device)
@@ -32,6 +32,7 @@ static inline hipError_t xb_counted_sync(hipStream_t s) { xb_waits++; return (hi
 #include "k_edges.h"
 #include "k_sums.h"
 #include "k_text.h"
+#include "k_format.h"
 
 // =============================================================================================
 // host side
@@ -63,6 +64,7 @@ namespace xbcomm { struct State; }
 struct xb_ctx {
     int device = 0;
     xbcomm::State *comm = nullptr;   // RCCL transport (comm.h), one process per GPU
+    struct FmtState *fmt = nullptr;  // density -> text writer between xb_format_begin and xb_format_end (host_format.h)
     hipStream_t stream = nullptr;
     Grid g{};
     bool has_grid = false;
@@ -285,6 +287,7 @@ extern "C" {
 const char *xb_last_error(void) { return g_err.c_str(); }
 
 #include "host_context.h"
+#include "host_format.h"
 #include "host_assign.h"
 #include "host_refine.h"
 #include "host_sums.h"

@@ -43,11 +43,13 @@ static void free_grid(xb_ctx *c) {
 }
 
 int xb_comm_destroy(xb_ctx *c);
+static void fmt_release(xb_ctx *c);
 void xb_destroy(xb_ctx *c) {
     if (!c) return;
     hipSetDevice(c->device);
     hipStreamSynchronize(c->stream);
     xb_comm_destroy(c);
+    fmt_release(c);
     for (auto &t : c->tk)
         for (auto &p : t.pending) { hipEventDestroy(p.first); hipEventDestroy(p.second); }
     free_grid(c);

@@ -8,21 +8,20 @@ Cartesian.  Only the 1.3e8-number text block (2.4 GB at 512^3) is handled differ
 bit-identical to numpy's string -> float64.  The charge density stays resident for the following
 `bader_calc` (the upload a `Bader` run would start with is skipped).
 
-The reference's writer (`pybader.io.vasp.write`) is untouched: `file_info['write_function']` is that very
-function when pybader is importable (None otherwise), so `Bader.write_volume` keeps working.
+`write` is the reference's writer (`pybader.io.vasp.write`, io/vasp.py:167-250) with the density block formatted on the
+device (`Context.format_density_text`, byte for byte the reference's python_format / fortran_format); `read` hands it
+out as `file_info['write_function']`, so `Bader.write_volume` / `export_volumes` work without pybader installed.
+Deliberate differences: the caller's arrays are left as they are (the reference multiplies the densities by the cell
+volume in place), and grids the reference cannot write (nx*ny*nz a multiple of 5, fewer than `buffer_size` lines of
+five) are written with the same layout rule.
 """
 import mmap
 import os
 
 import numpy as np
 
-from . import _lib, utils
+from . import _lib, textfmt, utils
 from .interface import distance_matrix, gradient_transform
-
-try:                                    # the export path (-e) keeps using the reference's writer
-    from pybader.io.vasp import write as _reference_write
-except Exception:                       # noqa: BLE001  (pybader absent, or its numba stack not importable)
-    _reference_write = None
 
 __extensions__ = ['chgcar', '.vasp']
 __args__ = ['charge_flag', 'spin_flag', 'buffer_size']
@@ -134,7 +133,7 @@ def read(fn, charge_flag=True, spin_flag=False, buffer_size=64, ctx=None):
         'prefix': prefix,
         'file_type': 'VASP',
         'buffer_size': buffer_size,
-        'write_function': _reference_write,
+        'write_function': write,
         'element_nums': atom_nums,
         'charge_flag': charge_flag,
         'spin_flag': spin_flag,
@@ -143,3 +142,47 @@ def read(fn, charge_flag=True, spin_flag=False, buffer_size=64, ctx=None):
     if atom_types is not None:
         file_info['elements'] = atom_types
     return density, lattice, atoms, file_info
+
+
+def header_number(v, prec):
+    """one coordinate of the lattice / atom lines (io/vasp.py:218-222, io/cube.py:222-234)"""
+    return f" {v:> {10}.{prec}f}"
+
+
+def header_precision(values):
+    """17 - max(int(max log10 |v|) + 9, 9) - 1 over the non-zero `values` (io/vasp.py:212-214, io/cube.py:208-213)"""
+    width = np.max(np.log10(np.abs(values))) + 9
+    return 17 - (max([int(width), 9]) + 1)
+
+
+def write(fn, atoms, lattice, density, file_info, prefix='', suffix='-CHGCAR', ctx=None):
+    """Write a VASP CHGCAR: `density['charge']` and/or `density['spin']` ([x][y][z], per volume as `read` returns them)
+    times the cell volume, header and number format as pybader.io.vasp.write (`file_info['fortran_format']` 0, 1 or 2).
+    The file is `prefix + fn + suffix`."""
+    ctx = ctx or _lib.default_context()
+    fn = prefix + fn + suffix
+    style = textfmt.style_of(file_info.get('fortran_format', 0))
+    lattice = np.asarray(lattice, dtype=np.float64)
+    atoms = np.asarray(atoms, dtype=np.float64)
+    lattice_vol = np.dot(lattice[0], np.cross(*lattice[1:]))
+    blocks = [k for k, flag in (('charge', 'charge_flag'), ('spin', 'spin_flag')) if file_info[flag]]
+    shape = np.asarray(density[blocks[-1]]).shape
+    lattice_prec = header_precision(lattice[lattice != 0])
+    with np.errstate(divide='ignore'):
+        atoms_prec = 17 - (max([np.max(np.log10(np.abs(atoms))).astype(int) + 9, 9]) + 1)
+    head = [file_info['comment'], f"{1:0< 10.7f}\n"]
+    for row in lattice:
+        head.append(''.join(header_number(v, lattice_prec) for v in row) + '\n')
+    if file_info.get('elements', None) is not None:
+        head.append('  '.join(file_info['elements']) + '\n')
+    head.append('  '.join(np.asarray(file_info['element_nums']).astype(str)) + '\n')
+    head.append('Cartesian\n')
+    for row in atoms:
+        head.append(''.join(header_number(v, atoms_prec) for v in row) + '\n')
+    head.append('\n')
+    x, y, z = shape
+    with open(fn, 'wb') as f:
+        f.write(''.join(head).encode())
+        for key in blocks:
+            f.write(f" {x:>5} {y:>5} {z:>5}\n".encode())
+            textfmt.write_block(f, ctx, density[key], lattice_vol, style, 11, 'chgcar')

@@ -89,6 +89,16 @@ def hash_noise(shape, seed):
     return ((z >> np.uint64(11)).astype(np.float64) * np.float64(2.0 ** -53)).reshape(tuple(int(s) for s in shape))
 
 
+
+def lognormal_bits(n, seed, spread=6):
+    """n signed float64 values spread over decades like lognormal samples, from integer arithmetic only (hash_noise):
+    a full 53-bit mantissa in [1, 2) times 2**e, e a sum of four uniform integers in [-spread*4, spread*4) -- bit-
+    reproducible on any numpy (the writer tests' random formatting vectors)."""
+    u = hash_noise((6, int(n)), seed)
+    m = 1.0 + u[0]
+    e = np.sum(np.floor(u[1:5] * (8 * spread)).astype(np.int64) - 4 * spread, axis=0)
+    return np.where(u[5] < 0.5, -1.0, 1.0) * np.ldexp(m, e)
+
 def round_sig(rho, digits):
     """Round to `digits` significant decimal digits the way a '%.{digits-1}E' text file does (CHG files carry 5)."""
     flat = np.ascontiguousarray(rho, dtype=np.float64).reshape(-1)
