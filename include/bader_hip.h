@@ -24,7 +24,7 @@ extern "C" {
 typedef struct xb_ctx xb_ctx;
 
 enum { XB_OK = 0, XB_E_ARG = -1, XB_E_HIP = -2, XB_E_STATE = -3, XB_E_LIMIT = -4, XB_E_COMM = -5,
-       XB_E_SHORT = -6 /* xb_parse_density_text: fewer numbers in the text than voxels in the grid */ };
+       XB_E_SHORT = -6 /* xb_parse_density_text / xb_parse_cube_text: fewer numbers in the text than the grid needs */ };
 
 /* label dtype codes accepted at the boundary: the reference narrows/widens labels between
  * int8/16/32/64 (utils.py:15-37 dtype_calc, jits.py:22-38 dtype matrix) */
@@ -66,6 +66,15 @@ int xb_download_density(xb_ctx *c, double *rho_host);
  * exact fast path go through strtod on the host (n_host of them).  SURVEY.md 8(f) rank 4. */
 int xb_parse_density_text(xb_ctx *c, const char *text, int64_t nbytes, double divisor, int64_t *n_tokens,
                           int64_t *n_host);
+/* The density block of a cube file (io/cube.py:93-123): `text` holds nx*ny*nz*nval (or more) whitespace separated
+ * decimal numbers in C order, nval values per voxel (token i is voxel i / nval, value i % nval; line breaks do not
+ * matter).  Only the tokens with i % nval == pick are converted (as xb_parse_density_text converts) and stored at
+ * voxel i / nval of the resident density: x * scale, or (rho + x) * scale with `accumulate` -- a sum of values is a
+ * chain of calls with scale 1 and the real scale on the last one, ((a + b) + c) * s left to right in float64.
+ * XB_E_SHORT: fewer than nx*ny*nz*nval numbers; XB_E_LIMIT: nx*ny*nz*nval above 2^31 - 1; XB_E_ARG: a malformed
+ * number among those converted, pick outside [0, nval). */
+int xb_parse_cube_text(xb_ctx *c, const char *text, int64_t nbytes, int64_t nval, int64_t pick, int accumulate,
+                       double scale, int64_t *n_tokens, int64_t *n_host);
 /* ---- density -> text (CHGCAR / cube writers) ------------------------------------------------------------------------
  * io/vasp.py:167-250 (vasp.write) and io/cube.py:186-240 (cube.write) format the density with utils.python_format
  * (' {:.11E}' per value, utils.py:85-94) or utils.fortran_format (utils.py:40-82), one value at a time in Python.  Here the

@@ -27,6 +27,7 @@ SYMBOLS = {
     'xb_upload_density': (_int, [_vp, _vp]),
     'xb_synth_density': (_int, [_vp, _pdbl, _pdbl, _i64, _dbl]),
     'xb_parse_density_text': (_int, [_vp, _vp, _i64, _dbl, _pi64, _pi64]),
+    'xb_parse_cube_text': (_int, [_vp, _vp, _i64, _i64, _i64, _int, _dbl, _pi64, _pi64]),
     'xb_download_density': (_int, [_vp, _vp]),
     'xb_format_begin': (_int, [_vp, _vp, _pi64, _int, _dbl, _int, _int, _vp, _i64, _i64, _pi64]),
     'xb_format_host_values': (_int, [_vp, _vp, _vp]),
@@ -127,7 +128,9 @@ class BaderHipError(RuntimeError):
     code = None
 
 
-XB_E_SHORT = -6   # xb_parse_density_text: the text holds fewer numbers than the grid has voxels
+XB_E_ARG = -1     # a bad argument, or a number in the text that does not convert
+XB_E_LIMIT = -4   # a size beyond what the library indexes
+XB_E_SHORT = -6   # xb_parse_density_text / xb_parse_cube_text: the text holds fewer numbers than the grid needs
 
 
 def load():
@@ -464,6 +467,18 @@ class Context:
         a, b = C.c_int64(), C.c_int64()
         self.resident_density = None            # also when the parse fails midway: rho is partly rewritten
         check(self.lib.xb_parse_density_text(self.h, _ptr(buf), buf.size, float(divisor), C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def parse_cube_text(self, text, scale, nval=1, pick=0, accumulate=False):
+        """the density block of a cube file (bytes or a uint8 array, C order, `nval` values per voxel) -> resident
+        density: value `pick` of every voxel times `scale`, or (resident + value) * scale with `accumulate`;
+        returns (numbers found, numbers converted by the host fallback)"""
+        buf = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray, memoryview)) else text
+        assert buf.dtype == np.uint8 and buf.flags.c_contiguous
+        a, b = C.c_int64(), C.c_int64()
+        self.resident_density = None            # also when the parse fails midway: rho is partly rewritten
+        check(self.lib.xb_parse_cube_text(self.h, _ptr(buf), buf.size, int(nval), int(pick), int(bool(accumulate)),
+                                          float(scale), C.byref(a), C.byref(b)))
         return a.value, b.value
 
     def format_density_text(self, values, scale, style, prec, layout):

@@ -315,12 +315,8 @@ int xb_download_density(xb_ctx *c, double *rho_host) {
     return XB_OK;
 }
 
-// ---- density block of a CHGCAR / CHG file: text -> resident rho (k_text.h) ----------------------
+// ---- density block of a CHGCAR / CHG or cube file: text -> resident rho (k_text.h) ----------------------
 static int read_counter(xb_ctx *c, int idx, int *out);
-__global__ void k_patch_doubles(const long long *__restrict__ at, const double *__restrict__ val, int n, double *out) {
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t < n) out[at[t]] = val[t];
-}
 // in-place exclusive scan of n ints on the device (levels of 2048)
 static int device_scan(xb_ctx *c, int *data, int n, int *scratch) {
     const int nb = (n + 2047) / 2048;
@@ -333,14 +329,15 @@ static int device_scan(xb_ctx *c, int *data, int n, int *scratch) {
     }
     return XB_OK;
 }
-int xb_parse_density_text(xb_ctx *c, const char *text, int64_t nbytes, double divisor, int64_t *n_tokens,
-                          int64_t *n_host) {
-    if (c) c->vac_by_tol = false;   // (the -1 labels no longer say "rho <= vac_tol" of the density on the card)
-    NEED_GRID("xb_parse_density_text");
-    const Grid &g = c->g;
-    if (!text || nbytes <= 0) return fail(XB_E_ARG, "xb_parse_density_text: empty text");
-    if (nbytes / (TPB * TXT_BYTES) >= (1LL << 31) - 2) return fail(XB_E_LIMIT, "xb_parse_density_text: text too large");
-    if (!(divisor == divisor) || divisor == 0.) return fail(XB_E_ARG, "xb_parse_density_text: bad divisor");
+// Upload `text`, count its tokens, scan the counts, convert the tokens `map` uses into c->rho (k_text_parse); the
+// tokens outside the device's exact fast path go through strtod here and are stored by k_text_patch.  The token
+// offsets of the scan are int: a text that could hold more than XB_INT_MAX numbers has its count checked in 64 bits.
+extern "C++" {  // (this file sits in bader_hip.hip's extern "C" block)
+template <class Map>
+static int parse_text(xb_ctx *c, const char *who, const char *text, int64_t nbytes, const Map &map, int64_t *n_tokens,
+                      int64_t *n_host) {
+    if (!text || nbytes <= 0) return fail(XB_E_ARG, "%s: empty text", who);
+    if (nbytes / (TPB * TXT_BYTES) >= (1LL << 31) - 2) return fail(XB_E_LIMIT, "%s: text too large", who);
     c->grad_valid = false; c->brick_max_valid = false;
     static const double P10[23] = {1e0, 1e1, 1e2, 1e3, 1e4, 1e5, 1e6, 1e7, 1e8, 1e9, 1e10, 1e11,
                                    1e12, 1e13, 1e14, 1e15, 1e16, 1e17, 1e18, 1e19, 1e20, 1e21, 1e22};
@@ -359,25 +356,32 @@ int xb_parse_density_text(xb_ctx *c, const char *text, int64_t nbytes, double di
     if (e == hipSuccess) e = hipMemcpyAsync(dtext, text, (size_t)nbytes, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(dp10, P10, sizeof P10, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemsetAsync(c->counters + 6, 0, sizeof(int), c->stream);
-    if (e != hipSuccess) { cleanup(); return fail(XB_E_HIP, "xb_parse_density_text: %s", hipGetErrorString(e)); }
+    if (e != hipSuccess) { cleanup(); return fail(XB_E_HIP, "%s: %s", who, hipGetErrorString(e)); }
     int last_count = 0, last_off = 0, n_todo = 0;
     k_text_count<<<nblk, TPB, 0, c->stream>>>(dtext, nbytes, counts);
     e = hipMemcpyAsync(&last_count, counts + nblk - 1, sizeof(int), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess) rc = device_scan(c, counts, nblk, counts + nblk);
+    if (e == hipSuccess && (nbytes + 1) / 2 > XB_INT_MAX) {  // a token takes two bytes with its blank: only here can the scan overflow
+        std::vector<int> blk(nblk);
+        e = hipMemcpyAsync(blk.data(), counts, (size_t)nblk * sizeof(int), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        long long sum = 0;
+        for (int b : blk) sum += b;
+        if (e == hipSuccess && sum > XB_INT_MAX) rc = fail(XB_E_LIMIT, "%s: %lld numbers in the text, at most %d", who, sum, XB_INT_MAX);
+    }
+    if (e == hipSuccess && rc == XB_OK) rc = device_scan(c, counts, nblk, counts + nblk);
     if (e == hipSuccess && rc == XB_OK) e = hipMemcpyAsync(&last_off, counts + nblk - 1, sizeof(int), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess && rc == XB_OK) e = hipStreamSynchronize(c->stream);
     const long long tokens = (long long)last_off + last_count;
-    if (e == hipSuccess && rc == XB_OK && tokens < c->N)
-        rc = fail(XB_E_SHORT, "xb_parse_density_text: %lld numbers in the text, the grid has %lld voxels", tokens, (long long)c->N);
+    if (e == hipSuccess && rc == XB_OK && tokens < map.count())
+        rc = fail(XB_E_SHORT, "%s: %lld numbers in the text, the grid needs %lld", who, tokens, map.count());
     if (e == hipSuccess && rc == XB_OK) {
-        k_text_parse<<<nblk, TPB, 0, c->stream>>>(dtext, nbytes, counts, dp10, divisor, g.nx, g.ny, g.nz, c->rho, dtodo,
-                                                 c->counters + 6, todo_cap);
+        k_text_parse<<<nblk, TPB, 0, c->stream>>>(dtext, nbytes, counts, dp10, map, c->rho, dtodo, c->counters + 6, todo_cap);
         e = hipGetLastError();
         if (e == hipSuccess) rc = read_counter(c, 6, &n_todo);
     }
     if (e == hipSuccess && rc == XB_OK && n_todo > todo_cap)
-        rc = fail(XB_E_LIMIT, "xb_parse_density_text: %d tokens need the host parser (cap %d)", n_todo, todo_cap);
+        rc = fail(XB_E_LIMIT, "%s: %d tokens need the host parser (cap %d)", who, n_todo, todo_cap);
     if (e == hipSuccess && rc == XB_OK && n_todo) {  // the rare tokens outside the exact fast path: strtod on the host
         std::vector<long long> todo(2 * (size_t)n_todo), at(n_todo);
         std::vector<double> val(n_todo);
@@ -389,28 +393,45 @@ int xb_parse_density_text(xb_ctx *c, const char *text, int64_t nbytes, double di
             while (end < nbytes && !(text[end] == ' ' || (text[end] >= 9 && text[end] <= 13))) end++;
             const std::string tok(text + off, text + end);
             char *stop = nullptr;
-            const double v = std::strtod(tok.c_str(), &stop);
-            if (stop == tok.c_str() || *stop != 0) rc = fail(XB_E_ARG, "xb_parse_density_text: could not convert '%s' to a number", tok.c_str());
-            const long long x = idx % g.nx, r = idx / g.nx;
-            at[k] = (x * g.ny + r % g.ny) * g.nz + r / g.ny;
-            val[k] = v / divisor;
+            val[k] = std::strtod(tok.c_str(), &stop);
+            if (stop == tok.c_str() || *stop != 0) rc = fail(XB_E_ARG, "%s: could not convert '%s' to a number", who, tok.c_str());
+            map.voxel(idx, at[k]);                                    // (only used tokens are listed)
         }
         if (e == hipSuccess && rc == XB_OK) {
-            long long *dat = dtodo;                                   // reuse: indices then values
+            long long *dat = dtodo;                                   // reuse: voxels then values
             double *dval = reinterpret_cast<double *>(dtodo + n_todo);
             e = hipMemcpyAsync(dat, at.data(), n_todo * sizeof(long long), hipMemcpyHostToDevice, c->stream);
             if (e == hipSuccess) e = hipMemcpyAsync(dval, val.data(), n_todo * sizeof(double), hipMemcpyHostToDevice, c->stream);
-            if (e == hipSuccess) k_patch_doubles<<<(n_todo + 255) / 256, 256, 0, c->stream>>>(dat, dval, n_todo, c->rho);
+            if (e == hipSuccess) k_text_patch<<<(n_todo + 255) / 256, 256, 0, c->stream>>>(dat, dval, n_todo, map, c->rho);
+            if (e == hipSuccess) e = hipGetLastError();
             if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
         }
     }
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     cleanup();
-    if (e != hipSuccess) return fail(XB_E_HIP, "xb_parse_density_text: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(XB_E_HIP, "%s: %s", who, hipGetErrorString(e));
     if (rc != XB_OK) return rc;
     if (n_tokens) *n_tokens = tokens;
     if (n_host) *n_host = n_todo;
     return XB_OK;
+}
+}  // extern "C++"
+int xb_parse_density_text(xb_ctx *c, const char *text, int64_t nbytes, double divisor, int64_t *n_tokens,
+                          int64_t *n_host) {
+    if (c) c->vac_by_tol = false;   // (the -1 labels no longer say "rho <= vac_tol" of the density on the card)
+    NEED_GRID("xb_parse_density_text");
+    if (!(divisor == divisor) || divisor == 0.) return fail(XB_E_ARG, "xb_parse_density_text: bad divisor");
+    const TxtFortran map{c->g.nx, c->g.ny, c->g.nz, divisor};
+    return parse_text(c, "xb_parse_density_text", text, nbytes, map, n_tokens, n_host);
+}
+int xb_parse_cube_text(xb_ctx *c, const char *text, int64_t nbytes, int64_t nval, int64_t pick, int accumulate,
+                       double scale, int64_t *n_tokens, int64_t *n_host) {
+    if (c) c->vac_by_tol = false;   // (the -1 labels no longer say "rho <= vac_tol" of the density on the card)
+    NEED_GRID("xb_parse_cube_text");
+    if (nval < 1 || pick < 0 || pick >= nval) return fail(XB_E_ARG, "xb_parse_cube_text: bad nval %lld / pick %lld", (long long)nval, (long long)pick);
+    if (nval > XB_INT_MAX / c->N) return fail(XB_E_LIMIT, "xb_parse_cube_text: %lld voxels x %lld values exceed %d numbers", (long long)c->N, (long long)nval, XB_INT_MAX);
+    const TxtCube map{(long long)c->N * nval, nval, pick, accumulate ? 1 : 0, scale};
+    return parse_text(c, "xb_parse_cube_text", text, nbytes, map, n_tokens, n_host);
 }
 
 int xb_synth_density(xb_ctx *c, const double lattice[9], const double *atoms5, int64_t n_atoms, double background) {

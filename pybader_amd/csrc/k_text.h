@@ -1,4 +1,4 @@
-// k_text.h -- device kernels of libbader_hip.so: the density block of a CHGCAR / CHG file, text -> resident rho.
+// k_text.h -- device kernels of libbader_hip.so: the density block of a CHGCAR / CHG or cube file, text -> resident rho.
 // Included by bader_hip.hip (one translation unit); see bader_kernels.h for the common device code.
 #pragma once
 
@@ -10,7 +10,8 @@
 // Here the text is uploaded as it is and parsed on the device:
 //   k_text_count   token starts per block (a token starts at a non-blank byte that follows a blank)
 //   (exclusive scan of the block counts)
-//   k_text_parse   every token start: decimal -> float64, divided, stored at its [x][y][z] position
+//   k_text_parse   every token start: decimal -> float64, stored at its [x][y][z] position by a map (TxtFortran:
+//                  divided by the cell volume; TxtCube: the cube block, C order, one of nval values per voxel)
 // Decimal -> binary is exact here: a token with a mantissa m < 2^53 and a decimal exponent |e| <= 22 is
 // m * 10^e or m / 10^-e with both operands exact doubles, i.e. ONE correctly rounded IEEE operation
 // (Clinger's fast path) -- every number a VASP / pybader writer produces (<= 17 digits would not fit, 11-12
@@ -115,30 +116,68 @@ __device__ __forceinline__ bool txt_parse(const unsigned char *__restrict__ p, c
     out = neg ? -v : v;
     return true;
 }
-// block_off: exclusive scan of the block counts.  Token i of the file (Fortran order, x fastest) is voxel
-// (i % nx, (i / nx) % ny, i / (nx ny)); tokens beyond nx*ny*nz are ignored.  todo: (byte offset, token index)
-// of the tokens left to the host.
+// Where token i of the text goes and how it is stored: the one difference between the CHGCAR and the cube block.
+// count(): tokens the grid takes (the rest of the text is ignored); voxel(i, v): false for a token that is not used,
+// else its voxel v of rho[x][y][z]; store(): the value written there.  voxel() runs on the host too (strtod fallback).
+struct TxtFortran {  // CHGCAR (io/vasp.py:97-104, 147-149): x fastest, divided by the cell volume
+    int nx, ny, nz;
+    double divisor;
+    __host__ __device__ long long count() const { return (long long)nx * ny * nz; }
+    __host__ __device__ bool voxel(long long i, long long &v) const {
+        const int x = (int)(i % nx);
+        const long long r = i / nx;
+        const int y = (int)(r % ny), z = (int)(r / ny);
+        v = ((long long)x * ny + y) * nz + z;
+        return true;
+    }
+    __device__ void store(double *__restrict__ rho, long long v, double x) const { rho[v] = x / divisor; }  // true division
+};
+struct TxtCube {  // cube (io/cube.py:93-123): C order, nval values per voxel, the one numbered `pick` used
+    long long ntok, nval, pick;  // ntok = nx*ny*nz*nval
+    int accumulate;
+    double scale;
+    __host__ __device__ long long count() const { return ntok; }
+    __host__ __device__ bool voxel(long long i, long long &v) const {
+        if (nval == 1) { v = i; return true; }
+        if (i % nval != pick) return false;
+        v = i / nval;
+        return true;
+    }
+    // store mode writes x * scale, never (0 + x) * scale: -0.0 + 0.0 would be +0.0
+    __device__ void store(double *__restrict__ rho, long long v, double x) const {
+        rho[v] = accumulate ? (rho[v] + x) * scale : x * scale;
+    }
+};
+
+// block_off: exclusive scan of the block counts.  Token i of the text goes where `map` says; tokens from
+// map.count() on are ignored.  todo: (byte offset, token index) of the used tokens left to the host.
+template <class Map>
 __global__ __launch_bounds__(TPB) void k_text_parse(const unsigned char *__restrict__ t, long long n,
                                                     const int *__restrict__ block_off, const double *__restrict__ p10,
-                                                    double divisor, int nx, int ny, int nz, double *__restrict__ rho,
-                                                    long long *todo, int *n_todo, int todo_cap) {
+                                                    Map map, double *__restrict__ rho, long long *todo, int *n_todo,
+                                                    int todo_cap) {
     const long long base = ((long long)blockIdx.x * TPB + threadIdx.x) * TXT_BYTES;
     const unsigned int starts = base < n ? txt_starts(t, base, n) : 0u;
     int total;
     long long idx = (long long)block_off[blockIdx.x] + block_scan_excl(__popc(starts), total);
-    const long long nvox = (long long)nx * ny * nz;
+    const long long ntok = map.count();
     for (unsigned int m = starts; m; m &= m - 1, idx++) {
-        if (idx >= nvox) break;
+        if (idx >= ntok) break;
+        long long vox;
+        if (!map.voxel(idx, vox)) continue;
         const long long at = base + (__ffs(m) - 1);
         double v;
-        if (txt_parse(t + at, t + n, p10, v)) {
-            const int x = (int)(idx % nx);
-            const long long r = idx / nx;
-            const int y = (int)(r % ny), z = (int)(r / ny);
-            rho[((long long)x * ny + y) * nz + z] = v / divisor;  // io/vasp.py:147-149, true division
-        } else {
+        if (txt_parse(t + at, t + n, p10, v)) map.store(rho, vox, v);
+        else {
             const int k = atomicAdd(n_todo, 1);
             if (k < todo_cap) { todo[2 * k] = at; todo[2 * k + 1] = idx; }
         }
     }
+}
+// the host's conversions of the todo tokens: val[t] (as strtod returned it) stored at voxel at[t] as `map` stores
+template <class Map>
+__global__ void k_text_patch(const long long *__restrict__ at, const double *__restrict__ val, int n, Map map,
+                             double *__restrict__ rho) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < n) map.store(rho, at[t], val[t]);
 }
