@@ -287,6 +287,7 @@ extern "C" {
 const char *xb_last_error(void) { return g_err.c_str(); }
 
 #include "host_context.h"
+#include "host_stages.h"
 #include "host_format.h"
 #include "host_assign.h"
 #include "host_refine.h"

@@ -9,12 +9,6 @@
 static int read_counter(xb_ctx *c, int idx, int *out);
 static GridL light(const Grid &g);
 
-// layout of the small device int buffer of the region growth (c->boxbuf): maximum / first brick of up to XB_REGIONS_MAX
-// regions (k_seed_bricks)
-enum { BB_TOTAL = 1 << 20, BB_REGMAX = 1 << 16, BB_REGFIRST = 1 << 17 };
-
-static bool table_windowed(const xb_ctx *c) { return c->g.wlen < c->g.nx; }
-
 // per-brick arrays that outlive an assignment: blab_buf (nbr ints: region label per brick) and brick_rec (nbr bytes)
 static int ensure_brick_bytes(xb_ctx *c, int nbr) {
     if (c->blab_alloc < nbr) {
@@ -37,13 +31,8 @@ static int ensure_grad(xb_ctx *c, bool force, bool boxes, bool main_rule) {
     if (c->grad_valid && !force && !boxes && c->grad_cover == 1 && c->brick_rec) {
         // records exist for the flagged bricks only, under the other tie rule: redo exactly those
         const int nb1r = (g.ny + BRK - 1) / BRK, nb2r = (g.nz + BRK - 1) / BRK, nbr = ((g.nx + BRK - 1) / BRK) * nb1r * nb2r;
-        const int small = (g.nx < 16 || g.ny < 16 || g.nz < 80);
         ScopedTimer t(c, 4);
-        GridS gs;
-        if (sym_grid(g, gs))
-            k_brick_records<GridS><<<4096, TPB, 0, c->stream>>>(gs, c->rho, c->grad, nullptr, nullptr, nbr, nb1r, nb2r, c->brick_rec, small);
-        else
-            k_brick_records<Grid><<<4096, TPB, 0, c->stream>>>(g, c->rho, c->grad, nullptr, nullptr, nbr, nb1r, nb2r, c->brick_rec, small);
+        launch_brick_records(c, nullptr, nullptr, nbr, nb1r, nb2r);
         HIPCHK(hipGetLastError());
         c->grad_rule = main_rule ? 1 : 0;
         return XB_OK;
@@ -54,18 +43,13 @@ static int ensure_grad(xb_ctx *c, bool force, bool boxes, bool main_rule) {
         // a retrace that walks on through a brick without records is redone by the from-rho kernel
         const int nb0 = (g.nx + BRK - 1) / BRK, nb1 = (g.ny + BRK - 1) / BRK, nb2 = (g.nz + BRK - 1) / BRK, nbr = nb0 * nb1 * nb2;
         if (int rc = ensure_brick_bytes(c, nbr)) return rc;
-        const int small = (g.nx < 16 || g.ny < 16 || g.nz < 80);
         ScopedTimer t(c, 4);
         int *buni = reinterpret_cast<int *>(c->st);
         if (!c->buni_valid) k_label_uniform_list<<<4096, TPB, 0, c->stream>>>(light(g), c->labels, nb1, nb2, nullptr, nbr, nullptr, nullptr, buni, 0, nbr);
         c->buni_valid = true;
         k_buni3<<<(nbr + 255) / 256, 256, 0, c->stream>>>(nb0, nb1, nb2, buni, buni + nbr);
         k_flag_mixed_bricks<<<(nbr + 255) / 256, 256, 0, c->stream>>>(nbr, buni + nbr, c->brick_rec);
-        GridS gs;
-        if (sym_grid(g, gs))
-            k_brick_records<GridS><<<4096, TPB, 0, c->stream>>>(gs, c->rho, c->grad, nullptr, nullptr, nbr, nb1, nb2, c->brick_rec, small);
-        else
-            k_brick_records<Grid><<<4096, TPB, 0, c->stream>>>(g, c->rho, c->grad, nullptr, nullptr, nbr, nb1, nb2, c->brick_rec, small);
+        launch_brick_records(c, nullptr, nullptr, nbr, nb1, nb2);
         HIPCHK(hipGetLastError());
         c->grad_valid = true;
         c->grad_cover = 1;
@@ -82,17 +66,12 @@ static int ensure_grad(xb_ctx *c, bool force, bool boxes, bool main_rule) {
     {
         const int nb0 = (g.nx + BRK - 1) / BRK, nb1 = (g.ny + BRK - 1) / BRK, nb2 = (g.nz + BRK - 1) / BRK, nbr = nb0 * nb1 * nb2;
         if (int rc = ensure_brick_bytes(c, nbr)) return rc;
-        const int small = (g.nx < 16 || g.ny < 16 || g.nz < 80);
         ScopedTimer t(c, 4);
         ScopedTimer tk(c, 5);
         // (a window is brick aligned: xb_set_table_window; bit 1 "may hold a maximum" everywhere: nothing is known about them)
         const int wb0 = table_windowed(c) ? g.wx0 / BRK : 0, wnb = table_windowed(c) ? g.wlen / BRK : nb0;
         k_flag_window_bricks<<<(nbr + 255) / 256, 256, 0, c->stream>>>(nb0, nb1 * nb2, wb0, wnb, (unsigned char)3, c->brick_rec);
-        GridS gs;
-        if (sym_grid(g, gs))
-            k_brick_records<GridS><<<4096, TPB, 0, c->stream>>>(gs, c->rho, c->grad, nullptr, nullptr, nbr, nb1, nb2, c->brick_rec, small);
-        else
-            k_brick_records<Grid><<<4096, TPB, 0, c->stream>>>(g, c->rho, c->grad, nullptr, nullptr, nbr, nb1, nb2, c->brick_rec, small);
+        launch_brick_records(c, nullptr, nullptr, nbr, nb1, nb2);
         HIPCHK(hipGetLastError());
     }
     c->grad_valid = true;
@@ -252,16 +231,10 @@ int xb_assign_trace(xb_ctx *c, int method, int64_t *n_local) {
     const int *box_max = nullptr;   // region id - 1 -> its maximum (set once the regions of this call exist)
     int *max_count_dev = c->counters + 0;   // where the kernels of this call count the maxima they note
     bool fast_slab = false;                 // windowed slab on passes A/B: the persistent trace, counts on the device
-    HIPCHK(hipMemsetAsync(c->counters, 0, 16 * sizeof(int), c->stream));
-    if (!c->first_clean) {  // a previous assignment did not finish: `first` may hold stale minima
-        k_fill<int><<<4096, TPB, 0, c->stream>>>(c->first, XB_INT_MAX, c->N);
-        HIPCHK(hipGetLastError());
-    }
-    c->first_clean = false;
-    c->regions_pending = false;
+    if (int rc = begin_assignment(c, c->counters, 16, false)) return rc;
     c->regions_neargrid = method == XB_METHOD_NEARGRID;
     if (method == XB_METHOD_NEARGRID) {
-        const int maxsteps = 8 * (g.nx + g.ny + g.nz) + 64;
+        const int maxsteps = trace_maxsteps(g);
         // the table is a pure function of the resident density, but it is part of the assignment
         // work: rebuilt on every call, never carried over from a previous assignment
         if (c->table_prebuilt) c->table_prebuilt = false;   // built by xb_table_build/xb_table_finish just now
@@ -306,20 +279,9 @@ int xb_assign_trace(xb_ctx *c, int method, int64_t *n_local) {
                     c->regions_pending = true;
                 }
                 int nwalk = 0;
-                if (fast_slab) {
-                    // the persistent trace of the one-GPU path (per-XCD cursors over the list, its length on the device): no
-                    // host wait before it.  A trajectory that leaves the table window lands on a list (in `stage`) and is
-                    // redone by the kernel that derives missing records from rho.
+                if (fast_slab) {   // the persistent trace of the one-GPU path: no host wait before it
                     ScopedTimer tw(c, 6);
-                    int *redo = (int *)c->stage;
-                    const int redo_cap = (int)std::min<size_t>(c->stage_bytes / sizeof(int), 0x7fffffffu);
-                    k_ng_trace_g<2, 0><<<std::max(1, c->trace_waves / XB_TRACE_WAVES), XB_WAVE * XB_TRACE_WAVES, 0, c->stream>>>(light(g), c->grad, box_max, c->blab, c->nbk[1], c->nbk[2], walk,
-                                                                                  c->fs, c->labels, c->first, c->max_list, c->max_cap, redo,
-                                                                                  redo_cap, maxsteps, c->has_vacuum ? 1 : 0, 8, 1);
-                    k_ng_trace_list<2><<<512, TPB, 0, c->stream>>>(
-                        light(g), c->grad, box_max, c->blab, c->nbk[1], c->nbk[2], redo, c->fs + FS_N_OVF, c->labels,
-                        c->first, c->max_list, max_count_dev, c->max_cap, c->ovf_list, c->counters + 1, c->ovf_cap,
-                        maxsteps, c->rho, c->dist_dev, c->has_vacuum ? 1 : 0);
+                    launch_persistent_trace(c, false, false, box_max, walk, c->has_vacuum ? 1 : 0, nullptr);
                 } else {
                 if (int rc = read_counter(c, 13, &nwalk)) return rc;
                 c->n_walk = nwalk;
@@ -387,7 +349,7 @@ int xb_assign_trace(xb_ctx *c, int method, int64_t *n_local) {
         c->box_voxels = 0;
         {
             ScopedTimer t(c, 1);
-            const int small = (g.nx < 16 || g.ny < 16 || g.nz < 80);
+            const int small = small_grid(g);
             const int nbr = ((g.nx + BRK - 1) / BRK) * ((g.ny + BRK - 1) / BRK) * ((g.nz + BRK - 1) / BRK);
             if (3LL * nbr > c->list_cap) return fail(XB_E_LIMIT, "xb_assign: scratch too small for the brick arrays of the pointer pass");
             dim3 grid((g.nz + GT_Z - 1) / GT_Z, (g.ny + GT_Y - 1) / GT_Y, (g.nx + GT_X - 1) / GT_X);
@@ -442,54 +404,26 @@ int xb_assign_finish(xb_ctx *c, const int64_t *max_idx_sorted, int64_t n_global)
     for (int64_t i = 0; i < n_global; i++) c->maxima_sorted[i] = (int)max_idx_sorted[i];
     c->label_wire = label_wire_for(n_global);
     const Grid &g = c->g;
-    const long long own = (long long)(g.x1 - g.x0) * g.nyz;
     if (n_global) {
         if (int rc = upload_pinned(c, c->max_aux, c->maxima_sorted.data(), n_global * sizeof(int))) return rc;
         k_set_rank<<<(unsigned)((n_global + 255) / 256), 256, 0, c->stream>>>(c->first, c->max_aux, (int)n_global);
         HIPCHK(hipGetLastError());
     }
     c->buni_valid = false; c->regions_labels = false;
-    if (c->regions_pending && c->blab) {
-        // (one brick-label lookup per 8 rows; 16-byte stores when the rows are aligned.  The launch covers 4-plane groups from x0 on)
-        if (g.nz % 4 == 0)
-            k_relabel_regions_brick<4><<<dim3((g.nz / 4 + 63) / 64, c->nbk[1], (g.x1 - g.x0 + 3) / 4), TPB, 0, c->stream>>>(
-                light(g), c->labels, c->first, c->blab, c->nbk[1], c->nbk[2], (c->box_max_tab ? c->box_max_tab : c->boxbuf + BB_REGMAX),
-                nullptr, nullptr, c->n_boxes);
-        else
-            k_relabel_regions_brick<1><<<dim3((g.nz + 63) / 64, c->nbk[1], (g.x1 - g.x0 + 3) / 4), TPB, 0, c->stream>>>(
-                light(g), c->labels, c->first, c->blab, c->nbk[1], c->nbk[2], (c->box_max_tab ? c->box_max_tab : c->boxbuf + BB_REGMAX),
-                nullptr, nullptr, c->n_boxes);
-        if (g.x1 - g.x0 == g.nx) {  // one slab: the per-brick label uniformity edge_find wants comes for free
-            const int nbr = c->nbk[0] * c->nbk[1] * c->nbk[2];
-            int *buni = reinterpret_cast<int *>(c->st);
-            k_buni_after_relabel<<<(nbr + 255) / 256, 256, 0, c->stream>>>(nbr, c->blab, (c->box_max_tab ? c->box_max_tab : c->boxbuf + BB_REGMAX), c->first, buni, nullptr, nullptr, nullptr, nullptr);
-            if (c->n_walk)
-                k_label_uniform_list<<<(c->n_walk + 3) / 4, TPB, 0, c->stream>>>(light(g), c->labels, c->nbk[1], c->nbk[2],
-                                                                                c->walk, c->n_walk, nullptr, nullptr, buni);
-            c->buni_valid = true;
-            c->buni_halo_safe = false;
-        } else if (!c->has_vacuum && g.nx % 8 == 0 && g.ny % 8 == 0 && g.nz % 8 == 0 && g.x0 % 8 == 0 && g.x1 % 8 == 0) {
-            // a slab: the regions' bricks are uniform on every rank, the owned walk-list bricks are scanned, every other
-            // brick counts as mixed -- right whatever the peers' halo planes bring, and no pass over the labels
-            const int nbr = c->nbk[0] * c->nbk[1] * c->nbk[2];
-            int *buni = reinterpret_cast<int *>(c->st);
-            k_fill<int><<<(nbr + 4 * TPB - 1) / (4 * TPB), TPB, 0, c->stream>>>(buni, XB_MIXED, nbr);
-            k_buni_after_relabel<<<(nbr + 255) / 256, 256, 0, c->stream>>>(nbr, c->blab, (c->box_max_tab ? c->box_max_tab : c->boxbuf + BB_REGMAX), c->first, buni, nullptr, nullptr, nullptr, nullptr);
-            if (c->n_walk)
-                k_label_uniform_list<<<(c->n_walk + 3) / 4, TPB, 0, c->stream>>>(light(g), c->labels, c->nbk[1], c->nbk[2],
-                                                                                c->walk, c->n_walk, nullptr, nullptr, buni);
-            c->buni_valid = true;
-            c->buni_halo_safe = true;
-        }
-    } else
-        k_relabel<<<nblocks(own), TPB, 0, c->stream>>>(g, c->labels, c->first, nullptr);
-    c->regions_labels = c->regions_pending && c->blab && !c->has_vacuum && c->regions_neargrid;   // certain bricks carry their (neargrid) region's label now
-    c->regions_pending = false;
+    const bool regions = c->regions_pending && c->blab;
+    int buni = BUNI_NONE;
+    if (regions && g.x1 - g.x0 == g.nx)   // one slab: the per-brick label uniformity edge_find wants comes for free
+        buni = BUNI_SCAN;
+    else if (regions && !c->has_vacuum && g.nx % 8 == 0 && g.ny % 8 == 0 && g.nz % 8 == 0 && g.x0 % 8 == 0 && g.x1 % 8 == 0)
+        buni = BUNI_MIXED;   // a slab: the regions' bricks are uniform on every rank, the owned walk-list bricks are scanned, no pass over the labels
+    launch_relabel(c, nullptr, (int)n_global, regions, c->box_max_tab ? c->box_max_tab : c->boxbuf + BB_REGMAX, buni, nullptr);
     HIPCHK(hipGetLastError());
-    if (n_global) {  // leave `first` clean (INT_MAX everywhere) for the next assignment
-        k_reset_first<<<(unsigned)((n_global + 255) / 256), 256, 0, c->stream>>>(c->first, c->max_aux, (int)n_global, nullptr, nullptr);
-        HIPCHK(hipGetLastError());
+    if (buni != BUNI_NONE) {
+        c->buni_valid = true;
+        c->buni_halo_safe = buni == BUNI_MIXED;
     }
+    c->regions_labels = regions && !c->has_vacuum && c->regions_neargrid;   // certain bricks carry their (neargrid) region's label now
+    c->regions_pending = false;
     HIPCHK(hipStreamSynchronize(c->stream));
     c->first_clean = true;
     return XB_OK;
@@ -507,14 +441,14 @@ static bool fused_ok(const xb_ctx *c) {
            g.nx >= 16 && g.ny >= 16 && g.nz >= 16;
 }
 static int assign_neargrid_tail(xb_ctx *c, int64_t *n_maxima);
-static int fused_numbering_launch(xb_ctx *c);
 
 // numbering + relabel on the device (skipped by their gate when the numbering has to be done on the host), the per-brick
 // uniformity for the edge sweep, `first` left clean, and the state block + the sorted maxima on their way to the host
-static int fused_relabel_launch(xb_ctx *c);
 static int fused_numbering_launch(xb_ctx *c) {
     k_number_maxima<<<1, 1024, 0, c->stream>>>(c->fs, c->first, c->max_list, c->max_cap, c->max_aux, c->fs + FS_TOTAL);
-    return fused_relabel_launch(c);
+    launch_relabel(c, c->fs, 0, c->regions_pending, c->box_max_tab, BUNI_SCAN, c->bres_last);
+    HIPCHK(hipGetLastError());
+    return XB_OK;
 }
 // More maxima than k_number_maxima sorts (XB_SORT_MAX): the bitmap numbering of k_fused.h (k_rank_*), then the same relabel
 // launches, and the sorted list to the host.  `nmax` maxima are noted, every walker has arrived.  Scratch: N / 4 bytes of `stage`
@@ -536,42 +470,17 @@ static int number_maxima_big(xb_ctx *c, int nmax) {
     k_rank_blocks<<<1, 1024, 0, c->stream>>>(bsum, (int)n_blocks);
     k_rank_assign<<<(nmax + 255) / 256, 256, 0, c->stream>>>(c->first, c->max_list, nmax, bits, wprefix, bsum, c->max_aux, c->fs);
     HIPCHK(hipGetLastError());
-    if (int rc = fused_relabel_launch(c)) return rc;
+    launch_relabel(c, c->fs, 0, c->regions_pending, c->box_max_tab, BUNI_SCAN, c->bres_last);
+    HIPCHK(hipGetLastError());
     c->maxima_sorted.resize(nmax);
     HIPCHK(hipMemcpyAsync(c->maxima_sorted.data(), c->max_aux, (size_t)nmax * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));   // (the scratch may go afterwards)
-    return XB_OK;
-}
-static int fused_relabel_launch(xb_ctx *c) {
-    Grid &g = c->g;
-    int *fs = c->fs;
-    const GridL gl = light(g);
-    const int nb1 = c->nbk[1], nb2 = c->nbk[2], nbr = c->nbk[0] * nb1 * nb2;
-    int *walk = c->walk, *box_max = c->box_max_tab, *bres = c->bres_last;
-    int *buni = reinterpret_cast<int *>(c->st);
-    if (c->regions_pending) {
-        if (g.nz % 4 == 0)
-            k_relabel_regions_brick<4><<<dim3((g.nz / 4 + 63) / 64, nb1, (g.nx + 3) / 4), TPB, 0, c->stream>>>(gl, c->labels, c->first, c->blab, nb1, nb2,
-                                                                                                        box_max, fs, fs + FS_SORT_OK);
-        else
-            k_relabel_regions_brick<1><<<dim3((g.nz + 63) / 64, nb1, (g.nx + 3) / 4), TPB, 0, c->stream>>>(gl, c->labels, c->first, c->blab, nb1, nb2,
-                                                                                                     box_max, fs, fs + FS_SORT_OK);
-        if (bres) k_buni_after_relabel<<<(nbr + 255) / 256, 256, 0, c->stream>>>(nbr, c->blab, box_max, c->first, buni, fs + FS_SORT_OK, walk, fs + FS_N_WALK, bres);
-        else {
-            k_buni_after_relabel<<<(nbr + 255) / 256, 256, 0, c->stream>>>(nbr, c->blab, box_max, c->first, buni, fs + FS_SORT_OK, nullptr, nullptr, nullptr);
-            k_label_uniform_list<<<2048, TPB, 0, c->stream>>>(gl, c->labels, nb1, nb2, walk, 0, fs + FS_N_WALK, fs + FS_SORT_OK, buni);
-        }
-    } else
-        k_relabel<<<nblocks(c->N), TPB, 0, c->stream>>>(g, c->labels, c->first, fs + FS_SORT_OK);
-    k_reset_first<<<8, 256, 0, c->stream>>>(c->first, c->max_aux, 0, fs + FS_N_MAX, fs + FS_SORT_OK);
-    HIPCHK(hipGetLastError());
     return XB_OK;
 }
 
 static int assign_neargrid_fused(xb_ctx *c, int64_t *n_maxima) {
     if (int rc = need_grad(c)) return rc;
     Grid &g = c->g;
-    const GridL gl0 = light(g);
     const int nb0 = (g.nx + BRK - 1) / BRK, nb1 = (g.ny + BRK - 1) / BRK, nb2 = (g.nz + BRK - 1) / BRK, nbr = nb0 * nb1 * nb2;
     const bool part = g.nx % BRK || g.ny % BRK || g.nz % BRK;   // the grid cuts its last bricks
     if (int rc = ensure_brick_bytes(c, nbr)) return rc;
@@ -580,8 +489,7 @@ static int assign_neargrid_fused(xb_ctx *c, int64_t *n_maxima) {
     int *seed = c->list, *bmask = c->list + nbr, *buf0 = c->list + 2 * nbr, *buf1 = c->list + 3 * nbr, *walk = c->list + 4 * nbr;
     int *box_max = c->boxbuf + BB_REGMAX, *box_first = c->boxbuf + BB_REGFIRST;
     int *bmaxv = walk;   // (free until the walk list is made)
-    int *bpot = c->list + 5 * nbr;   // brick potentials of the region growth (k_grow_parent); buf1 doubles as the parent array
-    const bool chase = true;   // provisional labels by one chase along the brick potentials
+    int *bpot = c->list + 5 * nbr;   // brick potentials of the region growth (k_grow_parent)
     int *bres = nullptr;   // per walk-list brick: the one maximum all its voxels ended on (k_ng_trace_g), for the edge sweep's uniformity
     c->box_max_tab = box_max;
     // (debug switch 32: wait after every stage and say so -- finds the kernel that does not come back)
@@ -595,66 +503,20 @@ static int assign_neargrid_fused(xb_ctx *c, int64_t *n_maxima) {
             fflush(stderr);
         }
     };
-    HIPCHK(hipMemsetAsync(fs, 0, FS_TOTAL * sizeof(int), c->stream));
-    if (!c->first_clean) {  // a previous assignment did not finish: `first` may hold stale minima
-        k_fill<int><<<4096, TPB, 0, c->stream>>>(c->first, XB_INT_MAX, c->N);
-        HIPCHK(hipGetLastError());
-    }
-    c->first_clean = false;
-    c->regions_pending = false;
-    c->buni_valid = false; c->regions_labels = false;
-    c->list_valid = false; c->chg_n = -1;
+    if (int rc = begin_assignment(c, fs, FS_TOTAL, true)) return rc;
     g.main_ties = 1;   // methods.neargrid's tie test (methods.py:324)
     const GridL gl = light(g);
-    (void)gl0;
     {   // brick masks + seeds
         ScopedTimer t4(c, 4);
         {
             ScopedTimer t5(c, 5);
-            const int small = (g.nx < 16 || g.ny < 16 || g.nz < 80);
-            dim3 grid((g.nz + GT_Z - 1) / GT_Z, (g.ny + GT_Y - 1) / GT_Y, (g.nx + GT_X - 1) / GT_X);
-            GridS gs;
-            const bool sym = sym_grid(g, gs);
-            {
-                // the assignment's tie rule (methods.py:324) is the template argument
-                int mirror = 0;
-                double mu_scale = 0.;
-                if (sym && c->opt_mirror) mirror_prefilter(g, mirror, mu_scale);
-                // (an orthogonal lattice has a diagonal T_grad: exact zeros off the diagonal)
-                const bool diag = c->opt_mask_diag && g.T[1] == 0. && g.T[2] == 0. && g.T[3] == 0. && g.T[5] == 0. && g.T[6] == 0. && g.T[7] == 0.;
-                if (part) {
-                    if (sym && diag) k_brick_masks<GridS, 1, true, true><<<grid, TPB, 0, c->stream>>>(gs, c->rho, small, bmask, bmaxv, fs + FS_TIES, 0, mu_scale, mirror, bpot);
-                    else if (sym) k_brick_masks<GridS, 1, false, true><<<grid, TPB, 0, c->stream>>>(gs, c->rho, small, bmask, bmaxv, fs + FS_TIES, 0, mu_scale, mirror, bpot);
-                    else k_brick_masks<Grid, 1, false, true><<<grid, TPB, 0, c->stream>>>(g, c->rho, small, bmask, bmaxv, fs + FS_TIES, 0, 0., 0, bpot);
-                } else
-                if (sym && diag) k_brick_masks<GridS, 1, true><<<grid, TPB, 0, c->stream>>>(gs, c->rho, small, bmask, bmaxv, fs + FS_TIES, 0, mu_scale, mirror, bpot);
-                else if (sym) k_brick_masks<GridS, 1, false><<<grid, TPB, 0, c->stream>>>(gs, c->rho, small, bmask, bmaxv, fs + FS_TIES, 0, mu_scale, mirror, bpot);
-                else k_brick_masks<Grid, 1, false><<<grid, TPB, 0, c->stream>>>(g, c->rho, small, bmask, bmaxv, fs + FS_TIES, 0, 0., 0, bpot);
-            }
+            launch_brick_masks(c, part, true, bmask, bmaxv, bpot);
         }
         stage_done("brick masks");
         c->grad_valid = true;
         c->grad_rule = 1;
         c->grad_cover = 1;
-        {
-            // seeds: the bricks that hold exactly one maximum (no cubes, no cap on the number of maxima); they are not
-            // fixed: the kill iteration certifies them like every other brick
-            k_seed_bricks<<<(nbr + 255) / 256, 256, 0, c->stream>>>(nbr, bmask, bmaxv, fs, seed, buf0, box_max, box_first);
-            if (chase) {   // provisional labels by one chase along the brick potentials instead of ~6 propagation launches
-                k_grow_parent<<<(nbr + TPB - 1) / TPB, TPB, 0, c->stream>>>(nb0, nb1, nb2, bmask, bpot, seed, buf1);
-                k_grow_chase<<<(nbr + TPB - 1) / TPB, TPB, 0, c->stream>>>(nbr, buf1, seed, buf0, 4 * (nb0 + nb1 + nb2) + 64, fs);
-            } else
-                k_seed_finish<<<1, 1, 0, c->stream>>>(fs);
-        }
-        // the worst-case schedule; after a chase only the kill iteration is left, which dies out within a few bricks of the
-        // dividing surfaces: a short schedule first, and a repeat of the whole assignment with the long one (FS_GROW_RETRY)
-        // for the rare density whose cascade runs deeper
-        const int long_schedule = 2 * ((std::max(std::max(nb0, nb1), nb2) + BG - 1) / BG) + 12;
-        const int launches = chase ? std::min(long_schedule, c->grow_kill_launches) : long_schedule;
-        const dim3 ggrid((nb2 + BG - 1) / BG, (nb1 + BG - 1) / BG, (nb0 + BG - 1) / BG);
-        for (int l = 0; l < launches; l++)   // each returns at once when the growth has finished (phase on the device)
-            k_brick_grow_dev<<<ggrid, BG * BG * BG, 0, c->stream>>>(nb0, nb1, nb2, bmask, seed, buf0, buf1, fs, BG, 0);
-        k_grow_finish<<<64, TPB, 0, c->stream>>>(nbr, seed, buf0, buf1, fs, c->blab_buf, box_first, bmask, c->brick_rec, 0, chase && launches < long_schedule ? 1 : 0);
+        launch_region_growth(c, nb0, nb1, nb2, bmask, bmaxv, bpot, seed, buf0, buf1, box_max, box_first, true);
         HIPCHK(hipGetLastError());
         stage_done("region growth");
     }
@@ -677,12 +539,7 @@ static int assign_neargrid_fused(xb_ctx *c, int64_t *n_maxima) {
         }
         {   // pass B: records for the bricks of the walk list only
             ScopedTimer t7(c, 7);
-            const int small = (g.nx < 16 || g.ny < 16 || g.nz < 80);
-            GridS gs;
-            if (sym_grid(g, gs))
-                k_brick_records<GridS><<<4096, TPB, 0, c->stream>>>(gs, c->rho, c->grad, walk, fs + FS_N_WALK, nbr, nb1, nb2, c->brick_rec, small);
-            else
-                k_brick_records<Grid><<<4096, TPB, 0, c->stream>>>(g, c->rho, c->grad, walk, fs + FS_N_WALK, nbr, nb1, nb2, c->brick_rec, small);
+            launch_brick_records(c, walk, fs + FS_N_WALK, nbr, nb1, nb2);
         }
         stage_done("walk list + records");
         if (c->has_vacuum)
@@ -694,25 +551,10 @@ static int assign_neargrid_fused(xb_ctx *c, int64_t *n_maxima) {
         }
         {
             ScopedTimer t6(c, 6);
-            const int maxsteps = 8 * (g.nx + g.ny + g.nz) + 64;
-            // the lean walker needs 24-bit index products and nothing else the fused path does not already guarantee (whole-grid
-            // table window, brick-label regions); 32-bit table offsets up to 2^27 voxels
-            const int lean = (gl.use24 && c->opt_lean) ? (c->N <= (1LL << 27) ? 2 : 1) : 0;
-#define XB_TRACE_ARGS gl, c->grad, box_max, c->blab, nb1, nb2, walk, fs, c->labels, c->first, c->max_list, c->max_cap, c->ovf_list, c->ovf_cap, \
-                      maxsteps, c->has_vacuum ? 1 : 0
-            // persistent workgroups of XB_TRACE_WAVES waves, one brick per pull (per-XCD cursors over the Morton-ordered walk list)
-            const int groups = std::max(1, c->trace_waves / XB_TRACE_WAVES);
-            if (lean) {   // the lean walker, the own brick's records in LDS
-                // (without vacuum the walkers also leave, per brick, whether all its voxels ended on one maximum: bres)
-                if (!c->has_vacuum) bres = c->list + 6 * nbr;
-                if (part) {
-                    if (lean == 2) k_ng_trace_g<2, 4, false, true><<<groups, XB_WAVE * XB_TRACE_WAVES, 0, c->stream>>>(XB_TRACE_ARGS, 8, 1, bres);
-                    else k_ng_trace_g<2, 3, false, true><<<groups, XB_WAVE * XB_TRACE_WAVES, 0, c->stream>>>(XB_TRACE_ARGS, 8, 1, bres);
-                } else if (lean == 2) k_ng_trace_g<2, 4><<<groups, XB_WAVE * XB_TRACE_WAVES, 0, c->stream>>>(XB_TRACE_ARGS, 8, 1, bres);
-                else k_ng_trace_g<2, 3><<<groups, XB_WAVE * XB_TRACE_WAVES, 0, c->stream>>>(XB_TRACE_ARGS, 8, 1, bres);
-            } else   // the generic walker (option 14 = 0: the tests' cross-check; planes or rows beyond 2^24 voxels); it tests every start voxel
-                k_ng_trace_g<2, 0><<<groups, XB_WAVE * XB_TRACE_WAVES, 0, c->stream>>>(XB_TRACE_ARGS, 8, 1);
-#undef XB_TRACE_ARGS
+            // (the lean walker needs nothing else the fused path does not already guarantee: whole-grid table window,
+            // brick-label regions; without vacuum its walkers also leave bres)
+            int *bres_buf = c->has_vacuum ? nullptr : c->list + 6 * nbr;
+            if (launch_persistent_trace(c, true, part, box_max, walk, c->has_vacuum ? 1 : 0, bres_buf)) bres = bres_buf;
         }
         HIPCHK(hipGetLastError());
         stage_done("trace");
@@ -763,16 +605,7 @@ static int assign_neargrid_tail(xb_ctx *c, int64_t *n_maxima) {
     int nmax = h[FS_N_MAX];
     if (nmax > c->max_cap) return fail(XB_E_LIMIT, "%d maxima exceed the table capacity %d", nmax, c->max_cap);
     c->stat_ovf_assign += novf;
-    if (h[FS_SORT_OK] && novf == 0) {
-        c->maxima_sorted.assign(h + FS_TOTAL, h + FS_TOTAL + nmax);
-        c->label_wire = label_wire_for(nmax);
-        c->regions_pending = false;
-        c->buni_valid = !c->has_vacuum;   // k_buni_after_relabel + k_label_uniform_list ran
-        c->regions_labels = !c->has_vacuum;
-        c->first_clean = true;
-        if (n_maxima) *n_maxima = nmax;
-        return XB_OK;
-    }
+    const int *sorted = h[FS_SORT_OK] && novf == 0 ? h + FS_TOTAL : nullptr;
     // rare: trajectories for the exact slow kernel and/or more maxima than the device sort takes
     if (novf > 0) {
         g.main_ties = 1;
@@ -782,7 +615,7 @@ static int assign_neargrid_tail(xb_ctx *c, int64_t *n_maxima) {
         // (216 atoms at 512^3: 19 K walkers listed; a window of eight left 11 for the slow kernel -- 0.35 ms of serial path scans per step --, 32 leave none).  What it cannot decide either goes on to the
         // slow kernel's tiers.  The second list lives in `stage` (free during an assignment).
         const GridL glt = light(g);
-        const int maxsteps = 8 * (g.nx + g.ny + g.nz) + 64;
+        const int maxsteps = trace_maxsteps(g);
         int *list2 = (int *)c->stage;
         const int cap2 = (int)std::min<size_t>(c->stage_bytes / sizeof(int), 0x7fffffffu);
         auto two_tiers = [&](int n_listed) -> int {
@@ -827,26 +660,16 @@ static int assign_neargrid_tail(xb_ctx *c, int64_t *n_maxima) {
         HIPCHK(hipStreamSynchronize(c->stream));
         nmax = h[FS_N_MAX];
         if (nmax > c->max_cap) return fail(XB_E_LIMIT, "%d maxima exceed the table capacity %d", nmax, c->max_cap);
-        if (h[FS_SORT_OK]) {
-            c->maxima_sorted.assign(h + FS_TOTAL, h + FS_TOTAL + nmax);
-            c->label_wire = label_wire_for(nmax);
-            c->regions_pending = false;
-            c->buni_valid = !c->has_vacuum;
-            c->regions_labels = !c->has_vacuum;
-            c->first_clean = true;
-            if (n_maxima) *n_maxima = nmax;
-            return XB_OK;
-        }
+        if (h[FS_SORT_OK]) sorted = h + FS_TOTAL;
     }
     // more maxima than the LDS sort takes (and every walker in): the bitmap numbering, on the device as well (round 6; the host
     // used to fetch the table, sort it and send the ranks back: 15 of the 66 ms of a noisy vacuum's step)
-    if (int rc = number_maxima_big(c, nmax)) return rc;
-    c->label_wire = label_wire_for(nmax);
-    c->regions_pending = false;
-    c->buni_valid = !c->has_vacuum;
+    if (!sorted) {
+        if (int rc = number_maxima_big(c, nmax)) return rc;
+    }
+    numbering_done(c, sorted, nmax, n_maxima);
+    c->buni_valid = !c->has_vacuum;   // k_buni_after_relabel + k_label_uniform_list ran
     c->regions_labels = !c->has_vacuum;
-    c->first_clean = true;
-    if (n_maxima) *n_maxima = nmax;
     return XB_OK;
 }
 
@@ -861,10 +684,7 @@ static bool assign_neargrid_complete(xb_ctx *c, int64_t *n_maxima) {
     c->n_boxes = h[FS_N_BOXES];
     c->box_voxels = (long long)h[FS_N_CERTAIN] * BRK * BRK * BRK;
     c->n_walk = h[FS_N_WALK];
-    c->maxima_sorted.assign(h + FS_TOTAL, h + FS_TOTAL + nmax);
-    c->label_wire = label_wire_for(nmax);
-    c->first_clean = true;
-    if (n_maxima) *n_maxima = nmax;
+    numbering_done(c, h + FS_TOTAL, nmax, n_maxima);
     return true;
 }
 
@@ -884,20 +704,12 @@ static int assign_ongrid_fused(xb_ctx *c, int64_t *n_maxima) {
     int *bmaxv = walk, *bpot = c->list + 5 * nbr;
     int *box_max = c->boxbuf + BB_REGMAX, *box_first = c->boxbuf + BB_REGFIRST;
     c->box_max_tab = box_max;
-    HIPCHK(hipMemsetAsync(fs, 0, FS_TOTAL * sizeof(int), c->stream));
-    if (!c->first_clean) {
-        k_fill<int><<<4096, TPB, 0, c->stream>>>(c->first, XB_INT_MAX, c->N);
-        HIPCHK(hipGetLastError());
-    }
-    c->first_clean = false;
-    c->regions_pending = false;
-    c->buni_valid = false; c->regions_labels = false;
-    c->list_valid = false; c->chg_n = -1;
+    if (int rc = begin_assignment(c, fs, FS_TOTAL, true)) return rc;
     c->zero_outside[0] = -1;
     const GridL gl = light(g);
     {
         ScopedTimer t(c, 1);
-        const int small = (g.nx < 16 || g.ny < 16 || g.nz < 80);
+        const int small = small_grid(g);
         dim3 grid((g.nz + GT_Z - 1) / GT_Z, (g.ny + GT_Y - 1) / GT_Y, (g.nx + GT_X - 1) / GT_X);
         GridS gs;
         if (sym_grid(g, gs)) {
@@ -910,15 +722,7 @@ static int assign_ongrid_fused(xb_ctx *c, int64_t *n_maxima) {
     }
     {
         ScopedTimer t4(c, 4);
-        k_seed_bricks<<<(nbr + 255) / 256, 256, 0, c->stream>>>(nbr, bmask, bmaxv, fs, seed, buf0, box_max, box_first);
-        k_grow_parent<<<(nbr + TPB - 1) / TPB, TPB, 0, c->stream>>>(nb0, nb1, nb2, bmask, bpot, seed, buf1);
-        k_grow_chase<<<(nbr + TPB - 1) / TPB, TPB, 0, c->stream>>>(nbr, buf1, seed, buf0, 4 * (nb0 + nb1 + nb2) + 64, fs);
-        const int long_schedule = 2 * ((std::max(std::max(nb0, nb1), nb2) + BG - 1) / BG) + 12;
-        const int launches = std::min(long_schedule, c->grow_kill_launches);
-        const dim3 ggrid((nb2 + BG - 1) / BG, (nb1 + BG - 1) / BG, (nb0 + BG - 1) / BG);
-        for (int l = 0; l < launches; l++)
-            k_brick_grow_dev<<<ggrid, BG * BG * BG, 0, c->stream>>>(nb0, nb1, nb2, bmask, seed, buf0, buf1, fs, BG, 0);
-        k_grow_finish<<<64, TPB, 0, c->stream>>>(nbr, seed, buf0, buf1, fs, c->blab_buf, box_first, bmask, c->brick_rec, 0, launches < long_schedule ? 1 : 0);
+        launch_region_growth(c, nb0, nb1, nb2, bmask, bmaxv, bpot, seed, buf0, buf1, box_max, box_first, true);
         HIPCHK(hipGetLastError());
     }
     c->grad_valid = false;          // (brick_rec is rewritten: bit 1 = holds a maximum, no records)
@@ -927,6 +731,7 @@ static int assign_ongrid_fused(xb_ctx *c, int64_t *n_maxima) {
     c->blab = c->blab_buf;
     c->regions_neargrid = false;   // (closed under the pointer moves only: the refinement's retraces must not stop on them)
     c->walk = walk;
+    c->bres_last = nullptr;
     c->nbk[0] = nb0; c->nbk[1] = nb1; c->nbk[2] = nb2;
     {
         ScopedTimer t0(c, 0);
@@ -941,18 +746,7 @@ static int assign_ongrid_fused(xb_ctx *c, int64_t *n_maxima) {
                                                         1 << 22);
         HIPCHK(hipGetLastError());
     }
-    k_number_maxima<<<1, 1024, 0, c->stream>>>(fs, c->first, c->max_list, c->max_cap, c->max_aux, fs + FS_TOTAL);
-    int *buni = reinterpret_cast<int *>(c->st);
-    if (g.nz % 4 == 0)
-        k_relabel_regions_brick<4><<<dim3((g.nz / 4 + 63) / 64, nb1, (g.nx + 3) / 4), TPB, 0, c->stream>>>(gl, c->labels, c->first, c->blab, nb1, nb2,
-                                                                                                    box_max, fs, fs + FS_SORT_OK);
-    else
-        k_relabel_regions_brick<1><<<dim3((g.nz + 63) / 64, nb1, (g.nx + 3) / 4), TPB, 0, c->stream>>>(gl, c->labels, c->first, c->blab, nb1, nb2,
-                                                                                                 box_max, fs, fs + FS_SORT_OK);
-    k_buni_after_relabel<<<(nbr + 255) / 256, 256, 0, c->stream>>>(nbr, c->blab, box_max, c->first, buni, fs + FS_SORT_OK, nullptr, nullptr, nullptr);
-    k_label_uniform_list<<<2048, TPB, 0, c->stream>>>(gl, c->labels, nb1, nb2, walk, 0, fs + FS_N_WALK, fs + FS_SORT_OK, buni);
-    k_reset_first<<<8, 256, 0, c->stream>>>(c->first, c->max_aux, 0, fs + FS_N_MAX, fs + FS_SORT_OK);
-    HIPCHK(hipGetLastError());
+    if (int rc = fused_numbering_launch(c)) return rc;
     HIPCHK(hipMemcpyAsync(c->host_ints, fs, (FS_TOTAL + XB_SORT_MAX) * sizeof(int), hipMemcpyDeviceToHost, c->stream));   // state block + sorted maxima: one transfer
     HIPCHK(hipStreamSynchronize(c->stream));
     const int *h = c->host_ints;
@@ -967,17 +761,12 @@ static int assign_ongrid_fused(xb_ctx *c, int64_t *n_maxima) {
     c->n_walk = h[FS_N_WALK];
     const int nmax = h[FS_N_MAX];
     if (nmax > c->max_cap) return fail(XB_E_LIMIT, "%d maxima exceed the table capacity %d", nmax, c->max_cap);
-    if (h[FS_SORT_OK]) c->maxima_sorted.assign(h + FS_TOTAL, h + FS_TOTAL + nmax);
-    else {   // more maxima than the LDS sort takes: the bitmap numbering + the same relabel launches (round 6)
-        c->bres_last = nullptr;
-        c->regions_pending = true;
+    const int *sorted = h[FS_SORT_OK] ? h + FS_TOTAL : nullptr;
+    if (!sorted) {   // more maxima than the LDS sort takes: the bitmap numbering + the same relabel launches (round 6)
         if (int rc = number_maxima_big(c, nmax)) return rc;
     }
-    c->label_wire = label_wire_for(nmax);
-    c->regions_pending = false;
+    numbering_done(c, sorted, nmax, n_maxima);
     c->buni_valid = true;
-    c->first_clean = true;
-    if (n_maxima) *n_maxima = nmax;
     return XB_OK;
 }
 

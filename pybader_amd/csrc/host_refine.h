@@ -24,7 +24,7 @@ static int edge_find_launch(xb_ctx *c, bool *dilate_owned) {
     {
         ScopedTimer t(c, 2);
         const GridL gl = light(g);
-        const int small = (g.nx < 16 || g.ny < 16 || g.nz < 80);
+        const int small = small_grid(g);
         int *buni = nullptr;
         // per-brick label uniformity first: grids of whole bricks (slabs), any grid of at least 16 voxels per axis on one slab
         // (the brick lattice is ceil(n / 8); a brick the grid cuts counts its voxels inside the grid)
@@ -266,7 +266,6 @@ static int refine_trace_impl(xb_ctx *c, int flag, int64_t *changed, int64_t *esc
     HIPCHK(hipMemsetAsync(c->counters, 0, 4 * sizeof(int), c->stream));
     int n_changed = 0, n_escaped = 0;
     if (n) {
-        const int maxsteps = 8 * (g.nx + g.ny + g.nz) + 64;
         Walker *wio_out = nullptr;
         int wio_cap = 0;
         if (int rc = ensure_grad(c, false, false, false)) return rc;
@@ -274,10 +273,7 @@ static int refine_trace_impl(xb_ctx *c, int flag, int64_t *changed, int64_t *esc
             ScopedTimer t(c, 3);
             const unsigned char *brec = c->grad_cover == 1 ? c->brick_rec : nullptr;
             const int regions_ok = brec && c->regions_labels && !c->has_vacuum ? 1 : 0;
-            // slabs: the regions' brick labels stop a retrace when the labels are this assignment's, there is no vacuum and
-            // the density has no tie voxel (the windowed masks are built under the assignment's tie rule only)
-            const int *slab_regions = (table_windowed(c) && c->blab && c->regions_labels && !c->has_vacuum && (c->grad_rule == 2 || c->slab_sparse) &&
-                                       g.nx % 8 == 0 && g.ny % 8 == 0 && g.nz % 8 == 0) ? c->blab : nullptr;
+            const int *slab_regions = slab_regions_of(c);
             // the lean kernel; the retraces whose walk goes on through a voxel without a record (a brick without records,
             // a voxel outside the table window of a slab) or out of the valid planes of a slab are redone by the from-rho
             // kernel (their count stays on the device: its grid strides over it).  On a slab that kernel parks the
@@ -295,15 +291,11 @@ static int refine_trace_impl(xb_ctx *c, int flag, int64_t *changed, int64_t *esc
                 }
             }
             HIPCHK(hipMemsetAsync(c->counters + 15, 0, sizeof(int), c->stream));
-            k_refine_trace<2, false><<<nblocks(n), TPB, 0, c->stream>>>(light(g), c->grad, c->labels, c->known, c->list, n, nullptr,
-                                                                        c->counters + 2, c->counters + 3, c->ovf_list, c->counters + 1,
-                                                                        c->ovf_cap, maxsteps, c->rho, c->dist_dev, brec, defer,
-                                                                        c->counters + 15, regions_ok, slab_regions, WalkerIO{});
+            launch_refine_trace<2, false>(c, nblocks(n), TPB, c->list, n, nullptr, c->counters + 2, c->counters + 3, c->ovf_list,
+                                          c->counters + 1, c->ovf_cap, brec, defer, c->counters + 15, regions_ok, slab_regions, WalkerIO{});
             if (brec || slab || table_windowed(c))
-                k_refine_trace<2, true><<<512, TPB, 0, c->stream>>>(light(g), c->grad, c->labels, c->known, defer, 0, c->counters + 15,
-                                                                    c->counters + 2, c->counters + 3, c->ovf_list, c->counters + 1,
-                                                                    c->ovf_cap, maxsteps, c->rho, c->dist_dev, brec, nullptr, nullptr, 0,
-                                                                    slab_regions, wio);
+                launch_refine_trace<2, true>(c, 512, TPB, defer, 0, c->counters + 15, c->counters + 2, c->counters + 3, c->ovf_list,
+                                             c->counters + 1, c->ovf_cap, brec, nullptr, nullptr, 0, slab_regions, wio);
             wio_out = wio.out; wio_cap = wio.out_cap;
         }
         HIPCHK(hipGetLastError());
@@ -380,13 +372,8 @@ int xb_walkers_continue(xb_ctx *c, const int64_t *walkers, int64_t n) {
     wio.res = (int *)c->walk_res; wio.res_count = c->counters + 17;
     wio.own0 = g.x0; wio.own1 = g.x1;
     const unsigned char *brec = c->grad_cover == 1 ? c->brick_rec : nullptr;
-    const int *slab_regions = (table_windowed(c) && c->blab && c->regions_labels && !c->has_vacuum && (c->grad_rule == 2 || c->slab_sparse) &&
-                               g.nx % 8 == 0 && g.ny % 8 == 0 && g.nz % 8 == 0) ? c->blab : nullptr;
-    const int maxsteps = 8 * (g.nx + g.ny + g.nz) + 64;
-    k_refine_trace<2, true, true><<<nblocks((int)n), TPB, 0, c->stream>>>(light(g), c->grad, c->labels, c->known, nullptr, (int)n, nullptr,
-                                                                         c->counters + 2, c->counters + 3, c->ovf_list, c->counters + 1,
-                                                                         c->ovf_cap, maxsteps, c->rho, c->dist_dev, brec, nullptr, nullptr, 0,
-                                                                         slab_regions, wio);
+    launch_refine_trace<2, true, true>(c, nblocks((int)n), TPB, nullptr, (int)n, nullptr, c->counters + 2, c->counters + 3, c->ovf_list,
+                                       c->counters + 1, c->ovf_cap, brec, nullptr, nullptr, 0, slab_regions_of(c), wio);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(c->host_ints, c->counters + 16, 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -689,7 +676,7 @@ static int refine_iteration_fused(xb_ctx *c, int64_t *edges, int64_t *changed, b
     c->chg_n = -1;
     {
         ScopedTimer t(c, 2);
-        const int small = (g.nx < 16 || g.ny < 16 || g.nz < 80);
+        const int small = small_grid(g);
         int *buni = nullptr;
         int ntiles_listed = 0;
         if (g.nx >= 16 && g.ny >= 16 && g.nz >= 16) {   // (any such grid: the brick lattice is ceil(n / 8))
@@ -726,16 +713,11 @@ static int refine_iteration_fused(xb_ctx *c, int64_t *edges, int64_t *changed, b
         if (int rc = need_grad(c)) return rc;
         ScopedTimer t(c, 4);
         const int nb0 = (g.nx + 7) / 8, nb1 = (g.ny + 7) / 8, nb2 = (g.nz + 7) / 8, nbr = nb0 * nb1 * nb2;
-        const int small = (g.nx < 16 || g.ny < 16 || g.nz < 80);
         unsigned char *band = reinterpret_cast<unsigned char *>(c->blab_buf);   // (the bricks' region labels have served: scratch)
         HIPCHK(hipMemsetAsync(band, 0, (size_t)nbr, c->stream));
         k_flag_band_bricks<<<4096, TPB, 0, c->stream>>>(gl, c->known, (const int *)c->stage, fs + FS_N_TILES, band);
         k_rec_set_bit0<<<(nbr + 255) / 256, 256, 0, c->stream>>>(nbr, c->brick_rec, band);
-        GridS gs;
-        if (sym_grid(g, gs))
-            k_brick_records<GridS><<<4096, TPB, 0, c->stream>>>(gs, c->rho, c->grad, nullptr, nullptr, nbr, nb1, nb2, c->brick_rec, small);
-        else
-            k_brick_records<Grid><<<4096, TPB, 0, c->stream>>>(g, c->rho, c->grad, nullptr, nullptr, nbr, nb1, nb2, c->brick_rec, small);
+        launch_brick_records(c, nullptr, nullptr, nbr, nb1, nb2);
         HIPCHK(hipGetLastError());
         c->grad_valid = true;
         c->grad_cover = 1;
@@ -744,7 +726,6 @@ static int refine_iteration_fused(xb_ctx *c, int64_t *edges, int64_t *changed, b
         c->blab = nullptr;
         c->table_stage = 0;
     }
-    const int maxsteps = 8 * (g.nx + g.ny + g.nz) + 64;
     const unsigned char *brec = c->grad_cover == 1 ? c->brick_rec : nullptr;
     const int regions_ok = c->grad_cover == 1 && c->regions_labels && !c->has_vacuum ? 1 : 0;
     {
@@ -752,15 +733,13 @@ static int refine_iteration_fused(xb_ctx *c, int64_t *edges, int64_t *changed, b
         int *defer = (int *)c->stage;
         WalkerIO wl{};   // (no walkers on one GPU)
         constexpr int XB_RT_BLOCK = 128;   // (threads per workgroup of the retrace kernel: 64 / 128 / 256 measured 0.512 / 0.495 / 0.514 ms on the whole list)
-        k_refine_trace<2, false><<<(unsigned)((c->N / 16 + XB_RT_BLOCK - 1) / XB_RT_BLOCK), XB_RT_BLOCK, 0, c->stream>>>(gl, c->grad, c->labels, c->known, c->list, 0, fs + FS_N_EDGES,
-                                                              fs + FS_CHANGED, fs + FS_ESCAPED, c->ovf_list, fs + FS_R_OVF,
-                                                              c->ovf_cap, maxsteps, c->rho, c->dist_dev, brec, defer, fs + FS_R_DEFER,
-                                                              regions_ok, nullptr, wl);
+        launch_refine_trace<2, false>(c, (unsigned)((c->N / 16 + XB_RT_BLOCK - 1) / XB_RT_BLOCK), XB_RT_BLOCK, c->list, 0, fs + FS_N_EDGES,
+                                      fs + FS_CHANGED, fs + FS_ESCAPED, c->ovf_list, fs + FS_R_OVF, c->ovf_cap, brec, defer, fs + FS_R_DEFER,
+                                      regions_ok, nullptr, wl);
         if (c->grad_cover == 1 && !regions_ok)   // the few retraces whose walk goes on through a brick without records (count on the
                                                   // device); with regions_ok a retrace stops on such a brick: nothing is deferred
-            k_refine_trace<2, true><<<512, TPB, 0, c->stream>>>(gl, c->grad, c->labels, c->known, (int *)c->stage, 0, fs + FS_R_DEFER,
-                                                               fs + FS_CHANGED, fs + FS_ESCAPED, c->ovf_list, fs + FS_R_OVF,
-                                                               c->ovf_cap, maxsteps, c->rho, c->dist_dev, c->brick_rec, nullptr, nullptr, 0, nullptr, wl);
+            launch_refine_trace<2, true>(c, 512, TPB, (int *)c->stage, 0, fs + FS_R_DEFER, fs + FS_CHANGED, fs + FS_ESCAPED, c->ovf_list,
+                                         fs + FS_R_OVF, c->ovf_cap, c->brick_rec, nullptr, nullptr, 0, nullptr, wl);
     }
     HIPCHK(hipGetLastError());
     int *hr = c->host_ints + 3000;   // (its own corner: an assignment's block may still wait to be read at the front, xb_assign_refine)
@@ -795,9 +774,8 @@ static int refine_iteration_fused(xb_ctx *c, int64_t *edges, int64_t *changed, b
         if (!can_defer && c->stage_bytes >= sizeof(int) * (size_t)novf) {
             int *list2 = (int *)c->stage;
             HIPCHK(hipMemsetAsync(c->counters + 1, 0, sizeof(int), c->stream));
-            k_refine_trace<XB_MID_K, false><<<nblocks(novf), TPB, 0, c->stream>>>(gl, c->grad, c->labels, c->known, c->ovf_list, novf, nullptr, fs + FS_CHANGED,
-                                                                          fs + FS_ESCAPED, list2, c->counters + 1, novf, maxsteps,
-                                                                          c->rho, c->dist_dev, brec, nullptr, nullptr, regions_ok, nullptr, WalkerIO{});
+            launch_refine_trace<XB_MID_K, false>(c, nblocks(novf), TPB, c->ovf_list, novf, nullptr, fs + FS_CHANGED, fs + FS_ESCAPED, list2,
+                                                 c->counters + 1, novf, brec, nullptr, nullptr, regions_ok, nullptr, WalkerIO{});
             HIPCHK(hipGetLastError());
             slow_list = list2;
             slow_n_dev = c->counters + 1;   // (the list's length stays on the device; novf bounds it)

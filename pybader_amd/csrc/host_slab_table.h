@@ -39,14 +39,7 @@ int xb_table_build(xb_ctx *c, int64_t *n_local_seeds) {
         {
             ScopedTimer t4(c, 4);
             ScopedTimer t5(c, 5);
-            const int small = (g.nx < 16 || g.ny < 16 || g.nz < 80);
-            dim3 grid((g.nz + GT_Z - 1) / GT_Z, (g.ny + GT_Y - 1) / GT_Y, (g.x1 - g.x0) / GT_X);
-            GridS gs;
-            int mirror = 0;
-            double mu_scale = 0.;
-            if (c->opt_mirror) mirror_prefilter(g, mirror, mu_scale);
-            if (sym_grid(g, gs)) k_brick_masks<GridS, 1, false><<<grid, TPB, 0, c->stream>>>(gs, c->rho, small, bmask, bmaxv, fs + FS_TIES, g.x0, mu_scale, mirror, nullptr);
-            else k_brick_masks<Grid, 1, false><<<grid, TPB, 0, c->stream>>>(g, c->rho, small, bmask, bmaxv, fs + FS_TIES, g.x0, 0., 0, nullptr);
+            launch_brick_masks(c, false, false, bmask, bmaxv, nullptr);
         }
         HIPCHK(hipGetLastError());
         int ties = 0;
@@ -102,7 +95,6 @@ int xb_table_finish(xb_ctx *c, const int64_t *seeds, int64_t n_seeds, int64_t an
         // every rank holds every brick's mask / maximum now: the same seeding + growth as on one GPU (replicated: the brick
         // arrays are tiny), then the 32-byte records for the uncertain bricks of THIS rank's window
         Grid &g = c->g;
-        const GridL gl = light(g);
         const int nb0 = g.nx / BRK, nb1 = g.ny / BRK, nb2 = g.nz / BRK, nbr = nb0 * nb1 * nb2;
         int *fs = c->fs;
         int *seed = c->list, *bmask = c->list + nbr, *buf0 = c->list + 2 * nbr, *buf1 = c->list + 3 * nbr, *bmaxv = c->list + 4 * nbr,
@@ -110,31 +102,14 @@ int xb_table_finish(xb_ctx *c, const int64_t *seeds, int64_t n_seeds, int64_t an
         int *box_max = c->boxbuf + BB_REGMAX, *box_first = c->boxbuf + BB_REGFIRST;
         c->box_max_tab = box_max;
         ScopedTimer t4(c, 4);
-        k_seed_bricks<<<(nbr + 255) / 256, 256, 0, c->stream>>>(nbr, bmask, bmaxv, fs, seed, buf0, box_max, box_first);
-        k_seed_finish<<<1, 1, 0, c->stream>>>(fs);
-        const int launches = 2 * ((std::max(std::max(nb0, nb1), nb2) + BG - 1) / BG) + 12;
-        const dim3 ggrid((nb2 + BG - 1) / BG, (nb1 + BG - 1) / BG, (nb0 + BG - 1) / BG);
-        for (int l = 0; l < launches; l++)
-            k_brick_grow_dev<<<ggrid, BG * BG * BG, 0, c->stream>>>(nb0, nb1, nb2, bmask, seed, buf0, buf1, fs, BG, 0);
-        k_grow_finish<<<64, TPB, 0, c->stream>>>(nbr, seed, buf0, buf1, fs, c->blab_buf, box_first, bmask, c->brick_rec, 0, 0);
+        launch_region_growth(c, nb0, nb1, nb2, bmask, bmaxv, nullptr, seed, buf0, buf1, box_max, box_first, false);
         c->blab = c->blab_buf;
         c->nbk[0] = nb0; c->nbk[1] = nb1; c->nbk[2] = nb2;
-        // the bricks of the window (it may wrap round the grid) that lie outside the regions get their records
-        const int per_plane = nb1 * nb2, w0 = g.wx0 / BRK, wn = g.wlen / BRK;
-        const int run1 = std::min(wn, nb0 - w0);
-        k_brick_walk_list<<<(nbr + 16 * TPB - 1) / (16 * TPB), TPB, 0, c->stream>>>(nbr, w0 * per_plane, (w0 + run1) * per_plane, c->blab, reclist,
-                                                                                   fs + FS_N_WALK);
-        if (wn > run1)
-            k_brick_walk_list<<<(nbr + 16 * TPB - 1) / (16 * TPB), TPB, 0, c->stream>>>(nbr, 0, (wn - run1) * per_plane, c->blab, reclist, fs + FS_N_WALK);
+        launch_window_bricks(c, reclist, fs + FS_N_WALK, nullptr);
         {
             ScopedTimer t7(c, 7);
-            const int small = (g.nx < 16 || g.ny < 16 || g.nz < 80);
             g.main_ties = 1;
-            GridS gs;
-            if (sym_grid(g, gs))
-                k_brick_records<GridS><<<4096, TPB, 0, c->stream>>>(gs, c->rho, c->grad, reclist, fs + FS_N_WALK, nbr, nb1, nb2, c->brick_rec, small);
-            else
-                k_brick_records<Grid><<<4096, TPB, 0, c->stream>>>(g, c->rho, c->grad, reclist, fs + FS_N_WALK, nbr, nb1, nb2, c->brick_rec, small);
+            launch_brick_records(c, reclist, fs + FS_N_WALK, nbr, nb1, nb2);
         }
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(c->host_ints, fs, FS_COUNT * sizeof(int), hipMemcpyDeviceToHost, c->stream));
@@ -142,7 +117,6 @@ int xb_table_finish(xb_ctx *c, const int64_t *seeds, int64_t n_seeds, int64_t an
         c->n_boxes = c->host_ints[FS_N_BOXES];
         c->box_voxels = (long long)c->host_ints[FS_N_CERTAIN] * BRK * BRK * BRK;
         if (!c->host_ints[FS_GROW_CONVERGED] || c->n_boxes == 0) c->blab = nullptr;   // no regions: plain tracing of the slab
-        (void)gl;
         c->table_stage = 2;
         c->table_prebuilt = true;
         return XB_OK;

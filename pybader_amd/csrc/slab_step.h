@@ -211,17 +211,7 @@ int xb_slab_assign_masks(xb_ctx *c, int rank, int nranks) {
     {
         ScopedTimer t4(c, 4);
         ScopedTimer t5(c, 5);
-        const int small = (g.nx < 16 || g.ny < 16 || g.nz < 80);
-        dim3 grid((g.nz + GT_Z - 1) / GT_Z, (g.ny + GT_Y - 1) / GT_Y, (g.x1 - g.x0) / GT_X);
-        GridS gs;
-        int mirror = 0;
-        double mu_scale = 0.;
-        const bool sym = sym_grid(g, gs);
-        if (sym && c->opt_mirror) mirror_prefilter(g, mirror, mu_scale);
-        const bool diag = c->opt_mask_diag && g.T[1] == 0. && g.T[2] == 0. && g.T[3] == 0. && g.T[5] == 0. && g.T[6] == 0. && g.T[7] == 0.;
-        if (sym && diag) k_brick_masks<GridS, 1, true><<<grid, TPB, 0, c->stream>>>(gs, c->rho, small, bmask, bmaxv, fs + FS_TIES, g.x0, mu_scale, mirror, bpot);
-        else if (sym) k_brick_masks<GridS, 1, false><<<grid, TPB, 0, c->stream>>>(gs, c->rho, small, bmask, bmaxv, fs + FS_TIES, g.x0, mu_scale, mirror, bpot);
-        else k_brick_masks<Grid, 1, false><<<grid, TPB, 0, c->stream>>>(g, c->rho, small, bmask, bmaxv, fs + FS_TIES, g.x0, 0., 0, bpot);
+        launch_brick_masks(c, false, true, bmask, bmaxv, bpot);
         k_slab_flag<<<1, 1, 0, c->stream>>>(fs, slab_flags(c), rank);
     }
     HIPCHK(hipGetLastError());
@@ -318,32 +308,12 @@ int xb_slab_assign_trace(xb_ctx *c) {
     int *box_max = c->boxbuf + BB_REGMAX, *box_first = c->boxbuf + BB_REGFIRST;
     c->box_max_tab = box_max;
     c->labels_zero_pending = false;   // every owned label is written, none is read (no vacuum; the halo planes are the peers')
-    HIPCHK(hipMemsetAsync(c->counters, 0, 16 * sizeof(int), c->stream));
-    if (!c->first_clean) {  // a previous assignment did not finish: `first` may hold stale minima
-        k_fill<int><<<4096, TPB, 0, c->stream>>>(c->first, XB_INT_MAX, c->N);
-        HIPCHK(hipGetLastError());
-    }
-    c->first_clean = false;
-    c->regions_pending = false;
-    c->buni_valid = false; c->regions_labels = false;
-    c->list_valid = false; c->chg_n = -1;
-    const bool chase = true;   // provisional labels by one chase along the brick potentials
+    if (int rc = begin_assignment(c, c->counters, 16, true)) return rc;
     {
         ScopedTimer t4(c, 4);
         k_slab_any_flag<<<1, 1, 0, c->stream>>>(slab_flags(c), c->slab_nranks, fs);
         // every rank holds every brick's mask / maximum / potential now: the same seeding + growth as on one GPU (replicated)
-        k_seed_bricks<<<(nbr + 255) / 256, 256, 0, c->stream>>>(nbr, bmask, bmaxv, fs, seed, buf0, box_max, box_first);
-        if (chase) {
-            k_grow_parent<<<(nbr + TPB - 1) / TPB, TPB, 0, c->stream>>>(nb0, nb1, nb2, bmask, bpot, seed, buf1);
-            k_grow_chase<<<(nbr + TPB - 1) / TPB, TPB, 0, c->stream>>>(nbr, buf1, seed, buf0, 4 * (nb0 + nb1 + nb2) + 64, fs);
-        } else
-            k_seed_finish<<<1, 1, 0, c->stream>>>(fs);
-        const int long_schedule = 2 * ((std::max(std::max(nb0, nb1), nb2) + BG - 1) / BG) + 12;
-        const int launches = chase ? std::min(long_schedule, c->grow_kill_launches) : long_schedule;
-        const dim3 ggrid((nb2 + BG - 1) / BG, (nb1 + BG - 1) / BG, (nb0 + BG - 1) / BG);
-        for (int l = 0; l < launches; l++)
-            k_brick_grow_dev<<<ggrid, BG * BG * BG, 0, c->stream>>>(nb0, nb1, nb2, bmask, seed, buf0, buf1, fs, BG, 0);
-        k_grow_finish<<<64, TPB, 0, c->stream>>>(nbr, seed, buf0, buf1, fs, c->blab_buf, box_first, bmask, c->brick_rec, 0, chase && launches < long_schedule ? 1 : 0);
+        launch_region_growth(c, nb0, nb1, nb2, bmask, bmaxv, bpot, seed, buf0, buf1, box_max, box_first, true);
         HIPCHK(hipGetLastError());
     }
     c->blab = c->blab_buf;
@@ -351,49 +321,20 @@ int xb_slab_assign_trace(xb_ctx *c) {
     c->nbk[0] = nb0; c->nbk[1] = nb1; c->nbk[2] = nb2;
     {
         ScopedTimer t0(c, 0);
-        // the bricks of the table window (it may wrap round the grid) outside the regions get their records; the owned ones
-        // among them are traced
-        const int per_plane = nb1 * nb2, w0 = g.wx0 / BRK, wn = g.wlen / BRK, run1 = std::min(wn, nb0 - w0);
-        const unsigned lgrid = (nbr + 16 * TPB - 1) / (16 * TPB);
-        k_brick_walk_list<<<lgrid, TPB, 0, c->stream>>>(nbr, w0 * per_plane, (w0 + run1) * per_plane, c->blab, reclist, fs + FS_N_RECL, fs + FS_GROW_RETRY);
-        if (wn > run1)
-            k_brick_walk_list<<<lgrid, TPB, 0, c->stream>>>(nbr, 0, (wn - run1) * per_plane, c->blab, reclist, fs + FS_N_RECL, fs + FS_GROW_RETRY);
-        k_brick_walk_list<<<lgrid, TPB, 0, c->stream>>>(nbr, (g.x0 / BRK) * per_plane, (g.x1 / BRK) * per_plane, c->blab, walk, fs + FS_N_WALK, fs + FS_GROW_RETRY);
+        // the window's bricks outside the regions get their records; the owned ones among them are traced
+        const int per_plane = nb1 * nb2;
+        launch_window_bricks(c, reclist, fs + FS_N_RECL, fs + FS_GROW_RETRY);
+        k_brick_walk_list<<<(nbr + 16 * TPB - 1) / (16 * TPB), TPB, 0, c->stream>>>(nbr, (g.x0 / BRK) * per_plane, (g.x1 / BRK) * per_plane, c->blab, walk, fs + FS_N_WALK, fs + FS_GROW_RETRY);
         {
             ScopedTimer t7(c, 7);
-            const int small = (g.nx < 16 || g.ny < 16 || g.nz < 80);
-            GridS gs;
-            if (sym_grid(g, gs))
-                k_brick_records<GridS><<<4096, TPB, 0, c->stream>>>(gs, c->rho, c->grad, reclist, fs + FS_N_RECL, nbr, nb1, nb2, c->brick_rec, small);
-            else
-                k_brick_records<Grid><<<4096, TPB, 0, c->stream>>>(g, c->rho, c->grad, reclist, fs + FS_N_RECL, nbr, nb1, nb2, c->brick_rec, small);
+            launch_brick_records(c, reclist, fs + FS_N_RECL, nbr, nb1, nb2);
         }
         k_note_certain_bricks<<<(nbr + 255) / 256, 256, 0, c->stream>>>(gl, nb0, nb1, nb2, (g.x0 / BRK) * per_plane, (g.x1 / BRK) * per_plane, c->blab,
                                                                       box_max, c->first, c->max_list, fs + FS_N_MAX, c->max_cap, fs + FS_GROW_RETRY);
         c->regions_pending = true;
         {
-            // the persistent trace (per-XCD cursors over the list, its length on the device).  A trajectory that leaves the
-            // table window lands on a list (in `stage`) and is redone by the kernel that derives missing records from rho.
             ScopedTimer tw(c, 6);
-            const int maxsteps = 8 * (g.nx + g.ny + g.nz) + 64;
-            int *redo = (int *)c->stage;
-            const int redo_cap = (int)std::min<size_t>(c->stage_bytes / sizeof(int), 0x7fffffffu);
-            // (the lean walker in workgroups of eight waves, one brick per pull, its records through LDS -- as on one GPU --
-            // when the index products fit 24 bits; 32-bit table offsets up to 2^27 window voxels)
-            const bool lean = gl.use24 && c->opt_lean;
-            const int groups = std::max(1, c->trace_waves / XB_TRACE_WAVES);
-            if (lean && (long long)g.wlen * g.nyz <= (1LL << 27))
-                k_ng_trace_g<2, 4, true><<<groups, XB_WAVE * XB_TRACE_WAVES, 0, c->stream>>>(gl, c->grad, box_max, c->blab, nb1, nb2, walk, fs, c->labels, c->first,
-                                                                               c->max_list, c->max_cap, redo, redo_cap, maxsteps, 0, 8, 1);
-            else if (lean)
-                k_ng_trace_g<2, 3, true><<<groups, XB_WAVE * XB_TRACE_WAVES, 0, c->stream>>>(gl, c->grad, box_max, c->blab, nb1, nb2, walk, fs, c->labels, c->first,
-                                                                               c->max_list, c->max_cap, redo, redo_cap, maxsteps, 0, 8, 1);
-            else
-                k_ng_trace_g<2, 0><<<groups, XB_WAVE * XB_TRACE_WAVES, 0, c->stream>>>(gl, c->grad, box_max, c->blab, nb1, nb2, walk, fs, c->labels, c->first,
-                                                                         c->max_list, c->max_cap, redo, redo_cap, maxsteps, 0, 8, 1);
-            k_ng_trace_list<2><<<512, TPB, 0, c->stream>>>(gl, c->grad, box_max, c->blab, nb1, nb2, redo, fs + FS_N_OVF, c->labels, c->first, c->max_list,
-                                                          fs + FS_N_MAX, c->max_cap, c->ovf_list, c->counters + 1, c->ovf_cap, maxsteps, c->rho,
-                                                          c->dist_dev, 0);
+            launch_persistent_trace(c, true, false, box_max, walk, 0, nullptr);
         }
         k_slab_pack_table<<<1, 256, 0, c->stream>>>(slab_tables(c) + (size_t)c->slab_rank * XB_TAB_INTS, c->max_list, c->first, fs, c->counters + 1);
     }
@@ -410,23 +351,12 @@ int xb_slab_assign_finish(xb_ctx *c, int64_t *n_maxima, int64_t *status) {
     NEED_GRID_RAW("xb_slab_assign_finish");
     if (c->slab_stage != 2) return fail(XB_E_STATE, "xb_slab_assign_finish: call xb_slab_assign_trace first");
     c->slab_stage = 0;
-    Grid &g = c->g;
-    const GridL gl = light(g);
-    const int nb1 = g.ny / BRK, nb2 = g.nz / BRK, nbr = (g.nx / BRK) * nb1 * nb2;
-    int *fs = c->fs, *walk = c->list + 4 * nbr, *box_max = c->boxbuf + BB_REGMAX;
-    int *buni = reinterpret_cast<int *>(c->st);
+    int *fs = c->fs;
     const int *tabs = slab_tables(c);
     k_slab_merge_min<<<c->slab_nranks, 256, 0, c->stream>>>(tabs, c->first);
     k_slab_merge_list<<<1, 1024, 0, c->stream>>>(tabs, c->slab_nranks, c->max_list, c->max_cap, fs);
     k_number_maxima<<<1, 1024, 0, c->stream>>>(fs, c->first, c->max_list, c->max_cap, c->max_aux);
-    k_relabel_regions_brick<4><<<dim3((g.nz / 4 + 63) / 64, nb1, (g.x1 - g.x0 + 3) / 4), TPB, 0, c->stream>>>(gl, c->labels, c->first, c->blab, nb1, nb2, box_max,
-                                                                                                          fs, fs + FS_SORT_OK);
-    // per-brick uniformity for the edge sweep: the regions' bricks are uniform on every rank, the owned walk-list bricks are
-    // scanned, every other brick counts as mixed -- right whatever the peers' halo planes bring
-    k_fill<int><<<(nbr + 4 * TPB - 1) / (4 * TPB), TPB, 0, c->stream>>>(buni, XB_MIXED, nbr);
-    k_buni_after_relabel<<<(nbr + 255) / 256, 256, 0, c->stream>>>(nbr, c->blab, box_max, c->first, buni, fs + FS_SORT_OK, nullptr, nullptr, nullptr);
-    k_label_uniform_list<<<2048, TPB, 0, c->stream>>>(gl, c->labels, nb1, nb2, walk, 0, fs + FS_N_WALK, fs + FS_SORT_OK, buni);
-    k_reset_first<<<8, 256, 0, c->stream>>>(c->first, c->max_aux, 0, fs + FS_N_MAX, fs + FS_SORT_OK);
+    launch_relabel(c, fs, 0, true, c->boxbuf + BB_REGMAX, BUNI_MIXED, nullptr);
     HIPCHK(hipGetLastError());
     // the ONE host wait of the assignment: state block + the sorted maxima
     HIPCHK(hipMemcpyAsync(c->host_ints, fs, FS_COUNT * sizeof(int), hipMemcpyDeviceToHost, c->stream));
@@ -455,15 +385,11 @@ int xb_slab_assign_finish(xb_ctx *c, int64_t *n_maxima, int64_t *status) {
     if (c->opt_dbg & 16)
         fprintf(stderr, "[slab %d] bricks traced %d, with records %d, trajectories redone beyond the table window %d, regions %d\n", c->slab_rank,
                 h[FS_N_WALK], h[FS_N_RECL], h[FS_N_REDO], h[FS_N_BOXES]);
-    const int nmax = h[FS_N_MAX];
-    c->maxima_sorted.assign(h + FS_COUNT, h + FS_COUNT + nmax);
-    c->label_wire = label_wire_for(nmax);
+    numbering_done(c, h + FS_COUNT, h[FS_N_MAX], n_maxima);
     c->buni_valid = true;
     c->buni_halo_safe = true;
     c->regions_labels = true;
-    c->first_clean = true;
     c->table_stage = 2;
-    if (n_maxima) *n_maxima = nmax;
     if (status) *status = 0;
     return XB_OK;
 }
@@ -493,11 +419,9 @@ int xb_slab_refine_pass(xb_ctx *c) {
     HIPCHK(hipMemsetAsync(c->counters + 6, 0, 18 * sizeof(int), c->stream));      // ... deferred [15], walker statistics [18..22) (the sweep's own counts [6], [22], [23] are spent)
     {
         ScopedTimer t(c, 3);
-        const int maxsteps = 8 * (g.nx + g.ny + g.nz) + 64;
         const unsigned char *brec = c->grad_cover == 1 ? c->brick_rec : nullptr;
         const int regions_ok = brec && c->regions_labels && !c->has_vacuum ? 1 : 0;
-        const int *slab_regions = (table_windowed(c) && c->blab && c->regions_labels && !c->has_vacuum && (c->grad_rule == 2 || c->slab_sparse) &&
-                                   g.nx % 8 == 0 && g.ny % 8 == 0 && g.nz % 8 == 0) ? c->blab : nullptr;
+        const int *slab_regions = slab_regions_of(c);
         // the deferred retraces in `stage` (at most one per owned voxel); the walkers go straight to this rank's part of block 6
         int *defer = (int *)c->stage;
         char *part = (char *)c->wbuf[0] + (size_t)c->slab_rank * walk_part(c->wcap);
@@ -506,12 +430,10 @@ int xb_slab_refine_pass(xb_ctx *c) {
         wio.out = (Walker *)(part + 16); wio.out_count = (int *)part;
         wio.out_cap = walk_send_of(c, c->wcap);
         const unsigned grid = (unsigned)std::min<long long>(nblocks((long long)(g.x1 - g.x0) * g.nyz / 16), 1 << 20);
-        k_refine_trace<2, false, false, true><<<grid, TPB, 0, c->stream>>>(gl, c->grad, c->labels, c->known, c->list, 0, c->counters + 5, c->counters + 2,
-                                                              c->counters + 3, c->ovf_list, c->counters + 1, c->ovf_cap, maxsteps, c->rho, c->dist_dev,
-                                                              brec, defer, c->counters + 15, regions_ok, slab_regions, wio);
-        k_refine_trace<2, true><<<512, TPB, 0, c->stream>>>(gl, c->grad, c->labels, c->known, defer, 0, c->counters + 15, c->counters + 2,
-                                                            c->counters + 3, c->ovf_list, c->counters + 1, c->ovf_cap, maxsteps, c->rho, c->dist_dev,
-                                                            brec, nullptr, nullptr, 0, slab_regions, wio);
+        launch_refine_trace<2, false, false, true>(c, grid, TPB, c->list, 0, c->counters + 5, c->counters + 2, c->counters + 3, c->ovf_list,
+                                                   c->counters + 1, c->ovf_cap, brec, defer, c->counters + 15, regions_ok, slab_regions, wio);
+        launch_refine_trace<2, true>(c, 512, TPB, defer, 0, c->counters + 15, c->counters + 2, c->counters + 3, c->ovf_list, c->counters + 1,
+                                     c->ovf_cap, brec, nullptr, nullptr, 0, slab_regions, wio);
     }
     k_slab_walk_clamp<<<1, 1, 0, c->stream>>>((int *)((char *)c->wbuf[0] + (size_t)c->slab_rank * walk_part(c->wcap)), c->counters + 20, walk_send_of(c, c->wcap),
                                               walk_results_of(c, c->wcap));
@@ -547,12 +469,8 @@ int xb_slab_walkers_round(xb_ctx *c, int src, int last) {
         wio.res = (int *)(part + 16 + (size_t)cap * sizeof(Walker)); wio.res_count = (int *)part + 1;
         wio.own0 = g.x0; wio.own1 = g.x1;
         const unsigned char *brec = c->grad_cover == 1 ? c->brick_rec : nullptr;
-        const int *slab_regions = (table_windowed(c) && c->blab && c->regions_labels && !c->has_vacuum && (c->grad_rule == 2 || c->slab_sparse) &&
-                                   g.nx % 8 == 0 && g.ny % 8 == 0 && g.nz % 8 == 0) ? c->blab : nullptr;
-        const int maxsteps = 8 * (g.nx + g.ny + g.nz) + 64;
-        k_refine_trace<2, true, true><<<std::min(cap / TPB, 512), TPB, 0, c->stream>>>(gl, c->grad, c->labels, c->known, nullptr, 0, n_in, c->counters + 2,
-                                                                              c->counters + 3, c->ovf_list, c->counters + 1, c->ovf_cap, maxsteps, c->rho,
-                                                                              c->dist_dev, brec, nullptr, nullptr, 0, slab_regions, wio);
+        launch_refine_trace<2, true, true>(c, std::min(cap / TPB, 512), TPB, nullptr, 0, n_in, c->counters + 2, c->counters + 3, c->ovf_list,
+                                           c->counters + 1, c->ovf_cap, brec, nullptr, nullptr, 0, slab_regions_of(c), wio);
         k_slab_walk_clamp<<<1, 1, 0, c->stream>>>((int *)part, c->counters + 20, walk_later_of(c, cap), walk_results_of(c, cap));
     } else {
         k_slab_pack_counts<<<1, 1, 0, c->stream>>>(slab_counts(c), c->counters, blk, c->slab_nranks, c->slab_rank, cap);
