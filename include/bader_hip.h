@@ -108,6 +108,40 @@ int xb_download_labels(xb_ctx *c, void *labels_host, int dtype);
 int xb_upload_known(xb_ctx *c, const int8_t *known_host);
 int xb_download_known(xb_ctx *c, int8_t *known_host);
 
+/* ---- arrays that already live on the device ---------------------------------------------------------------------------
+ * No counterpart in the reference (its arrays share one address space): the in-memory boundary for a caller whose density was
+ * produced on the GPU (a torch / CuPy tensor; pybader_amd/device.py reads __cuda_array_interface__).  The library keeps its own
+ * float64 C-order copy of the density, so every kernel's layout assumption and the parity guarantee hold.
+ *   xb_import_density   the device array at dev_ptr -- dtype XB_F32 / XB_F64, the grid's shape, `stride` in ELEMENTS (any int64: 0
+ *                       a broadcast axis, negative a flipped axis, dev_ptr then being the element [0][0][0]) -- becomes the
+ *                       resident density: np.ascontiguousarray(a).astype(np.float64), a move plus an exact widening (every
+ *                       finite value, +-inf and -0.0 bit for bit; a NaN stays a NaN).  Cached state as xb_upload_density.
+ *                       Contiguous float64 is one device-to-device copy, contiguous float32 a vectorised widening, a permuted
+ *                       layout (stride 1 on x or y) goes tile by tile through LDS, anything else is gathered voxel by voxel.
+ *   xb_import_labels    xb_upload_labels from a C-contiguous device array of XB_I8 / I16 / I32 / I64
+ *   xb_export_labels    xb_download_labels into one
+ *   xb_export_volume    utils.volume_mask (utils.py:461-476) into a C-contiguous device array: XB_F64 the bits of
+ *                       xb_volume_mask, XB_F32 that value rounded once
+ *   xb_device_alloc / xb_device_free   result arrays the library owns (the device side of xb_host_alloc / xb_host_free);
+ *                       xb_device_free waits for the device, so work still queued on the buffer ends first
+ *   xb_device_read      `bytes` of a device array to host memory (returns with the data there)
+ * CHECKS, all on the host before anything is queued, every failure XB_E_ARG: the pointer is device memory of the context's
+ * device, every element the shape and strides address lies inside the ONE allocation that holds the pointer, the dtype is one of
+ * those listed, the grid is set, and the array does not overlap the resident buffer it is copied from / into.  A wrong stride is
+ * an error code, never a memory fault; a refused call leaves the context as it was.
+ * ORDER: `stream` is the caller's hipStream_t (null: the legacy default stream).  The work starts after everything queued on
+ * `stream` so far and `stream` goes on after it (events in both directions): a source may be overwritten or freed, a destination
+ * read, on `stream` right after the call returns.  None of these calls adds a wait of the host (xb_import_labels keeps the
+ * one of xb_upload_labels, xb_device_read returns data). */
+enum { XB_F32 = 32, XB_F64 = 64 };
+int xb_import_density(xb_ctx *c, const void *dev_ptr, int dtype, const int64_t stride[3], void *stream);
+int xb_import_labels(xb_ctx *c, const void *dev_ptr, int dtype, void *stream);
+int xb_export_labels(xb_ctx *c, void *dev_ptr, int dtype, void *stream);
+int xb_export_volume(xb_ctx *c, int64_t vol_num, void *dev_ptr, int dtype, void *stream);
+int xb_device_alloc(int device, int64_t bytes, void **out);
+int xb_device_free(void *p);
+int xb_device_read(xb_ctx *c, void *dst_host, const void *dev_ptr, int64_t bytes, void *stream);
+
 /* ---- hot path, device resident ----------------------------------------------------------- */
 /* utils.vacuum_assign (utils.py:382-401) via Bader.volumes_init (interface.py:449-469):
  * labels := 0, then -1 where rho <= vac_tol (vac_tol NaN => no vacuum, the vacuum_tol=None case).
@@ -309,7 +343,7 @@ int xb_enable_timing(xb_ctx *c, int on);
  *   2   cross-check bits, each selecting the second implementation of one step so that a test can compare the two:
  *       1 no mirror prefilter in pass A, 2 the generic walker instead of the lean one, 4 the full T_grad . grad product on
  *       orthogonal lattices, 8 dilation from the edge list instead of tile by tile, 16 int32 label halos, 32 no front sharing
- *       in the edge_check chase;
+ *       in the edge_check chase, 64 xb_import_density gathers a permuted layout voxel by voxel instead of through the LDS tile;
  *   test plumbing -- 4 / 5 workgroups and LDS queue capacity of the edge_check chase (lowered to force the overflow
  *   hand-over), 17 kill launches scheduled after a chase (1 forces the repeat), 19 a rank may exchange planes with itself.
  * (Round 4 removed 0, 2, 9-12, 15, 21; round 6 removed 7, 8, 16, 22 -- routes and launch shapes nobody set -- and folded 13, 14,

@@ -37,6 +37,13 @@ SYMBOLS = {
     'xb_format_end': (_int, [_vp]),
     'xb_upload_labels': (_int, [_vp, _vp, _int]),
     'xb_download_labels': (_int, [_vp, _vp, _int]),
+    'xb_import_density': (_int, [_vp, _vp, _int, _pi64, _vp]),
+    'xb_import_labels': (_int, [_vp, _vp, _int, _vp]),
+    'xb_export_labels': (_int, [_vp, _vp, _int, _vp]),
+    'xb_export_volume': (_int, [_vp, _i64, _vp, _int, _vp]),
+    'xb_device_alloc': (_int, [_int, _i64, C.POINTER(_vp)]),
+    'xb_device_free': (_int, [_vp]),
+    'xb_device_read': (_int, [_vp, _vp, _vp, _i64, _vp]),
     'xb_upload_known': (_int, [_vp, _vp]),
     'xb_download_known': (_int, [_vp, _vp]),
     'xb_vacuum_assign': (_int, [_vp, _dbl, _dbl, _pdbl, _pdbl]),
@@ -322,6 +329,7 @@ class Context:
         h = C.c_void_p()
         check(self.lib.xb_create(int(device), C.byref(h)))
         self.h = h
+        self.device = int(device)
         self.shape = None
         # utils.resident(): identity of the host array the caller pinned / of the one whose content is on the device
         self.pinned_density = None
@@ -394,6 +402,64 @@ class Context:
             out = pinned_empty(self.shape, dtype) if pooled else np.empty(self.shape, dtype=dtype)
         assert out.flags.c_contiguous and out.shape == self.shape
         check(self.lib.xb_download_labels(self.h, _ptr(out), DTYPE_CODE[out.dtype]))
+        return out
+
+    # -- arrays that already live on the device (pybader_amd/device.py) ------------------------------
+    def _refuse_shape(self, what, shape):
+        err = BaderHipError(f'{what}: the device array has shape {tuple(shape)}, the grid {self.shape}')
+        err.code = XB_E_ARG
+        raise err
+
+    def import_density(self, obj):
+        """a float32 / float64 device array of any strides becomes the resident density (xb_import_density)"""
+        from . import device
+        d = device.describe(obj)
+        if d.shape != self.shape:
+            self._refuse_shape('import_density', d.shape)
+        if d.dtype not in device.FLOAT_CODE:
+            err = BaderHipError(f'import_density: dtype {d.dtype.name} is neither float32 nor float64')
+            err.code = XB_E_ARG
+            raise err
+        self.resident_density = None
+        st = (C.c_int64 * 3)(*d.strides)
+        check(self.lib.xb_import_density(self.h, C.c_void_p(d.ptr), device.FLOAT_CODE[d.dtype], st, device.stream_for(d)))
+
+    def _flat(self, what, obj, codes, writable):
+        from . import device
+        d = device.describe(obj, writable=writable)
+        if d.shape != self.shape:
+            self._refuse_shape(what, d.shape)
+        if d.dtype not in codes or not d.c_contiguous:
+            err = BaderHipError(f'{what}: a C-contiguous device array of {" / ".join(t.name for t in codes)} is required '
+                                f'(got {d.dtype.name}, element strides {d.strides})')
+            err.code = XB_E_ARG
+            raise err
+        return d, device.stream_for(d)
+
+    def import_labels(self, obj):
+        """a C-contiguous integer device array becomes the resident label map (xb_import_labels)"""
+        d, stream = self._flat('import_labels', obj, DTYPE_CODE, False)
+        self.drop_label_token()
+        check(self.lib.xb_import_labels(self.h, C.c_void_p(d.ptr), DTYPE_CODE[d.dtype], stream))
+
+    def export_labels(self, dtype=np.int32, out=None):
+        """the resident label map into `out` (a writable C-contiguous integer device array), else into a new
+        device.DeviceArray of `dtype`; returns it"""
+        from . import device
+        if out is None:
+            out = device.DeviceArray(self, self.shape, dtype)
+        d, stream = self._flat('export_labels', out, DTYPE_CODE, True)
+        check(self.lib.xb_export_labels(self.h, C.c_void_p(d.ptr), DTYPE_CODE[d.dtype], stream))
+        return out
+
+    def export_volume(self, vol_num, dtype=np.float64, out=None):
+        """utils.volume_mask on the device: the resident density where the label equals vol_num, zero elsewhere, into
+        `out` (writable, C-contiguous, float32 / float64) or a new device.DeviceArray of `dtype`; returns it"""
+        from . import device
+        if out is None:
+            out = device.DeviceArray(self, self.shape, dtype)
+        d, stream = self._flat('export_volume', out, device.FLOAT_CODE, True)
+        check(self.lib.xb_export_volume(self.h, int(vol_num), C.c_void_p(d.ptr), device.FLOAT_CODE[d.dtype], stream))
         return out
 
     def upload_known(self, known):

@@ -1,7 +1,7 @@
 // bader_hip.hip -- libbader_hip.so: HIP kernels + C ABI (include/bader_hip.h) for gfx950.  ONE translation unit:
-//   kernels    k_common.h k_masks.h k_fused.h k_trace.h k_ongrid.h k_edges.h k_sums.h k_text.h k_format.h (fmt_core.h)
+//   kernels    k_common.h k_masks.h k_fused.h k_trace.h k_ongrid.h k_edges.h k_sums.h k_text.h k_format.h (fmt_core.h) k_interop.h
 //   host side  this file (context struct, options, statistics, timing) + host_context.h (life cycle, transfers)
-//              + host_assign.h (the table outside an assignment, the assignments) + host_refine.h + host_sums.h + host_slab_table.h (host-driven slab calls) + comm.h (RCCL through the ABI)
+//              + host_assign.h (the table outside an assignment, the assignments) + host_refine.h + host_sums.h + host_slab_table.h (host-driven slab calls) + host_interop.h (device arrays in and out) + comm.h (RCCL through the ABI)
 //              + slab_step.h (the slab step with its control flow on the device)
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -shared (see pybader_amd/build.py).
 #include "bader_kernels.h"
@@ -33,6 +33,7 @@ static inline hipError_t xb_counted_sync(hipStream_t s) { xb_waits++; return (hi
 #include "k_sums.h"
 #include "k_text.h"
 #include "k_format.h"
+#include "k_interop.h"
 
 // =============================================================================================
 // host side
@@ -171,6 +172,8 @@ struct xb_ctx {
     int *host_ints = nullptr;  // pinned
     char *big_pin[2] = {nullptr, nullptr};   // two pinned chunks for the large transfers (staged_h2d / staged_d2h)
     hipEvent_t big_ev[2] = {nullptr, nullptr};
+    hipEvent_t io_ev = nullptr;   // orders the device-array entry points against the caller's stream (host_interop.h)
+    int opt_io_tiled = 1;      // xb_import_density: permuted layouts through the LDS tile (0: the plain strided gather; tests and the benchmark compare)
     char *pin = nullptr;       // pinned staging for the small host arrays a step uploads (pageable copies pin pages on the fly)
     size_t pin_bytes = 0;
     std::vector<int> maxima_sorted;  // global, label order
@@ -293,6 +296,7 @@ const char *xb_last_error(void) { return g_err.c_str(); }
 #include "host_refine.h"
 #include "host_sums.h"
 #include "host_slab_table.h"
+#include "host_interop.h"
 
 int xb_set_option(xb_ctx *c, int key, int value) {
     if (!c) return fail(XB_E_ARG, "null ctx");
@@ -304,6 +308,7 @@ int xb_set_option(xb_ctx *c, int key, int value) {
         c->opt_tile_dilate = !(value & 8);   // 8: the dilation of the edge sweep from the edge list instead of tile by tile
         c->opt_narrow_halo = !(value & 16);  // 16: label halos travel as int32
         c->opt_ec_share = !(value & 32);     // 32: every workgroup of the edge_check chase keeps what it wakes
+        c->opt_io_tiled = !(value & 64);     // 64: xb_import_density gathers a permuted layout voxel by voxel instead of tile by tile
     }
     else if (key == 3) c->opt_dbg = value;
     else if (key == 4 && value >= 1 && value <= 4096) c->opt_ec_groups = value;

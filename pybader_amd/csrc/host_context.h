@@ -58,6 +58,7 @@ void xb_destroy(xb_ctx *c) {
     hipHostFree(c->host_ints);
     hipHostFree(c->pin);
     for (int k = 0; k < 2; k++) { hipHostFree(c->big_pin[k]); if (c->big_ev[k]) hipEventDestroy(c->big_ev[k]); }
+    if (c->io_ev) hipEventDestroy(c->io_ev);
     hipStreamDestroy(c->stream);
     delete c;
 }

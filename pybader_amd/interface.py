@@ -8,6 +8,7 @@ numpy operations, in the same order, as the reference (they are inputs of every 
 bit-identical)."""
 import numpy as np
 
+from . import device
 from .thread_handlers import assign_to_atoms, bader_calc, bader_calc_refine, dtype_calc, refine, surface_distance
 from .utils import charge_sum, resident, vacuum_assign
 
@@ -86,12 +87,17 @@ class Bader:
         return np.abs(np.dot(self.lattice[0], np.cross(*self.lattice[1:])))       # interface.py:235-240
 
     @property
+    def grid_shape(self):
+        """the density's shape as a tuple of ints (a device array's shape need not be a tuple)"""
+        return tuple(int(n) for n in self.density.shape)
+
+    @property
     def voxel_lattice(self):
-        return np.divide(self.lattice, self.density.shape)                         # interface.py:261-265
+        return np.divide(self.lattice, self.grid_shape)                         # interface.py:261-265
 
     @property
     def voxel_volume(self):
-        return self.lattice_volume / np.prod(self.density.shape)                   # interface.py:267-271
+        return self.lattice_volume / np.prod(self.grid_shape)                   # interface.py:267-271
 
     @property
     def voxel_offset_fractional(self):
@@ -116,12 +122,12 @@ class Bader:
     @bader_maxima.setter
     def bader_maxima(self, maxima):                                                # interface.py:318-324
         maxima = np.add(maxima, self.voxel_offset_fractional)
-        self._bader_maxima = np.ascontiguousarray(np.divide(maxima, self.density.shape))
+        self._bader_maxima = np.ascontiguousarray(np.divide(maxima, self.grid_shape))
 
     # -- the step methods ---------------------------------------------------------------------
     def volumes_init(self, volumes=None):
         """interface.py:449-469."""
-        if volumes is None:
+        if volumes is None and not device.is_device_array(self.density):   # (a device density: vacuum_assign makes the map on the device)
             volumes = np.zeros(self.density.shape, dtype=dtype_calc(-np.prod(self.density.shape)))
         tol = np.float64('nan') if self.vacuum_tol is None else np.float64(self.vacuum_tol)
         volumes, self.vacuum_charge, self.vacuum_volume = vacuum_assign(
@@ -182,7 +188,7 @@ class Bader:
         for k, v in kwargs.items():
             setattr(self, k, v)
         ref = self.reference
-        if isinstance(ref, np.ndarray) and ref.dtype == np.float64 and ref.flags.c_contiguous:
+        if device.is_device_array(ref) or (isinstance(ref, np.ndarray) and ref.dtype == np.float64 and ref.flags.c_contiguous):
             with resident(ref):          # held still (and read-only) for the run: uploaded once, not per call
                 self._run()
         else:
@@ -241,6 +247,7 @@ class Bader:
             density['charge'] = volume_mask(volumes, self.charge, vol_num)
         if self.spin is not None:
             density['spin'] = volume_mask(volumes, self.spin, vol_num)
+        density = {k: v.to_host() if isinstance(v, device.DeviceArray) else v for k, v in density.items()}   # (the writers take host arrays)
         num = vol_num if vol_num != -1 else 'vacuum'
         self._file_info['comment'] = f"Bader {self.export_mode[0]}: {num}\n"
         self._file_info['fortran_format'] = self.fortran_format

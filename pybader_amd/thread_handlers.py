@@ -5,8 +5,8 @@ argument order, return values and silent-return cases, backed by libbader_hip.so
 thread blocks (thread_handlers.py:28-47); here the GPU library owns the decomposition."""
 import numpy as np
 
-from . import _lib, methods, refinement
-from .utils import atom_assign, dtype_calc, ensure_density, ensure_labels, fetch_labels, track_labels
+from . import _lib, device, methods, refinement
+from .utils import dev_reusable, atom_assign, dtype_calc, ensure_density, ensure_labels, fetch_labels, track_labels
 
 __all__ = ['bader_calc', 'refine', 'bader_calc_refine', 'assign_to_atoms', 'surface_distance', 'dtype_calc']
 
@@ -18,23 +18,43 @@ def _say(*a):
         print(*a)
 
 
+def _start_labels(ctx, volumes, on_device):
+    """the map an assignment starts from: `volumes` (host or device), or -- None, with a device density only -- a
+    fresh map without vacuum, which costs no transfer at all"""
+    if volumes is None and on_device:
+        ctx.vacuum_assign(None, 1.0)           # (drops the label token itself)
+    else:
+        ensure_labels(ctx, volumes)
+
+
+def _fetch_result(ctx, volumes, dtype, on_device):
+    """the label map of `dtype` after an assignment: in place in `volumes` when it has that dtype and is contiguous,
+    else a new array (thread_handlers.py:70-74) -- a device.DeviceArray when the density is a device array"""
+    if on_device:
+        if device.is_device_array(volumes) and dev_reusable(volumes, dtype):
+            return fetch_labels(ctx, volumes)
+        return fetch_labels(ctx, dtype=dtype, on_device=True)
+    if volumes.dtype == dtype and volumes.flags.c_contiguous:
+        return fetch_labels(ctx, volumes)
+    return fetch_labels(ctx, dtype=dtype)
+
+
 def bader_calc(method, density, volumes, dist_mat, T_grad, threads):
     """thread_handlers.bader_calc (thread_handlers.py:15-75).
 
-    returns (bader_max int64[N,3] voxel indices, volumes narrowed to dtype_calc(-N))."""
+    returns (bader_max int64[N,3] voxel indices, volumes narrowed to dtype_calc(-N)).  With a device array as
+    `density` (pybader_amd/device.py) the map is a device.DeviceArray and `volumes` may be None (no vacuum)."""
     if method not in methods.__contains__:
         raise AttributeError(f"module 'pybader.methods' has no attribute '{method}'")   # getattr, line 26
     ctx = _lib.default_context()
     ctx.set_grid(density.shape, dist_mat, T_grad)
+    on_device = device.is_device_array(density) or device.is_device_array(volumes)
     ensure_density(ctx, density)
-    ensure_labels(ctx, volumes)
+    _start_labels(ctx, volumes, on_device)
     n = ctx.assign(method)
     bader_max = ctx.maxima()
     dtype = np.dtype(dtype_calc(-n))                                                   # lines 70-74
-    if volumes.dtype == dtype and volumes.flags.c_contiguous:
-        fetch_labels(ctx, volumes)
-    else:
-        volumes = fetch_labels(ctx, dtype=dtype)
+    volumes = _fetch_result(ctx, volumes, dtype, on_device)
     return bader_max, volumes
 
 
@@ -54,8 +74,8 @@ def refine(method, refine_mode, density, volumes, dist_mat, T_grad, threads):
     refine.last_log = log
     if not any(changed for _, changed in log):
         track_labels(ctx, volumes)                 # no voxel was relabelled: the host copy is still the device's
-    elif volumes.flags.c_contiguous:
-        fetch_labels(ctx, volumes)
+    elif device.is_device_array(volumes) or volumes.flags.c_contiguous:
+        fetch_labels(ctx, volumes)             # (a device array must be writable and C-contiguous: export_labels refuses others)
     else:
         volumes.__setitem__(Ellipsis, ctx.download_labels(volumes.dtype))
     _say_log(log)
@@ -85,17 +105,15 @@ def bader_calc_refine(method, refine_method, refine_mode, density, volumes, dist
         return bader_calc(method, density, volumes, dist_mat, T_grad, threads)
     ctx = _lib.default_context()
     ctx.set_grid(density.shape, dist_mat, T_grad)
+    on_device = device.is_device_array(density) or device.is_device_array(volumes)
     ensure_density(ctx, density)
-    ensure_labels(ctx, volumes)
+    _start_labels(ctx, volumes, on_device)
     n, log = ctx.assign_refine(method, check_mode, iters)
     _say(f"\n  Refining {check_mode} edges:")
     refine.last_log = log
     bader_max = ctx.maxima()
     dtype = np.dtype(dtype_calc(-n))
-    if volumes.dtype == dtype and volumes.flags.c_contiguous:
-        fetch_labels(ctx, volumes)
-    else:
-        volumes = fetch_labels(ctx, dtype=dtype)
+    volumes = _fetch_result(ctx, volumes, dtype, on_device)
     _say_log(log)
     return bader_max, volumes
 
@@ -109,7 +127,7 @@ def assign_to_atoms(bader_max, atoms, lattice, volumes, threads):
         ctx.set_grid(volumes.shape, np.zeros(27), np.zeros(9))
     ensure_labels(ctx, volumes)
     ctx.volume_assign(bader_atoms)
-    atom_volumes = fetch_labels(ctx, dtype=np.dtype(dtype_calc(-atoms.shape[0])))
+    atom_volumes = fetch_labels(ctx, dtype=np.dtype(dtype_calc(-atoms.shape[0])), on_device=device.is_device_array(volumes))
     return bader_atoms, bader_distance, atom_volumes
 
 
