@@ -312,10 +312,21 @@ int xb_slab_walk_layout(xb_ctx *c, int64_t out[5]);
  * xb_slab_walk_layout again; a rank that exports more loses the surplus to the host-driven path queries, as with a full part.
  * Replaces nothing in the reference (its threads share memory, thread_handlers.py:154-232). */
 int xb_slab_walk_send(xb_ctx *c, int64_t walkers);
-/* local[8], global[8]: edges, changed, escaped, walkers still travelling after the last round (all ranks; not summed),
- * retraces redone by the exact slow kernel (then local[1], local[2] are the counts after it and the caller sums once more),
- * walkers lost to a full block or stuck (their voxels stay parked: xb_escaped_paths), this rank's travelling walkers
- * (xb_walkers_fetch), 0 */
+/* the int64 entries of block 5 and of local[] / global[] below (pybader_amd/_lib.py mirrors them) */
+enum {
+    XB_XC_EDGES = 0,      /* edge voxels of the sweep */
+    XB_XC_CHANGED = 1,    /* voxels relabelled, by retraces and by applied walker results */
+    XB_XC_ESCAPED = 2,    /* retraces that left their rank's valid planes (exported as walkers or parked) */
+    XB_XC_TRAVELLING = 3, /* walkers still travelling after the last round: all ranks' already, so global[] holds nranks times it */
+    XB_XC_SLOW = 4,       /* retraces for the exact slow kernel: xb_slab_refine_counts runs them, local[XB_XC_CHANGED] and
+                           * local[XB_XC_ESCAPED] are the counts after it and the caller sums once more */
+    XB_XC_LOST = 5,       /* walkers or results lost to a full block, or stuck (their voxels stay parked: xb_escaped_paths) */
+    XB_XC_MINE = 6,       /* this rank's travelling walkers (xb_walkers_fetch) */
+    XB_XC_ROUNDS = 7,     /* byte k (k < 4) != 0: this rank carried walkers on in round k; summed: how many ranks did -- the
+                           * scheduler sizes the next pass's rounds by it */
+    XB_XC_COUNT = 8
+};
+/* local[XB_XC_COUNT]: this rank's entries; global[XB_XC_COUNT]: their sums over the ranks */
 int xb_slab_refine_counts(xb_ctx *c, int64_t *local, int64_t *global);
 int xb_slab_block(xb_ctx *c, int which, void **dev_ptr, int64_t *bytes_total, int64_t *own_offset, int64_t *own_bytes);
 /* bytes [off, off + bytes) of a block from (to_device 1) or to (0) host memory: the host-staged transports */

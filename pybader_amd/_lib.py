@@ -12,6 +12,9 @@ LIB_PATH = os.environ.get('XB_LIBRARY') or os.path.join(HERE, 'libbader_hip.so')
 METHODS = {'ongrid': 0, 'neargrid': 1}          # methods.__contains__ (methods.py:12)
 REFINE_MODES = {'all': 0, 'changed': 1}         # refine_mode[0] (thread_handlers.py:201-205)
 DTYPE_CODE = {np.dtype(np.int8): 1, np.dtype(np.int16): 2, np.dtype(np.int32): 4, np.dtype(np.int64): 8}
+# the int64 entries of the slab step's block 5 (the XB_XC_* enum of include/bader_hip.h)
+(XB_XC_EDGES, XB_XC_CHANGED, XB_XC_ESCAPED, XB_XC_TRAVELLING, XB_XC_SLOW, XB_XC_LOST, XB_XC_MINE, XB_XC_ROUNDS,
+ XB_XC_COUNT) = range(9)
 
 # every symbol include/bader_hip.h declares: (restype, argtypes)
 _vp, _i64, _dbl, _int = C.c_void_p, C.c_int64, C.c_double, C.c_int
@@ -837,9 +840,8 @@ class Context:
         return [int(v) for v in out]
 
     def slab_refine_counts(self):
-        """-> (local, summed): int64[8] each -- edges, changed, escaped, walkers still travelling (all ranks), slow-path
-        retraces, walkers lost or stuck, this rank's travelling walkers, 0"""
-        loc, glo = np.zeros(8, np.int64), np.zeros(8, np.int64)
+        """-> (local, summed): int64[XB_XC_COUNT] each, indexed by the XB_XC_* constants"""
+        loc, glo = np.zeros(XB_XC_COUNT, np.int64), np.zeros(XB_XC_COUNT, np.int64)
         check(self.lib.xb_slab_refine_counts(self.h, loc.ctypes.data_as(_pi64), glo.ctypes.data_as(_pi64)))
         return loc, glo
 

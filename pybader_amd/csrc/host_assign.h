@@ -6,7 +6,6 @@
 // the bricks near label boundaries (one GPU, any grid of at least 16 voxels per axis), the same bricks again under the other tie
 // rule, or -- where no trapping regions are built -- the records of every brick of the table window.  All of it is pass B
 // (k_brick_records).
-static int read_counter(xb_ctx *c, int idx, int *out);
 static GridL light(const Grid &g);
 
 // per-brick arrays that outlive an assignment: blab_buf (nbr ints: region label per brick) and brick_rec (nbr bytes)
@@ -120,12 +119,6 @@ static int download_pinned(xb_ctx *c, void *dst, const void *src_dev, size_t byt
     memcpy(dst, c->pin, bytes);
     return XB_OK;
 }
-static int read_counter(xb_ctx *c, int idx, int *out) {
-    HIPCHK(hipMemcpyAsync(c->host_ints, c->counters + idx, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    *out = c->host_ints[0];
-    return XB_OK;
-}
 
 #define XB_MID_K 32   // voxels of the exact path window of the middle tier (k_ng_trace_list / k_refine_trace over the lean kernels' undecided walkers)
 // The exact slow kernel over ovf_list[0..n): whole path in scratch, membership by scanning it (methods.py:411 / refinement.py:200).
@@ -141,9 +134,9 @@ static int read_counter(xb_ctx *c, int idx, int *out) {
 // and 2 frees.)
 static int run_slow(xb_ctx *c, int n, int refine, int *max_count = nullptr, int *changed = nullptr, int *escaped = nullptr, const int *list_in = nullptr,
                     const int *n_dev = nullptr, bool stage_free = false) {
-    if (!max_count) max_count = c->counters + 0;
-    if (!changed) changed = c->counters + 2;
-    if (!escaped) escaped = c->counters + 3;
+    if (!max_count) max_count = c->counters + CT_N_MAX;
+    if (!changed) changed = c->counters + CT_CHANGED;
+    if (!escaped) escaped = c->counters + CT_ESCAPED;
     if (n <= 0) return XB_OK;
     const size_t budget = (size_t)128 << 20;   // ints of path scratch per launch (512 MB)
     // (+ a last tier of 2^20, below; debug switch 64: tiers of 3 / 5 / 8 voxels, so that a test reaches every one of them)
@@ -229,9 +222,9 @@ int xb_assign_trace(xb_ctx *c, int method, int64_t *n_local) {
         c->labels_zero_pending = false;
     else if (int rc_ = settle_labels(c)) return rc_;
     const int *box_max = nullptr;   // region id - 1 -> its maximum (set once the regions of this call exist)
-    int *max_count_dev = c->counters + 0;   // where the kernels of this call count the maxima they note
+    int *max_count_dev = c->counters + CT_N_MAX;   // where the kernels of this call count the maxima they note
     bool fast_slab = false;                 // windowed slab on passes A/B: the persistent trace, counts on the device
-    if (int rc = begin_assignment(c, c->counters, 16, false)) return rc;
+    if (int rc = begin_assignment(c, c->counters + CT_N_MAX, CT_INTS(CT_N_MAX, CT_REDO), false)) return rc;
     c->regions_neargrid = method == XB_METHOD_NEARGRID;
     if (method == XB_METHOD_NEARGRID) {
         const int maxsteps = trace_maxsteps(g);
@@ -258,13 +251,13 @@ int xb_assign_trace(xb_ctx *c, int method, int64_t *n_local) {
                 // 512^3, 6.9 vs 7.7 ms for half of 1024^3)
                 fast_slab = table_windowed(c) && c->slab_sparse &&
                             (long long)(g.x1 - g.x0) * g.ny * g.nz >= 65536LL * 512;
-                int *walk_count = c->counters + 13;
+                int *walk_count = c->counters + CT_N_WALK;
                 if (fast_slab) {   // the state block of the device-side control flow: list length, cursors, maxima and redo counts
                     HIPCHK(hipMemsetAsync(c->fs, 0, FS_TOTAL * sizeof(int), c->stream));
                     walk_count = c->fs + FS_N_WALK;
                     max_count_dev = c->fs + FS_N_MAX;
                 } else
-                    HIPCHK(hipMemsetAsync(c->counters + 13, 0, sizeof(int), c->stream));
+                    HIPCHK(hipMemsetAsync(c->counters + CT_N_WALK, 0, sizeof(int), c->stream));
                 k_brick_walk_list<<<(nbr + 16 * TPB - 1) / (16 * TPB), TPB, 0, c->stream>>>(nbr, (g.x0 / 8) * c->nbk[1] * c->nbk[2],
                                                                          (g.x1 / 8) * c->nbk[1] * c->nbk[2], c->blab, walk, walk_count);
                 if (c->has_vacuum) {
@@ -283,7 +276,7 @@ int xb_assign_trace(xb_ctx *c, int method, int64_t *n_local) {
                     ScopedTimer tw(c, 6);
                     launch_persistent_trace(c, false, false, box_max, walk, c->has_vacuum ? 1 : 0, nullptr);
                 } else {
-                if (int rc = read_counter(c, 13, &nwalk)) return rc;
+                if (int rc = read_counter(c, CT_N_WALK, &nwalk)) return rc;
                 c->n_walk = nwalk;
                 }
                 if (nwalk) {
@@ -295,19 +288,19 @@ int xb_assign_trace(xb_ctx *c, int method, int64_t *n_local) {
                         // length stays on the device) and is redone by the kernel that derives missing records from rho
                         int *redo = (int *)c->stage;
                         const int redo_cap = (int)std::min<size_t>(c->stage_bytes / sizeof(int), 0x7fffffffu);
-                        HIPCHK(hipMemsetAsync(c->counters + 15, 0, sizeof(int), c->stream));
+                        HIPCHK(hipMemsetAsync(c->counters + CT_REDO, 0, sizeof(int), c->stream));
                         k_ng_trace<2, false><<<nblk, tpb, 0, c->stream>>>(
                             light(g), c->grad, box_max, c->blab, c->nbk[1], c->nbk[2], walk, nwalk, c->labels,
-                            c->first, c->max_list, c->counters + 0, c->max_cap, redo, c->counters + 15, redo_cap,
+                            c->first, c->max_list, c->counters + CT_N_MAX, c->max_cap, redo, c->counters + CT_REDO, redo_cap,
                             maxsteps, opt, c->rho, c->dist_dev, c->has_vacuum ? 1 : 0);
                         k_ng_trace_list<2><<<512, TPB, 0, c->stream>>>(
-                            light(g), c->grad, box_max, c->blab, c->nbk[1], c->nbk[2], redo, c->counters + 15, c->labels,
-                            c->first, c->max_list, c->counters + 0, c->max_cap, c->ovf_list, c->counters + 1, c->ovf_cap,
+                            light(g), c->grad, box_max, c->blab, c->nbk[1], c->nbk[2], redo, c->counters + CT_REDO, c->labels,
+                            c->first, c->max_list, c->counters + CT_N_MAX, c->max_cap, c->ovf_list, c->counters + CT_N_OVF, c->ovf_cap,
                             maxsteps, c->rho, c->dist_dev, c->has_vacuum ? 1 : 0);
                     } else
                         k_ng_trace<2, false><<<nblk, tpb, 0, c->stream>>>(
                             light(g), c->grad, box_max, c->blab, c->nbk[1], c->nbk[2], walk, nwalk, c->labels,
-                            c->first, c->max_list, c->counters + 0, c->max_cap, c->ovf_list, c->counters + 1, c->ovf_cap,
+                            c->first, c->max_list, c->counters + CT_N_MAX, c->max_cap, c->ovf_list, c->counters + CT_N_OVF, c->ovf_cap,
                             maxsteps, opt, c->rho, c->dist_dev, c->has_vacuum ? 1 : 0);
                 }
             } else {
@@ -316,25 +309,25 @@ int xb_assign_trace(xb_ctx *c, int method, int64_t *n_local) {
                     : (long long)(g.x1 - g.x0) * g.ny * ((g.nz + 63) / 64);
                 (table_windowed(c) ? k_ng_trace<2, true> : k_ng_trace<2, false>)<<<(unsigned)((waves + tpb / XB_WAVE - 1) / (tpb / XB_WAVE)), tpb, 0, c->stream>>>(
                     light(g), c->grad, box_max, c->blab, c->nbk[1], c->nbk[2], nullptr, 0, c->labels,
-                    c->first, c->max_list, c->counters + 0, c->max_cap, c->ovf_list, c->counters + 1, c->ovf_cap,
+                    c->first, c->max_list, c->counters + CT_N_MAX, c->max_cap, c->ovf_list, c->counters + CT_N_OVF, c->ovf_cap,
                     maxsteps, opt, c->rho, c->dist_dev, c->has_vacuum ? 1 : 0);
             }
         }
         HIPCHK(hipGetLastError());
         int novf = 0;
         if (fast_slab) {   // one wait: overflows, the list length (xb_assign_finish scans those bricks)
-            HIPCHK(hipMemcpyAsync(c->host_ints, c->counters + 1, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipMemcpyAsync(c->host_ints, c->counters + CT_N_OVF, sizeof(int), hipMemcpyDeviceToHost, c->stream));
             HIPCHK(hipMemcpyAsync(c->host_ints + 1, c->fs + FS_N_WALK, sizeof(int), hipMemcpyDeviceToHost, c->stream));
             HIPCHK(hipStreamSynchronize(c->stream));
             novf = c->host_ints[0];
             c->n_walk = c->host_ints[1];
-        } else if (int rc = read_counter(c, 1, &novf)) return rc;
+        } else if (int rc = read_counter(c, CT_N_OVF, &novf)) return rc;
         if (novf > c->ovf_cap) return fail(XB_E_LIMIT, "%d trajectories need the slow path (cap %d)", novf, c->ovf_cap);
         c->stat_ovf_assign += novf;
         if (novf > 0) {
-            if (fast_slab) {   // the exact slow kernel counts its maxima in counters[0]: carry the count over
-                HIPCHK(hipMemcpyAsync(c->counters + 0, max_count_dev, sizeof(int), hipMemcpyDeviceToDevice, c->stream));
-                max_count_dev = c->counters + 0;
+            if (fast_slab) {   // the exact slow kernel counts its maxima in counters[CT_N_MAX]: carry the count over
+                HIPCHK(hipMemcpyAsync(c->counters + CT_N_MAX, max_count_dev, sizeof(int), hipMemcpyDeviceToDevice, c->stream));
+                max_count_dev = c->counters + CT_N_MAX;
             }
             if (int rc = run_slow(c, novf, 0)) return rc;
         }
@@ -361,15 +354,15 @@ int xb_assign_trace(xb_ctx *c, int method, int64_t *n_local) {
         HIPCHK(hipGetLastError());
         box_max = c->boxbuf + BB_REGMAX;
         for (int it = 0; it < 64; it++) {
-            HIPCHK(hipMemsetAsync(c->counters + 4, 0, sizeof(int), c->stream));
-            k_og_jump<<<nblocks(c->N), TPB, 0, c->stream>>>(g, c->labels, c->counters + 4);
+            HIPCHK(hipMemsetAsync(c->counters + CT_OG_MOVED, 0, sizeof(int), c->stream));
+            k_og_jump<<<nblocks(c->N), TPB, 0, c->stream>>>(g, c->labels, c->counters + CT_OG_MOVED);
             HIPCHK(hipGetLastError());
             int nd = 0;
-            if (int rc = read_counter(c, 4, &nd)) return rc;
+            if (int rc = read_counter(c, CT_OG_MOVED, &nd)) return rc;
             if (!nd) break;
             if (it == 63) return fail(XB_E_LIMIT, "ongrid pointer jumping did not converge");
         }
-        k_note_roots<<<nblocks(own), TPB, 0, c->stream>>>(g, c->labels, c->first, c->max_list, c->counters + 0, c->max_cap);
+        k_note_roots<<<nblocks(own), TPB, 0, c->stream>>>(g, c->labels, c->first, c->max_list, c->counters + CT_N_MAX, c->max_cap);
         HIPCHK(hipGetLastError());
     } else
         return fail(XB_E_ARG, "xb_assign: unknown method %d", method);
@@ -619,31 +612,31 @@ static int assign_neargrid_tail(xb_ctx *c, int64_t *n_maxima) {
         int *list2 = (int *)c->stage;
         const int cap2 = (int)std::min<size_t>(c->stage_bytes / sizeof(int), 0x7fffffffu);
         auto two_tiers = [&](int n_listed) -> int {
-            c->host_ints[3100] = n_listed;
-            HIPCHK(hipMemcpyAsync(c->counters + 15, c->host_ints + 3100, sizeof(int), hipMemcpyHostToDevice, c->stream));
-            HIPCHK(hipMemsetAsync(c->counters + 1, 0, sizeof(int), c->stream));
-            k_ng_trace_list<XB_MID_K><<<512, TPB, 0, c->stream>>>(glt, c->grad, box_max, c->blab, nb1, nb2, c->ovf_list, c->counters + 15, c->labels, c->first,
-                                                          c->max_list, fs + FS_N_MAX, c->max_cap, list2, c->counters + 1, cap2, maxsteps, c->rho, c->dist_dev,
+            c->host_ints[HI_UPLOAD] = n_listed;
+            HIPCHK(hipMemcpyAsync(c->counters + CT_MID_LISTED, c->host_ints + HI_UPLOAD, sizeof(int), hipMemcpyHostToDevice, c->stream));
+            HIPCHK(hipMemsetAsync(c->counters + CT_MID_LEFT, 0, sizeof(int), c->stream));
+            k_ng_trace_list<XB_MID_K><<<512, TPB, 0, c->stream>>>(glt, c->grad, box_max, c->blab, nb1, nb2, c->ovf_list, c->counters + CT_MID_LISTED, c->labels, c->first,
+                                                          c->max_list, fs + FS_N_MAX, c->max_cap, list2, c->counters + CT_MID_LEFT, cap2, maxsteps, c->rho, c->dist_dev,
                                                           c->has_vacuum ? 1 : 0);
             HIPCHK(hipGetLastError());
             // (what the wider window leaves is a subset of what it was given: the list's length stays on the device, n_listed bounds it)
             if (c->opt_dbg & 4) {
                 int m2 = 0;
-                if (int rc2 = read_counter(c, 1, &m2)) return rc2;
+                if (int rc2 = read_counter(c, CT_MID_LEFT, &m2)) return rc2;
                 fprintf(stderr, "[assign] %d walkers listed, %d left for the exact slow kernel after the %d-voxel window\n", n_listed, m2, XB_MID_K);
             }
             if (n_listed > cap2) return fail(XB_E_LIMIT, "%d walkers for the exact slow path exceed its list (%d)", n_listed, cap2);
-            return run_slow(c, n_listed, 0, fs + FS_N_MAX, nullptr, nullptr, list2, c->counters + 1, true);
+            return run_slow(c, n_listed, 0, fs + FS_N_MAX, nullptr, nullptr, list2, c->counters + CT_MID_LEFT, true);
         };
         int rc = two_tiers(std::min(novf, c->ovf_cap));
         // more walkers than the list holds (a density that is noise almost everywhere): the unlisted ones still carry -2 in the
         // walk-list bricks -- list and run them a list's worth at a time (round 5: this used to fail the call)
         for (int left = novf - c->ovf_cap; !rc && left > 0;) {
-            HIPCHK(hipMemsetAsync(c->counters + 1, 0, sizeof(int), c->stream));
-            k_list_unfinished<<<4096, TPB, 0, c->stream>>>(gl, walk, fs + FS_N_WALK, nb1, nb2, c->labels, c->ovf_list, c->counters + 1, c->ovf_cap);
+            HIPCHK(hipMemsetAsync(c->counters + CT_N_OVF, 0, sizeof(int), c->stream));
+            k_list_unfinished<<<4096, TPB, 0, c->stream>>>(gl, walk, fs + FS_N_WALK, nb1, nb2, c->labels, c->ovf_list, c->counters + CT_N_OVF, c->ovf_cap);
             HIPCHK(hipGetLastError());
             int m = 0;
-            if ((rc = read_counter(c, 1, &m))) break;
+            if ((rc = read_counter(c, CT_N_OVF, &m))) break;
             if (m == 0) break;
             rc = two_tiers(std::min(m, c->ovf_cap));
             left = m - c->ovf_cap;

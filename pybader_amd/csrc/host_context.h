@@ -21,12 +21,12 @@ int xb_create(int device, xb_ctx **out) {
     c->device = device;
     HIPCHK(hipStreamCreate(&c->stream));
     HIPCHK(hipMalloc(&c->counters, (1024 + XB_SORT_MAX) * sizeof(int)));   // (counters, the state block fs, and behind it the sorted maxima for the one copy of an assignment's wait)
-    c->fs = c->counters + 128;
+    c->fs = c->counters + CT_FS;
     HIPCHK(hipMalloc(&c->counters64, 16 * sizeof(unsigned long long)));
     HIPCHK(hipMalloc(&c->dsum, 16 * sizeof(double)));
     HIPCHK(hipMalloc(&c->dist_dev, 36 * sizeof(double)));  // dist_mat (27) then T_grad (9): make_rec_rho
     HIPCHK(hipMalloc(&c->boxbuf, (size_t)(1 << 20) * sizeof(int)));
-    HIPCHK(hipHostMalloc(&c->host_ints, 4096 * sizeof(int)));
+    HIPCHK(hipHostMalloc(&c->host_ints, HI_TOTAL * sizeof(int)));
     *out = c;
     return XB_OK;
 }
@@ -317,7 +317,13 @@ int xb_download_density(xb_ctx *c, double *rho_host) {
 }
 
 // ---- density block of a CHGCAR / CHG or cube file: text -> resident rho (k_text.h) ----------------------
-static int read_counter(xb_ctx *c, int idx, int *out);
+// one slot of c->counters (CT_*) through the front of host_ints: a wait
+static int read_counter(xb_ctx *c, int idx, int *out) {
+    HIPCHK(hipMemcpyAsync(c->host_ints, c->counters + idx, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    *out = c->host_ints[0];
+    return XB_OK;
+}
 // in-place exclusive scan of n ints on the device (levels of 2048)
 static int device_scan(xb_ctx *c, int *data, int n, int *scratch) {
     const int nb = (n + 2047) / 2048;
@@ -356,7 +362,7 @@ static int parse_text(xb_ctx *c, const char *who, const char *text, int64_t nbyt
     if (e == hipSuccess) e = hipMalloc(&dtodo, (size_t)todo_cap * 2 * sizeof(long long));
     if (e == hipSuccess) e = hipMemcpyAsync(dtext, text, (size_t)nbytes, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(dp10, P10, sizeof P10, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(c->counters + 6, 0, sizeof(int), c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(c->counters + CT_TEXT_TODO, 0, sizeof(int), c->stream);
     if (e != hipSuccess) { cleanup(); return fail(XB_E_HIP, "%s: %s", who, hipGetErrorString(e)); }
     int last_count = 0, last_off = 0, n_todo = 0;
     k_text_count<<<nblk, TPB, 0, c->stream>>>(dtext, nbytes, counts);
@@ -377,9 +383,9 @@ static int parse_text(xb_ctx *c, const char *who, const char *text, int64_t nbyt
     if (e == hipSuccess && rc == XB_OK && tokens < map.count())
         rc = fail(XB_E_SHORT, "%s: %lld numbers in the text, the grid needs %lld", who, tokens, map.count());
     if (e == hipSuccess && rc == XB_OK) {
-        k_text_parse<<<nblk, TPB, 0, c->stream>>>(dtext, nbytes, counts, dp10, map, c->rho, dtodo, c->counters + 6, todo_cap);
+        k_text_parse<<<nblk, TPB, 0, c->stream>>>(dtext, nbytes, counts, dp10, map, c->rho, dtodo, c->counters + CT_TEXT_TODO, todo_cap);
         e = hipGetLastError();
-        if (e == hipSuccess) rc = read_counter(c, 6, &n_todo);
+        if (e == hipSuccess) rc = read_counter(c, CT_TEXT_TODO, &n_todo);
     }
     if (e == hipSuccess && rc == XB_OK && n_todo > todo_cap)
         rc = fail(XB_E_LIMIT, "%s: %d tokens need the host parser (cap %d)", who, n_todo, todo_cap);
@@ -477,11 +483,11 @@ int xb_upload_labels(xb_ctx *c, const void *labels_host, int dtype) {
         }
     }
     // vacuum voxels present?  (the reference's callers hand bader_calc the volumes_init map: -1 only with a vacuum_tol)
-    HIPCHK(hipMemsetAsync(c->counters + 14, 0, sizeof(int), c->stream));
-    k_any_equal<<<2048, TPB, 0, c->stream>>>(c->labels, c->N, -1, c->counters + 14);
+    HIPCHK(hipMemsetAsync(c->counters + CT_ANY_EQUAL, 0, sizeof(int), c->stream));
+    k_any_equal<<<2048, TPB, 0, c->stream>>>(c->labels, c->N, -1, c->counters + CT_ANY_EQUAL);
     HIPCHK(hipGetLastError());
     int any = 0;
-    if (int rc = read_counter(c, 14, &any)) return rc;
+    if (int rc = read_counter(c, CT_ANY_EQUAL, &any)) return rc;
     c->has_vacuum = any != 0;
     return XB_OK;
 }

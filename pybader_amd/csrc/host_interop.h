@@ -170,11 +170,11 @@ int xb_import_labels(xb_ctx *c, const void *dev_ptr, int dtype, void *stream) {
     HIPCHK(hipGetLastError());
     if (int rc = io_before_caller(c, s)) return rc;
     // vacuum voxels present?  (as xb_upload_labels asks: its one wait, not one more)
-    HIPCHK(hipMemsetAsync(c->counters + 14, 0, sizeof(int), c->stream));
-    k_any_equal<<<2048, TPB, 0, c->stream>>>(c->labels, c->N, -1, c->counters + 14);
+    HIPCHK(hipMemsetAsync(c->counters + CT_ANY_EQUAL, 0, sizeof(int), c->stream));
+    k_any_equal<<<2048, TPB, 0, c->stream>>>(c->labels, c->N, -1, c->counters + CT_ANY_EQUAL);
     HIPCHK(hipGetLastError());
     int any = 0;
-    if (int rc = read_counter(c, 14, &any)) return rc;
+    if (int rc = read_counter(c, CT_ANY_EQUAL, &any)) return rc;
     c->has_vacuum = any != 0;
     return XB_OK;
 }

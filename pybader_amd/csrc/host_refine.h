@@ -8,8 +8,28 @@ static void plane_range(const Grid &g, int ext, int &xa, int &np) {
     else { xa = ((g.x0 - ext) % g.nx + g.nx) % g.nx; np = own + 2 * ext; }
 }
 
-// the sweep's launches; the edge count stays on the device (counters[5]).  *dilate_owned: the owned edges still have to
-// dilate from the list (k_edge_dilate_list over counters[5] entries)
+// known := 2 on the planes [p0, p0 + np) modulo nx
+static int preset_known_planes(xb_ctx *c, int p0, int np) {
+    const Grid &g = c->g;
+    const int run1 = std::min(np, g.nx - p0);
+    HIPCHK(hipMemsetAsync(c->known + (size_t)p0 * g.nyz, 2, (size_t)run1 * g.nyz, c->stream));
+    if (np > run1) HIPCHK(hipMemsetAsync(c->known, 2, (size_t)(np - run1) * g.nyz, c->stream));
+    return XB_OK;
+}
+// Per-brick label uniformity in front of an edge sweep: the bricks [b_off, b_off + count) scanned by scan_grid workgroups unless the
+// resident flags are valid, then the 27-brick version the sweep reads, built behind them (`st`: N bytes >= 2 nbr ints) and returned
+static int *launch_brick_uniformity(xb_ctx *c, const GridL &gl, int b_off, int count, unsigned scan_grid) {
+    const Grid &g = c->g;
+    const int nb0 = (g.nx + 7) / 8, nb1 = (g.ny + 7) / 8, nb2 = (g.nz + 7) / 8, nbr = nb0 * nb1 * nb2;
+    int *buni = reinterpret_cast<int *>(c->st);
+    if (!c->buni_valid)
+        k_label_uniform_list<<<scan_grid, TPB, 0, c->stream>>>(gl, c->labels, nb1, nb2, nullptr, count, nullptr, nullptr, buni, b_off, nbr);
+    k_buni3<<<(nbr + 255) / 256, 256, 0, c->stream>>>(nb0, nb1, nb2, buni, buni + nbr);
+    return buni + nbr;
+}
+
+// the sweep's launches; the edge count stays on the device (CT_N_EDGES).  *dilate_owned: the owned edges still have to
+// dilate from the list (k_edge_dilate_list over CT_N_EDGES entries)
 static int edge_find_launch(xb_ctx *c, bool *dilate_owned) {
     const Grid &g = c->g;
     const bool whole = (g.x1 - g.x0 == g.nx);
@@ -20,7 +40,7 @@ static int edge_find_launch(xb_ctx *c, bool *dilate_owned) {
     const bool all = whole || (g.x1 - g.x0) + 2 * c->halo >= g.nx;
     plane_range(g, all ? g.nx : c->halo - 1, xa, np);
     plane_range(g, all ? g.nx : c->halo - 2, xb_, npd);
-    HIPCHK(hipMemsetAsync(c->counters + 5, 0, sizeof(int), c->stream));
+    HIPCHK(hipMemsetAsync(c->counters + CT_N_EDGES, 0, sizeof(int), c->stream));
     {
         ScopedTimer t(c, 2);
         const GridL gl = light(g);
@@ -29,29 +49,23 @@ static int edge_find_launch(xb_ctx *c, bool *dilate_owned) {
         // per-brick label uniformity first: grids of whole bricks (slabs), any grid of at least 16 voxels per axis on one slab
         // (the brick lattice is ceil(n / 8); a brick the grid cuts counts its voxels inside the grid)
         if ((g.nx % 8 == 0 && g.ny % 8 == 0 && g.nz % 8 == 0) || (whole && g.nx >= 16 && g.ny >= 16 && g.nz >= 16)) {
-            buni = reinterpret_cast<int *>(c->st);             // N bytes >= 2 nbr ints; edge_check reuses st later
-            const int nb0 = (g.nx + 7) / 8, nb1 = (g.ny + 7) / 8, nb2 = (g.nz + 7) / 8;
-            const int nbr = nb0 * nb1 * nb2, per_plane = nb1 * nb2;
-            if (!c->buni_valid) {
-                // a slab only scans the bricks its sweep can look at (the swept planes +- one brick)
-                int b_off = 0, count = nbr;
-                if (!all && np + 32 < g.nx) {
-                    const int p0 = ((xa - 8) % g.nx + g.nx) % g.nx;
-                    b_off = (p0 / 8) * per_plane;
-                    count = ((np + 8 + 7 + (p0 % 8)) / 8 + 1) * per_plane;
-                }
-                k_label_uniform_list<<<(unsigned)std::min(4096, (count + 3) / 4), TPB, 0, c->stream>>>(gl, c->labels, nb1, nb2, nullptr, count, nullptr, nullptr, buni, b_off, nbr);
-                c->buni_halo_safe = false;
+            const int per_plane = ((g.ny + 7) / 8) * ((g.nz + 7) / 8);
+            // a slab only scans the bricks its sweep can look at (the swept planes +- one brick)
+            int b_off = 0, count = ((g.nx + 7) / 8) * per_plane;
+            if (!all && np + 32 < g.nx) {
+                const int p0 = ((xa - 8) % g.nx + g.nx) % g.nx;
+                b_off = (p0 / 8) * per_plane;
+                count = ((np + 8 + 7 + (p0 % 8)) / 8 + 1) * per_plane;
             }
-            k_buni3<<<(nbr + 255) / 256, 256, 0, c->stream>>>(nb0, nb1, nb2, buni, buni + nbr);
-            buni += nbr;   // the sweep reads the 27-brick version
+            if (!c->buni_valid) c->buni_halo_safe = false;
+            buni = launch_brick_uniformity(c, gl, b_off, count, (unsigned)std::min(4096, (count + 3) / 4));
         }
         const GradRec *G = c->grad_valid ? c->grad : nullptr;
         const unsigned char *brec = c->grad_valid && c->grad_cover == 1 ? c->brick_rec : nullptr;
         if (whole || all) {
             dim3 grid((g.nz + ET_Z - 1) / ET_Z, (g.ny + ET_Y - 1) / ET_Y, (np + ET_X - 1) / ET_X);
             k_edge_flag_tiled<<<grid, TPB, 0, c->stream>>>(gl, c->rho, c->labels, c->known, xa, np, c->list,
-                                                           c->counters + 5, small, buni, G, brec, c->has_vacuum ? 0 : 1);
+                                                           c->counters + CT_N_EDGES, small, buni, G, brec, c->has_vacuum ? 0 : 1);
             if (!whole)
                 k_edge_dilate<<<nblocks((long long)npd * g.nyz), TPB, 0, c->stream>>>(g, c->known, xb_, npd, -2);
         } else if (buni && g.x0 % ET_X == 0 && g.x1 % ET_X == 0 && g.ny % ET_Y == 0 &&
@@ -63,44 +77,38 @@ static int edge_find_launch(xb_ctx *c, bool *dilate_owned) {
             const int own = g.x1 - g.x0, side4 = (c->halo - 1 + ET_X - 1) / ET_X * ET_X;
             const int nty = g.ny / ET_Y, ntz = (g.nz + ET_Z - 1) / ET_Z;
             const int left0 = ((g.x0 - side4) % g.nx + g.nx) % g.nx, right0 = g.x1 % g.nx;
-            auto preset = [&](int p0, int np_) -> int {
-                const int run1 = std::min(np_, g.nx - p0);
-                HIPCHK(hipMemsetAsync(c->known + (size_t)p0 * g.nyz, 2, (size_t)run1 * g.nyz, c->stream));
-                if (np_ > run1) HIPCHK(hipMemsetAsync(c->known, 2, (size_t)(np_ - run1) * g.nyz, c->stream));
-                return XB_OK;
-            };
-            if (int rc = preset(left0, side4 + own + side4)) return rc;
+            if (int rc = preset_known_planes(c, left0, side4 + own + side4)) return rc;
             const int n_own = (own / ET_X) * nty * ntz, n_halo = 2 * (side4 / ET_X) * nty * ntz;
             int *tiles_own = (int *)c->stage, *tiles_halo = tiles_own + n_own, *halo_list = tiles_halo + n_halo;
-            HIPCHK(hipMemsetAsync(c->counters + 6, 0, sizeof(int), c->stream));
-            HIPCHK(hipMemsetAsync(c->counters + 22, 0, 2 * sizeof(int), c->stream));
+            HIPCHK(hipMemsetAsync(c->counters + CT_HALO_EDGES, 0, sizeof(int), c->stream));
+            HIPCHK(hipMemsetAsync(c->counters + CT_TILES_OWN, 0, CT_INTS(CT_TILES_OWN, CT_TILES_HALO) * sizeof(int), c->stream));
             GridL ga = gl;
             ga.x0 = 0; ga.x1 = g.nx;    // (lists every edge of the planes it sweeps)
-            k_edge_tile_list<<<(n_own + TPB - 1) / TPB, TPB, 0, c->stream>>>(gl, buni, tiles_own, c->counters + 22, g.x0 / ET_X, own / ET_X);
-            k_edge_tile_list<<<(n_halo / 2 + TPB - 1) / TPB, TPB, 0, c->stream>>>(gl, buni, tiles_halo, c->counters + 23, left0 / ET_X, side4 / ET_X);
-            k_edge_tile_list<<<(n_halo / 2 + TPB - 1) / TPB, TPB, 0, c->stream>>>(gl, buni, tiles_halo, c->counters + 23, right0 / ET_X, side4 / ET_X);
-            k_edge_flag_listed<<<std::min(n_own, 2048), TPB, 0, c->stream>>>(gl, c->rho, c->labels, c->known, c->list, c->counters + 5, small, G, brec,
-                                                            c->has_vacuum ? 0 : 1, tiles_own, c->counters + 22);
-            k_edge_flag_listed<<<std::min(n_halo, 2048), TPB, 0, c->stream>>>(ga, c->rho, c->labels, c->known, halo_list, c->counters + 6, small, G, brec,
-                                                             c->has_vacuum ? 0 : 1, tiles_halo, c->counters + 23);
-            k_edge_dilate_list<<<2048, TPB, 0, c->stream>>>(gl, c->known, halo_list, 0, c->counters + 6);
+            k_edge_tile_list<<<(n_own + TPB - 1) / TPB, TPB, 0, c->stream>>>(gl, buni, tiles_own, c->counters + CT_TILES_OWN, g.x0 / ET_X, own / ET_X);
+            k_edge_tile_list<<<(n_halo / 2 + TPB - 1) / TPB, TPB, 0, c->stream>>>(gl, buni, tiles_halo, c->counters + CT_TILES_HALO, left0 / ET_X, side4 / ET_X);
+            k_edge_tile_list<<<(n_halo / 2 + TPB - 1) / TPB, TPB, 0, c->stream>>>(gl, buni, tiles_halo, c->counters + CT_TILES_HALO, right0 / ET_X, side4 / ET_X);
+            k_edge_flag_listed<<<std::min(n_own, 2048), TPB, 0, c->stream>>>(gl, c->rho, c->labels, c->known, c->list, c->counters + CT_N_EDGES, small, G, brec,
+                                                            c->has_vacuum ? 0 : 1, tiles_own, c->counters + CT_TILES_OWN);
+            k_edge_flag_listed<<<std::min(n_halo, 2048), TPB, 0, c->stream>>>(ga, c->rho, c->labels, c->known, halo_list, c->counters + CT_HALO_EDGES, small, G, brec,
+                                                             c->has_vacuum ? 0 : 1, tiles_halo, c->counters + CT_TILES_HALO);
+            k_edge_dilate_list<<<2048, TPB, 0, c->stream>>>(gl, c->known, halo_list, 0, c->counters + CT_HALO_EDGES);
         } else {
             // a slab: the owned planes (their edges make the list), then the halo planes each side -- their edges go to a
             // second list (in `stage`, length on the device) that only serves the dilation (refinement.py:385-404)
             const int own = g.x1 - g.x0, side = c->halo - 1;
             int *halo_list = (int *)c->stage;
-            HIPCHK(hipMemsetAsync(c->counters + 6, 0, sizeof(int), c->stream));
+            HIPCHK(hipMemsetAsync(c->counters + CT_HALO_EDGES, 0, sizeof(int), c->stream));
             GridL ga = gl;
             ga.x0 = 0; ga.x1 = g.nx;    // (lists every edge of the planes it sweeps)
             dim3 grid((g.nz + ET_Z - 1) / ET_Z, (g.ny + ET_Y - 1) / ET_Y, (own + ET_X - 1) / ET_X);
             k_edge_flag_tiled<<<grid, TPB, 0, c->stream>>>(gl, c->rho, c->labels, c->known, g.x0, own, c->list,
-                                                           c->counters + 5, small, buni, G, brec, c->has_vacuum ? 0 : 1);
+                                                           c->counters + CT_N_EDGES, small, buni, G, brec, c->has_vacuum ? 0 : 1);
             grid.z = (side + ET_X - 1) / ET_X;
             k_edge_flag_tiled<<<grid, TPB, 0, c->stream>>>(ga, c->rho, c->labels, c->known, xa, side, halo_list,
-                                                           c->counters + 6, small, buni, G, brec, c->has_vacuum ? 0 : 1);
+                                                           c->counters + CT_HALO_EDGES, small, buni, G, brec, c->has_vacuum ? 0 : 1);
             k_edge_flag_tiled<<<grid, TPB, 0, c->stream>>>(ga, c->rho, c->labels, c->known, g.x1 % g.nx, side, halo_list,
-                                                           c->counters + 6, small, buni, G, brec, c->has_vacuum ? 0 : 1);
-            k_edge_dilate_list<<<2048, TPB, 0, c->stream>>>(gl, c->known, halo_list, 0, c->counters + 6);
+                                                           c->counters + CT_HALO_EDGES, small, buni, G, brec, c->has_vacuum ? 0 : 1);
+            k_edge_dilate_list<<<2048, TPB, 0, c->stream>>>(gl, c->known, halo_list, 0, c->counters + CT_HALO_EDGES);
         }
     }
     HIPCHK(hipGetLastError());
@@ -114,7 +122,7 @@ int xb_edge_find(xb_ctx *c, int64_t *edges) {
     c->chg_n = -1;   // `known` is rewritten: the changed-voxel list of an earlier retrace pass no longer describes it
     if (int rc = edge_find_launch(c, &dilate_owned)) return rc;
     int n = 0;
-    if (int rc = read_counter(c, 5, &n)) return rc;
+    if (int rc = read_counter(c, CT_N_EDGES, &n)) return rc;
     if (dilate_owned && n) {  // the list holds every owned edge: dilate from it
         ScopedTimer t(c, 2);
         k_edge_dilate_list<<<nblocks(n), TPB, 0, c->stream>>>(light(g), c->known, c->list, n, nullptr);
@@ -129,11 +137,11 @@ int xb_edge_find(xb_ctx *c, int64_t *edges) {
 static int compact(xb_ctx *c, int value, int *n_out) {
     const Grid &g = c->g;
     const long long own = (long long)(g.x1 - g.x0) * g.nyz;
-    HIPCHK(hipMemsetAsync(c->counters + 5, 0, sizeof(int), c->stream));
+    HIPCHK(hipMemsetAsync(c->counters + CT_N_COMPACT, 0, sizeof(int), c->stream));
     k_compact_known16<<<nblocks((own + 16 * CK_CHUNKS - 1) / (16 * CK_CHUNKS)), TPB, 0, c->stream>>>(light(g), c->known, value, c->list,
-                                                                                               c->counters + 5);
+                                                                                               c->counters + CT_N_COMPACT);
     HIPCHK(hipGetLastError());
-    return read_counter(c, 5, n_out);
+    return read_counter(c, CT_N_COMPACT, n_out);
 }
 
 // ---- remote path queries (slab scheduler) -------------------------------------------------------
@@ -161,8 +169,8 @@ int xb_escaped_paths(xb_ctx *c, int64_t max_len, int64_t *n_paths, int64_t *n_vo
             const int m = std::min(chunk, n - o);
             int *dfirst = dlen + m, *doff = dlen + 2 * chunk;
             k_trace_slow<<<(m + 63) / 64, 64, 0, c->stream>>>(c->g, c->rho, c->labels, c->known, c->known, c->list + o, m, path,
-                                                             lmax, 2, c->first, c->max_list, c->counters + 0, c->max_cap,
-                                                             c->counters + 2, c->counters + 3, c->counters + 8, dlen);
+                                                             lmax, 2, c->first, c->max_list, c->counters + CT_N_MAX, c->max_cap,
+                                                             c->counters + CT_CHANGED, c->counters + CT_ESCAPED, c->counters + CT_ESC_ERR, dlen);
             hipError_t e = hipMemcpyAsync(len.data(), dlen, 2 * m * sizeof(int), hipMemcpyDeviceToHost, c->stream);
             if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
             if (e != hipSuccess) { rc = fail(XB_E_HIP, "xb_escaped_paths: %s", hipGetErrorString(e)); break; }
@@ -263,7 +271,8 @@ static int refine_trace_impl(xb_ctx *c, int flag, int64_t *changed, int64_t *esc
     c->buni_valid = false;  // ... and may relabel edge voxels; st is also edge_check's scratch
     c->walk_n_out = 0; c->walk_n_res = 0; c->walk_out_dev = nullptr;
     c->walk_host.clear(); c->res_host.clear();
-    HIPCHK(hipMemsetAsync(c->counters, 0, 4 * sizeof(int), c->stream));
+    static_assert(CT_ESCAPED == CT_N_MAX + 3 && CT_WALK_OUT == CT_N_MAX + 16, "one memset clears maxima .. escaped; one copy brings back everything up to the exported walkers");
+    HIPCHK(hipMemsetAsync(c->counters + CT_N_MAX, 0, CT_INTS(CT_N_MAX, CT_ESCAPED) * sizeof(int), c->stream));
     int n_changed = 0, n_escaped = 0;
     if (n) {
         Walker *wio_out = nullptr;
@@ -284,28 +293,28 @@ static int refine_trace_impl(xb_ctx *c, int flag, int64_t *changed, int64_t *esc
             if (flag == -2 && slab) {
                 const size_t off = (((size_t)n * sizeof(int)) + 255) & ~(size_t)255;
                 if (off + sizeof(Walker) <= c->stage_bytes) {
-                    HIPCHK(hipMemsetAsync(c->counters + 16, 0, sizeof(int), c->stream));
-                    wio.out = (Walker *)((char *)c->stage + off); wio.out_count = c->counters + 16;
+                    HIPCHK(hipMemsetAsync(c->counters + CT_WALK_OUT, 0, sizeof(int), c->stream));
+                    wio.out = (Walker *)((char *)c->stage + off); wio.out_count = c->counters + CT_WALK_OUT;
                     wio.out_cap = (int)std::min<size_t>((c->stage_bytes - off) / sizeof(Walker), 1u << 30);
                     c->walk_out_dev = wio.out;
                 }
             }
-            HIPCHK(hipMemsetAsync(c->counters + 15, 0, sizeof(int), c->stream));
-            launch_refine_trace<2, false>(c, nblocks(n), TPB, c->list, n, nullptr, c->counters + 2, c->counters + 3, c->ovf_list,
-                                          c->counters + 1, c->ovf_cap, brec, defer, c->counters + 15, regions_ok, slab_regions, WalkerIO{});
+            HIPCHK(hipMemsetAsync(c->counters + CT_DEFER, 0, sizeof(int), c->stream));
+            launch_refine_trace<2, false>(c, nblocks(n), TPB, c->list, n, nullptr, c->counters + CT_CHANGED, c->counters + CT_ESCAPED, c->ovf_list,
+                                          c->counters + CT_N_OVF, c->ovf_cap, brec, defer, c->counters + CT_DEFER, regions_ok, slab_regions, WalkerIO{});
             if (brec || slab || table_windowed(c))
-                launch_refine_trace<2, true>(c, 512, TPB, defer, 0, c->counters + 15, c->counters + 2, c->counters + 3, c->ovf_list,
-                                             c->counters + 1, c->ovf_cap, brec, nullptr, nullptr, 0, slab_regions, wio);
+                launch_refine_trace<2, true>(c, 512, TPB, defer, 0, c->counters + CT_DEFER, c->counters + CT_CHANGED, c->counters + CT_ESCAPED, c->ovf_list,
+                                             c->counters + CT_N_OVF, c->ovf_cap, brec, nullptr, nullptr, 0, slab_regions, wio);
             wio_out = wio.out; wio_cap = wio.out_cap;
         }
         HIPCHK(hipGetLastError());
-        // one wait for everything the kernels counted: overflows [1], changed [2], escaped [3], exported walkers [16]
-        HIPCHK(hipMemcpyAsync(c->host_ints, c->counters, 17 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        // one wait for everything the kernels counted: overflows, changed, escaped, exported walkers
+        HIPCHK(hipMemcpyAsync(c->host_ints, c->counters + CT_N_MAX, CT_INTS(CT_N_MAX, CT_WALK_OUT) * sizeof(int), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
-        const int novf = c->host_ints[1];
-        n_changed = c->host_ints[2]; n_escaped = c->host_ints[3];
+        const int novf = c->host_ints[CT_N_OVF];
+        n_changed = c->host_ints[CT_CHANGED]; n_escaped = c->host_ints[CT_ESCAPED];
         if (wio_out) {
-            c->walk_n_out = std::min(c->host_ints[16], wio_cap);
+            c->walk_n_out = std::min(c->host_ints[CT_WALK_OUT], wio_cap);
             c->walk_host.resize((size_t)c->walk_n_out * (sizeof(Walker) / 8));
             if (int rc = download_pinned(c, c->walk_host.data(), wio_out, (size_t)c->walk_n_out * sizeof(Walker))) return rc;
         }
@@ -313,7 +322,7 @@ static int refine_trace_impl(xb_ctx *c, int flag, int64_t *changed, int64_t *esc
         c->stat_ovf_refine += novf;
         if (novf > 0) {
             if (int rc = run_slow(c, novf, 1)) return rc;
-            HIPCHK(hipMemcpyAsync(c->host_ints, c->counters + 2, 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipMemcpyAsync(c->host_ints, c->counters + CT_CHANGED, CT_INTS(CT_CHANGED, CT_ESCAPED) * sizeof(int), hipMemcpyDeviceToHost, c->stream));
             HIPCHK(hipStreamSynchronize(c->stream));
             n_changed = c->host_ints[0]; n_escaped = c->host_ints[1];
         }
@@ -364,18 +373,19 @@ int xb_walkers_continue(xb_ctx *c, const int64_t *walkers, int64_t n) {
     const size_t bytes = (size_t)n * sizeof(Walker);
     if (int rc = ensure_walker_bufs(c, n)) return rc;
     if (int rc = upload_pinned(c, c->walk_in, walkers, bytes)) return rc;
-    HIPCHK(hipMemsetAsync(c->counters + 16, 0, 4 * sizeof(int), c->stream));
-    HIPCHK(hipMemsetAsync(c->counters + 1, 0, 3 * sizeof(int), c->stream));
+    static_assert(CT_WALK_STUCK == CT_WALK_OUT + 3 && CT_ESCAPED == CT_N_OVF + 2, "two memsets clear the walkers' four counts and overflows .. escaped");
+    HIPCHK(hipMemsetAsync(c->counters + CT_WALK_OUT, 0, CT_INTS(CT_WALK_OUT, CT_WALK_STUCK) * sizeof(int), c->stream));
+    HIPCHK(hipMemsetAsync(c->counters + CT_N_OVF, 0, CT_INTS(CT_N_OVF, CT_ESCAPED) * sizeof(int), c->stream));
     WalkerIO wio{};
     wio.in = (const Walker *)c->walk_in;
-    wio.out = (Walker *)c->walk_out2; wio.out_count = c->counters + 16; wio.out_cap = (int)n;
-    wio.res = (int *)c->walk_res; wio.res_count = c->counters + 17;
+    wio.out = (Walker *)c->walk_out2; wio.out_count = c->counters + CT_WALK_OUT; wio.out_cap = (int)n;
+    wio.res = (int *)c->walk_res; wio.res_count = c->counters + CT_WALK_RES;
     wio.own0 = g.x0; wio.own1 = g.x1;
     const unsigned char *brec = c->grad_cover == 1 ? c->brick_rec : nullptr;
-    launch_refine_trace<2, true, true>(c, nblocks((int)n), TPB, nullptr, (int)n, nullptr, c->counters + 2, c->counters + 3, c->ovf_list,
-                                       c->counters + 1, c->ovf_cap, brec, nullptr, nullptr, 0, slab_regions_of(c), wio);
+    launch_refine_trace<2, true, true>(c, nblocks((int)n), TPB, nullptr, (int)n, nullptr, c->counters + CT_CHANGED, c->counters + CT_ESCAPED, c->ovf_list,
+                                       c->counters + CT_N_OVF, c->ovf_cap, brec, nullptr, nullptr, 0, slab_regions_of(c), wio);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(c->host_ints, c->counters + 16, 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(c->host_ints, c->counters + CT_WALK_OUT, CT_INTS(CT_WALK_OUT, CT_WALK_RES) * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     c->walk_n_out = c->host_ints[0]; c->walk_n_res = c->host_ints[1];
     c->walk_out_dev = wio.out;
@@ -407,11 +417,11 @@ int xb_walkers_apply(xb_ctx *c, const int64_t *results, int64_t n, int64_t *chan
     if (int rc = ensure_walker_bufs(c, n)) return rc;
     int *d = (int *)c->walk_res;    // (the results of the last xb_walkers_continue were fetched to the host already)
     if (int rc = upload_pinned(c, d, pairs.data(), pairs.size() * sizeof(int))) return rc;
-    HIPCHK(hipMemsetAsync(c->counters + 18, 0, 2 * sizeof(int), c->stream));
+    HIPCHK(hipMemsetAsync(c->counters + CT_WALK_CHANGED, 0, CT_INTS(CT_WALK_CHANGED, CT_WALK_STUCK) * sizeof(int), c->stream));
     k_walkers_apply<<<(unsigned)((n + 255) / 256), 256, 0, c->stream>>>(light(g), d, (int)n, g.x0, g.x1, c->labels, c->known,
-                                                                      c->counters + 18, c->counters + 19);
+                                                                      c->counters + CT_WALK_CHANGED, c->counters + CT_WALK_STUCK);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(c->host_ints, c->counters + 18, 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(c->host_ints, c->counters + CT_WALK_CHANGED, CT_INTS(CT_WALK_CHANGED, CT_WALK_STUCK) * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     c->list_valid = false; c->chg_n = -1; c->buni_valid = false;
     if (changed) *changed = c->host_ints[0];
@@ -457,15 +467,14 @@ static int edge_check_resolve(xb_ctx *c, int n, const int8_t *cls, int near_xa, 
             HIPCHK(hipMemsetAsync(c->ec_pflag, 0, (size_t)c->N + 16, c->stream));
         }
         ec_word *pend_w = c->ec_pend;
-        // counters: 6 / 24 the seed list and the overflow list of a chase pass (alternating), 25 undecided voxels, 7 new edges,
-        // 27 processed voxels, 26 the next pass's list -- zeroed together; the host reads 24 once (did the LDS queues spill?) and
-        // the rest with the results
-        HIPCHK(hipMemsetAsync(c->counters + 6, 0, 2 * sizeof(int), c->stream));
-        HIPCHK(hipMemsetAsync(c->counters + 24, 0, 4 * sizeof(int), c->stream));
+        // the CT_EC_* counters zeroed together; the host reads CT_EC_SEEDS_B once (did the LDS queues spill?) and the rest with the results
+        static_assert(CT_EC_NEW == CT_EC_SEEDS_A + 1 && CT_EC_DONE == CT_EC_SEEDS_B + 3, "two memsets clear edge_check's counters");
+        HIPCHK(hipMemsetAsync(c->counters + CT_EC_SEEDS_A, 0, CT_INTS(CT_EC_SEEDS_A, CT_EC_NEW) * sizeof(int), c->stream));
+        HIPCHK(hipMemsetAsync(c->counters + CT_EC_SEEDS_B, 0, CT_INTS(CT_EC_SEEDS_B, CT_EC_DONE) * sizeof(int), c->stream));
         if (cls) k_ec_init_cls<<<nblocks(n), TPB, 0, c->stream>>>(g, c->known, c->list, n, cls, pend_w);
         else k_ec_init<<<(nblocks(n) + 7) & ~7u, TPB, 0, c->stream>>>(g, c->rho, c->labels, c->known, c->list, n, pend_w);
         k_ec_first<<<(unsigned)std::min<long long>(nblocks(n), 4096), TPB, 0, c->stream>>>(g, c->known, pend_w, c->list, n, buf[0],
-                                                                                         c->counters + 6, cap);
+                                                                                         c->counters + CT_EC_SEEDS_A, cap);
         HIPCHK(hipGetLastError());
         const int groups = std::max(1, std::min(256, c->opt_ec_groups));
         // (round 5: the workgroups share out a long front through mailboxes -- k_ec_chase)
@@ -477,21 +486,21 @@ static int edge_check_resolve(xb_ctx *c, int n, const int8_t *cls, int near_xa, 
         int n_seeds = 1;
         for (int pass = 0; n_seeds > 0; pass++) {
             if (pass > 256) return fail(XB_E_LIMIT, "xb_edge_check: queue overflow passes did not drain");
-            int *cnt_in = c->counters + ((pass & 1) ? 24 : 6), *cnt_out = c->counters + ((pass & 1) ? 6 : 24);
-            if (pass) HIPCHK(hipMemsetAsync(cnt_out, 0, sizeof(int), c->stream));
+            const int slot_in = (pass & 1) ? CT_EC_SEEDS_B : CT_EC_SEEDS_A, slot_out = (pass & 1) ? CT_EC_SEEDS_A : CT_EC_SEEDS_B;
+            if (pass) HIPCHK(hipMemsetAsync(c->counters + slot_out, 0, sizeof(int), c->stream));
             if (share) {
                 HIPCHK(hipMemsetAsync(share, 0, ec_share_bytes(groups), c->stream));
             }
-            k_ec_chase<<<groups, EC_CHASE_THREADS, 0, c->stream>>>(g, c->known, pend_w, buf[pass & 1], cnt_in, buf[1 - (pass & 1)], cnt_out,
+            k_ec_chase<<<groups, EC_CHASE_THREADS, 0, c->stream>>>(g, c->known, pend_w, buf[pass & 1], c->counters + slot_in, buf[1 - (pass & 1)], c->counters + slot_out,
                                                                    cap, c->opt_ec_qcap, share);
             HIPCHK(hipGetLastError());
             // (with the first pass's overflow count also k_ec_first's own seed count: k_ec_chase clamps what it reads to the
             // list's capacity, so a list that was too small must fail HERE, not later as "undecided" -- ADVICE r4)
-            if (pass == 0) HIPCHK(hipMemcpyAsync(c->host_ints + 1, c->counters + 6, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-            if (share) HIPCHK(hipMemcpyAsync(c->host_ints + 2, share + 32, sizeof(int), hipMemcpyDeviceToHost, c->stream));   // (the sharing's error flag)
-            if (int rc = read_counter(c, (pass & 1) ? 6 : 24, &n_seeds)) return rc;
-            if (n_seeds > cap || (pass == 0 && c->host_ints[1] > cap)) return fail(XB_E_LIMIT, "xb_edge_check: seed list too small");
-            if (share && c->host_ints[2]) return fail(XB_E_STATE, "xb_edge_check: a reserved mailbox slot of the chase was never filled");
+            if (pass == 0) HIPCHK(hipMemcpyAsync(c->host_ints + HI_EC_SEEDS0, c->counters + CT_EC_SEEDS_A, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+            if (share) HIPCHK(hipMemcpyAsync(c->host_ints + HI_EC_SHARE_ERR, share + 32, sizeof(int), hipMemcpyDeviceToHost, c->stream));   // (the sharing's error flag)
+            if (int rc = read_counter(c, slot_out, &n_seeds)) return rc;
+            if (n_seeds > cap || (pass == 0 && c->host_ints[HI_EC_SEEDS0] > cap)) return fail(XB_E_LIMIT, "xb_edge_check: seed list too small");
+            if (share && c->host_ints[HI_EC_SHARE_ERR]) return fail(XB_E_STATE, "xb_edge_check: a reserved mailbox slot of the chase was never filled");
             if (c->opt_dbg & 4) {
                 fprintf(stderr, "edge_check pass %d: %d overflowed (%d groups)\n", pass, n_seeds, groups);
 #ifdef XB_EC_PROBE
@@ -523,25 +532,26 @@ static int edge_check_resolve(xb_ctx *c, int n, const int8_t *cls, int near_xa, 
             }
         }
     }
-    HIPCHK(hipMemsetAsync(c->counters + 25, 0, sizeof(int), c->stream));
-    k_ec_collect<<<nblocks(n), TPB, 0, c->stream>>>(c->known, c->list, n, c->st, c->counters + 25);
+    HIPCHK(hipMemsetAsync(c->counters + CT_EC_UNDECIDED, 0, sizeof(int), c->stream));
+    k_ec_collect<<<nblocks(n), TPB, 0, c->stream>>>(c->known, c->list, n, c->st, c->counters + CT_EC_UNDECIDED);
     if (near_np < g.nx) k_ec_keep_near<<<nblocks(n), TPB, 0, c->stream>>>(g, c->list, n, c->st, near_xa, near_np);
-    HIPCHK(hipMemsetAsync(c->counters64, 0, 2 * sizeof(unsigned long long), c->stream));
+    HIPCHK(hipMemsetAsync(c->counters64 + C64_EC_EDGES, 0, CT_INTS(C64_EC_EDGES, C64_EC_CHECKED) * sizeof(unsigned long long), c->stream));
     const int new_cap = (int)std::min<long long>(c->list_cap - n, 0x7fffffffLL);   // the rest of `list` behind the compacted edges
-    HIPCHK(hipMemsetAsync(c->counters + 7, 0, sizeof(int), c->stream));
-    HIPCHK(hipMemsetAsync(c->counters + 26, 0, 2 * sizeof(int), c->stream));
-    k_ec_mark<<<nblocks(n), TPB, 0, c->stream>>>(c->list, n, c->st, c->ec_pflag, (int8_t)1, plist, c->counters + 27, plist_cap);
-    k_ec_apply<<<(unsigned)std::min<long long>(nblocks(27LL * n), 4096), TPB, 0, c->stream>>>(g, c->rho, c->labels, c->known, plist, c->counters + 27,
-                                                  c->counters64 + 1, c->list + n, c->counters + 7, new_cap, c->ec_pflag);
+    HIPCHK(hipMemsetAsync(c->counters + CT_EC_NEW, 0, sizeof(int), c->stream));
+    static_assert(CT_EC_DONE == CT_EC_NEXT + 1, "one memset clears the next pass's list length and the processed count");
+    HIPCHK(hipMemsetAsync(c->counters + CT_EC_NEXT, 0, CT_INTS(CT_EC_NEXT, CT_EC_DONE) * sizeof(int), c->stream));
+    k_ec_mark<<<nblocks(n), TPB, 0, c->stream>>>(c->list, n, c->st, c->ec_pflag, (int8_t)1, plist, c->counters + CT_EC_DONE, plist_cap);
+    k_ec_apply<<<(unsigned)std::min<long long>(nblocks(27LL * n), 4096), TPB, 0, c->stream>>>(g, c->rho, c->labels, c->known, plist, c->counters + CT_EC_DONE,
+                                                  c->counters64 + C64_EC_CHECKED, c->list + n, c->counters + CT_EC_NEW, new_cap, c->ec_pflag);
     k_ec_mark<<<nblocks(n), TPB, 0, c->stream>>>(c->list, n, c->st, c->ec_pflag, (int8_t)0, nullptr, nullptr, 0);   // (the flags are zero again)
     k_ec_restore<<<nblocks(n), TPB, 0, c->stream>>>(c->known, c->list, n);
     {   // -1 ring around the new edges (-3): from their list (its length stays on the device) -- a list that may not fit (a
         // grid most of whose voxels changed) is read back, and a full-grid sweep takes over if it did not
         if (new_cap >= std::min<long long>(27LL * n, c->N))
-            k_edge_dilate_list<<<(unsigned)std::min<long long>(nblocks(n), 4096), TPB, 0, c->stream>>>(light(g), c->known, c->list + n, 0, c->counters + 7);
+            k_edge_dilate_list<<<(unsigned)std::min<long long>(nblocks(n), 4096), TPB, 0, c->stream>>>(light(g), c->known, c->list + n, 0, c->counters + CT_EC_NEW);
         else {
             int n_new = 0;
-            if (int rc = read_counter(c, 7, &n_new)) return rc;
+            if (int rc = read_counter(c, CT_EC_NEW, &n_new)) return rc;
             if (n_new > new_cap) k_edge_dilate<<<nblocks(c->N), TPB, 0, c->stream>>>(g, c->known, 0, g.nx, -3);
             else if (n_new) k_edge_dilate_list<<<nblocks(n_new), TPB, 0, c->stream>>>(light(g), c->known, c->list + n, n_new, nullptr);
         }
@@ -549,17 +559,17 @@ static int edge_check_resolve(xb_ctx *c, int n, const int8_t *cls, int near_xa, 
     // (the sweep also lists the voxels flagged -2 afterwards, the retrace list of the next pass, into `list` itself: its
     // compacted entries and the new-edge list behind them have served)
     const int fin_cap = (int)std::min<long long>(c->list_cap, 0x7fffffffLL);
-    k_ec_finish<<<(unsigned)std::min<long long>(nblocks((c->N + 15) / 16), 2048), TPB, 0, c->stream>>>(c->known, c->N, c->counters64,
-                                                                                                      count_lo, count_hi, c->list, c->counters + 26, fin_cap);
+    k_ec_finish<<<(unsigned)std::min<long long>(nblocks((c->N + 15) / 16), 2048), TPB, 0, c->stream>>>(c->known, c->N, c->counters64 + C64_EC_EDGES,
+                                                                                                      count_lo, count_hi, c->list, c->counters + CT_EC_NEXT, fin_cap);
     HIPCHK(hipGetLastError());
     unsigned long long r[2];
-    HIPCHK(hipMemcpyAsync(r, c->counters64, sizeof r, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(c->host_ints, c->counters + 25, 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));   // undecided, list length
+    HIPCHK(hipMemcpyAsync(r, c->counters64 + C64_EC_EDGES, sizeof r, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(c->host_ints, c->counters + CT_EC_UNDECIDED, CT_INTS(CT_EC_UNDECIDED, CT_EC_NEXT) * sizeof(int), hipMemcpyDeviceToHost, c->stream));   // undecided, list length
     HIPCHK(hipStreamSynchronize(c->stream));
     if (c->host_ints[0]) return fail(XB_E_STATE, "xb_edge_check: %d edge voxels left undecided", c->host_ints[0]);
     if (c->host_ints[1] <= fin_cap) { c->list_n = c->host_ints[1]; c->list_valid = true; }   // (else: the next pass compacts the flags itself)
-    if (edges) *edges = (int64_t)r[0];
-    if (checked) *checked = (int64_t)(r[1] + r[0]);  // refinement.py:479 + 504
+    if (edges) *edges = (int64_t)r[C64_EC_EDGES];
+    if (checked) *checked = (int64_t)(r[C64_EC_CHECKED] + r[C64_EC_EDGES]);  // refinement.py:479 + 504
     return XB_OK;
 }
 
@@ -576,14 +586,14 @@ int xb_edge_check(xb_ctx *c, int64_t *checked, int64_t *edges) {
         n = chg_n;
         if (n) {
             HIPCHK(hipMemcpyAsync(c->list, (int *)c->stage + c->N, (size_t)n * sizeof(int), hipMemcpyDeviceToDevice, c->stream));
-            HIPCHK(hipMemcpyAsync(c->host_ints + 8, c->fs + FS_N_CHGLIST, sizeof(int), hipMemcpyDeviceToHost, c->stream));   // (checked below)
+            HIPCHK(hipMemcpyAsync(c->host_ints + HI_EC_CHGLIST, c->fs + FS_N_CHGLIST, sizeof(int), hipMemcpyDeviceToHost, c->stream));   // (checked below)
             listed = true;
         }
     } else if (int rc = compact(c, -2, &n)) return rc;
     if (int rc = edge_check_resolve(c, n, nullptr, 0, g.nx, 0, c->N, checked, edges)) return rc;
     // (the list was launched after the retrace pass's wait, its length taken from the pass's count of relabelled voxels: the
     // kernel's own count came back with the first wait above and must agree)
-    if (listed && c->host_ints[8] != n) return fail(XB_E_STATE, "xb_edge_check: %d voxels listed for %d relabelled ones", c->host_ints[8], n);
+    if (listed && c->host_ints[HI_EC_CHGLIST] != n) return fail(XB_E_STATE, "xb_edge_check: %d voxels listed for %d relabelled ones", c->host_ints[HI_EC_CHGLIST], n);
     return XB_OK;
 }
 
@@ -635,12 +645,8 @@ int xb_edge_check_global(xb_ctx *c, const int64_t *idx, const int8_t *cls, int64
         i32[k] = (int)idx[k];
     }
     // planes outside this rank's valid range hold stale flags: neutralise them, then flag the whole global list
-    if (g.vlen < g.nx) {
-        const int a = g.vx0 + g.vlen;   // invalid planes: [a, a + nx - vlen) modulo nx
-        const int len = g.nx - g.vlen, first = a % g.nx, run1 = std::min(len, g.nx - first);
-        HIPCHK(hipMemsetAsync(c->known + (size_t)first * g.nyz, 2, (size_t)run1 * g.nyz, c->stream));
-        if (len > run1) HIPCHK(hipMemsetAsync(c->known, 2, (size_t)(len - run1) * g.nyz, c->stream));
-    }
+    if (g.vlen < g.nx)   // invalid planes: [vx0 + vlen, vx0 + nx) modulo nx
+        if (int rc = preset_known_planes(c, (g.vx0 + g.vlen) % g.nx, g.nx - g.vlen)) return rc;
     int8_t *dcls = c->st + (c->N - n);   // the tail of `st` (its head receives the decisions of k_ec_collect)
     if (2 * n > c->N || 2 * n > c->list_cap) return fail(XB_E_LIMIT, "xb_edge_check_global: list longer than half the grid / the list buffer");
     if (int rc = upload_pinned(c, c->list, i32.data(), n * sizeof(int))) return rc;
@@ -679,14 +685,8 @@ static int refine_iteration_fused(xb_ctx *c, int64_t *edges, int64_t *changed, b
         const int small = small_grid(g);
         int *buni = nullptr;
         int ntiles_listed = 0;
-        if (g.nx >= 16 && g.ny >= 16 && g.nz >= 16) {   // (any such grid: the brick lattice is ceil(n / 8))
-            const int nb0 = (g.nx + 7) / 8, nb1 = (g.ny + 7) / 8, nb2 = (g.nz + 7) / 8, nbr = nb0 * nb1 * nb2;
-            buni = reinterpret_cast<int *>(c->st);
-            if (!c->buni_valid)
-                k_label_uniform_list<<<4096, TPB, 0, c->stream>>>(gl, c->labels, nb1, nb2, nullptr, nbr, nullptr, nullptr, buni, 0, nbr);
-            k_buni3<<<(nbr + 255) / 256, 256, 0, c->stream>>>(nb0, nb1, nb2, buni, buni + nbr);
-            buni += nbr;
-        }
+        if (g.nx >= 16 && g.ny >= 16 && g.nz >= 16)   // (any such grid, every brick)
+            buni = launch_brick_uniformity(c, gl, 0, ((g.nx + 7) / 8) * ((g.ny + 7) / 8) * ((g.nz + 7) / 8), 4096);
         const unsigned char *brec = (c->grad_valid && c->grad_cover == 1) || late_records ? c->brick_rec : nullptr;
         if (buni) {
             // flags preset to "known", then only the tiles that are not of one non-vacuum label with their surroundings
@@ -742,7 +742,7 @@ static int refine_iteration_fused(xb_ctx *c, int64_t *edges, int64_t *changed, b
                                          fs + FS_R_OVF, c->ovf_cap, c->brick_rec, nullptr, nullptr, 0, nullptr, wl);
     }
     HIPCHK(hipGetLastError());
-    int *hr = c->host_ints + 3000;   // (its own corner: an assignment's block may still wait to be read at the front, xb_assign_refine)
+    int *hr = c->host_ints + HI_REFINE;   // (its own corner: an assignment's block may still wait to be read at the front, xb_assign_refine)
     HIPCHK(hipMemcpyAsync(hr, fs + FS_N_EDGES, 7 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     if (c->pending_assign && !assign_neargrid_complete(c, &c->pending_n_maxima)) return XB_STEP_REDO;   // (nothing below is to be trusted)
@@ -773,15 +773,15 @@ static int refine_iteration_fused(xb_ctx *c, int64_t *edges, int64_t *changed, b
         const bool can_defer = c->grad_cover == 1 && !regions_ok;
         if (!can_defer && c->stage_bytes >= sizeof(int) * (size_t)novf) {
             int *list2 = (int *)c->stage;
-            HIPCHK(hipMemsetAsync(c->counters + 1, 0, sizeof(int), c->stream));
+            HIPCHK(hipMemsetAsync(c->counters + CT_MID_LEFT, 0, sizeof(int), c->stream));
             launch_refine_trace<XB_MID_K, false>(c, nblocks(novf), TPB, c->ovf_list, novf, nullptr, fs + FS_CHANGED, fs + FS_ESCAPED, list2,
-                                                 c->counters + 1, novf, brec, nullptr, nullptr, regions_ok, nullptr, WalkerIO{});
+                                                 c->counters + CT_MID_LEFT, novf, brec, nullptr, nullptr, regions_ok, nullptr, WalkerIO{});
             HIPCHK(hipGetLastError());
             slow_list = list2;
-            slow_n_dev = c->counters + 1;   // (the list's length stays on the device; novf bounds it)
+            slow_n_dev = c->counters + CT_MID_LEFT;   // (the list's length stays on the device; novf bounds it)
             if (c->opt_dbg & 4) {
                 int m2 = 0;
-                if (int rc = read_counter(c, 1, &m2)) return rc;
+                if (int rc = read_counter(c, CT_MID_LEFT, &m2)) return rc;
                 fprintf(stderr, "[refine] %d retraces listed, %d left for the exact slow kernel after the %d-voxel window\n", novf, m2, XB_MID_K);
             }
         }

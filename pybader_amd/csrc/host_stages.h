@@ -22,6 +22,7 @@ static const int *slab_regions_of(const xb_ctx *c) {
 
 // The prologue of an assignment: `counts` (n ints) zeroed, `first` refilled when a previous assignment did not finish (it may
 // hold stale minima); invalidate: the label-derived state (brick uniformity, region labels, edge lists) goes too.
+static_assert(CT_REDO == CT_N_MAX + 15, "a host-driven assignment zeroes CT_N_MAX .. CT_REDO at once");
 static int begin_assignment(xb_ctx *c, int *counts, int n, bool invalidate) {
     HIPCHK(hipMemsetAsync(counts, 0, n * sizeof(int), c->stream));
     if (!c->first_clean) {
@@ -127,7 +128,7 @@ static bool launch_persistent_trace(xb_ctx *c, bool lean_ok, bool part, const in
                                                                8, 1, lean ? bres : nullptr);
     if (window)
         k_ng_trace_list<2><<<512, TPB, 0, c->stream>>>(light(g), c->grad, box_max, c->blab, c->nbk[1], c->nbk[2], ovf, c->fs + FS_N_OVF, c->labels,
-                                                       c->first, c->max_list, c->fs + FS_N_MAX, c->max_cap, c->ovf_list, c->counters + 1,
+                                                       c->first, c->max_list, c->fs + FS_N_MAX, c->max_cap, c->ovf_list, c->counters + CT_N_OVF,
                                                        c->ovf_cap, trace_maxsteps(g), c->rho, c->dist_dev, has_vacuum);
     return lean != 0;
 }

@@ -1200,7 +1200,8 @@ __global__ __launch_bounds__(TPB) void k_ec_first(Grid g, int8_t *known, ec_word
 // round.  All cross-workgroup traffic is device-scope atomics on the status and counter words (they resolve at
 // the device coherence point; the workgroups sit on different XCDs, one L2 each) -- no __threadfence(): on the
 // 8-XCD gfx950 an agent-scope fence writes back and invalidates the XCD's L2 (~2 us each).
-// Queue overflows go to `ovf` and seed the next launch.
+// Queue overflows go to `ovf` and seed the next launch: the host swaps the two lists and their lengths (CT_EC_SEEDS_A /
+// CT_EC_SEEDS_B, k_fused.h) from one launch to the next.
 #define EC_CHASE_THREADS 1024
 #define EC_Q 6000   // queue entries per buffer (2 buffers of 64-bit entries, 94 KB of LDS)
 // Round 5: SHARING A LONG FRONT.  A workgroup keeps what it wakes, and the fronts are few: without sharing the workgroup that

@@ -41,6 +41,63 @@ enum {
     FS_TOTAL = FS_CURSOR0 + 8 * FS_CURSOR_STRIDE
 };
 
+// The older scratch block c->counters (ints, device) of the host-driven calls, the windowed slab table and the device-driven
+// slab step; `fs` lies behind it (CT_FS).  Nothing zeroes it as a whole: every user clears the slots it counts into.  A slot
+// with several names serves roles that are never live together; the alias says why.
+enum {
+    CT_N_MAX = 0,        // maxima noted by the host-driven assignment kernels and by the exact slow kernel (k_trace_slow)
+    CT_N_OVF = 1,        // walks listed in ovf_list for the exact slow kernel (assignment, retrace, k_list_unfinished)
+    CT_MID_LEFT = CT_N_OVF,   // ... what the middle tier leaves of them (list in `stage`): it starts after the host has read CT_N_OVF
+    CT_CHANGED = 2,      // retraces that relabelled their start voxel
+    CT_ESCAPED = 3,      // retraces that left the valid planes of a slab
+    CT_OG_MOVED = 4,     // k_og_jump: some pointer still moved in this launch
+    CT_N_EDGES = 5,      // length of c->list after an edge sweep
+    CT_N_COMPACT = CT_N_EDGES,   // ... after compact(): it rewrites the same list, so the sweep's count is dead by then
+    CT_HALO_EDGES = 6,   // slab sweep: edges of the halo planes (second list, only dilated from); spent when the sweep's launches end
+    CT_EC_SEEDS_A = CT_HALO_EDGES,   // edge_check: seeds of the even chase passes, overflows of the odd ones; runs between sweeps
+    CT_TEXT_TODO = CT_HALO_EDGES,    // text parser: tokens left to the host's strtod; a density is parsed outside any refinement
+    CT_EC_NEW = 7,       // edge_check: new edges listed behind the compacted ones (k_ec_apply)
+    CT_ESC_ERR = 8,      // xb_escaped_paths: k_trace_slow's error flag (neither written nor read: that mode reports a cut path in its lengths)
+    CT_N_WALK = 13,      // host-driven assignment: bricks on the walk list
+    CT_ANY_EQUAL = 14,   // k_any_equal: some label equals the value asked for
+    CT_REDO = 15,        // assignment: trajectories that left the table window, listed for the from-rho kernel
+    CT_DEFER = CT_REDO,  // retrace: the same list for the retraces (an assignment and a retrace pass never overlap on a stream)
+    CT_MID_LISTED = CT_REDO,   // fused assignment's tail: walkers handed to the middle tier (uploaded); no table window there
+    CT_WALK_OUT = 16,    // walkers exported by a retrace pass or re-exported by xb_walkers_continue
+    CT_WALK_RES = 17,    // (start voxel, label) results of xb_walkers_continue
+    CT_WALK_CHANGED = 18,   // voxels relabelled by applied walker results
+    CT_WALK_STUCK = 19,  // results that need the exact slow path (stay parked)
+    CT_WALK_LOST = 20,   // slab step: walkers or results lost to a full part
+    CT_WALK_ROUNDS = 21, // slab step: byte k != 0: this rank carried walkers on in round k
+    CT_TILES_OWN = 22,   // slab sweep: listed tiles of the owned planes
+    CT_TILES_HALO = 23,  // ... of the halo planes
+    CT_EC_SEEDS_B = 24,  // edge_check: overflows of the even chase passes, seeds of the odd ones
+    CT_EC_UNDECIDED = 25,   // edge_check: voxels the resolution left undecided (must be none)
+    CT_EC_NEXT = 26,     // edge_check: voxels flagged -2 afterwards, the next pass's retrace list (k_ec_finish)
+    CT_EC_DONE = 27,     // edge_check: processed voxels listed for k_ec_apply
+    CT_COUNT = 28,
+    CT_FS = 128          // where `fs` starts
+};
+static_assert(CT_COUNT <= CT_FS, "fs lies behind the counters");
+#define CT_INTS(first, last) ((last) - (first) + 1)   // slots first..last, for the memsets and copies that span several
+// ... the pairs among them (the longer ranges assert their layout where they are used)
+static_assert(CT_ESCAPED == CT_CHANGED + 1 && CT_WALK_RES == CT_WALK_OUT + 1 && CT_WALK_STUCK == CT_WALK_CHANGED + 1 &&
+              CT_TILES_HALO == CT_TILES_OWN + 1 && CT_EC_NEXT == CT_EC_UNDECIDED + 1, "slots cleared or read back as a pair");
+// c->counters64 (unsigned long long): [0] also counts the voxels of xb_vacuum_assign and xb_label_sum
+enum { C64_EC_EDGES = 0, C64_EC_CHECKED = 1 };   // edge_check: new edges in the counted range; boxes re-classified (k_ec_apply)
+static_assert(C64_EC_CHECKED == C64_EC_EDGES + 1, "cleared and read back as a pair");
+// Fixed corners of the pinned host_ints (HI_TOTAL ints).  The front belongs to whoever waits next: one int of read_counter, or
+// the FS_TOTAL + XB_SORT_MAX ints of a fused assignment's state block and sorted maxima.
+enum {
+    HI_EC_SEEDS0 = 1,    // edge_check chase: k_ec_first's seed count, read with pass 0's read_counter (front: that counter)
+    HI_EC_SHARE_ERR = 2, // ... and the sharing block's error flag
+    HI_EC_CHGLIST = 8,   // xb_edge_check: FS_N_CHGLIST, queued before edge_check_resolve whose read_counters use the front
+    HI_SLAB_DBG = 64,    // xb_slab_refine_counts (debug): CT_DEFER, behind block 5's 16 int64 at the front
+    HI_REFINE = 3000,    // refine_iteration_fused: its 7 counters; a deferred assignment's block may still wait at the front
+    HI_UPLOAD = 3100,    // one-int upload source of the fused assignment's tail (the block at the front is still being read)
+    HI_TOTAL = 4096
+};
+
 #define XB_REGIONS_MAX 65535   // trapping regions seeded by bricks (k_seed_bricks)
 
 #define XB_BOXES_MAX 1024   // regions whose rank sits in the LDS table of the relabel kernels (the others are looked up)
@@ -265,6 +322,7 @@ __global__ void k_seed_finish(int *fs) {
 // numbers maxima in scan order); first[m] := rank.  One block, bitonic sort in LDS; more than XB_SORT_MAX maxima
 // (noisy data) leave FS_SORT_OK = 0 and the host sorts instead.
 #define XB_SORT_MAX 2048
+static_assert(FS_TOTAL + XB_SORT_MAX <= HI_REFINE && HI_UPLOAD < HI_TOTAL, "host_ints: the far corners lie behind an assignment's block");
 __global__ __launch_bounds__(1024) void k_number_maxima(int *fs, int *first, const int *__restrict__ max_list, int max_cap,
                                                         int *sorted, int *sorted2 = nullptr) {
     __shared__ unsigned long long key[XB_SORT_MAX];

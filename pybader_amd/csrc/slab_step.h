@@ -24,7 +24,7 @@
 #define XB_TAB_ROWS 1024                    // maxima a rank reports through block 4 (more: status 2)
 #define XB_TAB_INTS (2 + 2 * XB_TAB_ROWS)   // [rows or -1, unused, (maximum, first voxel) ...]
 #define XB_SLAB_RANKS_MAX 64
-#define XB_XCNT 8                           // counters of a refinement pass (int64): edges, changed, escaped, walkers, overflows
+#define XB_XCNT XB_XC_COUNT                 // counters of a refinement pass (int64): the XB_XC_* entries of block 5 (bader_hip.h)
 // blocks 6 / 7: the walkers of a refinement pass (retraces that left their rank's valid planes, k_edges.h) and the results of
 // the ones carried on, one part per rank: [walkers, results, 0, 0][cap walkers][cap (start voxel, label) pairs].
 // The exchanges are blind (no count goes through the host), so the parts travel at fixed sizes: the pass itself may export
@@ -92,10 +92,10 @@ __global__ __launch_bounds__(1024) void k_slab_merge_list(const int *__restrict_
     __syncthreads();
     if (threadIdx.x == 0) fs[FS_N_MAX] = s_n;
 }
-// counters[18..22): voxels relabelled by applied walker results, stuck results, walkers / results lost to a full part, one
-// byte per round: this rank carried walkers on in it (summed over the ranks: how many did -- the scheduler sizes the next
-// pass's rounds by it).
-// blk: the block the last round gathered (its walkers are still travelling: xcnt[3], the same number on every rank)
+// This rank's XB_XC_* entries of block 5 from the pass's CT_* counters: relabelled voxels by retraces and by applied walker
+// results together, stuck results and walkers / results lost to a full part together, and CT_WALK_ROUNDS, one byte per round:
+// this rank carried walkers on in it (summed over the ranks: how many did -- the scheduler sizes the next pass's rounds by it).
+// blk: the block the last round gathered (its walkers are still travelling: XB_XC_TRAVELLING, the same number on every rank)
 __global__ void k_slab_pack_counts(long long *xcnt, const int *counters, const char *blk, int nranks, int rank, int cap) {
     long long open = 0, mine = 0;
     for (int r = 0; blk && r < nranks; r++) {
@@ -103,8 +103,9 @@ __global__ void k_slab_pack_counts(long long *xcnt, const int *counters, const c
         open += n;
         if (r == rank) mine = n;
     }
-    xcnt[0] = counters[5]; xcnt[1] = (long long)counters[2] + counters[18]; xcnt[2] = counters[3]; xcnt[3] = open; xcnt[4] = counters[1];
-    xcnt[5] = (long long)counters[19] + counters[20]; xcnt[6] = mine; xcnt[7] = counters[21];
+    xcnt[XB_XC_EDGES] = counters[CT_N_EDGES]; xcnt[XB_XC_CHANGED] = (long long)counters[CT_CHANGED] + counters[CT_WALK_CHANGED];
+    xcnt[XB_XC_ESCAPED] = counters[CT_ESCAPED]; xcnt[XB_XC_TRAVELLING] = open; xcnt[XB_XC_SLOW] = counters[CT_N_OVF];
+    xcnt[XB_XC_LOST] = (long long)counters[CT_WALK_STUCK] + counters[CT_WALK_LOST]; xcnt[XB_XC_MINE] = mine; xcnt[XB_XC_ROUNDS] = counters[CT_WALK_ROUNDS];
 }
 // a part that ran full: the surplus is lost (those retraces stay parked and are resolved by the path queries)
 __global__ void k_slab_walk_clamp(int *hdr, int *lost, int cap, int rcap) {
@@ -308,7 +309,7 @@ int xb_slab_assign_trace(xb_ctx *c) {
     int *box_max = c->boxbuf + BB_REGMAX, *box_first = c->boxbuf + BB_REGFIRST;
     c->box_max_tab = box_max;
     c->labels_zero_pending = false;   // every owned label is written, none is read (no vacuum; the halo planes are the peers')
-    if (int rc = begin_assignment(c, c->counters, 16, true)) return rc;
+    if (int rc = begin_assignment(c, c->counters + CT_N_MAX, CT_INTS(CT_N_MAX, CT_REDO), true)) return rc;
     {
         ScopedTimer t4(c, 4);
         k_slab_any_flag<<<1, 1, 0, c->stream>>>(slab_flags(c), c->slab_nranks, fs);
@@ -336,7 +337,7 @@ int xb_slab_assign_trace(xb_ctx *c) {
             ScopedTimer tw(c, 6);
             launch_persistent_trace(c, true, false, box_max, walk, 0, nullptr);
         }
-        k_slab_pack_table<<<1, 256, 0, c->stream>>>(slab_tables(c) + (size_t)c->slab_rank * XB_TAB_INTS, c->max_list, c->first, fs, c->counters + 1);
+        k_slab_pack_table<<<1, 256, 0, c->stream>>>(slab_tables(c) + (size_t)c->slab_rank * XB_TAB_INTS, c->max_list, c->first, fs, c->counters + CT_N_OVF);
     }
     HIPCHK(hipGetLastError());
     g.main_ties = 0;
@@ -408,15 +409,17 @@ int xb_slab_refine_pass(xb_ctx *c) {
     const GridL gl = light(g);
     if (dilate_owned) {
         ScopedTimer t(c, 2);
-        k_edge_dilate_list<<<2048, TPB, 0, c->stream>>>(gl, c->known, c->list, 0, c->counters + 5);
+        k_edge_dilate_list<<<2048, TPB, 0, c->stream>>>(gl, c->known, c->list, 0, c->counters + CT_N_EDGES);
     }
     c->g.main_ties = 0;
     c->list_valid = false; c->chg_n = -1;
     c->buni_valid = false;
     c->walk_n_out = 0; c->walk_n_res = 0; c->walk_out_dev = nullptr;
     c->walk_host.clear(); c->res_host.clear();
-    HIPCHK(hipMemsetAsync(c->counters, 0, 5 * sizeof(int), c->stream));           // overflows, changed, escaped ...
-    HIPCHK(hipMemsetAsync(c->counters + 6, 0, 18 * sizeof(int), c->stream));      // ... deferred [15], walker statistics [18..22) (the sweep's own counts [6], [22], [23] are spent)
+    // everything but the sweep's edge count: overflows, changed, escaped ... deferred, the walker statistics (the sweep's own halo and tile counts are spent)
+    static_assert(CT_OG_MOVED == CT_N_MAX + 4 && CT_N_EDGES == CT_OG_MOVED + 1 && CT_HALO_EDGES == CT_N_EDGES + 1 && CT_TILES_HALO == CT_HALO_EDGES + 17, "two memsets either side of CT_N_EDGES");
+    HIPCHK(hipMemsetAsync(c->counters + CT_N_MAX, 0, CT_INTS(CT_N_MAX, CT_OG_MOVED) * sizeof(int), c->stream));
+    HIPCHK(hipMemsetAsync(c->counters + CT_HALO_EDGES, 0, CT_INTS(CT_HALO_EDGES, CT_TILES_HALO) * sizeof(int), c->stream));
     {
         ScopedTimer t(c, 3);
         const unsigned char *brec = c->grad_cover == 1 ? c->brick_rec : nullptr;
@@ -430,12 +433,12 @@ int xb_slab_refine_pass(xb_ctx *c) {
         wio.out = (Walker *)(part + 16); wio.out_count = (int *)part;
         wio.out_cap = walk_send_of(c, c->wcap);
         const unsigned grid = (unsigned)std::min<long long>(nblocks((long long)(g.x1 - g.x0) * g.nyz / 16), 1 << 20);
-        launch_refine_trace<2, false, false, true>(c, grid, TPB, c->list, 0, c->counters + 5, c->counters + 2, c->counters + 3, c->ovf_list,
-                                                   c->counters + 1, c->ovf_cap, brec, defer, c->counters + 15, regions_ok, slab_regions, wio);
-        launch_refine_trace<2, true>(c, 512, TPB, defer, 0, c->counters + 15, c->counters + 2, c->counters + 3, c->ovf_list, c->counters + 1,
+        launch_refine_trace<2, false, false, true>(c, grid, TPB, c->list, 0, c->counters + CT_N_EDGES, c->counters + CT_CHANGED, c->counters + CT_ESCAPED, c->ovf_list,
+                                                   c->counters + CT_N_OVF, c->ovf_cap, brec, defer, c->counters + CT_DEFER, regions_ok, slab_regions, wio);
+        launch_refine_trace<2, true>(c, 512, TPB, defer, 0, c->counters + CT_DEFER, c->counters + CT_CHANGED, c->counters + CT_ESCAPED, c->ovf_list, c->counters + CT_N_OVF,
                                      c->ovf_cap, brec, nullptr, nullptr, 0, slab_regions, wio);
     }
-    k_slab_walk_clamp<<<1, 1, 0, c->stream>>>((int *)((char *)c->wbuf[0] + (size_t)c->slab_rank * walk_part(c->wcap)), c->counters + 20, walk_send_of(c, c->wcap),
+    k_slab_walk_clamp<<<1, 1, 0, c->stream>>>((int *)((char *)c->wbuf[0] + (size_t)c->slab_rank * walk_part(c->wcap)), c->counters + CT_WALK_LOST, walk_send_of(c, c->wcap),
                                               walk_results_of(c, c->wcap));
     HIPCHK(hipGetLastError());
     c->slab_stage = 3;
@@ -458,20 +461,20 @@ int xb_slab_walkers_round(xb_ctx *c, int src, int last) {
     const int cap = c->wcap;
     char *part = (char *)c->wbuf[1 - src] + (size_t)c->slab_rank * walk_part(cap);
     int *n_in = (int *)((char *)c->wk_in + (size_t)cap * sizeof(Walker));
-    k_slab_walk_apply<<<pgrid, 256, 0, c->stream>>>(gl, blk, g.x0, g.x1, c->labels, c->known, c->counters + 18, c->counters + 19, cap,
+    k_slab_walk_apply<<<pgrid, 256, 0, c->stream>>>(gl, blk, g.x0, g.x1, c->labels, c->known, c->counters + CT_WALK_CHANGED, c->counters + CT_WALK_STUCK, cap,
                                                     last ? nullptr : (int *)part, n_in);
     if (!last) {
-        k_slab_walk_collect<<<pgrid, 256, 0, c->stream>>>(gl, blk, g.x0, g.x1, (Walker *)c->wk_in, n_in, c->counters + 20, cap);
-        k_slab_walk_clamp_in<<<1, 1, 0, c->stream>>>(n_in, c->counters + 21, c->walk_round++, cap);
+        k_slab_walk_collect<<<pgrid, 256, 0, c->stream>>>(gl, blk, g.x0, g.x1, (Walker *)c->wk_in, n_in, c->counters + CT_WALK_LOST, cap);
+        k_slab_walk_clamp_in<<<1, 1, 0, c->stream>>>(n_in, c->counters + CT_WALK_ROUNDS, c->walk_round++, cap);
         WalkerIO wio{};
         wio.in = (const Walker *)c->wk_in;
         wio.out = (Walker *)(part + 16); wio.out_count = (int *)part; wio.out_cap = walk_later_of(c, cap);
         wio.res = (int *)(part + 16 + (size_t)cap * sizeof(Walker)); wio.res_count = (int *)part + 1;
         wio.own0 = g.x0; wio.own1 = g.x1;
         const unsigned char *brec = c->grad_cover == 1 ? c->brick_rec : nullptr;
-        launch_refine_trace<2, true, true>(c, std::min(cap / TPB, 512), TPB, nullptr, 0, n_in, c->counters + 2, c->counters + 3, c->ovf_list,
-                                           c->counters + 1, c->ovf_cap, brec, nullptr, nullptr, 0, slab_regions_of(c), wio);
-        k_slab_walk_clamp<<<1, 1, 0, c->stream>>>((int *)part, c->counters + 20, walk_later_of(c, cap), walk_results_of(c, cap));
+        launch_refine_trace<2, true, true>(c, std::min(cap / TPB, 512), TPB, nullptr, 0, n_in, c->counters + CT_CHANGED, c->counters + CT_ESCAPED, c->ovf_list,
+                                           c->counters + CT_N_OVF, c->ovf_cap, brec, nullptr, nullptr, 0, slab_regions_of(c), wio);
+        k_slab_walk_clamp<<<1, 1, 0, c->stream>>>((int *)part, c->counters + CT_WALK_LOST, walk_later_of(c, cap), walk_results_of(c, cap));
     } else {
         k_slab_pack_counts<<<1, 1, 0, c->stream>>>(slab_counts(c), c->counters, blk, c->slab_nranks, c->slab_rank, cap);
         c->walk_last = src;
@@ -483,7 +486,7 @@ int xb_slab_walkers_round(xb_ctx *c, int src, int last) {
 
 // ONE host wait: this rank's counters and their sums over the ranks (block 5 after its all-reduce): edges, changed,
 // escaped, exported walkers, retraces for the exact slow kernel.  Exported walkers are fetched here (xb_walkers_fetch);
-// retraces for the slow kernel are run here, and local[1], local[2] then hold the counts after them (the caller sums again).
+// retraces for the slow kernel are run here, and local[XB_XC_CHANGED], local[XB_XC_ESCAPED] then hold the counts after them (the caller sums again).
 int xb_slab_refine_counts(xb_ctx *c, int64_t *local, int64_t *global) {
     NEED_GRID("xb_slab_refine_counts");
     if (c->slab_stage != 3) return fail(XB_E_STATE, "xb_slab_refine_counts: call xb_slab_refine_pass first");
@@ -493,28 +496,28 @@ int xb_slab_refine_counts(xb_ctx *c, int64_t *local, int64_t *global) {
     HIPCHK(hipStreamSynchronize(c->stream));
     long long loc[XB_XCNT], glo[XB_XCNT];
     for (int i = 0; i < XB_XCNT; i++) { loc[i] = h[i]; glo[i] = h[XB_XCNT + i]; }
-    c->list_n = (int)loc[0];
+    c->list_n = (int)loc[XB_XC_EDGES];
     if (c->opt_dbg & 16) {
-        HIPCHK(hipMemcpyAsync(c->host_ints + 64, c->counters + 15, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(c->host_ints + HI_SLAB_DBG, c->counters + CT_DEFER, sizeof(int), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
-        fprintf(stderr, "[slab %d] edges %lld, retraces redone from rho %d, exported %lld\n", c->slab_rank, loc[0], c->host_ints[64], loc[2]);
+        fprintf(stderr, "[slab %d] edges %lld, retraces redone from rho %d, exported %lld\n", c->slab_rank, loc[XB_XC_EDGES], c->host_ints[HI_SLAB_DBG], loc[XB_XC_ESCAPED]);
     }
     c->walk_n_out = 0; c->walk_n_res = 0;
-    if (loc[6] > 0 && c->walk_last >= 0) {   // walkers still travelling after the rounds: the scheduler's host loop takes them on
-        c->walk_n_out = (int)loc[6];
+    if (loc[XB_XC_MINE] > 0 && c->walk_last >= 0) {   // walkers still travelling after the rounds: the scheduler's host loop takes them on
+        c->walk_n_out = (int)loc[XB_XC_MINE];
         c->walk_host.resize((size_t)c->walk_n_out * (sizeof(Walker) / 8));
         const char *part = (const char *)c->wbuf[c->walk_last] + (size_t)c->slab_rank * walk_part(c->wcap);
         if (int rc = download_pinned(c, c->walk_host.data(), part + 16, (size_t)c->walk_n_out * sizeof(Walker))) return rc;
     }
-    const int novf = (int)loc[4];
+    const int novf = (int)loc[XB_XC_SLOW];
     if (novf > c->ovf_cap) return fail(XB_E_LIMIT, "%d retraces need the slow path (cap %d)", novf, c->ovf_cap);
     c->stat_ovf_refine += novf;
     if (novf > 0) {
         if (int rc = run_slow(c, novf, 1)) return rc;
-        HIPCHK(hipMemcpyAsync(c->host_ints, c->counters + 2, 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipMemcpyAsync(c->host_ints + 2, c->counters + 18, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(c->host_ints, c->counters + CT_CHANGED, CT_INTS(CT_CHANGED, CT_ESCAPED) * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(c->host_ints + 2, c->counters + CT_WALK_CHANGED, sizeof(int), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
-        loc[1] = (long long)c->host_ints[0] + c->host_ints[2]; loc[2] = c->host_ints[1];
+        loc[XB_XC_CHANGED] = (long long)c->host_ints[0] + c->host_ints[2]; loc[XB_XC_ESCAPED] = c->host_ints[1];
     }
     for (int i = 0; i < XB_XCNT; i++) { if (local) local[i] = loc[i]; if (global) global[i] = glo[i]; }
     return XB_OK;
@@ -539,7 +542,7 @@ int xb_comm_allgather_block(xb_ctx *c, int which, const int64_t *first, const in
     NCCL_GROUP_END(ge, "xb_comm_allgather_block");
     return XB_OK;
 }
-// block 5: summed[0..8) := sum over ranks of local[0..8)
+// block 5: summed[0..XB_XC_COUNT) := sum over ranks of local[0..XB_XC_COUNT)
 int xb_comm_allreduce_block(xb_ctx *c) {
     if (int rc = comm_need(c, "xb_comm_allreduce_block")) return rc;
     if (!c->xbuf) return fail(XB_E_STATE, "xb_comm_allreduce_block: no block");

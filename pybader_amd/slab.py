@@ -18,6 +18,9 @@ import time
 
 import numpy as np
 
+from ._lib import (XB_XC_CHANGED, XB_XC_EDGES, XB_XC_ESCAPED, XB_XC_LOST, XB_XC_MINE, XB_XC_ROUNDS, XB_XC_SLOW,
+                   XB_XC_TRAVELLING)   # the entries of slab_refine_counts()
+
 
 def slab_ranges(nx, nranks):
     """Contiguous planes of axis 0 per rank.  A grid of whole 8^3 bricks with at least one brick per rank is split on brick
@@ -265,23 +268,23 @@ class SlabRunner:
             self.comm.allreduce_block(self.be)
         with _Phase(self, 'refine_wait'), self._guard('refinement pass'):
             loc, glo = self.be.slab_refine_counts()
-        edges, changed = int(glo[0]), int(glo[1])
+        edges, changed = int(glo[XB_XC_EDGES]), int(glo[XB_XC_CHANGED])
         if os.environ.get('XB_SLAB_DEBUG'):
             print(f'[rank {self.comm.rank}] refinement pass: local {loc.tolist()} summed {glo.tolist()}', file=sys.stderr, flush=True)
-        if glo[4]:      # rare: some retraces went through the exact slow kernel after the sums were taken
+        if glo[XB_XC_SLOW]:      # rare: some retraces went through the exact slow kernel after the sums were taken
             with _Phase(self, 'sums'):
-                changed, = self.comm.sum(int(loc[1]))
+                changed, = self.comm.sum(int(loc[XB_XC_CHANGED]))
         # (rounds of the next pass: as many as carried a walker on in this one, two more after a pass that left some travelling
         # -- those went through the host-driven loop below; every rank sees the same sums)
-        used = max([k + 1 for k in range(4) if (int(glo[7]) >> (8 * k)) & 0xff] or [0])
-        self._walker_rounds = min(6, max(1, used) + (2 if loc[3] else 0))
-        # (glo[2]: retraces that left their rank's planes, all ranks and rounds together; three times the mean share covers the uneven
-        # split between ranks -- the interior slabs of an 8-atom cell export twice the mean; glo[5]: lost or stuck -> the capacity again)
-        self._walk_send = 0 if glo[5] else max(2048, 3 * int(glo[2]) // max(1, self.comm.size))
-        if glo[2]:
+        used = max([k + 1 for k in range(4) if (int(glo[XB_XC_ROUNDS]) >> (8 * k)) & 0xff] or [0])
+        self._walker_rounds = min(6, max(1, used) + (2 if loc[XB_XC_TRAVELLING] else 0))
+        # (XB_XC_ESCAPED: retraces that left their rank's planes, all ranks and rounds together; three times the mean share covers the uneven
+        # split between ranks -- the interior slabs of an 8-atom cell export twice the mean; XB_XC_LOST: lost or stuck -> the capacity again)
+        self._walk_send = 0 if glo[XB_XC_LOST] else max(2048, 3 * int(glo[XB_XC_ESCAPED]) // max(1, self.comm.size))
+        if glo[XB_XC_ESCAPED]:
             self.n_fallbacks += 1
-        if loc[3] or glo[5]:
-            changed += self._finish_escaped(int(loc[6] + loc[5]))
+        if loc[XB_XC_TRAVELLING] or glo[XB_XC_LOST]:
+            changed += self._finish_escaped(int(loc[XB_XC_MINE] + loc[XB_XC_LOST]))
             self.n_fallbacks -= 1
         return edges, changed
 

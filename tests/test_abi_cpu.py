@@ -26,6 +26,20 @@ def test_header_and_binding_agree(lib):
         assert hasattr(lib, name), name
 
 
+def test_slab_count_enum_and_binding_agree():
+    """The XB_XC_* entries of the slab step's block 5 cross the ABI by position: the header's enum and the
+    constants _lib.py mirrors name the same entries with the same values, and none is missing on either side."""
+    hdr = open(os.path.join(ROOT, 'include', 'bader_hip.h')).read()
+    hdr = re.sub(r'/\*.*?\*/', '', hdr, flags=re.S)
+    body, = re.findall(r'enum\s*\{([^}]*\bXB_XC_[^}]*)\}', hdr)
+    declared = {name: int(value) for name, value in re.findall(r'\b(XB_XC_[A-Z0-9_]+)\s*=\s*(\d+)', body)}
+    assert len(declared) == len(re.findall(r'\bXB_XC_[A-Z0-9_]+', body)), 'every enumerator states its value'
+    mirrored = {name: getattr(_lib, name) for name in dir(_lib) if name.startswith('XB_XC_')}
+    assert declared == mirrored, set(declared.items()) ^ set(mirrored.items())
+    entries = sorted(v for k, v in declared.items() if k != 'XB_XC_COUNT')
+    assert entries == list(range(declared['XB_XC_COUNT'])) and declared['XB_XC_COUNT'] == 8
+
+
 def test_no_gpu_fails_loudly(lib):
     if lib.xb_device_count() > 0:
         pytest.skip('a GPU is present')
