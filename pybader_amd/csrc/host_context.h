@@ -73,6 +73,16 @@ void *xb_stream(xb_ctx *c) { return (void *)c->stream; }
 // `list` and `stage` hold lists over the planes a rank works on (edges, tiles, walkers, dtype staging) and a few
 // per-brick arrays: the whole grid's worth on one GPU, the slab + halo (+ tile rounding) on a slab.  Grown on demand,
 // never shrunk while the grid stays; contents are scratch between calls EXCEPT the walk list (set up after this).
+// `stage` also takes two things whose size the ATOM count sets, not the grid: the lattice + atom table of xb_synth_density
+// (16 + 5 n doubles, n <= XB_SYNTH_ATOMS_MAX) and the lattice + atoms + minima of xb_surface_distance (16 + 4 n doubles,
+// n <= XB_SURFACE_ATOMS_MAX).  On a tiny grid N * 8 bytes hold neither (3x3x3: 216 bytes, eight atoms need 448), so `stage`
+// never gets less than XB_STAGE_FLOOR, which covers both maxima; both calls check their bytes against stage_bytes as well.
+// (The dtype staging and xb_volume_mask go through `stage` a chunk of stage_bytes at a time; the slab branch has 64 MiB.)
+#define XB_SYNTH_ATOMS_MAX 4096
+#define XB_SURFACE_ATOMS_MAX 100000
+#define XB_STAGE_FLOOR ((size_t)4 << 20)
+static_assert((16 + 5 * (size_t)XB_SYNTH_ATOMS_MAX) * sizeof(double) <= XB_STAGE_FLOOR &&
+              (16 + 4 * (size_t)XB_SURFACE_ATOMS_MAX) * sizeof(double) <= XB_STAGE_FLOOR, "stage floor below a documented atom maximum");
 static int need_scratch(xb_ctx *c) {
     const Grid &g = c->g;
     const long long N = c->N ? c->N : (long long)g.nx * g.nyz;
@@ -80,7 +90,7 @@ static int need_scratch(xb_ctx *c) {
     long long planes = own + 2LL * (std::max(c->halo, 16) + 16);
     if (own == g.nx || planes >= g.nx) planes = g.nx;
     const long long list_want = planes == g.nx ? N : std::max<long long>(planes * g.nyz, 8 * (N / 512) + 4096);
-    const size_t stage_want = planes == g.nx ? (size_t)N * 8 : std::max<size_t>((size_t)planes * g.nyz * 8, (size_t)64 << 20);
+    const size_t stage_want = planes == g.nx ? std::max<size_t>((size_t)N * 8, XB_STAGE_FLOOR) : std::max<size_t>((size_t)planes * g.nyz * 8, (size_t)64 << 20);
     if (c->list_cap < list_want) {
         HIPCHK(hipStreamSynchronize(c->stream));
         hipFree(c->list); c->list = nullptr; c->list_cap = 0;
@@ -444,7 +454,9 @@ int xb_parse_cube_text(xb_ctx *c, const char *text, int64_t nbytes, int64_t nval
 int xb_synth_density(xb_ctx *c, const double lattice[9], const double *atoms5, int64_t n_atoms, double background) {
     if (c) c->vac_by_tol = false;   // (the -1 labels no longer say "rho <= vac_tol" of the density on the card)
     NEED_GRID("xb_synth_density");
-    if (n_atoms < 0 || n_atoms > 4096) return fail(XB_E_ARG, "xb_synth_density: bad atom count");
+    if (n_atoms < 0 || n_atoms > XB_SYNTH_ATOMS_MAX) return fail(XB_E_ARG, "xb_synth_density: bad atom count");
+    if ((16 + 5 * (size_t)n_atoms) * sizeof(double) > c->stage_bytes)   // (never with need_scratch's floor)
+        return fail(XB_E_LIMIT, "xb_synth_density: %lld atoms do not fit the scratch buffer", (long long)n_atoms);
     c->grad_valid = false; c->brick_max_valid = false;
     double *tmp = (double *)c->stage;
     HIPCHK(hipMemcpyAsync(tmp, lattice, 9 * sizeof(double), hipMemcpyHostToDevice, c->stream));

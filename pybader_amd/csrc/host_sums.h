@@ -85,7 +85,9 @@ int xb_atom_assign(const double *b_max, int64_t n_max, const double *atoms, int6
 int xb_surface_distance(xb_ctx *c, const double lattice[9], const double *atoms_cart, int64_t n_atoms,
                         double *min_d2, int64_t *edges_out) {
     NEED_GRID("xb_surface_distance");
-    if (n_atoms <= 0 || n_atoms > 100000) return fail(XB_E_ARG, "xb_surface_distance: bad atom count");
+    if (n_atoms <= 0 || n_atoms > XB_SURFACE_ATOMS_MAX) return fail(XB_E_ARG, "xb_surface_distance: bad atom count");
+    if ((16 + 4 * (size_t)n_atoms) * sizeof(double) > c->stage_bytes)   // (never with need_scratch's floor)
+        return fail(XB_E_LIMIT, "xb_surface_distance: %lld atoms do not fit the scratch buffer", (long long)n_atoms);
     int64_t edges = 0;
     if (int rc = xb_edge_find(c, &edges)) return rc;
     if (edges_out) *edges_out = edges;
@@ -106,11 +108,16 @@ int xb_surface_distance(xb_ctx *c, const double lattice[9], const double *atoms_
 
 int xb_volume_mask(xb_ctx *c, int64_t vol_num, double *out_host) {
     NEED_GRID("xb_volume_mask");
-    double *tmp = (double *)c->stage;  // N*8 bytes
-    k_volume_mask<<<nblocks(c->N), TPB, 0, c->stream>>>(c->rho, c->labels, (int)vol_num, tmp, c->N);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out_host, tmp, c->N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    // through `stage`, a chunk at a time when it is smaller than the grid (a slab's `stage` holds its planes, not N doubles)
+    double *tmp = (double *)c->stage;
+    const long long per = std::max<long long>(1, (long long)(c->stage_bytes / sizeof(double)));
+    for (long long o = 0; o < c->N; o += per) {
+        const long long n = std::min(per, c->N - o);
+        k_volume_mask<<<nblocks(n), TPB, 0, c->stream>>>(c->rho + o, c->labels + o, (int)vol_num, tmp, n);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(out_host + o, tmp, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));   // (`stage` is free again)
+    }
     return XB_OK;
 }
 

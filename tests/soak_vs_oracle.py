@@ -1,10 +1,12 @@
 """Random soak of the one-GPU pipeline against the CPU oracle (test infrastructure; run by hand on a GPU box, and in a short
 seeded form by tests/test_gpu_soak.py):
 
-    python tests/soak_vs_oracle.py [cases] [seed] [--method neargrid|ongrid] [--odd | --oddbig | --big]
+    python tests/soak_vs_oracle.py [cases] [seed] [--method neargrid|ongrid] [--odd | --oddbig | --big | --tiny | --thin]
 
 Each case: a random grid shape (whole 8^3 bricks, or anything from 10 to 60 with --odd: the routes for grids that are not
-made of bricks), one of four lattices, optional noise / plateaus / vacuum tolerance, a random refinement mode.  The library's
+made of bricks; every axis from 3 to 9 with --tiny: grids below one 8^3 brick, down to the axes of 3 and 4 voxels on which the
+planes x-2 and x+1 or x+2 are one plane; one such axis beside two of 16 to 96 with --thin: a short axis on both sides of the
+routes' `>= 16` and `nz < 80` tests), one of four lattices, optional noise / plateaus / vacuum tolerance, a random refinement mode.  The library's
 assignment (map, maxima in basin order) must equal the oracle's -- the own-trajectory map of methods.neargrid's stepping
 rule, or methods.ongrid's map -- and its refinement of that map the oracle's refinement, log and map.  Round 3: 1 800 cases
 of this soak found the slow kernel applying the vacuum rule to labels nobody had written (fixed, regression test in
@@ -22,8 +24,9 @@ HEX = np.array([[6.0, 0.0, 0.0], [-3.0, 5.196152422706632, 0.0], [0.0, 0.0, 7.0]
 ORTHO = np.array([[5.0, 0.0, 0.0], [0.0, 6.5, 0.0], [0.0, 0.0, 7.25]])
 
 
-def run(cases, seed, method='neargrid', odd=False, verbose=False, big=False, oddbig=False):
-    """-> descriptions of the cases whose result differs from the oracle's"""
+def run(cases, seed, method='neargrid', odd=False, verbose=False, big=False, oddbig=False, tiny=False, thin=False, shapes=None):
+    """-> descriptions of the cases whose result differs from the oracle's.  `shapes`: a list of grid shapes that replace the
+    drawn ones, case by case (everything else of a case is drawn as always)"""
     import oracle
     from pybader_amd import _lib, synth
     from pybader_amd.interface import distance_matrix, gradient_transform
@@ -39,8 +42,15 @@ def run(cases, seed, method='neargrid', odd=False, verbose=False, big=False, odd
             shape = tuple(int(rng.integers(41, 150)) for _ in range(3))
         elif odd:
             shape = tuple(int(rng.integers(10, 61)) for _ in range(3))
+        elif tiny:    # (--tiny: below one brick, axes of 3 and 4 voxels included)
+            shape = tuple(int(rng.integers(3, 10)) for _ in range(3))
+        elif thin:    # (--thin: one short axis, the other two on either side of the routes' axis-length tests)
+            short = int(rng.integers(3))
+            shape = tuple(int(rng.integers(3, 10)) if j == short else int(rng.choice([16, 24, 40, 80, 96])) for j in range(3))
         elif rng.random() < 0.3:
             shape = (shape[0], shape[1], int(rng.choice([64, 128])))     # whole tiles in z: the tile-wise dilation
+        if shapes is not None:
+            shape = tuple(int(v) for v in shapes[k])
         lname, lat = lattices[int(rng.integers(4))]
         noise = float(rng.choice([0.0, 0.0, 1e-6, 1e-3, 3e-2]))
         quant = float(rng.choice([0.0, 0.0, 0.0, 1.0 / 32]))
@@ -92,7 +102,7 @@ if __name__ == '__main__':
     if '--method' in sys.argv:
         args.remove(method)
     failures = run(int(args[0]) if args else 20, int(args[1]) if len(args) > 1 else 1, method, '--odd' in sys.argv, verbose=True, big='--big' in sys.argv,
-                   oddbig='--oddbig' in sys.argv)
+                   oddbig='--oddbig' in sys.argv, tiny='--tiny' in sys.argv, thin='--thin' in sys.argv)
     print('\n'.join(failures))
     print('bad cases:', len(failures))
     sys.exit(1 if failures else 0)
