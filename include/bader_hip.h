@@ -51,7 +51,9 @@ void *xb_stream(xb_ctx *c);                      /* the hipStream_t every kernel
  * slab scheduler; x0=0,x1=nx for one GPU).  Every rank holds the full density.
  * SIZE LIMIT (the reference indexes with int64 throughout, methods.py / refinement.py): voxel indices are int32 on the
  * device, so a grid needs nx*ny*nz < 2^31 - 1 voxels (1024^3 = 2^30 fits; 1290^3 is the largest cube) -- more returns
- * XB_E_LIMIT before anything is allocated.  Every entry point works up to that size. */
+ * XB_E_LIMIT before anything is allocated.  Every entry point works up to that size.
+ * An axis of one or two voxels (it meets itself through the wrap) is accepted for the transfers, xb_vacuum_assign and the weight
+ * method; the assignment, refinement, table and sum entry points answer XB_E_ARG on such a grid. */
 int xb_set_grid(xb_ctx *c, const int64_t shape[3], const double dist_mat[27], const double T_grad[9],
                 int64_t x0, int64_t x1);
 int xb_upload_density(xb_ctx *c, const double *rho_host);           /* H2D, nx*ny*nz float64 */
@@ -229,6 +231,30 @@ int xb_assign_refine(xb_ctx *c, int method, int mode, int64_t iters, int64_t *n_
 
 /* utils.charge_sum (utils.py:235-252) via Bader.sum_volumes (interface.py:492-525) */
 int xb_charge_sum(xb_ctx *c, double voxel_volume, int64_t n_labels, double *charge, double *volume);
+/* ---- the weight method (Yu & Trinkle, J. Chem. Phys. 134, 064111; `bader -b weight`) -- no counterpart in the reference ----
+ * Charge and volume per maximum with the surface voxels split fractionally, next to xb_charge_sum.  The resident density is the
+ * partition field rho, the resident labels are read for their -1 marks (vacuum: absent, sends and receives nothing); neither is
+ * written.  alpha[27]: the neighbour weights facet area / distance of the voxel lattice's Voronoi cell (pybader_amd.weight.
+ * voronoi_weights), row-major [3][3][3] with index 2 == -1 like dist_mat, centre 0, symmetric bit for bit, finite, >= 0.
+ *   flux          f_ij = alpha_d * max(rho_j - rho_i, 0), S_i = sum_d f_ij in the table's C order, J_ij = f_ij / S_i;
+ *                 S_i == 0: voxel i is a maximum (every voxel of a plateau is its own)
+ *   accumulation  A_i = q_i + sum_d J_ji * A_j over the neighbours with f_ji > 0, same order; V_i with 1 for q_i
+ *   result        per maximum m, in ascending voxel index: A_m * voxel_volume, V_m * voxel_volume
+ * A pure function of its inputs (one writer per A_i, fixed order, no contraction): bit-identical to a float64 loop that visits
+ * the voxels in ascending rho.  The integrand q: q_host (nx*ny*nz float64, C order), NULL for rho itself, or with
+ * xb_weight_sum_device a device array under the CHECKS and ORDER of xb_import_density.
+ * XB_E_STATE: no grid, a context that holds a slab, or voxels left over on an empty frontier (a NaN in the density).
+ *   xb_weight_fetch   the results of the last call: linear voxel index, charge, volume of each maximum
+ *   xb_weight_stats   out = {levels, levels run as batched launches, levels run in the single-workgroup tail, batches (host waits
+ *                     of the level loop), voxels finished, largest frontier handed on by a batched level, device bytes of the
+ *                     method's own buffers (also counted by xb_memory_stats)} */
+int xb_weight_sum(xb_ctx *c, const double alpha[27], double voxel_volume, const double *q_host, int64_t *n_maxima);
+int xb_weight_sum_device(xb_ctx *c, const double alpha[27], double voxel_volume, const void *dev_ptr, int dtype,
+                         const int64_t stride[3], void *stream, int64_t *n_maxima);
+int xb_weight_fetch(xb_ctx *c, int64_t *max_idx, double *charge, double *volume, int64_t capacity);
+int xb_weight_stats(xb_ctx *c, int64_t out[7]);
+/* frees the method's device buffers (25 N bytes, kept between calls while the grid stays) and the fetched results */
+int xb_weight_release(xb_ctx *c);
 /* utils.volume_assign (utils.py:404-421): labels[v] = swap[labels[v]] for labels >= 0 */
 int xb_volume_assign(xb_ctx *c, const int64_t *swap, int64_t n_swap);
 /* utils.atom_assign (utils.py:185-232): nearest atom of every maximum over the 27 periodic images (one
@@ -344,7 +370,7 @@ int xb_kernel_time_reset(xb_ctx *c);
 /* on: 0 off, 1 every timer, otherwise a mask: bit k + 1 switches timer `which` = k on (event pairs between dependent kernels
  * cost stream time: a benchmark keeps only the dominant kernel's timer on inside its timed region) */
 int xb_enable_timing(xb_ctx *c, int on);
-/* Switches (nine keys).  A USER of the library sets none of them: every default is the measured best, and no switch changes a
+/* Switches (ten keys).  A USER of the library sets none of them: every default is the measured best, and no switch but 30 changes a
  * result.  What each is for:
  *   6   drop the cached gradient-field table (benchmarks: a table kept from an earlier step would hide 1.6 ms per step);
  *   3   debug (bit 2 edge_check passes, bit 4 slab statistics, bit 5 wait after every stage of an assignment, bit 6 the exact
@@ -355,6 +381,8 @@ int xb_enable_timing(xb_ctx *c, int on);
  *       1 no mirror prefilter in pass A, 2 the generic walker instead of the lean one, 4 the full T_grad . grad product on
  *       orthogonal lattices, 8 dilation from the edge list instead of tile by tile, 16 int32 label halos, 32 no front sharing
  *       in the edge_check chase, 64 xb_import_density gathers a permuted layout voxel by voxel instead of through the LDS tile;
+ *   30  xb_weight_sum ignores the resident labels (1: no voxel is vacuum, the labels are not read; pybader_amd.weight sets it for
+ *       a call without a label map and clears it again) -- the one switch that selects an input rather than an implementation;
  *   test plumbing -- 4 / 5 workgroups and LDS queue capacity of the edge_check chase (lowered to force the overflow
  *   hand-over), 17 kill launches scheduled after a chase (1 forces the repeat), 19 a rank may exchange planes with itself.
  * (Round 4 removed 0, 2, 9-12, 15, 21; round 6 removed 7, 8, 16, 22 -- routes and launch shapes nobody set -- and folded 13, 14,

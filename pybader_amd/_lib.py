@@ -74,6 +74,11 @@ SYMBOLS = {
     'xb_refine': (_int, [_vp, _int, _i64, _vp, _i64, _pi64]),
     'xb_assign_refine': (_int, [_vp, _int, _int, _i64, _pi64, _vp, _i64, _pi64]),
     'xb_charge_sum': (_int, [_vp, _dbl, _i64, _vp, _vp]),
+    'xb_weight_sum': (_int, [_vp, _pdbl, _dbl, _vp, _pi64]),
+    'xb_weight_sum_device': (_int, [_vp, _pdbl, _dbl, _vp, _int, _pi64, _vp, _pi64]),
+    'xb_weight_fetch': (_int, [_vp, _vp, _vp, _vp, _i64]),
+    'xb_weight_stats': (_int, [_vp, _pi64]),
+    'xb_weight_release': (_int, [_vp]),
     'xb_volume_assign': (_int, [_vp, _vp, _i64]),
     'xb_atom_assign': (_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp]),
     'xb_surface_distance': (_int, [_vp, _vp, _vp, _i64, _vp, _pi64]),
@@ -139,6 +144,7 @@ class BaderHipError(RuntimeError):
 
 
 XB_E_ARG = -1     # a bad argument, or a number in the text that does not convert
+XB_E_STATE = -3   # a call the context's state does not allow (no grid, a slab where the whole grid is needed)
 XB_E_LIMIT = -4   # a size beyond what the library indexes
 XB_E_SHORT = -6   # xb_parse_density_text / xb_parse_cube_text: the text holds fewer numbers than the grid needs
 
@@ -693,6 +699,55 @@ class Context:
         ch, vo = np.zeros(n_labels, np.float64), np.zeros(n_labels, np.float64)
         check(self.lib.xb_charge_sum(self.h, float(voxel_volume), int(n_labels), _ptr(ch), _ptr(vo)))
         return ch, vo
+
+    def weight_sum(self, alpha, voxel_volume, q=None, use_labels=True):
+        """the weight method on the resident density and labels (xb_weight_sum): `q` None integrates the resident density
+        itself, a host array or a float32 / float64 device array of any strides another field of the grid's shape;
+        `use_labels` False: no voxel is vacuum and the resident labels are not read (neither way are they written);
+        -> (linear voxel index int64[M], charge f64[M], volume f64[M]) of the maxima in ascending voxel index"""
+        self.set_option(30, 0 if use_labels else 1)
+        try:
+            return self._weight_sum(alpha, voxel_volume, q)
+        finally:
+            self.set_option(30, 0)
+
+    def weight_release(self):
+        """free the weight method's device buffers (they are kept between calls while the grid stays)"""
+        check(self.lib.xb_weight_release(self.h))
+
+    def _weight_sum(self, alpha, voxel_volume, q):
+        from . import device
+        al = _f64(alpha).reshape(27)
+        n = C.c_int64()
+        if q is not None and device.is_device_array(q):
+            d = device.describe(q)
+            if d.shape != self.shape:
+                self._refuse_shape('weight_sum', d.shape)
+            if d.dtype not in device.FLOAT_CODE:
+                err = BaderHipError(f'weight_sum: dtype {d.dtype.name} is neither float32 nor float64')
+                err.code = XB_E_ARG
+                raise err
+            st = (C.c_int64 * 3)(*d.strides)
+            check(self.lib.xb_weight_sum_device(self.h, al.ctypes.data_as(_pdbl), float(voxel_volume), C.c_void_p(d.ptr),
+                                                device.FLOAT_CODE[d.dtype], st, device.stream_for(d), C.byref(n)))
+        else:
+            if q is not None:
+                q = _f64(q)
+                if q.shape != self.shape:
+                    self._refuse_shape('weight_sum', q.shape)
+            check(self.lib.xb_weight_sum(self.h, al.ctypes.data_as(_pdbl), float(voxel_volume),
+                                         None if q is None else _ptr(q), C.byref(n)))
+        idx, ch, vo = np.zeros(n.value, np.int64), np.zeros(n.value, np.float64), np.zeros(n.value, np.float64)
+        check(self.lib.xb_weight_fetch(self.h, _ptr(idx), _ptr(ch), _ptr(vo), n.value))
+        return idx, ch, vo
+
+    def weight_stats(self):
+        """the last weight_sum: levels, how many ran as batched launches and how many in the single-workgroup tail,
+        batches (host waits), voxels finished, largest batched frontier, device bytes of the method's buffers"""
+        out = (C.c_int64 * 7)()
+        check(self.lib.xb_weight_stats(self.h, out))
+        keys = ('levels', 'levels_batched', 'levels_tail', 'batches', 'voxels', 'peak_frontier', 'bytes')
+        return dict(zip(keys, (int(v) for v in out)))
 
     def volume_assign(self, swap):
         self.drop_label_token()

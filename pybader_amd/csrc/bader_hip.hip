@@ -1,7 +1,7 @@
 // bader_hip.hip -- libbader_hip.so: HIP kernels + C ABI (include/bader_hip.h) for gfx950.  ONE translation unit:
-//   kernels    k_common.h k_masks.h k_fused.h k_trace.h k_ongrid.h k_edges.h k_sums.h k_text.h k_format.h (fmt_core.h) k_interop.h
+//   kernels    k_common.h k_masks.h k_fused.h k_trace.h k_ongrid.h k_edges.h k_sums.h k_text.h k_format.h (fmt_core.h) k_interop.h k_weight.h
 //   host side  this file (context struct, options, statistics, timing) + host_context.h (life cycle, transfers)
-//              + host_assign.h (the table outside an assignment, the assignments) + host_refine.h + host_sums.h + host_slab_table.h (host-driven slab calls) + host_interop.h (device arrays in and out) + comm.h (RCCL through the ABI)
+//              + host_assign.h (the table outside an assignment, the assignments) + host_refine.h + host_sums.h + host_slab_table.h (host-driven slab calls) + host_interop.h (device arrays in and out) + host_weight.h (the weight method) + comm.h (RCCL through the ABI)
 //              + slab_step.h (the slab step with its control flow on the device)
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -shared (see pybader_amd/build.py).
 #include "bader_kernels.h"
@@ -34,6 +34,7 @@ static inline hipError_t xb_counted_sync(hipStream_t s) { xb_waits++; return (hi
 #include "k_text.h"
 #include "k_format.h"
 #include "k_interop.h"
+#include "k_weight.h"
 
 // =============================================================================================
 // host side
@@ -190,6 +191,19 @@ struct xb_ctx {
     unsigned timing = 0;   // bit k: timer k records its events (xb_enable_timing)
     TimedKernel tk[8];
     long long n_alloc = 0;
+    bool thin = false;         // an axis has fewer than 3 voxels: transfers, the vacuum sweep and the weight method only (NEED_GRID)
+    // the weight method (host_weight.h): accumulators, pending counts, the two work lists, S when `stage` cannot hold it, the
+    // level loop's state block; the last call's statistics and results
+    double *w_A = nullptr, *w_V = nullptr, *w_S = nullptr;
+    unsigned char *w_pending = nullptr;
+    int *w_list[2] = {nullptr, nullptr};
+    int *w_state = nullptr;
+    long long w_cap = 0;       // voxels the weight buffers hold (0: not allocated)
+    long long w_stat[6] = {0, 0, 0, 0, 0, 0};
+    bool w_have = false;
+    bool w_ignore_labels = false;   // option 30: the next xb_weight_sum treats no voxel as vacuum and does not read the labels
+    std::vector<int64_t> w_idx;
+    std::vector<double> w_charge, w_volume;
 };
 
 // utils.dtype_calc(-n) as a byte width (utils.py:25-37): the narrowest signed type for labels 0..n-1 and -1
@@ -297,6 +311,7 @@ const char *xb_last_error(void) { return g_err.c_str(); }
 #include "host_sums.h"
 #include "host_slab_table.h"
 #include "host_interop.h"
+#include "host_weight.h"
 
 int xb_set_option(xb_ctx *c, int key, int value) {
     if (!c) return fail(XB_E_ARG, "null ctx");
@@ -317,6 +332,7 @@ int xb_set_option(xb_ctx *c, int key, int value) {
     else if (key == 17 && value >= 1) c->grow_kill_launches = value;
     else if (key == 19) c->opt_self_exchange = value != 0;
     else if (key == 24) c->opt_async_comm = value != 0;
+    else if (key == 30) c->w_ignore_labels = value != 0;
     else return fail(XB_E_ARG, "xb_set_option: unknown key %d", key);
     return XB_OK;
 }
@@ -342,7 +358,8 @@ int xb_memory_stats(xb_ctx *c, int64_t *bytes_total, int64_t *bytes_table, int64
     if (!c || !c->has_grid) return fail(XB_E_STATE, "xb_memory_stats: no grid");
     const long long N = c->N;
     const long long table = c->grad_cap * (long long)sizeof(GradRec);
-    const long long scratch = c->list_cap * 4 + (long long)c->stage_bytes + c->ec_buf_cap * 4 + (c->ec_pend ? 8 * N + 16 : 0);
+    const long long scratch = c->list_cap * 4 + (long long)c->stage_bytes + c->ec_buf_cap * 4 + (c->ec_pend ? 8 * N + 16 : 0) +
+                              (c->w_cap ? 25 * c->w_cap + (c->w_S ? 8 * c->w_cap : 0) : 0) /* the weight method's buffers */;
     const long long fixed = 8 * N /* rho */ + 4 * N /* labels */ + (N + 16) /* known */ + 4 * N /* first */ + N /* st */ +
                             2LL * c->max_cap * 4 + (long long)c->ovf_cap * 4 + c->blab_alloc * 5 + (long long)c->walk_cap * 3 * 80 +
                             (1 << 22) /* boxbuf */;

@@ -31,7 +31,9 @@ int xb_create(int device, xb_ctx **out) {
     return XB_OK;
 }
 
+static void weight_free(xb_ctx *c);
 static void free_grid(xb_ctx *c) {
+    weight_free(c);
     hipFree(c->rho); hipFree(c->grad); hipFree(c->labels); hipFree(c->known); hipFree(c->first); hipFree(c->list);
     hipFree(c->st); hipFree(c->stage); hipFree(c->ec_pend); c->ec_pend = nullptr; hipFree(c->ec_share); c->ec_share = nullptr; hipFree(c->ec_pflag); c->ec_pflag = nullptr; hipFree(c->max_list); hipFree(c->max_aux); hipFree(c->ovf_list);
     hipFree(c->blab_buf); c->blab_buf = nullptr; c->blab_alloc = 0; c->labels_zero_pending = false;
@@ -136,8 +138,13 @@ static void set_valid_range(xb_ctx *c) {
 int xb_set_grid(xb_ctx *c, const int64_t shape[3], const double dist_mat[27], const double T_grad[9],
                 int64_t x0, int64_t x1) {
     if (!c || !shape) return fail(XB_E_ARG, "xb_set_grid: null argument");
-    for (int j = 0; j < 3; j++)
-        if (shape[j] < 3) return fail(XB_E_ARG, "xb_set_grid: every axis needs >= 3 voxels (got %lld)", (long long)shape[j]);
+    // An axis of one or two voxels meets itself through the wrap: the assignment, refinement and table kernels are not written
+    // for that (NEED_GRID refuses them such a grid); the transfers, the vacuum sweep and the weight method (NEED_GRID_THIN) are.
+    bool thin = false;
+    for (int j = 0; j < 3; j++) {
+        if (shape[j] < 1) return fail(XB_E_ARG, "xb_set_grid: every axis needs >= 1 voxel (got %lld)", (long long)shape[j]);
+        thin = thin || shape[j] < 3;
+    }
     const long long N = (long long)shape[0] * shape[1] * shape[2];
     if (N >= 2147483647LL) return fail(XB_E_LIMIT, "xb_set_grid: %lld voxels exceed the int32 index range", N);
     if (x0 < 0 || x1 > shape[0] || x0 >= x1) return fail(XB_E_ARG, "xb_set_grid: bad slab [%lld,%lld)", (long long)x0, (long long)x1);
@@ -175,6 +182,7 @@ int xb_set_grid(xb_ctx *c, const int64_t shape[3], const double dist_mat[27], co
     }
     if (T_grad && memcmp(g.T, T_grad, sizeof g.T) != 0) { memcpy(g.T, T_grad, sizeof g.T); c->grad_valid = false; c->brick_max_valid = false; }
     c->N = N;
+    c->thin = thin;
     c->halo = (x0 == 0 && x1 == shape[0]) ? g.nx : 0;
     set_valid_range(c);
     g.wx0 = 0; g.wlen = g.nx;      // table window: whole grid unless xb_set_table_window says otherwise
@@ -225,11 +233,17 @@ static int settle_labels(xb_ctx *c) {
     }
     return XB_OK;
 }
-#define NEED_GRID_RAW(name) \
+#define NEED_GRID_RAW_THIN(name) \
     if (!c || !c->has_grid) return fail(XB_E_STATE, name ": call xb_set_grid first"); \
     HIPCHK(hipSetDevice(c->device))
+#define NEED_GRID_RAW(name) \
+    NEED_GRID_RAW_THIN(name); \
+    if (c->thin) return fail(XB_E_ARG, name ": every axis needs >= 3 voxels (the grid is %d x %d x %d)", c->g.nx, c->g.ny, c->g.nz)
 #define NEED_GRID(name) \
     NEED_GRID_RAW(name); \
+    if (int rc_ = settle_labels(c)) return rc_
+#define NEED_GRID_THIN(name) \
+    NEED_GRID_RAW_THIN(name); \
     if (int rc_ = settle_labels(c)) return rc_
 
 // Large host <-> device transfers of PAGEABLE host memory (every numpy array at the boundary): the runtime stages them
@@ -313,14 +327,14 @@ static int staged_d2h(xb_ctx *c, void *dst_host, const void *src_dev, size_t byt
 
 int xb_upload_density(xb_ctx *c, const double *rho_host) {
     if (c) c->vac_by_tol = false;   // (the -1 labels no longer say "rho <= vac_tol" of the density on the card)
-    NEED_GRID("xb_upload_density");
+    NEED_GRID_THIN("xb_upload_density");
     c->grad_valid = false; c->brick_max_valid = false;
     if (int rc = staged_h2d(c, c->rho, rho_host, c->N * sizeof(double))) return rc;
     HIPCHK(hipStreamSynchronize(c->stream));
     return XB_OK;
 }
 int xb_download_density(xb_ctx *c, double *rho_host) {
-    NEED_GRID("xb_download_density");
+    NEED_GRID_THIN("xb_download_density");
     HIPCHK(hipMemcpyAsync(rho_host, c->rho, c->N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     return XB_OK;
@@ -470,7 +484,7 @@ int xb_synth_density(xb_ctx *c, const double lattice[9], const double *atoms5, i
 static size_t dtype_size(int dtype) { return (dtype == XB_I8 || dtype == XB_I16 || dtype == XB_I32 || dtype == XB_I64) ? (size_t)dtype : 0; }
 
 int xb_upload_labels(xb_ctx *c, const void *labels_host, int dtype) {
-    NEED_GRID_RAW("xb_upload_labels");
+    NEED_GRID_RAW_THIN("xb_upload_labels");
     c->labels_zero_pending = false;   // every label is overwritten
     c->zero_outside[0] = -1;
     c->list_valid = false; c->chg_n = -1;
@@ -504,7 +518,7 @@ int xb_upload_labels(xb_ctx *c, const void *labels_host, int dtype) {
     return XB_OK;
 }
 int xb_download_labels(xb_ctx *c, void *labels_host, int dtype) {
-    NEED_GRID("xb_download_labels");
+    NEED_GRID_THIN("xb_download_labels");
     const size_t sz = dtype_size(dtype);
     if (!sz) return fail(XB_E_ARG, "xb_download_labels: bad dtype code %d", dtype);
     if (dtype == XB_I32) {
@@ -554,7 +568,7 @@ int xb_download_known(xb_ctx *c, int8_t *known_host) {
 }
 
 int xb_vacuum_assign(xb_ctx *c, double vac_tol, double voxel_volume, double *vac_charge, double *vac_volume) {
-    NEED_GRID_RAW("xb_vacuum_assign");
+    NEED_GRID_RAW_THIN("xb_vacuum_assign");
     c->buni_valid = false; c->regions_labels = false;
     c->label_wire = 1;   // every valid plane holds 0 / -1 from here on
     c->labels_zero_pending = false;

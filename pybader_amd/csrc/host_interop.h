@@ -89,20 +89,21 @@ int xb_device_free(void *p) {
 }
 
 extern "C++" {
+// (dst: the resident density, or the weight method's integrand buffer)
 template <typename T>
-static int io_import_density(xb_ctx *c, const T *src, const int64_t st[3]) {
+static int io_import_density(xb_ctx *c, const T *src, const int64_t st[3], double *dst) {
     const Grid &g = c->g;
     const long long N = c->N, sx = st[0], sy = st[1], sz = st[2];
     const bool contiguous = sz == 1 && sy == g.nz && sx == g.nyz;
     long long first = 0;
     if (contiguous && sizeof(T) == 8) {
-        HIPCHK(hipMemcpyAsync(c->rho, src, (size_t)N * 8, hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(dst, src, (size_t)N * 8, hipMemcpyDeviceToDevice, c->stream));
         return XB_OK;
     }
     if constexpr (sizeof(T) == 4)
         if (contiguous && (uintptr_t)src % 16 == 0) {
             const long long n4 = N / 4;
-            k_io_widen4<<<nblocks(n4), TPB, 0, c->stream>>>(src, c->rho, n4);
+            k_io_widen4<<<nblocks(n4), TPB, 0, c->stream>>>(src, dst, n4);
             HIPCHK(hipGetLastError());
             first = 4 * n4;      // (the up to three values behind the last whole group: the gather below)
             if (first == N) return XB_OK;
@@ -112,12 +113,12 @@ static int io_import_density(xb_ctx *c, const T *src, const int64_t st[3]) {
         const int nf = fy ? g.ny : g.nx, no = fy ? g.nx : g.ny;
         const int tiles_f = (nf + IO_TILE - 1) / IO_TILE, tiles_z = (g.nz + IO_TILE - 1) / IO_TILE;
         const long long blocks = (long long)tiles_f * tiles_z * no;   // < N / 9 + ...: fits the grid's 2^31 - 1
-        k_io_tiled<T><<<(unsigned)blocks, TPB, 0, c->stream>>>(src, c->rho, no, nf, g.nz, fy ? sx : sy, sz, fy ? (long long)g.nyz : g.nz,
+        k_io_tiled<T><<<(unsigned)blocks, TPB, 0, c->stream>>>(src, dst, no, nf, g.nz, fy ? sx : sy, sz, fy ? (long long)g.nyz : g.nz,
                                                               fy ? (long long)g.nz : g.nyz, tiles_f, tiles_z);
         HIPCHK(hipGetLastError());
         return XB_OK;
     }
-    k_io_gather<T><<<nblocks(N - first), TPB, 0, c->stream>>>(src, c->rho, g.ny, g.nz, sx, sy, sz, first, N);
+    k_io_gather<T><<<nblocks(N - first), TPB, 0, c->stream>>>(src, dst, g.ny, g.nz, sx, sy, sz, first, N);
     HIPCHK(hipGetLastError());
     return XB_OK;
 }
@@ -136,11 +137,11 @@ int xb_import_density(xb_ctx *c, const void *dev_ptr, int dtype, const int64_t s
     if (io_overlaps(lo, hi, c->rho, (size_t)c->N * 8)) return fail(XB_E_ARG, "xb_import_density: the source overlaps the resident density");
     // from here on as xb_upload_density
     c->vac_by_tol = false;   // (the -1 labels no longer say "rho <= vac_tol" of the density on the card)
-    NEED_GRID("xb_import_density");
+    NEED_GRID_THIN("xb_import_density");
     c->grad_valid = false; c->brick_max_valid = false;
     const hipStream_t s = (hipStream_t)stream;
     if (int rc = io_after_caller(c, s)) return rc;
-    if (int rc = dtype == XB_F32 ? io_import_density(c, (const float *)dev_ptr, stride) : io_import_density(c, (const double *)dev_ptr, stride)) return rc;
+    if (int rc = dtype == XB_F32 ? io_import_density(c, (const float *)dev_ptr, stride, c->rho) : io_import_density(c, (const double *)dev_ptr, stride, c->rho)) return rc;
     return io_before_caller(c, s);
 }
 
@@ -188,7 +189,7 @@ int xb_export_labels(xb_ctx *c, void *dev_ptr, int dtype, void *stream) {
     uintptr_t lo, hi;
     if (int rc = io_check_flat(c, "xb_export_labels", dev_ptr, sz, &lo, &hi)) return rc;
     if (io_overlaps(lo, hi, c->labels, (size_t)c->N * 4)) return fail(XB_E_ARG, "xb_export_labels: the destination overlaps the resident labels");
-    NEED_GRID("xb_export_labels");
+    NEED_GRID_THIN("xb_export_labels");
     const hipStream_t s = (hipStream_t)stream;
     if (int rc = io_after_caller(c, s)) return rc;
     const long long N = c->N;

@@ -201,6 +201,33 @@ class Bader:
             self.method, self.refine_method, self.refine_mode, self.reference, self.bader_volumes,
             self.distance_matrix, self.T_grad, self.threads)
 
+    weight_flag = False   # True: _run ends with weight_charges() (no other step changes)
+
+    def weight_charges(self):
+        """Weight-method (Yu & Trinkle) charges next to the grid ones -- no counterpart in the reference.  Sets
+        weight_maxima (voxel indices), weight_charge, weight_volume per maximum of the reference density, weight_atoms (the
+        nearest atom of each, utils.atom_assign) and atoms_weight_charge / atoms_weight_volume (/ atoms_weight_spin with
+        spin_bool): each atom sums its maxima on the host in ascending maximum order.  Vacuum voxels (vacuum_tol) are
+        absent, as in the grid sums.  Needs the atom map of bader_to_atom_distance() when a vacuum tolerance is set."""
+        from .utils import atom_assign
+        from .weight import weight_sum
+        volumes = self.atoms_volumes if self.vacuum_tol is not None else None
+        self.weight_maxima, self.weight_charge, self.weight_volume = weight_sum(
+            self.reference, self.density, self.lattice, volumes)
+        frac = np.divide(np.add(self.weight_maxima, self.voxel_offset_fractional), self.grid_shape)
+        n = self.atoms.shape[0]
+        if self.weight_maxima.shape[0]:
+            self.weight_atoms, _ = atom_assign(np.dot(frac, self.lattice), self.atoms, self.lattice)
+        else:
+            self.weight_atoms = np.zeros(0, np.int64)
+        self.atoms_weight_charge, self.atoms_weight_volume = np.zeros(n), np.zeros(n)
+        np.add.at(self.atoms_weight_charge, self.weight_atoms, self.weight_charge)      # (unbuffered: one add per maximum, in order)
+        np.add.at(self.atoms_weight_volume, self.weight_atoms, self.weight_volume)
+        if self.spin_bool:
+            _, spin, _ = weight_sum(self.reference, self.spin, self.lattice, volumes)
+            self.atoms_weight_spin = np.zeros(n)
+            np.add.at(self.atoms_weight_spin, self.weight_atoms, spin)
+
     fused = True      # _run issues bader_calc + refine as one call where the two are adjacent (False: the reference's two calls)
 
     def _run(self):
@@ -220,6 +247,8 @@ class Bader:
         self.min_surface_distance()
         self.sum_volumes()
         self.export_volumes()
+        if self.weight_flag:
+            self.weight_charges()
 
     def export_volumes(self):
         """The export loop of Bader.__call__ (interface.py:417-436): `export_mode` = ('volumes' | 'atoms', [numbers]),
