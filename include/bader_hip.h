@@ -231,6 +231,26 @@ int xb_assign_refine(xb_ctx *c, int method, int mode, int64_t iters, int64_t *n_
 
 /* utils.charge_sum (utils.py:235-252) via Bader.sum_volumes (interface.py:492-525) */
 int xb_charge_sum(xb_ctx *c, double voxel_volume, int64_t n_labels, double *charge, double *volume);
+/* ---- moments of the density per label about a centre (atomic dipoles and quadrupoles; the multipole module of the Henkelman
+ * group's `bader` program) -- no counterpart in the reference ----
+ * Next to xb_charge_sum: one pass over the owned planes [x0, x1) of the resident density and labels (a slab rank gets its partial
+ * sums); nothing resident is written.  lattice[9]: the cell, a row per axis; centres_cart[n][3]: the centre of label a, Cartesian.
+ * Every owned voxel v = (p0, p1, p2) whose label a satisfies 0 <= a < n contributes (labels < 0 and >= n are skipped):
+ *   position  as utils.surface_dist (utils.py:357-359), left to right:
+ *             pc[j] = lat[j]*p0/nx;  pc[j] += lat[3+j]*p1/ny;  pc[j] += lat[6+j]*p2/nz
+ *   image     the 27 images x, y, z = -1..1 in that nesting order, pbc[j] = (lat[j]*x + lat[3+j]*y) + lat[6+j]*z,
+ *             e[j] = pc[j] - (centre[a][j] + pbc[j]),  d2 = (e0*e0 + e1*e1) + e2*e2;  the image kept is the first with a strictly
+ *             smaller d2, starting from the largest double (a tie keeps the earlier image);  d[j] = the e[j] of that image
+ *   terms     with w = rho[v] and t_j = w*d[j] formed first:
+ *             w,  t_0, t_1, t_2,  t_0*d0, t_0*d1, t_0*d2,  t_1*d1, t_1*d2,  t_2*d2
+ *   result    moments[a][0..9] = the ten sums of these terms over the label's voxels, each multiplied once by voxel_volume
+ *             (m0; m1 x y z; m2 xx xy xz yy yz zz);  volume[a] = the voxel count times voxel_volume
+ * The terms are a pure function of their inputs (no contraction); the order of the sums is free (float atomics, as xb_charge_sum).
+ * n <= 224 labels sum in LDS bins per block, more in global memory; waves that hold one label add once per wave.
+ * XB_E_STATE: no grid, or a grid that has received no density or no labels yet;  XB_E_ARG: n < 1 or a null pointer;
+ * XB_E_LIMIT: n above (2^31 - 1) / 10.  Timer 8 of xb_kernel_time; its buffer is counted by xb_memory_stats. */
+int xb_moment_sum(xb_ctx *c, const double lattice[9], const double *centres_cart, int64_t n, double voxel_volume,
+                  double *moments /* n*10 */, double *volume /* n */);
 /* ---- the weight method (Yu & Trinkle, J. Chem. Phys. 134, 064111; `bader -b weight`) -- no counterpart in the reference ----
  * Charge and volume per maximum with the surface voxels split fractionally, next to xb_charge_sum.  The resident density is the
  * partition field rho, the resident labels are read for their -1 marks (vacuum: absent, sends and receives nothing); neither is
@@ -364,7 +384,7 @@ int xb_host_waits(int64_t *n);
 /* HIP-event timing of the stages, measured on the context's stream: accumulated milliseconds and launch
  * count since the last reset.  which: 0 neargrid assignment after pass A (walk list, records, walker trace),
  * 1 the ongrid pointer pass (k_og_masks), 2 edge_find, 3 refine trace, 4 pass A + region growth (and records built
- * for a refinement), 5 k_brick_masks alone, 6 the trace kernel alone, 7 k_brick_records alone. */
+ * for a refinement), 5 k_brick_masks alone, 6 the trace kernel alone, 7 k_brick_records alone, 8 the kernels of xb_moment_sum. */
 int xb_kernel_time(xb_ctx *c, int which, double *ms_total, int64_t *launches);
 int xb_kernel_time_reset(xb_ctx *c);
 /* on: 0 off, 1 every timer, otherwise a mask: bit k + 1 switches timer `which` = k on (event pairs between dependent kernels

@@ -74,6 +74,7 @@ SYMBOLS = {
     'xb_refine': (_int, [_vp, _int, _i64, _vp, _i64, _pi64]),
     'xb_assign_refine': (_int, [_vp, _int, _int, _i64, _pi64, _vp, _i64, _pi64]),
     'xb_charge_sum': (_int, [_vp, _dbl, _i64, _vp, _vp]),
+    'xb_moment_sum': (_int, [_vp, _pdbl, _pdbl, _i64, _dbl, _pdbl, _pdbl]),
     'xb_weight_sum': (_int, [_vp, _pdbl, _dbl, _vp, _pi64]),
     'xb_weight_sum_device': (_int, [_vp, _pdbl, _dbl, _vp, _int, _pi64, _vp, _pi64]),
     'xb_weight_fetch': (_int, [_vp, _vp, _vp, _vp, _i64]),
@@ -699,6 +700,16 @@ class Context:
         ch, vo = np.zeros(n_labels, np.float64), np.zeros(n_labels, np.float64)
         check(self.lib.xb_charge_sum(self.h, float(voxel_volume), int(n_labels), _ptr(ch), _ptr(vo)))
         return ch, vo
+
+    def moment_sum(self, lattice, centres, voxel_volume):
+        """moments of the resident density per resident label about `centres` (Cartesian, [n, 3]; the cell's `lattice` a row per
+        axis) over the owned planes (xb_moment_sum) -> (moments f64[n, 10]: m0, m1 x y z, m2 xx xy xz yy yz zz; volume f64[n])"""
+        lat, ce = _f64(lattice).reshape(9), _f64(centres).reshape(-1, 3)
+        n = ce.shape[0]
+        mo, vo = np.zeros((n, 10), np.float64), np.zeros(n, np.float64)
+        check(self.lib.xb_moment_sum(self.h, lat.ctypes.data_as(_pdbl), ce.ctypes.data_as(_pdbl), n, float(voxel_volume),
+                                     mo.ctypes.data_as(_pdbl), vo.ctypes.data_as(_pdbl)))
+        return mo, vo
 
     def weight_sum(self, alpha, voxel_volume, q=None, use_labels=True):
         """the weight method on the resident density and labels (xb_weight_sum): `q` None integrates the resident density

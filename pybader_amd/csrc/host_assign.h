@@ -212,6 +212,7 @@ static int run_slow(xb_ctx *c, int n, int refine, int *max_count = nullptr, int 
 
 int xb_assign_trace(xb_ctx *c, int method, int64_t *n_local) {
     NEED_GRID_RAW("xb_assign_trace");
+    c->have_labels = true;   // (the assignment writes every owned label)
     if (int rc = need_grad(c)) return rc;
     const Grid &g = c->g;
     const long long own = (long long)(g.x1 - g.x0) * g.nyz;
@@ -767,6 +768,7 @@ static int assign_ongrid_fused(xb_ctx *c, int64_t *n_maxima) {
 static int sort_and_finish(xb_ctx *c, int64_t n, int64_t *n_maxima);
 int xb_assign(xb_ctx *c, int method, int64_t *n_maxima) {
     NEED_GRID_RAW("xb_assign");
+    c->have_labels = true;   // (the assignment writes every owned label)
     if (method == XB_METHOD_NEARGRID && fused_ok(c)) {
         if (c->has_vacuum) { if (int rc = settle_labels(c)) return rc; }
         else c->labels_zero_pending = false;   // every label is overwritten, none is read

@@ -861,6 +861,7 @@ static int refine_impl(xb_ctx *c, int mode, int64_t iters, int64_t *log, int64_t
 // without vacuum, the two ordinary calls run instead.
 int xb_assign_refine(xb_ctx *c, int method, int mode, int64_t iters, int64_t *n_maxima, int64_t *log, int64_t log_capacity, int64_t *n_iters) {
     NEED_GRID_RAW("xb_assign_refine");
+    c->have_labels = true;   // (the assignment writes every owned label)
     if (n_iters) *n_iters = 0;
     const bool fused = c->g.x0 == 0 && c->g.x1 == c->g.nx && !table_windowed(c);
     if (method == XB_METHOD_NEARGRID && fused && fused_ok(c) && !c->has_vacuum && iters != 0 && (mode == XB_REFINE_ALL || mode == XB_REFINE_CHANGED)) {

@@ -131,10 +131,14 @@ int xb_table_finish(xb_ctx *c, const int64_t *seeds, int64_t n_seeds, int64_t an
 void *xb_labels_ptr(xb_ctx *c) {
     if (!c) return nullptr;
     settle_labels(c);
+    c->have_labels = true;   // (whoever holds the pointer may write them)
     return (void *)c->labels;
 }
 void *xb_known_ptr(xb_ctx *c) { return c ? (void *)c->known : nullptr; }
-void *xb_density_ptr(xb_ctx *c) { return c ? (void *)c->rho : nullptr; }
+void *xb_density_ptr(xb_ctx *c) {
+    if (c) c->have_rho = true;   // (whoever holds the pointer may write it)
+    return c ? (void *)c->rho : nullptr;
+}
 int64_t xb_plane_elems(xb_ctx *c) { return c ? c->g.nyz : 0; }
 
 int xb_copy_planes(xb_ctx *c, int which, int to_device, void *host, int64_t xa, int64_t xb) {
@@ -147,6 +151,7 @@ int xb_copy_planes(xb_ctx *c, int which, int to_device, void *host, int64_t xa, 
     // (planes from outside: any label may arrive -- but the halo's wire width must stay a collectively agreed value, so it is
     // widened only when a label of these planes does not fit it: never for planes of peers that ran the same assignment)
     if (to_device && which == 0) {
+        c->have_labels = true;
         c->zero_outside[0] = -1;
         c->label_wire = std::max(c->label_wire, labels_fit_wire((const int32_t *)host, (xb - xa) * c->g.nyz));
     }

@@ -198,6 +198,7 @@ int xb_slab_supported(xb_ctx *c, int nranks, int64_t *ok) {
 
 int xb_slab_assign_masks(xb_ctx *c, int rank, int nranks) {
     NEED_GRID_RAW("xb_slab_assign_masks");
+    c->have_labels = true;   // (the assignment writes every owned label)
     if (rank < 0 || rank >= nranks) return fail(XB_E_ARG, "xb_slab_assign_masks: bad rank");
     if (!slab_step_ok(c, nranks)) return fail(XB_E_STATE, "xb_slab_assign_masks: this slab cannot take the device-driven step (see xb_slab_supported)");
     if (int rc = need_grad(c)) return rc;

@@ -228,6 +228,25 @@ class Bader:
             self.atoms_weight_spin = np.zeros(n)
             np.add.at(self.atoms_weight_spin, self.weight_atoms, spin)
 
+    multipole_flag = False   # True: _run ends with multipole_moments() (no other step changes)
+
+    def multipole_moments(self):
+        """Moments of the charge density per atom about the atom (and, unless speed_flag dropped the map, per Bader volume
+        about its maximum) -- no counterpart in the reference.  Sets atoms_moments [n, 10] (multipole.moment_sum's rows),
+        atoms_dipole [n, 3] and atoms_quadrupole [n, 3, 3] (electronic, in e * length and e * length^2; see
+        pybader_amd.multipole for units and sign), atoms_spin_moments with spin_bool, and bader_moments.  Labels are
+        atoms_volumes and centres atoms - voxel_offset, as in min_surface_distance."""
+        from .multipole import dipole, moment_sum, quadrupole
+        centres = self.atoms - self.voxel_offset
+        self.atoms_moments, _ = moment_sum(self.density, self.atoms_volumes, self.lattice, centres, self.voxel_volume)
+        self.atoms_dipole = dipole(self.atoms_moments)
+        self.atoms_quadrupole = quadrupole(self.atoms_moments)
+        if self.spin_bool:
+            self.atoms_spin_moments, _ = moment_sum(self.spin, self.atoms_volumes, self.lattice, centres, self.voxel_volume)
+        if hasattr(self, 'bader_volumes'):
+            self.bader_moments, _ = moment_sum(self.density, self.bader_volumes, self.lattice,
+                                               self.bader_maxima - self.voxel_offset, self.voxel_volume)
+
     fused = True      # _run issues bader_calc + refine as one call where the two are adjacent (False: the reference's two calls)
 
     def _run(self):
@@ -249,6 +268,8 @@ class Bader:
         self.export_volumes()
         if self.weight_flag:
             self.weight_charges()
+        if self.multipole_flag:
+            self.multipole_moments()
 
     def export_volumes(self):
         """The export loop of Bader.__call__ (interface.py:417-436): `export_mode` = ('volumes' | 'atoms', [numbers]),
