@@ -251,6 +251,36 @@ int xb_charge_sum(xb_ctx *c, double voxel_volume, int64_t n_labels, double *char
  * XB_E_LIMIT: n above (2^31 - 1) / 10.  Timer 8 of xb_kernel_time; its buffer is counted by xb_memory_stats. */
 int xb_moment_sum(xb_ctx *c, const double lattice[9], const double *centres_cart, int64_t n, double voxel_volume,
                   double *moments /* n*10 */, double *volume /* n */);
+/* ---- which labels share a surface: facet counts and the saddle per pair of labels (interatomic surfaces, the grid estimate of the
+ * bond critical point, the barrier a persistence filter of spurious maxima needs) -- no counterpart in the reference ----
+ * Next to xb_charge_sum: two passes over the resident density rho (the field the labels were made from) and the resident labels of
+ * the whole grid; nothing resident is written.  n: the number of labels; dirs[n_dirs][3]: the active directions, each in
+ * {-1,0,1}^3 \ {0}, none twice or with its negative (pybader_amd.adjacency.active_directions: of the 13 offsets d > -d in tuple
+ * order those whose facet of the voxel lattice's Voronoi cell has an area >= 1e-10 * V_voxel^(2/3), ascending: 3 for an orthogonal
+ * cell, up to 7 for a triclinic one).
+ *   facets    every voxel v = (p0, p1, p2) owns, for each direction k, the facet towards u = v + d_k, wrapped periodically on every
+ *             axis; its id is f = lin(v) * 8 + k with lin the C-order index (unique for n_dirs <= 8).  The facet counts when
+ *             a = label[v] and b = label[u] both lie in [0, n) and a != b; its pair is (min(a, b), max(a, b)).  Labels < 0 and >= n
+ *             make a facet count for nothing.  An axis of length 1 gives no facets along it (u == v); an axis of length 2 gives two
+ *             facets between the same two voxels, one owned by each, and both count.
+ *   per pair  facets[k]: the number of its facets in direction k;  saddle: the maximum over its facets of s = the smaller of
+ *             rho[v], rho[u], "smaller" and "maximum" both in the total order of key(x) = bits(x) ^ (bits(x) >> 63 ? ~0 : 1 << 63)
+ *             compared as uint64 (it equals < on ordinary values, puts -0.0 below +0.0 and is defined for NaN);  saddle_facet: the
+ *             smallest facet id among the pair's facets whose s has the maximal key
+ *   result    the pairs in ascending (a, b).  Counts are integers, the saddle a maximum of existing bits, ties go to an index:
+ *             nothing depends on scheduling and every number is exact.
+ * n <= 256 labels use a triangular table in global memory, more an open-addressing hash table (key a << 32 | b, 64-bit
+ * compare-and-swap) that a counting pass sizes: a power of two >= twice the counting facets.  The table is allocated on demand, kept
+ * while the grid's shape stays, counted by xb_memory_stats and freed by xb_adjacency_release.  The occupied entries are compacted on
+ * the device and sorted by key on the host.
+ *   xb_adjacency_fetch   the pairs of the last call: a[i] < b[i], facets[i * n_dirs + k], saddle[i], saddle_facet[i]
+ * XB_E_STATE: no grid, a grid that has received no density or no labels yet, a context that holds a slab (fetch: no result);
+ * XB_E_ARG: n < 1, n_dirs outside 1..13, a direction outside {-1,0,1}^3 \ {0}, given twice or together with its negative, a null
+ * pointer, capacity < n_pairs in fetch;  XB_E_LIMIT: n > 2^31 - 1.  Timer 9 of xb_kernel_time. */
+int xb_adjacency(xb_ctx *c, const int32_t *dirs /* n_dirs*3 */, int n_dirs, int64_t n, int64_t *n_pairs);
+int xb_adjacency_fetch(xb_ctx *c, int32_t *a, int32_t *b, int64_t *facets /* cap*n_dirs */, double *saddle,
+                       int64_t *saddle_facet, int64_t capacity);
+int xb_adjacency_release(xb_ctx *c);
 /* ---- the weight method (Yu & Trinkle, J. Chem. Phys. 134, 064111; `bader -b weight`) -- no counterpart in the reference ----
  * Charge and volume per maximum with the surface voxels split fractionally, next to xb_charge_sum.  The resident density is the
  * partition field rho, the resident labels are read for their -1 marks (vacuum: absent, sends and receives nothing); neither is
@@ -384,7 +414,8 @@ int xb_host_waits(int64_t *n);
 /* HIP-event timing of the stages, measured on the context's stream: accumulated milliseconds and launch
  * count since the last reset.  which: 0 neargrid assignment after pass A (walk list, records, walker trace),
  * 1 the ongrid pointer pass (k_og_masks), 2 edge_find, 3 refine trace, 4 pass A + region growth (and records built
- * for a refinement), 5 k_brick_masks alone, 6 the trace kernel alone, 7 k_brick_records alone, 8 the kernels of xb_moment_sum. */
+ * for a refinement), 5 k_brick_masks alone, 6 the trace kernel alone, 7 k_brick_records alone, 8 the kernels of xb_moment_sum,
+ * 9 the kernels of xb_adjacency (one interval per group of launches between two host waits). */
 int xb_kernel_time(xb_ctx *c, int which, double *ms_total, int64_t *launches);
 int xb_kernel_time_reset(xb_ctx *c);
 /* on: 0 off, 1 every timer, otherwise a mask: bit k + 1 switches timer `which` = k on (event pairs between dependent kernels

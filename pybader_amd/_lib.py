@@ -75,6 +75,9 @@ SYMBOLS = {
     'xb_assign_refine': (_int, [_vp, _int, _int, _i64, _pi64, _vp, _i64, _pi64]),
     'xb_charge_sum': (_int, [_vp, _dbl, _i64, _vp, _vp]),
     'xb_moment_sum': (_int, [_vp, _pdbl, _pdbl, _i64, _dbl, _pdbl, _pdbl]),
+    'xb_adjacency': (_int, [_vp, _vp, _int, _i64, _pi64]),
+    'xb_adjacency_fetch': (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64]),
+    'xb_adjacency_release': (_int, [_vp]),
     'xb_weight_sum': (_int, [_vp, _pdbl, _dbl, _vp, _pi64]),
     'xb_weight_sum_device': (_int, [_vp, _pdbl, _dbl, _vp, _int, _pi64, _vp, _pi64]),
     'xb_weight_fetch': (_int, [_vp, _vp, _vp, _vp, _i64]),
@@ -710,6 +713,22 @@ class Context:
         check(self.lib.xb_moment_sum(self.h, lat.ctypes.data_as(_pdbl), ce.ctypes.data_as(_pdbl), n, float(voxel_volume),
                                      mo.ctypes.data_as(_pdbl), vo.ctypes.data_as(_pdbl)))
         return mo, vo
+
+    def adjacency(self, dirs, n):
+        """which of the resident labels 0 .. n - 1 share a surface (xb_adjacency; `dirs` int[K, 3], the active directions) ->
+        (pairs int32[P, 2] ascending with a < b, facets int64[P, K], saddle f64[P], saddle_facet int64[P])"""
+        d = np.ascontiguousarray(dirs, dtype=np.int32).reshape(-1, 3)
+        k, np_ = d.shape[0], C.c_int64()
+        check(self.lib.xb_adjacency(self.h, _ptr(d), k, int(n), C.byref(np_)))
+        p = int(np_.value)
+        a, b = np.zeros(p, np.int32), np.zeros(p, np.int32)
+        facets, saddle, sfacet = np.zeros((p, k), np.int64), np.zeros(p, np.float64), np.zeros(p, np.int64)
+        check(self.lib.xb_adjacency_fetch(self.h, _ptr(a), _ptr(b), _ptr(facets), _ptr(saddle), _ptr(sfacet), p))
+        return np.stack([a, b], axis=1), facets, saddle, sfacet
+
+    def adjacency_release(self):
+        """free the pair table of xb_adjacency (it is kept between calls while the grid's shape stays) and the fetched pairs"""
+        check(self.lib.xb_adjacency_release(self.h))
 
     def weight_sum(self, alpha, voxel_volume, q=None, use_labels=True):
         """the weight method on the resident density and labels (xb_weight_sum): `q` None integrates the resident density

@@ -33,9 +33,11 @@ int xb_create(int device, xb_ctx **out) {
 
 static void weight_free(xb_ctx *c);
 static void moments_free(xb_ctx *c);
+static void adjacency_free(xb_ctx *c);
 static void free_grid(xb_ctx *c) {
     weight_free(c);
     moments_free(c);
+    adjacency_free(c);
     c->have_rho = c->have_labels = false;
     hipFree(c->rho); hipFree(c->grad); hipFree(c->labels); hipFree(c->known); hipFree(c->first); hipFree(c->list);
     hipFree(c->st); hipFree(c->stage); hipFree(c->ec_pend); c->ec_pend = nullptr; hipFree(c->ec_share); c->ec_share = nullptr; hipFree(c->ec_pflag); c->ec_pflag = nullptr; hipFree(c->max_list); hipFree(c->max_aux); hipFree(c->ovf_list);
@@ -171,7 +173,7 @@ int xb_set_grid(xb_ctx *c, const int64_t shape[3], const double dist_mat[27], co
     }
     c->zero_outside[0] = -1;
     Grid &g = c->g;
-    if (g.nx != (int)shape[0] || g.ny != (int)shape[1] || g.nz != (int)shape[2]) { c->grad_valid = false; c->brick_max_valid = false; c->have_rho = c->have_labels = false; }
+    if (g.nx != (int)shape[0] || g.ny != (int)shape[1] || g.nz != (int)shape[2]) { c->grad_valid = false; c->brick_max_valid = false; c->have_rho = c->have_labels = false; adjacency_free(c); }
     if (dist_mat && !T_grad) return fail(XB_E_ARG, "xb_set_grid: dist_mat without T_grad");
     g.nx = (int)shape[0]; g.ny = (int)shape[1]; g.nz = (int)shape[2];
     g.nyz = g.ny * g.nz;

@@ -121,6 +121,8 @@ class Bader:
 
     @bader_maxima.setter
     def bader_maxima(self, maxima):                                                # interface.py:318-324
+        if self.adjacency_flag:   # (the integer voxels: bond_surfaces reads rho there)
+            self._bader_maxima_voxels = np.array(maxima, dtype=np.int64).reshape(-1, 3)
         maxima = np.add(maxima, self.voxel_offset_fractional)
         self._bader_maxima = np.ascontiguousarray(np.divide(maxima, self.grid_shape))
 
@@ -247,6 +249,31 @@ class Bader:
             self.bader_moments, _ = moment_sum(self.density, self.bader_volumes, self.lattice,
                                                self.bader_maxima - self.voxel_offset, self.voxel_volume)
 
+    adjacency_flag = False   # True: _run ends with bond_surfaces() (no other step changes)
+
+    def bond_surfaces(self):
+        """Which atoms (and, unless speed_flag dropped the map, which Bader volumes) share a surface -- no counterpart in the
+        reference.  From atoms_volumes on the reference density: atoms_adjacency (a pybader_amd.adjacency.Adjacency: pairs,
+        facets, area, saddle_density, saddle_voxels, saddle_position), atoms_bond_area [P], atoms_bond_density [P] (the density
+        at the highest point of the interatomic surface: the grid estimate of rho at the bond critical point) and
+        atoms_bond_position [P, 3] (Cartesian, voxel_offset added).  From bader_volumes: bader_adjacency and
+        bader_persistence [n_maxima], a volume's maximum minus its highest saddle with a volume whose maximum is higher
+        (+inf without one): small for a spurious maximum.  The maxima's integer voxels are kept by bader_calc() while
+        adjacency_flag is set (_bader_maxima_voxels)."""
+        from .adjacency import adjacency, persistence
+        a = adjacency(self.reference, self.atoms_volumes, self.lattice, self.atoms.shape[0], self.voxel_offset)
+        self.atoms_adjacency = a
+        self.atoms_bond_area, self.atoms_bond_density, self.atoms_bond_position = a.area, a.saddle_density, a.saddle_position
+        if hasattr(self, 'bader_volumes'):
+            vox = getattr(self, '_bader_maxima_voxels', None)
+            if vox is None:
+                raise RuntimeError('bond_surfaces: set adjacency_flag before bader_calc(), which then keeps the maxima\'s voxels')
+            b = adjacency(self.reference, self.bader_volumes, self.lattice, vox.shape[0], self.voxel_offset)
+            self.bader_adjacency = b
+            at = device.to_host(self.reference) if device.is_device_array(self.reference) else np.asarray(self.reference)
+            rho_max = np.asarray(at[vox[:, 0], vox[:, 1], vox[:, 2]], dtype=np.float64)
+            self.bader_persistence = persistence(b.pairs, b.saddle_density, rho_max)
+
     fused = True      # _run issues bader_calc + refine as one call where the two are adjacent (False: the reference's two calls)
 
     def _run(self):
@@ -270,6 +297,8 @@ class Bader:
             self.weight_charges()
         if self.multipole_flag:
             self.multipole_moments()
+        if self.adjacency_flag:
+            self.bond_surfaces()
 
     def export_volumes(self):
         """The export loop of Bader.__call__ (interface.py:417-436): `export_mode` = ('volumes' | 'atoms', [numbers]),

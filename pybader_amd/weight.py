@@ -57,6 +57,39 @@ def _facet_area(r, others):
     return _area(poly)
 
 
+def _pair_offsets():
+    """one offset of each +-d pair of {-1, 0, 1}^3 \\ {0}: the 13 with d > -d, in ascending tuple order"""
+    return [d for d in itertools.product(range(-1, 2), repeat=3) if d > tuple(-x for x in d)]
+
+
+def voronoi_areas(voxel_lattice, who='voronoi_areas'):
+    """area[i, j, k] = a_d for the 26 offsets d in {-1, 0, 1}^3 \\ {0}: the area of the facet the bisector plane of r_d = d . L
+    contributes to the Voronoi (Wigner-Seitz) cell of the voxel lattice L (one row per axis).  Indexed like
+    voronoi_weights; a facet below AREA_TOL * V_voxel^(2/3) is 0; a_d == a_{-d} exactly (computed once per pair).  Raises
+    ValueError as voronoi_weights does (which divides these areas by |r_d|)."""
+    L = np.asarray(voxel_lattice, dtype=np.float64).reshape(3, 3)
+    vol = abs(float(np.linalg.det(L)))
+    if not np.isfinite(vol) or vol == 0.0:
+        raise ValueError(f'{who}: the voxel lattice is singular')
+    tol = AREA_TOL * vol ** (2.0 / 3.0)
+    offsets = [d for d in itertools.product(range(-2, 3), repeat=3) if d != (0, 0, 0)]
+    vec = {d: np.array(d, dtype=np.float64) @ L for d in offsets}
+    areas = np.zeros((3, 3, 3), dtype=np.float64)
+    for d in offsets:
+        if d < tuple(-x for x in d):          # one of each +-d pair
+            continue
+        r = vec[d]
+        area = _facet_area(r, [vec[o] for o in offsets if o != d])
+        if area < tol:
+            continue
+        if max(abs(x) for x in d) > 1:
+            raise ValueError(f'{who}: the offset {d} contributes a facet to the Voronoi cell of the voxel lattice: '
+                             'it is too skewed for the 26-neighbour stencil')
+        areas[tuple(x % 3 for x in d)] = area
+        areas[tuple(-x % 3 for x in d)] = area
+    return areas
+
+
 def voronoi_weights(voxel_lattice):
     """alpha[i, j, k] = a_d / |r_d| for the 26 offsets d in {-1, 0, 1}^3 \\ {0}: r_d = d . L, a_d the area of the facet the
     bisector plane of r_d contributes to the Voronoi (Wigner-Seitz) cell of the voxel lattice L (one row per axis).
@@ -67,23 +100,13 @@ def voronoi_weights(voxel_lattice):
     The cell is cut out by the bisector planes of all offsets in {-2..2}^3; a facet from an offset outside {-1, 0, 1}^3
     raises ValueError: the voxel lattice is too skewed for a 26-neighbour stencil (reduce the cell first)."""
     L = np.asarray(voxel_lattice, dtype=np.float64).reshape(3, 3)
-    vol = abs(float(np.linalg.det(L)))
-    if not np.isfinite(vol) or vol == 0.0:
-        raise ValueError('voronoi_weights: the voxel lattice is singular')
-    tol = AREA_TOL * vol ** (2.0 / 3.0)
-    offsets = [d for d in itertools.product(range(-2, 3), repeat=3) if d != (0, 0, 0)]
-    vec = {d: np.array(d, dtype=np.float64) @ L for d in offsets}
+    areas = voronoi_areas(L, 'voronoi_weights')
     alpha = np.zeros((3, 3, 3), dtype=np.float64)
-    for d in offsets:
-        if d < tuple(-x for x in d):          # one of each +-d pair
+    for d in _pair_offsets():
+        area = areas[tuple(x % 3 for x in d)]
+        if area == 0.0:
             continue
-        r = vec[d]
-        area = _facet_area(r, [vec[o] for o in offsets if o != d])
-        if area < tol:
-            continue
-        if max(abs(x) for x in d) > 1:
-            raise ValueError(f'voronoi_weights: the offset {d} contributes a facet to the Voronoi cell of the voxel lattice: '
-                             'it is too skewed for the 26-neighbour stencil')
+        r = np.array(d, dtype=np.float64) @ L
         a = area / float(np.sqrt(r @ r))
         alpha[tuple(x % 3 for x in d)] = a
         alpha[tuple(-x % 3 for x in d)] = a

@@ -1,0 +1,138 @@
+#!/usr/bin/env python3
+"""What the basin adjacency costs on one GPU (csrc/k_adjacency.h, host_adjacency.h):
+
+    python tools/bench_adjacency.py [--size 512] [--warmup 2] [--repeats 7] [--limit 120] [--cases 8,216,noisy]
+
+Three label maps at size^3, each from the neargrid assignment of a density generated on the device:
+
+    atoms8    the 8-atom cubic cell of bench.py, labels per atom          (n = 8: the dense route; also forced through the hash
+                                                                           route by asking for n past the dense limit)
+    atoms216  the 216-atom cell of bench.py's user leg, labels per atom   (n = 216: the dense route, and the hash route likewise)
+    noisy     the 8-atom cell with uniform noise in its vacuum, per Bader volume (n in the millions: the hash route)
+
+Per case, warm-up first, then median / min / max of the repeats of
+    adjacency_ms     xb_adjacency + xb_adjacency_fetch, host clock around the call (its host waits, the compaction's transfer
+                     and the host sort are inside)
+    kernel_ms        the kernels of the same calls alone (timer 9 of xb_kernel_time, HIP events)
+    charge_sum_ms    xb_charge_sum on the same labels, the same way: the yardstick, it streams 12 B per voxel once
+and ratio = kernel_ms / charge_sum_ms (medians), roofline_share = (24 B * voxels / kernel time) / --hbm-gbs: two passes.
+
+Every timed step runs under --limit seconds (a watchdog thread ends the process with status 124); run the tool under a limit
+from outside as well.  Prints one JSON line."""
+import argparse
+import json
+import os
+import re
+import statistics
+import sys
+import threading
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from pybader_amd import _lib, adjacency, synth                       # noqa: E402
+from pybader_amd.interface import distance_matrix, gradient_transform   # noqa: E402
+
+with open(os.path.join(os.path.dirname(_lib.__file__), 'csrc', 'k_adjacency.h')) as _f:
+    AJ_DENSE = int(re.search(r'^#define AJ_DENSE (\d+)', _f.read(), re.M).group(1))
+
+
+def limited(seconds, what, fn):
+    """run fn() under a time limit of its own"""
+    def overrun():
+        sys.stderr.write(f'bench_adjacency: {what} exceeded {seconds} s\n')
+        sys.stderr.flush()
+        os._exit(124)
+    t = threading.Timer(seconds, overrun)
+    t.daemon = True
+    t.start()
+    try:
+        return fn()
+    finally:
+        t.cancel()
+
+
+def stats(x):
+    return {'median': statistics.median(x), 'min': min(x), 'max': max(x)}
+
+
+def timed(ctx, fn, warmup, repeats, limit, what, timer=None):
+    wall, dev = [], []
+    for k in range(warmup + repeats):
+        if timer is not None:
+            ctx.kernel_time_reset()
+        ctx.sync()
+        t0 = time.perf_counter()
+        limited(limit, what, fn)
+        ctx.sync()
+        if k >= warmup:
+            wall.append((time.perf_counter() - t0) * 1e3)
+            if timer is not None:
+                dev.append(ctx.kernel_time(timer)[0])
+    return stats(wall), (stats(dev) if dev else None)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--size', type=int, default=512)
+    ap.add_argument('--warmup', type=int, default=2)
+    ap.add_argument('--repeats', type=int, default=7)
+    ap.add_argument('--limit', type=float, default=120.0)
+    ap.add_argument('--cases', default='8,216,noisy')
+    ap.add_argument('--hbm-gbs', type=float, default=8000.0, help='the HBM bandwidth the roofline share refers to (MI355X: 8 TB/s peak)')
+    a = ap.parse_args()
+    shape = (a.size,) * 3
+    nvox = float(np.prod(shape))
+    lat = synth.CUBIC6
+    vl = lat / np.array(shape, dtype=np.float64)[:, None]
+    vv = abs(np.linalg.det(lat)) / np.prod(shape)
+    dirs, _ = adjacency.active_directions(vl)
+    ctx = _lib.Context(0)
+    ctx.set_grid(shape, distance_matrix(vl), gradient_transform(vl))
+    out = {'shape': list(shape), 'aj_dense': AJ_DENSE, 'n_dirs': int(dirs.shape[0]), 'hbm_gbs': a.hbm_gbs, 'cases': {}}
+    for case in a.cases.split(','):
+        atoms = synth.atoms_jittered_grid(6) if case == '216' else synth.ATOMS8
+        limited(a.limit, 'density', lambda: ctx.synth_density(lat, atoms, synth.BACKGROUND))
+        if case == 'noisy':
+            rho = ctx.download_density()
+            rho += np.where(rho < 0.2, 2e-3 * np.random.default_rng(11).random(shape), 0.0)
+            ctx.upload_density(rho)
+            del rho
+        ctx.vacuum_assign(None, vv)
+        n = limited(a.limit, 'assign', lambda: ctx.assign('neargrid'))
+        res = {'n_maxima': int(n)}
+        if case != 'noisy':       # per atom: every maximum to its nearest atom, as Bader.bader_to_atom_distance does
+            maxima = np.dot(ctx.maxima() / np.array(shape, dtype=np.float64), lat)
+            owner, _ = _lib.atom_assign(maxima, synth.atoms_cartesian(atoms, lat), lat)
+            ctx.volume_assign(owner)
+            n = atoms.shape[0]
+        res['n_labels'] = int(n)
+        routes = [('', n)]
+        if n <= AJ_DENSE:         # the same labels through the hash route: labels nobody carries past the dense limit
+            routes.append(('_hash_route', AJ_DENSE + 1))
+        ctx.enable_timing(only=[9])
+        for tag, m in routes:
+            wall, dev = timed(ctx, lambda: ctx.adjacency(dirs, m), a.warmup, a.repeats, a.limit, 'adjacency', timer=9)
+            res['adjacency_ms' + tag], res['kernel_ms' + tag] = wall, dev
+        ctx.enable_timing(False)
+        res['charge_sum_ms'], _ = timed(ctx, lambda: ctx.charge_sum(vv, n), a.warmup, a.repeats, a.limit, 'charge_sum')
+        for tag, _ in routes:
+            k = res['kernel_ms' + tag]['median']
+            res['ratio' + tag] = k / res['charge_sum_ms']['median']
+            res['roofline_share' + tag] = 24.0 * nvox / (k * 1e-3) / (a.hbm_gbs * 1e9)
+        pairs, facets, saddle, _ = ctx.adjacency(dirs, n)
+        res['n_pairs'] = int(pairs.shape[0])
+        res['facets_total'] = int(facets.sum())
+        with_table = ctx.memory_stats()[2]
+        res['saddle_max'] = float(saddle.max()) if saddle.size else None
+        ctx.adjacency_release()
+        res['table_bytes'] = int(with_table - ctx.memory_stats()[2])
+        out['cases'][case] = res
+    print(json.dumps(out))
+    ctx.close()
+
+
+if __name__ == '__main__':
+    main()
