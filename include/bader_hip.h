@@ -281,6 +281,40 @@ int xb_adjacency(xb_ctx *c, const int32_t *dirs /* n_dirs*3 */, int n_dirs, int6
 int xb_adjacency_fetch(xb_ctx *c, int32_t *a, int32_t *b, int64_t *facets /* cap*n_dirs */, double *saddle,
                        int64_t *saddle_facet, int64_t capacity);
 int xb_adjacency_release(xb_ctx *c);
+/* ---- merge Bader volumes below a persistence threshold (the filter of spurious maxima the saddles above are for) -- no
+ * counterpart in the reference ----
+ * Reads the resident density rho (the field the labels were made from) and the resident labels of the whole grid; nothing
+ * resident is written.  n: the number of labels; dirs[n_dirs][3]: exactly the active directions of xb_adjacency, under the same
+ * checks; max_idx[n]: the linear C-order voxel of each label's maximum; tol; max_rounds.  Every quantity is exact.
+ *   notation  key() is the total order of xb_adjacency;  peak[m] = rho[max_idx[m]];  label b is ABOVE a iff key(peak[b]) >
+ *             key(peak[a]), or the keys are equal and b < a: a strict total order on the labels.  (pybader_amd.adjacency.persistence
+ *             puts two maxima of the same bits above neither.  Here one is above the other on purpose: a plateau split into two
+ *             maxima must be able to merge, and parents strictly above their children make the parent pointers a forest.)
+ *   state     cur[m], the current root of the original label m; at first m
+ *   a round   facets, wrapping, the rules for axes of length 1 and 2 and "labels < 0 or >= n count for nothing" are those of
+ *             xb_adjacency.  The facet (v, k) with u = v + d_k has A = cur[label[v]], B = cur[label[u]] and counts when both lie in
+ *             [0, n) and A != B; then sk = the smaller key of rho[v], rho[u], `lower` is the one of A, B the other is above and
+ *             `upper` the other.  Per root m that was `lower` on a counting facet: best[m] = the largest sk, target[m] = the smallest
+ *             label among the `upper`s of the facets with sk == best[m], pers[m] = peak[m] - unkey(best[m]) (one float64
+ *             subtraction); every other root has pers[m] = +inf.  m merges iff pers[m] < tol (false for a NaN): parent[m] =
+ *             target[m], else parent[m] = m.  cur'[m] = the end of the parent chain from cur[m].
+ *   rounds    repeat until one merges nothing or max_rounds have run.  Integer atomics in any order give the same result.
+ *   results   rounds, n_survivors, converged (the last round merged nothing); per original label m (xb_merge_fetch): root[m] = the
+ *             final cur[m];  merge_round[m] = the round, from 0, in which the root m merged, -1 if it survives;
+ *             merge_persistence[m] = pers[m] of that round, for a survivor of the last round run.  A label no voxel carries has no
+ *             facet and survives as its own root.
+ * Per round two streaming passes shaped as xb_adjacency's (atomic max of sk into best[lower]; atomic min of `upper` into
+ * target[lower]) and a kernel per label; the roots are found by pointer doubling; one host wait per round.  The current root
+ * reaches the passes by a gather through an n-entry table, read only by lanes on a boundary of the original labels.  Its buffer,
+ * 44 bytes per label, is allocated on demand, kept while the grid's shape stays, counted by xb_memory_stats and freed by
+ * xb_merge_release.
+ * XB_E_STATE: no grid, a grid that has received no density or no labels yet, a context that holds a slab (fetch: no result);
+ * XB_E_ARG: the direction faults of xb_adjacency, n < 1, a null pointer, max_rounds < 1, tol negative or NaN (+inf is allowed), a
+ * max_idx outside [0, N), capacity < n in fetch;  XB_E_LIMIT: n > 2^31 - 1.  All found on the host before any launch.  Timer 10 of
+ * xb_kernel_time. */
+int xb_merge_basins(xb_ctx *c, const int32_t *dirs, int n_dirs, int64_t n, const int64_t *max_idx, double tol, int64_t max_rounds, int64_t *rounds, int64_t *n_survivors, int *converged);
+int xb_merge_fetch(xb_ctx *c, int32_t *root, int32_t *merge_round, double *merge_persistence, int64_t capacity);
+int xb_merge_release(xb_ctx *c);
 /* ---- the weight method (Yu & Trinkle, J. Chem. Phys. 134, 064111; `bader -b weight`) -- no counterpart in the reference ----
  * Charge and volume per maximum with the surface voxels split fractionally, next to xb_charge_sum.  The resident density is the
  * partition field rho, the resident labels are read for their -1 marks (vacuum: absent, sends and receives nothing); neither is
@@ -415,7 +449,8 @@ int xb_host_waits(int64_t *n);
  * count since the last reset.  which: 0 neargrid assignment after pass A (walk list, records, walker trace),
  * 1 the ongrid pointer pass (k_og_masks), 2 edge_find, 3 refine trace, 4 pass A + region growth (and records built
  * for a refinement), 5 k_brick_masks alone, 6 the trace kernel alone, 7 k_brick_records alone, 8 the kernels of xb_moment_sum,
- * 9 the kernels of xb_adjacency (one interval per group of launches between two host waits). */
+ * 9 the kernels of xb_adjacency (one interval per group of launches between two host waits), 10 the kernels of xb_merge_basins
+ * (likewise: the initialisation, each round's two passes and decision, each round's pointer doubling). */
 int xb_kernel_time(xb_ctx *c, int which, double *ms_total, int64_t *launches);
 int xb_kernel_time_reset(xb_ctx *c);
 /* on: 0 off, 1 every timer, otherwise a mask: bit k + 1 switches timer `which` = k on (event pairs between dependent kernels

@@ -78,6 +78,9 @@ SYMBOLS = {
     'xb_adjacency': (_int, [_vp, _vp, _int, _i64, _pi64]),
     'xb_adjacency_fetch': (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64]),
     'xb_adjacency_release': (_int, [_vp]),
+    'xb_merge_basins': (_int, [_vp, _vp, _int, _i64, _vp, _dbl, _i64, _pi64, _pi64, C.POINTER(_int)]),
+    'xb_merge_fetch': (_int, [_vp, _vp, _vp, _vp, _i64]),
+    'xb_merge_release': (_int, [_vp]),
     'xb_weight_sum': (_int, [_vp, _pdbl, _dbl, _vp, _pi64]),
     'xb_weight_sum_device': (_int, [_vp, _pdbl, _dbl, _vp, _int, _pi64, _vp, _pi64]),
     'xb_weight_fetch': (_int, [_vp, _vp, _vp, _vp, _i64]),
@@ -729,6 +732,24 @@ class Context:
     def adjacency_release(self):
         """free the pair table of xb_adjacency (it is kept between calls while the grid's shape stays) and the fetched pairs"""
         check(self.lib.xb_adjacency_release(self.h))
+
+    def merge_basins(self, dirs, max_idx, tol, max_rounds=64):
+        """merge the resident labels 0 .. n - 1 whose persistence lies below `tol`, round by round (xb_merge_basins; `dirs`
+        int[K, 3], the active directions; `max_idx` int[n], the linear voxel of each label's maximum) ->
+        (root int32[n], merge_round int32[n], merge_persistence f64[n], rounds, n_survivors, converged)"""
+        d = np.ascontiguousarray(dirs, dtype=np.int32).reshape(-1, 3)
+        idx = np.ascontiguousarray(max_idx, dtype=np.int64).reshape(-1)
+        n, rounds, left, conv = idx.shape[0], C.c_int64(), C.c_int64(), C.c_int()
+        check(self.lib.xb_merge_basins(self.h, _ptr(d), d.shape[0], n, _ptr(idx), float(tol), int(max_rounds), C.byref(rounds),
+                                       C.byref(left), C.byref(conv)))
+        root, rnd, pers = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.float64)
+        check(self.lib.xb_merge_fetch(self.h, _ptr(root), _ptr(rnd), _ptr(pers), n))
+        return root, rnd, pers, int(rounds.value), int(left.value), bool(conv.value)
+
+    def merge_release(self):
+        """free the per-label buffer of xb_merge_basins (it is kept between calls while the grid's shape stays) and the
+        fetched results"""
+        check(self.lib.xb_merge_release(self.h))
 
     def weight_sum(self, alpha, voxel_volume, q=None, use_labels=True):
         """the weight method on the resident density and labels (xb_weight_sum): `q` None integrates the resident density

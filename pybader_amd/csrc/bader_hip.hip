@@ -1,7 +1,7 @@
 // bader_hip.hip -- libbader_hip.so: HIP kernels + C ABI (include/bader_hip.h) for gfx950.  ONE translation unit:
-//   kernels    k_common.h k_masks.h k_fused.h k_trace.h k_ongrid.h k_edges.h k_sums.h k_text.h k_format.h (fmt_core.h) k_interop.h k_weight.h k_moments.h k_adjacency.h
+//   kernels    k_common.h k_masks.h k_fused.h k_trace.h k_ongrid.h k_edges.h k_sums.h k_text.h k_format.h (fmt_core.h) k_interop.h k_weight.h k_moments.h k_adjacency.h k_merge.h
 //   host side  this file (context struct, options, statistics, timing) + host_context.h (life cycle, transfers)
-//              + host_assign.h (the table outside an assignment, the assignments) + host_refine.h + host_sums.h + host_slab_table.h (host-driven slab calls) + host_interop.h (device arrays in and out) + host_weight.h (the weight method) + host_moments.h (moments per label) + host_adjacency.h (surfaces between labels) + comm.h (RCCL through the ABI)
+//              + host_assign.h (the table outside an assignment, the assignments) + host_refine.h + host_sums.h + host_slab_table.h (host-driven slab calls) + host_interop.h (device arrays in and out) + host_weight.h (the weight method) + host_moments.h (moments per label) + host_adjacency.h (surfaces between labels) + host_merge.h (merging volumes by persistence) + comm.h (RCCL through the ABI)
 //              + slab_step.h (the slab step with its control flow on the device)
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -shared (see pybader_amd/build.py).
 #include "bader_kernels.h"
@@ -37,6 +37,7 @@ static inline hipError_t xb_counted_sync(hipStream_t s) { xb_waits++; return (hi
 #include "k_weight.h"
 #include "k_moments.h"
 #include "k_adjacency.h"
+#include "k_merge.h"
 
 // =============================================================================================
 // host side
@@ -192,6 +193,7 @@ struct xb_ctx {
     bool list_valid = false;   // ... when this is set (by xb_edge_find)
     unsigned timing = 0;   // bit k: timer k records its events (xb_enable_timing)
     TimedKernel tk[10];
+    TimedKernel tk_merge;      // timer XB_TIMER_MERGE, next to the ten stage timers (timer_of)
     long long n_alloc = 0;
     bool thin = false;         // an axis has fewer than 3 voxels: transfers, the vacuum sweep and the weight method only (NEED_GRID)
     // the weight method (host_weight.h): accumulators, pending counts, the two work lists, S when `stage` cannot hold it, the
@@ -217,6 +219,12 @@ struct xb_ctx {
     std::vector<int32_t> aj_a, aj_b;
     std::vector<int64_t> aj_facets, aj_sfacet;
     std::vector<double> aj_saddle;
+    // xb_merge_basins (host_merge.h): the per-label buffer and the labels it holds; the last call's results
+    void *mg_buf = nullptr;
+    int64_t mg_cap = 0;
+    bool mg_have = false;
+    std::vector<int32_t> mg_root, mg_round;
+    std::vector<double> mg_pers;
     // has anything been put into the density / the labels of this grid?  (xb_moment_sum refuses a grid without; set by every
     // call that writes them or hands their pointer out, cleared when the grid's shape changes)
     bool have_rho = false, have_labels = false;
@@ -296,6 +304,9 @@ static void mirror_prefilter(const Grid &g, int &mirror, double &mu_scale) {
     mu_scale = std::ldexp(1. + 1. / dmin, -48);
 }
 
+#define XB_TIMER_MERGE 10
+static inline TimedKernel &timer_of(xb_ctx *c, int which) { return which == XB_TIMER_MERGE ? c->tk_merge : c->tk[which]; }
+
 struct ScopedTimer {
     xb_ctx *c;
     int which;
@@ -310,7 +321,7 @@ struct ScopedTimer {
     ~ScopedTimer() {
         if ((c->timing >> which) & 1u) {
             hipEventRecord(b, c->stream);
-            c->tk[which].pending.push_back({a, b});
+            timer_of(c, which).pending.push_back({a, b});
         }
     }
 };
@@ -330,6 +341,7 @@ const char *xb_last_error(void) { return g_err.c_str(); }
 #include "host_weight.h"
 #include "host_moments.h"
 #include "host_adjacency.h"
+#include "host_merge.h"
 
 int xb_set_option(xb_ctx *c, int key, int value) {
     if (!c) return fail(XB_E_ARG, "null ctx");
@@ -379,7 +391,8 @@ int xb_memory_stats(xb_ctx *c, int64_t *bytes_total, int64_t *bytes_table, int64
     const long long scratch = c->list_cap * 4 + (long long)c->stage_bytes + c->ec_buf_cap * 4 + (c->ec_pend ? 8 * N + 16 : 0) +
                               (c->w_cap ? 25 * c->w_cap + (c->w_S ? 8 * c->w_cap : 0) : 0) /* the weight method's buffers */ +
                               (long long)c->m_cap * 8 /* xb_moment_sum's buffer */ +
-                              (long long)c->aj_bytes /* xb_adjacency's pair table */;
+                              (long long)c->aj_bytes /* xb_adjacency's pair table */ +
+                              (long long)c->mg_cap * MG_BYTES /* xb_merge_basins' per-label buffer */;
     const long long fixed = 8 * N /* rho */ + 4 * N /* labels */ + (N + 16) /* known */ + 4 * N /* first */ + N /* st */ +
                             2LL * c->max_cap * 4 + (long long)c->ovf_cap * 4 + c->blab_alloc * 5 + (long long)c->walk_cap * 3 * 80 +
                             (1 << 22) /* boxbuf */;
@@ -439,7 +452,8 @@ int xb_kernel_time_reset(xb_ctx *c) {
     if (!c) return fail(XB_E_ARG, "null ctx");
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipStreamSynchronize(c->stream));
-    for (auto &t : c->tk) {
+    for (int which = 0; which <= XB_TIMER_MERGE; which++) {
+        TimedKernel &t = timer_of(c, which);
         for (auto &p : t.pending) { hipEventDestroy(p.first); hipEventDestroy(p.second); }
         t.pending.clear();
         t.ms = 0.;
@@ -448,10 +462,11 @@ int xb_kernel_time_reset(xb_ctx *c) {
     return XB_OK;
 }
 int xb_kernel_time(xb_ctx *c, int which, double *ms_total, int64_t *launches) {
-    if (!c || which < 0 || which > 9) return fail(XB_E_ARG, "xb_kernel_time: bad argument");
+    const bool merge_timer = c && which == XB_TIMER_MERGE;   // stands next to the ten stage timers
+    if (!merge_timer && (!c || which < 0 || which > 9)) return fail(XB_E_ARG, "xb_kernel_time: bad argument");
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipStreamSynchronize(c->stream));
-    TimedKernel &t = c->tk[which];
+    TimedKernel &t = timer_of(c, which);
     for (auto &p : t.pending) {
         float ms = 0.f;
         HIPCHK(hipEventElapsedTime(&ms, p.first, p.second));

@@ -54,29 +54,36 @@ static int adjacency_run(xb_ctx *c, const Route &R, const AjDirs &D, int n, size
 }
 }  // extern "C++"
 
-int xb_adjacency(xb_ctx *c, const int32_t *dirs, int n_dirs, int64_t n, int64_t *n_pairs) {
-    if (!c || !c->has_grid) return fail(XB_E_STATE, "xb_adjacency: call xb_set_grid first");
-    if (!dirs || !n_pairs) return fail(XB_E_ARG, "xb_adjacency: null argument");
-    if (n < 1) return fail(XB_E_ARG, "xb_adjacency: %lld labels", (long long)n);
-    if (n > XB_INT_MAX) return fail(XB_E_LIMIT, "xb_adjacency: %lld labels exceed %d", (long long)n, XB_INT_MAX);
-    if (n_dirs < 1 || n_dirs > AJ_MAX_DIRS) return fail(XB_E_ARG, "xb_adjacency: %d directions (1 .. %d)", n_dirs, AJ_MAX_DIRS);
-    AjDirs D;
+// the active directions of a call, checked: each in {-1,0,1}^3 \ {0}, none twice or together with its negative (xb_merge_basins
+// takes the same list under the same rules)
+static int adjacency_dirs(const char *who, const int32_t *dirs, int n_dirs, AjDirs &D) {
+    if (n_dirs < 1 || n_dirs > AJ_MAX_DIRS) return fail(XB_E_ARG, "%s: %d directions (1 .. %d)", who, n_dirs, AJ_MAX_DIRS);
     D.n = n_dirs;
     bool seen[27] = {false};
     for (int k = 0; k < n_dirs; k++) {
         int code = 0, neg = 0;
         for (int j = 0; j < 3; j++) {
             const int d = dirs[3 * k + j];
-            if (d < -1 || d > 1) return fail(XB_E_ARG, "xb_adjacency: direction %d has a step of %d", k, d);
+            if (d < -1 || d > 1) return fail(XB_E_ARG, "%s: direction %d has a step of %d", who, k, d);
             D.d[k][j] = d;
             code = code * 3 + (d + 1);
             neg = neg * 3 + (1 - d);
         }
-        if (code == 13) return fail(XB_E_ARG, "xb_adjacency: direction %d is (0, 0, 0)", k);
-        if (seen[code] || seen[neg]) return fail(XB_E_ARG, "xb_adjacency: direction %d is given twice or together with its negative", k);
+        if (code == 13) return fail(XB_E_ARG, "%s: direction %d is (0, 0, 0)", who, k);
+        if (seen[code] || seen[neg]) return fail(XB_E_ARG, "%s: direction %d is given twice or together with its negative", who, k);
         seen[code] = true;
     }
     for (int k = n_dirs; k < AJ_MAX_DIRS; k++) D.d[k][0] = D.d[k][1] = D.d[k][2] = 0;
+    return XB_OK;
+}
+
+int xb_adjacency(xb_ctx *c, const int32_t *dirs, int n_dirs, int64_t n, int64_t *n_pairs) {
+    if (!c || !c->has_grid) return fail(XB_E_STATE, "xb_adjacency: call xb_set_grid first");
+    if (!dirs || !n_pairs) return fail(XB_E_ARG, "xb_adjacency: null argument");
+    if (n < 1) return fail(XB_E_ARG, "xb_adjacency: %lld labels", (long long)n);
+    if (n > XB_INT_MAX) return fail(XB_E_LIMIT, "xb_adjacency: %lld labels exceed %d", (long long)n, XB_INT_MAX);
+    AjDirs D;
+    if (int rc = adjacency_dirs("xb_adjacency", dirs, n_dirs, D)) return rc;
     if (c->g.x1 - c->g.x0 != c->g.nx)
         return fail(XB_E_STATE, "xb_adjacency: the context holds a slab [%d, %d) of %d planes; the adjacency needs the whole grid", c->g.x0, c->g.x1, c->g.nx);
     if (!c->have_rho) return fail(XB_E_STATE, "xb_adjacency: no density on this grid yet");

@@ -34,10 +34,12 @@ int xb_create(int device, xb_ctx **out) {
 static void weight_free(xb_ctx *c);
 static void moments_free(xb_ctx *c);
 static void adjacency_free(xb_ctx *c);
+static void merge_free(xb_ctx *c);
 static void free_grid(xb_ctx *c) {
     weight_free(c);
     moments_free(c);
     adjacency_free(c);
+    merge_free(c);
     c->have_rho = c->have_labels = false;
     hipFree(c->rho); hipFree(c->grad); hipFree(c->labels); hipFree(c->known); hipFree(c->first); hipFree(c->list);
     hipFree(c->st); hipFree(c->stage); hipFree(c->ec_pend); c->ec_pend = nullptr; hipFree(c->ec_share); c->ec_share = nullptr; hipFree(c->ec_pflag); c->ec_pflag = nullptr; hipFree(c->max_list); hipFree(c->max_aux); hipFree(c->ovf_list);
@@ -59,6 +61,7 @@ void xb_destroy(xb_ctx *c) {
     fmt_release(c);
     for (auto &t : c->tk)
         for (auto &p : t.pending) { hipEventDestroy(p.first); hipEventDestroy(p.second); }
+    for (auto &p : c->tk_merge.pending) { hipEventDestroy(p.first); hipEventDestroy(p.second); }
     free_grid(c);
     hipFree(c->counters); hipFree(c->counters64); hipFree(c->dsum); hipFree(c->dist_dev); hipFree(c->boxbuf);
     hipFree(c->walk_in); hipFree(c->walk_out2); hipFree(c->walk_res); hipFree(c->xbuf); hipFree(c->wbuf[0]); hipFree(c->wbuf[1]); hipFree(c->wk_in);
@@ -173,7 +176,7 @@ int xb_set_grid(xb_ctx *c, const int64_t shape[3], const double dist_mat[27], co
     }
     c->zero_outside[0] = -1;
     Grid &g = c->g;
-    if (g.nx != (int)shape[0] || g.ny != (int)shape[1] || g.nz != (int)shape[2]) { c->grad_valid = false; c->brick_max_valid = false; c->have_rho = c->have_labels = false; adjacency_free(c); }
+    if (g.nx != (int)shape[0] || g.ny != (int)shape[1] || g.nz != (int)shape[2]) { c->grad_valid = false; c->brick_max_valid = false; c->have_rho = c->have_labels = false; adjacency_free(c); merge_free(c); }
     if (dist_mat && !T_grad) return fail(XB_E_ARG, "xb_set_grid: dist_mat without T_grad");
     g.nx = (int)shape[0]; g.ny = (int)shape[1]; g.nz = (int)shape[2];
     g.nyz = g.ny * g.nz;

@@ -121,7 +121,7 @@ class Bader:
 
     @bader_maxima.setter
     def bader_maxima(self, maxima):                                                # interface.py:318-324
-        if self.adjacency_flag:   # (the integer voxels: bond_surfaces reads rho there)
+        if self.adjacency_flag or self.persistence_tol is not None:   # (the integer voxels: bond_surfaces and merge_volumes read rho there)
             self._bader_maxima_voxels = np.array(maxima, dtype=np.int64).reshape(-1, 3)
         maxima = np.add(maxima, self.voxel_offset_fractional)
         self._bader_maxima = np.ascontiguousarray(np.divide(maxima, self.grid_shape))
@@ -274,17 +274,36 @@ class Bader:
             rho_max = np.asarray(at[vox[:, 0], vox[:, 1], vox[:, 2]], dtype=np.float64)
             self.bader_persistence = persistence(b.pairs, b.saddle_density, rho_max)
 
+    persistence_tol = None   # a value: _run merges the Bader volumes below this persistence before their first use (None: no step changes)
+
+    def merge_volumes(self):
+        """Merge the Bader volumes whose persistence lies below persistence_tol (pybader_amd.merge.merge_basins on the
+        reference density) -- no counterpart in the reference.  bader_volumes becomes the relabelled map, bader_maxima the
+        survivors' voxels, bader_merge the merge.Merge (root, merge_round, merge_persistence, survivors, swap in the labels
+        before the merge): every later step sees the simplified partition.  The maxima's integer voxels are kept by
+        bader_calc() while persistence_tol is set (_bader_maxima_voxels)."""
+        from .merge import merge_basins
+        vox = getattr(self, '_bader_maxima_voxels', None)
+        if vox is None:
+            raise RuntimeError('merge_volumes: set persistence_tol before bader_calc(), which then keeps the maxima\'s voxels')
+        m = merge_basins(self.reference, self.bader_volumes, self.lattice, vox, self.persistence_tol)
+        self.bader_volumes = m.apply(self.bader_volumes)
+        self.bader_maxima = vox[m.survivors]
+        self.bader_merge = m
+
     fused = True      # _run issues bader_calc + refine as one call where the two are adjacent (False: the reference's two calls)
 
     def _run(self):
         self.volumes_init()
         if not self.speed_flag and self.fused:
             self.bader_calc_refine()
-            self.sum_volumes(bader=True)
         else:
             self.bader_calc()
-        if not self.speed_flag and not self.fused:
-            self.refine_volumes(self.bader_volumes)
+            if not self.speed_flag:
+                self.refine_volumes(self.bader_volumes)
+        if self.persistence_tol is not None:   # the Bader map is final and nobody has used it yet
+            self.merge_volumes()
+        if not self.speed_flag:
             self.sum_volumes(bader=True)
         self.bader_to_atom_distance()
         if self.speed_flag:
