@@ -248,7 +248,7 @@ int xb_charge_sum(xb_ctx *c, double voxel_volume, int64_t n_labels, double *char
  * The terms are a pure function of their inputs (no contraction); the order of the sums is free (float atomics, as xb_charge_sum).
  * n <= 224 labels sum in LDS bins per block, more in global memory; waves that hold one label add once per wave.
  * XB_E_STATE: no grid, or a grid that has received no density or no labels yet;  XB_E_ARG: n < 1 or a null pointer;
- * XB_E_LIMIT: n above (2^31 - 1) / 10.  Timer 8 of xb_kernel_time; its buffer is counted by xb_memory_stats. */
+ * XB_E_LIMIT: n above (2^31 - 1) / 10.  XB_TIMER_MOMENTS of xb_kernel_time; its buffer is counted by xb_memory_stats. */
 int xb_moment_sum(xb_ctx *c, const double lattice[9], const double *centres_cart, int64_t n, double voxel_volume,
                   double *moments /* n*10 */, double *volume /* n */);
 /* ---- which labels share a surface: facet counts and the saddle per pair of labels (interatomic surfaces, the grid estimate of the
@@ -276,7 +276,7 @@ int xb_moment_sum(xb_ctx *c, const double lattice[9], const double *centres_cart
  *   xb_adjacency_fetch   the pairs of the last call: a[i] < b[i], facets[i * n_dirs + k], saddle[i], saddle_facet[i]
  * XB_E_STATE: no grid, a grid that has received no density or no labels yet, a context that holds a slab (fetch: no result);
  * XB_E_ARG: n < 1, n_dirs outside 1..13, a direction outside {-1,0,1}^3 \ {0}, given twice or together with its negative, a null
- * pointer, capacity < n_pairs in fetch;  XB_E_LIMIT: n > 2^31 - 1.  Timer 9 of xb_kernel_time. */
+ * pointer, capacity < n_pairs in fetch;  XB_E_LIMIT: n > 2^31 - 1.  XB_TIMER_ADJACENCY of xb_kernel_time. */
 int xb_adjacency(xb_ctx *c, const int32_t *dirs /* n_dirs*3 */, int n_dirs, int64_t n, int64_t *n_pairs);
 int xb_adjacency_fetch(xb_ctx *c, int32_t *a, int32_t *b, int64_t *facets /* cap*n_dirs */, double *saddle,
                        int64_t *saddle_facet, int64_t capacity);
@@ -310,8 +310,8 @@ int xb_adjacency_release(xb_ctx *c);
  * xb_merge_release.
  * XB_E_STATE: no grid, a grid that has received no density or no labels yet, a context that holds a slab (fetch: no result);
  * XB_E_ARG: the direction faults of xb_adjacency, n < 1, a null pointer, max_rounds < 1, tol negative or NaN (+inf is allowed), a
- * max_idx outside [0, N), capacity < n in fetch;  XB_E_LIMIT: n > 2^31 - 1.  All found on the host before any launch.  Timer 10 of
- * xb_kernel_time. */
+ * max_idx outside [0, N), capacity < n in fetch;  XB_E_LIMIT: n > 2^31 - 1.  All found on the host before any launch.
+ * XB_TIMER_MERGE of xb_kernel_time. */
 int xb_merge_basins(xb_ctx *c, const int32_t *dirs, int n_dirs, int64_t n, const int64_t *max_idx, double tol, int64_t max_rounds, int64_t *rounds, int64_t *n_survivors, int *converged);
 int xb_merge_fetch(xb_ctx *c, int32_t *root, int32_t *merge_round, double *merge_persistence, int64_t capacity);
 int xb_merge_release(xb_ctx *c);
@@ -445,34 +445,78 @@ int xb_slab_block_copy(xb_ctx *c, int which, int to_device, void *host, int64_t 
 int xb_host_waits(int64_t *n);
 
 /* ---- measurement ------------------------------------------------------------------------- */
-/* HIP-event timing of the stages, measured on the context's stream: accumulated milliseconds and launch
- * count since the last reset.  which: 0 neargrid assignment after pass A (walk list, records, walker trace),
- * 1 the ongrid pointer pass (k_og_masks), 2 edge_find, 3 refine trace, 4 pass A + region growth (and records built
- * for a refinement), 5 k_brick_masks alone, 6 the trace kernel alone, 7 k_brick_records alone, 8 the kernels of xb_moment_sum,
- * 9 the kernels of xb_adjacency (one interval per group of launches between two host waits), 10 the kernels of xb_merge_basins
- * (likewise: the initialisation, each round's two passes and decision, each round's pointer doubling). */
+/* The numbered vocabulary below (timer slots, option keys, their values and bits) is FROZEN: benchmarks and tools pass the values
+ * as plain integers, so a name may be added but no value changes or is used again.  pybader_amd/_lib.py mirrors every name. */
+/* `which` of xb_kernel_time, and the bit (k + 1) of xb_enable_timing's mask */
+enum {
+    XB_TIMER_ASSIGN = 0,        /* the neargrid assignment after pass A: walk list, records, walker trace */
+    XB_TIMER_OG_MASKS = 1,      /* the ongrid pointer pass (k_og_masks) */
+    XB_TIMER_EDGE_FIND = 2,     /* edge_find */
+    XB_TIMER_REFINE_TRACE = 3,  /* the refinement's retraces */
+    XB_TIMER_MASKS_GROWTH = 4,  /* pass A + region growth (and records built for a refinement) */
+    XB_TIMER_BRICK_MASKS = 5,   /* k_brick_masks alone */
+    XB_TIMER_TRACE = 6,         /* the trace kernel alone */
+    XB_TIMER_BRICK_RECORDS = 7, /* k_brick_records alone */
+    XB_TIMER_MOMENTS = 8,       /* the kernels of xb_moment_sum */
+    XB_TIMER_ADJACENCY = 9,     /* the kernels of xb_adjacency: one interval per group of launches between two host waits */
+    XB_TIMER_MERGE = 10,        /* the kernels of xb_merge_basins, likewise: the initialisation, each round's two passes and decision,
+                                 * each round's pointer doubling */
+    XB_TIMER_COUNT = 11
+};
+/* HIP-event timing of the stages, measured on the context's stream: accumulated milliseconds and launch count of timer `which`
+ * (XB_TIMER_*) since the last reset.  XB_E_ARG: `which` outside [0, XB_TIMER_COUNT). */
 int xb_kernel_time(xb_ctx *c, int which, double *ms_total, int64_t *launches);
 int xb_kernel_time_reset(xb_ctx *c);
 /* on: 0 off, 1 every timer, otherwise a mask: bit k + 1 switches timer `which` = k on (event pairs between dependent kernels
  * cost stream time: a benchmark keeps only the dominant kernel's timer on inside its timed region) */
 int xb_enable_timing(xb_ctx *c, int on);
-/* Switches (ten keys).  A USER of the library sets none of them: every default is the measured best, and no switch but 30 changes a
- * result.  What each is for:
- *   6   drop the cached gradient-field table (benchmarks: a table kept from an earlier step would hide 1.6 ms per step);
- *   3   debug (bit 2 edge_check passes, bit 4 slab statistics, bit 5 wait after every stage of an assignment, bit 6 the exact
- *       slow path with tiers of 3 / 5 / 8 path voxels, so that a test reaches its last tier);
- *   24  collectives return without waiting (set by pybader_amd.slab itself);
- *   1   trapping regions (0: plain full trajectories from a record per voxel) -- the exactness cross-check of the whole design;
- *   2   cross-check bits, each selecting the second implementation of one step so that a test can compare the two:
- *       1 no mirror prefilter in pass A, 2 the generic walker instead of the lean one, 4 the full T_grad . grad product on
- *       orthogonal lattices, 8 dilation from the edge list instead of tile by tile, 16 int32 label halos, 32 no front sharing
- *       in the edge_check chase, 64 xb_import_density gathers a permuted layout voxel by voxel instead of through the LDS tile;
- *   30  xb_weight_sum ignores the resident labels (1: no voxel is vacuum, the labels are not read; pybader_amd.weight sets it for
- *       a call without a label map and clears it again) -- the one switch that selects an input rather than an implementation;
- *   test plumbing -- 4 / 5 workgroups and LDS queue capacity of the edge_check chase (lowered to force the overflow
- *   hand-over), 17 kill launches scheduled after a chase (1 forces the repeat), 19 a rank may exchange planes with itself.
- * (Round 4 removed 0, 2, 9-12, 15, 21; round 6 removed 7, 8, 16, 22 -- routes and launch shapes nobody set -- and folded 13, 14,
- * 18, 20, 25, 29 into the bits of key 2.) */
+/* `key` of xb_set_option */
+enum {
+    XB_OPT_REGIONS = 1,           /* XB_REGIONS_* bits; without both of them: plain full trajectories from a record per voxel -- the
+                                   * exactness cross-check of the whole design */
+    XB_OPT_CROSS_CHECK = 2,       /* XB_CHECK_* bits, each selecting the second implementation of one step so that a test can compare
+                                   * the two */
+    XB_OPT_DEBUG = 3,             /* XB_DBG_* bits */
+    XB_OPT_EC_GROUPS = 4,         /* test plumbing: workgroups of the edge_check chase, 1..4096 (default 256) ... */
+    XB_OPT_EC_QCAP = 5,           /* ... and its LDS queue capacity, from 2 up to the default (lowered to force the overflow hand-over) */
+    XB_OPT_DROP_TABLE = 6,        /* drop the cached gradient-field table (benchmarks: a table kept from an earlier step would hide
+                                   * 1.6 ms per step); the value is not kept, see XB_DROP_TABLE_AND_MAXIMA */
+    XB_OPT_KILL_LAUNCHES = 17,    /* test plumbing: kill launches scheduled after a chase, >= 1 (default 6; 1 forces the repeat) */
+    XB_OPT_SELF_EXCHANGE = 19,    /* test plumbing: a rank may exchange planes with itself */
+    XB_OPT_ASYNC_COMM = 24,       /* collectives return without waiting (set by pybader_amd.slab itself) */
+    XB_OPT_WEIGHT_NO_LABELS = 30  /* xb_weight_sum ignores the resident labels (1: no voxel is vacuum, the labels are not read;
+                                   * pybader_amd.weight sets it for a call without a label map and clears it again) -- the one switch
+                                   * that selects an input rather than an implementation */
+};
+/* value of XB_OPT_REGIONS: both bits by default.  Trapping regions are built, per 8^3 brick, only with BOTH bits set; one bit alone
+ * selects the same plain path as 0 */
+enum {
+    XB_REGIONS_BOXES = 1,
+    XB_REGIONS_BRICKS = 2
+};
+/* value of XB_OPT_DROP_TABLE that also forgets which bricks hold a 26-neighbour maximum (any other value keeps that) */
+enum { XB_DROP_TABLE_AND_MAXIMA = 2 };
+/* value of XB_OPT_CROSS_CHECK: a set bit selects the second implementation */
+enum {
+    XB_CHECK_NO_MIRROR = 1,       /* pass A runs the exact ongrid plane test for every open face (no mirror prefilter) */
+    XB_CHECK_GENERIC_WALKER = 2,  /* the generic walker instead of the lean one */
+    XB_CHECK_FULL_TGRAD = 4,      /* the full T_grad . grad product on orthogonal lattices too */
+    XB_CHECK_LIST_DILATE = 8,     /* the dilation of the edge sweep from the edge list instead of tile by tile */
+    XB_CHECK_WIDE_HALO = 16,      /* label halos travel as int32 */
+    XB_CHECK_NO_EC_SHARE = 32,    /* no front sharing in the edge_check chase: every workgroup keeps what it wakes */
+    XB_CHECK_IO_GATHER = 64       /* xb_import_density gathers a permuted layout voxel by voxel instead of through the LDS tile */
+};
+/* value of XB_OPT_DEBUG (bits 1, 2 and 8 are not in use) */
+enum {
+    XB_DBG_EC_PASSES = 4,         /* print the passes of edge_check and what the middle tier leaves for the exact slow kernel */
+    XB_DBG_SLAB_STATS = 16,       /* print the statistics of the device-driven slab step */
+    XB_DBG_STAGE_WAIT = 32,       /* wait after every stage of an assignment and say so */
+    XB_DBG_SHORT_TIERS = 64       /* the exact slow path with tiers of 3 / 5 / 8 path voxels, so that a test reaches its last tier */
+};
+/* Switches.  A USER of the library sets none of them: every default is the measured best, and no switch but
+ * XB_OPT_WEIGHT_NO_LABELS changes a result.  A key that is not an XB_OPT_* value, or a value outside the range its key states, is
+ * XB_E_ARG.  (Round 4 removed keys 0, 2, 9-12, 15, 21; round 6 removed 7, 8, 16, 22 -- routes and launch shapes nobody set -- and
+ * folded 13, 14, 18, 20, 25, 29 into the bits of XB_OPT_CROSS_CHECK.) */
 int xb_set_option(xb_ctx *c, int key, int value);
 /* device bytes held for the grid (density, labels, flags, numbering + the table of the window planes + scratch sized by the
  * slab): what a rank of the slab decomposition costs; the reference's blocks are copies of the block extent
@@ -495,7 +539,7 @@ int xb_slow_path_stats(xb_ctx *c, int64_t *assign_total, int64_t *refine_total);
 /* retraces redone by the from-rho kernel since the context was created (their walk went on through a brick whose
  * records the sparse table does not hold) */
 int xb_deferred_stats(xb_ctx *c, int64_t *refine_total);
-/* region growth: assignments repeated because the scheduled kill launches (option 17; 6 after a chase) did not reach the
+/* region growth: assignments repeated because the scheduled kill launches (XB_OPT_KILL_LAUNCHES; 6 after a chase) did not reach the
  * fixpoint, and the schedule this context uses now (raised to the worst case by the first repeat) */
 int xb_growth_stats(xb_ctx *c, int64_t *retries, int64_t *kill_launches);
 

@@ -15,6 +15,25 @@ DTYPE_CODE = {np.dtype(np.int8): 1, np.dtype(np.int16): 2, np.dtype(np.int32): 4
 # the int64 entries of the slab step's block 5 (the XB_XC_* enum of include/bader_hip.h)
 (XB_XC_EDGES, XB_XC_CHANGED, XB_XC_ESCAPED, XB_XC_TRAVELLING, XB_XC_SLOW, XB_XC_LOST, XB_XC_MINE, XB_XC_ROUNDS,
  XB_XC_COUNT) = range(9)
+# xb_kernel_time's `which` (the XB_TIMER_* enum; like every value below frozen: benchmarks pass them as plain integers)
+(XB_TIMER_ASSIGN, XB_TIMER_OG_MASKS, XB_TIMER_EDGE_FIND, XB_TIMER_REFINE_TRACE, XB_TIMER_MASKS_GROWTH, XB_TIMER_BRICK_MASKS,
+ XB_TIMER_TRACE, XB_TIMER_BRICK_RECORDS, XB_TIMER_MOMENTS, XB_TIMER_ADJACENCY, XB_TIMER_MERGE, XB_TIMER_COUNT) = range(12)
+# xb_set_option's `key` (the XB_OPT_* enum), each key's value on the lines after it
+XB_OPT_REGIONS = 1
+XB_REGIONS_BOXES, XB_REGIONS_BRICKS = 1, 2
+XB_OPT_CROSS_CHECK = 2
+(XB_CHECK_NO_MIRROR, XB_CHECK_GENERIC_WALKER, XB_CHECK_FULL_TGRAD, XB_CHECK_LIST_DILATE, XB_CHECK_WIDE_HALO,
+ XB_CHECK_NO_EC_SHARE, XB_CHECK_IO_GATHER) = (1, 2, 4, 8, 16, 32, 64)
+XB_OPT_DEBUG = 3
+XB_DBG_EC_PASSES, XB_DBG_SLAB_STATS, XB_DBG_STAGE_WAIT, XB_DBG_SHORT_TIERS = 4, 16, 32, 64
+XB_OPT_EC_GROUPS = 4
+XB_OPT_EC_QCAP = 5
+XB_OPT_DROP_TABLE = 6
+XB_DROP_TABLE_AND_MAXIMA = 2
+XB_OPT_KILL_LAUNCHES = 17
+XB_OPT_SELF_EXCHANGE = 19
+XB_OPT_ASYNC_COMM = 24
+XB_OPT_WEIGHT_NO_LABELS = 30
 
 # every symbol include/bader_hip.h declares: (restype, argtypes)
 _vp, _i64, _dbl, _int = C.c_void_p, C.c_int64, C.c_double, C.c_int
@@ -756,11 +775,11 @@ class Context:
         itself, a host array or a float32 / float64 device array of any strides another field of the grid's shape;
         `use_labels` False: no voxel is vacuum and the resident labels are not read (neither way are they written);
         -> (linear voxel index int64[M], charge f64[M], volume f64[M]) of the maxima in ascending voxel index"""
-        self.set_option(30, 0 if use_labels else 1)
+        self.set_option(XB_OPT_WEIGHT_NO_LABELS, 0 if use_labels else 1)
         try:
             return self._weight_sum(alpha, voxel_volume, q)
         finally:
-            self.set_option(30, 0)
+            self.set_option(XB_OPT_WEIGHT_NO_LABELS, 0)
 
     def weight_release(self):
         """free the weight method's device buffers (they are kept between calls while the grid stays)"""
@@ -993,11 +1012,12 @@ class Context:
         return int(n.value)
 
     def enable_timing(self, on=True, only=None):
-        """on: all timers; only=[k, ...]: just these (xb_kernel_time's `which`)"""
+        """on: all timers; only=[k, ...]: just these (XB_TIMER_* constants)"""
         mask = int(bool(on)) if only is None else sum(2 << int(k) for k in only)
         check(self.lib.xb_enable_timing(self.h, mask))
 
     def kernel_time(self, which):
+        """-> (milliseconds, launches) of timer `which` (an XB_TIMER_* constant) since the last reset"""
         ms, n = C.c_double(), C.c_int64()
         check(self.lib.xb_kernel_time(self.h, int(which), C.byref(ms), C.byref(n)))
         return ms.value, n.value
@@ -1006,6 +1026,7 @@ class Context:
         check(self.lib.xb_kernel_time_reset(self.h))
 
     def set_option(self, key, value):
+        """key: an XB_OPT_* constant; value: what the key's comment in include/bader_hip.h states"""
         check(self.lib.xb_set_option(self.h, int(key), int(value)))
 
     def box_stats(self):

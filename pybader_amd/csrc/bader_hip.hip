@@ -86,13 +86,26 @@ struct xb_ctx {
     int *box_max_tab = nullptr; // region id - 1 -> voxel of the region's maximum (inside boxbuf: BB_BOXMAX or BB_REGMAX)
     int n_boxes = 0;
     long long box_voxels = 0;
-    int opt_boxes = 1;
-    int opt_bricks = 1;
-    int opt_dbg = 0;
-    int opt_ec_groups = 256;    // workgroups of k_ec_chase (at most one per CU)
-    int opt_ec_share = 1;       // k_ec_chase: a long queue sheds its surplus into other workgroups' mailboxes (0: every workgroup keeps what it wakes; A/B, option 29)
+    // what xb_set_option keeps (XB_OPT_* in bader_hip.h).  Not here: XB_OPT_KILL_LAUNCHES, which the library raises itself
+    // (grow_kill_launches), and XB_OPT_DROP_TABLE, an action on grad_valid / brick_max_valid that keeps no value
+    struct Options {
+        int boxes = 1, bricks = 1; // XB_OPT_REGIONS: its bits XB_REGIONS_BOXES and XB_REGIONS_BRICKS; trapping regions are built only with both
+        // XB_OPT_CROSS_CHECK, a field per XB_CHECK_* bit: 1 (the implementation in use) unless the bit is set
+        int mirror = 1;            // pass A: mirror prefilter of the ongrid face test (k_masks.h, bm_mirror)
+        int lean = 1;              // persistent trace: the lean walker (k_trace.h, ng_walk_lean); 0: ng_walk_wave (tests compare)
+        int mask_diag = 1;         // pass A: the three-product form of T_grad . grad on orthogonal lattices (tests compare)
+        int tile_dilate = 1;       // the dilation of the edge sweep tile by tile (k_edge_dilate_tiles) instead of from the edge list (tests compare)
+        int narrow_halo = 1;       // label halos travel as dtype_calc(-n_maxima) (int8 / int16) instead of int32 (comm.h)
+        int ec_share = 1;          // k_ec_chase: a long queue sheds its surplus into other workgroups' mailboxes (0: every workgroup keeps what it wakes; A/B, XB_CHECK_NO_EC_SHARE)
+        int io_tiled = 1;          // xb_import_density: permuted layouts through the LDS tile (0: the plain strided gather; tests and the benchmark compare)
+        int dbg = 0;               // XB_OPT_DEBUG: XB_DBG_* bits
+        int ec_groups = 256;       // XB_OPT_EC_GROUPS: workgroups of k_ec_chase (at most one per CU)
+        int ec_qcap = EC_Q;        // XB_OPT_EC_QCAP: LDS queue entries used per buffer (smaller only in tests)
+        int self_exchange = 0;     // XB_OPT_SELF_EXCHANGE, tests only: xb_comm_exchange_planes accepts this rank as its own peer (one GPU exercises pack / send / recv / unpack)
+        int async_comm = 0;        // XB_OPT_ASYNC_COMM: collectives return without waiting (they are ordered on the context's stream); the device-driven slab step sets it
+        bool weight_no_labels = false;   // XB_OPT_WEIGHT_NO_LABELS: the next xb_weight_sum treats no voxel as vacuum and does not read the labels
+    } opt;
     int *ec_share = nullptr;    // the sharing block of k_ec_chase (activity count, mailbox tails and slots), allocated on first use
-    int opt_ec_qcap = EC_Q;     // LDS queue entries used per buffer (smaller only in tests)
     std::vector<int64_t> esc_starts, esc_offsets, esc_vox;  // xb_escaped_paths -> xb_escaped_paths_fetch
     unsigned long long *ec_pend = nullptr;  // edge_check's counter word per voxel (8 N bytes, allocated on first use)
     int8_t *ec_pflag = nullptr;             // ... and a flag byte per voxel, set on the processed voxels while their boxes are applied (zero otherwise)
@@ -138,18 +151,11 @@ struct xb_ctx {
     void *wk_in = nullptr;                // the walkers this rank carries on in a round (+ their count)
     int wbuf_ranks = 0, walk_last = -1, walk_round = 0, wcap = 0;
     int walk_send = 0;          // walkers of a rank's part that travel in the pass's own gather (0: the capacity; xb_slab_walk_send)
-    int opt_async_comm = 0;    // collectives return without waiting (they are ordered on the context's stream); the device-driven slab step sets it
-    int opt_tile_dilate = 1;   // the dilation of the edge sweep tile by tile (k_edge_dilate_tiles) instead of from the edge list (tests compare)
-    int opt_self_exchange = 0; // tests only: xb_comm_exchange_planes accepts this rank as its own peer (one GPU exercises pack / send / recv / unpack)
-    int opt_mask_diag = 1;     // pass A: the three-product form of T_grad . grad on orthogonal lattices (tests compare)
-    int opt_narrow_halo = 1;   // label halos travel as dtype_calc(-n_maxima) (int8 / int16) instead of int32 (comm.h)
-    int grow_kill_launches = 6;   // kill launches scheduled after a chase (raised to the worst case by the first assignment that needs more)
+    int grow_kill_launches = 6;   // XB_OPT_KILL_LAUNCHES: kill launches scheduled after a chase (raised to the worst case by the first assignment that needs more)
     long long stat_grow_retries = 0;
     bool defer_wait = false;     // xb_assign_refine: the assignment queues its result transfer and returns without waiting ...
     bool pending_assign = false; // ... and its results are still to be read (after the refinement's first wait)
     int64_t pending_n_maxima = 0;
-    int opt_lean = 1;          // persistent trace: the lean walker (k_trace.h, ng_walk_lean); 0: ng_walk_wave (tests compare)
-    int opt_mirror = 1;        // pass A: mirror prefilter of the ongrid face test (k_masks.h, bm_mirror)
     int grad_rule = 0;         // which tie rule the resident table obeys: 0 refinement.py:111, 1 methods.py:324, 2 both
                                // (the density has no voxel where they differ)
     int *labels = nullptr;
@@ -177,7 +183,6 @@ struct xb_ctx {
     char *big_pin[2] = {nullptr, nullptr};   // two pinned chunks for the large transfers (staged_h2d / staged_d2h)
     hipEvent_t big_ev[2] = {nullptr, nullptr};
     hipEvent_t io_ev = nullptr;   // orders the device-array entry points against the caller's stream (host_interop.h)
-    int opt_io_tiled = 1;      // xb_import_density: permuted layouts through the LDS tile (0: the plain strided gather; tests and the benchmark compare)
     char *pin = nullptr;       // pinned staging for the small host arrays a step uploads (pageable copies pin pages on the fly)
     size_t pin_bytes = 0;
     std::vector<int> maxima_sorted;  // global, label order
@@ -192,8 +197,7 @@ struct xb_ctx {
     int list_n = 0;            // entries of `list` that hold the owned known == -2 voxels ...
     bool list_valid = false;   // ... when this is set (by xb_edge_find)
     unsigned timing = 0;   // bit k: timer k records its events (xb_enable_timing)
-    TimedKernel tk[10];
-    TimedKernel tk_merge;      // timer XB_TIMER_MERGE, next to the ten stage timers (timer_of)
+    TimedKernel tk[XB_TIMER_COUNT];
     long long n_alloc = 0;
     bool thin = false;         // an axis has fewer than 3 voxels: transfers, the vacuum sweep and the weight method only (NEED_GRID)
     // the weight method (host_weight.h): accumulators, pending counts, the two work lists, S when `stage` cannot hold it, the
@@ -205,7 +209,6 @@ struct xb_ctx {
     long long w_cap = 0;       // voxels the weight buffers hold (0: not allocated)
     long long w_stat[6] = {0, 0, 0, 0, 0, 0};
     bool w_have = false;
-    bool w_ignore_labels = false;   // option 30: the next xb_weight_sum treats no voxel as vacuum and does not read the labels
     std::vector<int64_t> w_idx;
     std::vector<double> w_charge, w_volume;
     // xb_moment_sum (host_moments.h): its one buffer (image vectors, position table, centres, sums, counts) and its size in doubles
@@ -304,9 +307,6 @@ static void mirror_prefilter(const Grid &g, int &mirror, double &mu_scale) {
     mu_scale = std::ldexp(1. + 1. / dmin, -48);
 }
 
-#define XB_TIMER_MERGE 10
-static inline TimedKernel &timer_of(xb_ctx *c, int which) { return which == XB_TIMER_MERGE ? c->tk_merge : c->tk[which]; }
-
 struct ScopedTimer {
     xb_ctx *c;
     int which;
@@ -321,7 +321,7 @@ struct ScopedTimer {
     ~ScopedTimer() {
         if ((c->timing >> which) & 1u) {
             hipEventRecord(b, c->stream);
-            timer_of(c, which).pending.push_back({a, b});
+            c->tk[which].pending.push_back({a, b});
         }
     }
 };
@@ -345,25 +345,29 @@ const char *xb_last_error(void) { return g_err.c_str(); }
 
 int xb_set_option(xb_ctx *c, int key, int value) {
     if (!c) return fail(XB_E_ARG, "null ctx");
-    if (key == 1) { c->opt_boxes = value & 1; c->opt_bricks = (value >> 1) & 1; }
-    else if (key == 2) {   // cross-checks: a second implementation of the same step, for the tests that compare the two
-        c->opt_mirror = !(value & 1);        // 1: pass A runs the exact ongrid plane test for every open face (no mirror prefilter)
-        c->opt_lean = !(value & 2);          // 2: the generic walker ng_walk_wave instead of the lean one
-        c->opt_mask_diag = !(value & 4);     // 4: the full T_grad . grad product on orthogonal lattices too
-        c->opt_tile_dilate = !(value & 8);   // 8: the dilation of the edge sweep from the edge list instead of tile by tile
-        c->opt_narrow_halo = !(value & 16);  // 16: label halos travel as int32
-        c->opt_ec_share = !(value & 32);     // 32: every workgroup of the edge_check chase keeps what it wakes
-        c->opt_io_tiled = !(value & 64);     // 64: xb_import_density gathers a permuted layout voxel by voxel instead of tile by tile
+    bool ok = true;   // false: the key's value is out of range (reported as the unknown key is)
+    switch (key) {
+    case XB_OPT_REGIONS: c->opt.boxes = (value & XB_REGIONS_BOXES) != 0; c->opt.bricks = (value & XB_REGIONS_BRICKS) != 0; break;
+    case XB_OPT_CROSS_CHECK:
+        c->opt.mirror = !(value & XB_CHECK_NO_MIRROR);
+        c->opt.lean = !(value & XB_CHECK_GENERIC_WALKER);
+        c->opt.mask_diag = !(value & XB_CHECK_FULL_TGRAD);
+        c->opt.tile_dilate = !(value & XB_CHECK_LIST_DILATE);
+        c->opt.narrow_halo = !(value & XB_CHECK_WIDE_HALO);
+        c->opt.ec_share = !(value & XB_CHECK_NO_EC_SHARE);
+        c->opt.io_tiled = !(value & XB_CHECK_IO_GATHER);
+        break;
+    case XB_OPT_DEBUG: c->opt.dbg = value; break;
+    case XB_OPT_EC_GROUPS: if ((ok = value >= 1 && value <= 4096)) c->opt.ec_groups = value; break;
+    case XB_OPT_EC_QCAP: if ((ok = value >= 2 && value <= EC_Q)) c->opt.ec_qcap = value; break;
+    case XB_OPT_DROP_TABLE: c->grad_valid = false; if (value == XB_DROP_TABLE_AND_MAXIMA) c->brick_max_valid = false; break;   // (a refinement rebuilds the table)
+    case XB_OPT_KILL_LAUNCHES: if ((ok = value >= 1)) c->grow_kill_launches = value; break;
+    case XB_OPT_SELF_EXCHANGE: c->opt.self_exchange = value != 0; break;
+    case XB_OPT_ASYNC_COMM: c->opt.async_comm = value != 0; break;
+    case XB_OPT_WEIGHT_NO_LABELS: c->opt.weight_no_labels = value != 0; break;
+    default: ok = false;
     }
-    else if (key == 3) c->opt_dbg = value;
-    else if (key == 4 && value >= 1 && value <= 4096) c->opt_ec_groups = value;
-    else if (key == 5 && value >= 2 && value <= EC_Q) c->opt_ec_qcap = value;
-    else if (key == 6) { c->grad_valid = false; if (value == 2) c->brick_max_valid = false; }  // drop the cached gradient-field table (a refinement rebuilds it)
-    else if (key == 17 && value >= 1) c->grow_kill_launches = value;
-    else if (key == 19) c->opt_self_exchange = value != 0;
-    else if (key == 24) c->opt_async_comm = value != 0;
-    else if (key == 30) c->w_ignore_labels = value != 0;
-    else return fail(XB_E_ARG, "xb_set_option: unknown key %d", key);
+    if (!ok) return fail(XB_E_ARG, "xb_set_option: unknown key %d", key);
     return XB_OK;
 }
 int xb_growth_stats(xb_ctx *c, int64_t *retries, int64_t *kill_launches) {
@@ -445,15 +449,14 @@ int xb_enable_timing(xb_ctx *c, int on) {
     if (!c) return fail(XB_E_ARG, "null ctx");
     // 0: off; 1: every timer; otherwise bit k + 1 switches timer k on (an event pair costs ~10 us of an idle stream between
     // dependent kernels: a benchmark times its step with the dominant kernel's timer alone)
-    c->timing = on == 0 ? 0u : (on == 1 ? 0xFFFFu : ((unsigned)on >> 1));
+    c->timing = on == 0 ? 0u : (on == 1 ? (1u << XB_TIMER_COUNT) - 1u : ((unsigned)on >> 1));
     return XB_OK;
 }
 int xb_kernel_time_reset(xb_ctx *c) {
     if (!c) return fail(XB_E_ARG, "null ctx");
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipStreamSynchronize(c->stream));
-    for (int which = 0; which <= XB_TIMER_MERGE; which++) {
-        TimedKernel &t = timer_of(c, which);
+    for (TimedKernel &t : c->tk) {
         for (auto &p : t.pending) { hipEventDestroy(p.first); hipEventDestroy(p.second); }
         t.pending.clear();
         t.ms = 0.;
@@ -462,11 +465,10 @@ int xb_kernel_time_reset(xb_ctx *c) {
     return XB_OK;
 }
 int xb_kernel_time(xb_ctx *c, int which, double *ms_total, int64_t *launches) {
-    const bool merge_timer = c && which == XB_TIMER_MERGE;   // stands next to the ten stage timers
-    if (!merge_timer && (!c || which < 0 || which > 9)) return fail(XB_E_ARG, "xb_kernel_time: bad argument");
+    if (!c || which < 0 || which >= XB_TIMER_COUNT) return fail(XB_E_ARG, "xb_kernel_time: bad argument");
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipStreamSynchronize(c->stream));
-    TimedKernel &t = timer_of(c, which);
+    TimedKernel &t = c->tk[which];
     for (auto &p : t.pending) {
         float ms = 0.f;
         HIPCHK(hipEventElapsedTime(&ms, p.first, p.second));

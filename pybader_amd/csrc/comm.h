@@ -168,9 +168,9 @@ int xb_comm_exchange_planes(xb_ctx *c, int which, int n_send, const int32_t *sen
     const size_t es = which == 0 ? 4 : 1;
     char *base = which == 0 ? (char *)c->labels : (char *)c->known;
     const int dt = which == 0 ? xbcomm::ncclInt32 : xbcomm::ncclInt8;
-    // (a send to oneself is refused: no slab is its own neighbour -- except for the one-GPU test of this very path, option 19)
+    // (a send to oneself is refused: no slab is its own neighbour -- except for the one-GPU test of this very path, XB_OPT_SELF_EXCHANGE)
     auto bad = [&](int peer, int64_t xa, int64_t xb) {
-        return peer < 0 || peer >= c->comm->size || (peer == c->comm->rank && !c->opt_self_exchange) || xa < 0 || xb > g.nx || xa >= xb;
+        return peer < 0 || peer >= c->comm->size || (peer == c->comm->rank && !c->opt.self_exchange) || xa < 0 || xb > g.nx || xa >= xb;
     };
     for (int i = 0; i < n_send; i++) if (bad(send_peer[i], send_xa[i], send_xb[i])) return fail(XB_E_ARG, "xb_comm_exchange_planes: bad send %d", i);
     for (int i = 0; i < n_recv; i++) if (bad(recv_peer[i], recv_xa[i], recv_xb[i])) return fail(XB_E_ARG, "xb_comm_exchange_planes: bad recv %d", i);
@@ -180,7 +180,7 @@ int xb_comm_exchange_planes(xb_ctx *c, int which, int n_send, const int32_t *sen
     // the staging buffer before the group, widened back behind it, all on the context's stream.
     // (the width follows whoever wrote the resident labels last -- xb_ctx::label_wire -- not the last assignment's basin count:
     // an uploaded map with more basins than the assignment before it must not be truncated)
-    const int wire = (which == 0 && c->opt_narrow_halo) ? c->label_wire : (int)es;
+    const int wire = (which == 0 && c->opt.narrow_halo) ? c->label_wire : (int)es;
     size_t total = 0;
     for (int i = 0; i < n_send; i++) total += (size_t)(send_xb[i] - send_xa[i]) * g.nyz;
     for (int i = 0; i < n_recv; i++) total += (size_t)(recv_xb[i] - recv_xa[i]) * g.nyz;
@@ -228,7 +228,7 @@ int xb_comm_exchange_planes(xb_ctx *c, int which, int n_send, const int32_t *sen
         for (int i = 0; i < n_send; i++) t += (size_t)(send_xb[i] - send_xa[i]) * g.nyz;
         c->comm->bytes_sent += (unsigned long long)t * (packed ? (size_t)wire : es);
     }
-    if (!c->opt_async_comm) HIPCHK(hipStreamSynchronize(c->stream));   // (option 24: whatever reads the planes next is ordered behind them)
+    if (!c->opt.async_comm) HIPCHK(hipStreamSynchronize(c->stream));   // (XB_OPT_ASYNC_COMM: whatever reads the planes next is ordered behind them)
     return XB_OK;
 }
 

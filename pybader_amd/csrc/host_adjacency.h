@@ -28,7 +28,7 @@ static int adjacency_run(xb_ctx *c, const Route &R, const AjDirs &D, int n, size
     unsigned long long n_pairs = 0;
     HIPCHK(hipMemsetAsync(cnt, 0, sizeof(unsigned long long), c->stream));
     {
-        ScopedTimer timer(c, 9);
+        ScopedTimer timer(c, XB_TIMER_ADJACENCY);
         k_aj_init<<<(unsigned)std::min<size_t>((n_slots * R.stride + TPB - 1) / TPB, (size_t)1 << 18), TPB, 0, c->stream>>>(R.ent, n_slots, R.stride);
         k_aj_pass1<Route><<<blocks, TPB, 0, c->stream>>>(R, g, D, c->rho, c->labels, n, c->N);
         k_aj_pass2<Route><<<blocks, TPB, 0, c->stream>>>(R, g, D, c->rho, c->labels, n, c->N);
@@ -44,7 +44,7 @@ static int adjacency_run(xb_ctx *c, const Route &R, const AjDirs &D, int n, size
     HIPCHK(out.alloc((size_t)n_pairs * width));
     HIPCHK(hipMemsetAsync(cnt, 0, sizeof(unsigned long long), c->stream));
     {
-        ScopedTimer timer(c, 9);
+        ScopedTimer timer(c, XB_TIMER_ADJACENCY);
         k_aj_compact<Route><<<cand_blocks, TPB, 0, c->stream>>>(R, n_cand, cnt, n_pairs, out.p);
     }
     HIPCHK(hipGetLastError());
@@ -100,7 +100,7 @@ int xb_adjacency(xb_ctx *c, const int32_t *dirs, int n_dirs, int64_t n, int64_t 
         unsigned long long facets = 0;
         HIPCHK(hipMemsetAsync(c->counters64, 0, sizeof(unsigned long long), c->stream));
         {
-            ScopedTimer timer(c, 9);
+            ScopedTimer timer(c, XB_TIMER_ADJACENCY);
             k_aj_count<<<nblocks((c->N + AJ_PER_THREAD - 1) / AJ_PER_THREAD), TPB, 0, c->stream>>>(c->g, D, c->labels, (int)n, c->N, c->counters64);
         }
         HIPCHK(hipGetLastError());

@@ -30,7 +30,7 @@ static int ensure_grad(xb_ctx *c, bool force, bool boxes, bool main_rule) {
     if (c->grad_valid && !force && !boxes && c->grad_cover == 1 && c->brick_rec) {
         // records exist for the flagged bricks only, under the other tie rule: redo exactly those
         const int nb1r = (g.ny + BRK - 1) / BRK, nb2r = (g.nz + BRK - 1) / BRK, nbr = ((g.nx + BRK - 1) / BRK) * nb1r * nb2r;
-        ScopedTimer t(c, 4);
+        ScopedTimer t(c, XB_TIMER_MASKS_GROWTH);
         launch_brick_records(c, nullptr, nullptr, nbr, nb1r, nb2r);
         HIPCHK(hipGetLastError());
         c->grad_rule = main_rule ? 1 : 0;
@@ -42,7 +42,7 @@ static int ensure_grad(xb_ctx *c, bool force, bool boxes, bool main_rule) {
         // a retrace that walks on through a brick without records is redone by the from-rho kernel
         const int nb0 = (g.nx + BRK - 1) / BRK, nb1 = (g.ny + BRK - 1) / BRK, nb2 = (g.nz + BRK - 1) / BRK, nbr = nb0 * nb1 * nb2;
         if (int rc = ensure_brick_bytes(c, nbr)) return rc;
-        ScopedTimer t(c, 4);
+        ScopedTimer t(c, XB_TIMER_MASKS_GROWTH);
         int *buni = reinterpret_cast<int *>(c->st);
         if (!c->buni_valid) k_label_uniform_list<<<4096, TPB, 0, c->stream>>>(light(g), c->labels, nb1, nb2, nullptr, nbr, nullptr, nullptr, buni, 0, nbr);
         c->buni_valid = true;
@@ -59,14 +59,14 @@ static int ensure_grad(xb_ctx *c, bool force, bool boxes, bool main_rule) {
         return XB_OK;
     }
     // No trapping regions to lean on (a grid below 16 voxels on an axis, a slab that cuts bricks or whose grid is not made of
-    // whole bricks, option 1 = 0): the record of EVERY voxel of the table window, by pass B over all its bricks, and the
+    // whole bricks, XB_OPT_REGIONS without both bits): the record of EVERY voxel of the table window, by pass B over all its bricks, and the
     // trajectories are traced in full.  (Round 1-3 kept k_grad_field and closed seed cubes around at most 1023 maxima for
     // these cases: a second pipeline to keep exact, retired in round 4.)
     {
         const int nb0 = (g.nx + BRK - 1) / BRK, nb1 = (g.ny + BRK - 1) / BRK, nb2 = (g.nz + BRK - 1) / BRK, nbr = nb0 * nb1 * nb2;
         if (int rc = ensure_brick_bytes(c, nbr)) return rc;
-        ScopedTimer t(c, 4);
-        ScopedTimer tk(c, 5);
+        ScopedTimer t(c, XB_TIMER_MASKS_GROWTH);
+        ScopedTimer t_masks(c, XB_TIMER_BRICK_MASKS);
         // (a window is brick aligned: xb_set_table_window; bit 1 "may hold a maximum" everywhere: nothing is known about them)
         const int wb0 = table_windowed(c) ? g.wx0 / BRK : 0, wnb = table_windowed(c) ? g.wlen / BRK : nb0;
         k_flag_window_bricks<<<(nbr + 255) / 256, 256, 0, c->stream>>>(nb0, nb1 * nb2, wb0, wnb, (unsigned char)3, c->brick_rec);
@@ -139,8 +139,8 @@ static int run_slow(xb_ctx *c, int n, int refine, int *max_count = nullptr, int 
     if (!escaped) escaped = c->counters + CT_ESCAPED;
     if (n <= 0) return XB_OK;
     const size_t budget = (size_t)128 << 20;   // ints of path scratch per launch (512 MB)
-    // (+ a last tier of 2^20, below; debug switch 64: tiers of 3 / 5 / 8 voxels, so that a test reaches every one of them)
-    const int tiers[3] = {(c->opt_dbg & 64) ? 3 : 64, (c->opt_dbg & 64) ? 5 : 2048, (c->opt_dbg & 64) ? 8 : 1 << 15};
+    // (+ a last tier of 2^20, below; XB_DBG_SHORT_TIERS: tiers of 3 / 5 / 8 voxels, so that a test reaches every one of them)
+    const int tiers[3] = {(c->opt.dbg & XB_DBG_SHORT_TIERS) ? 3 : 64, (c->opt.dbg & XB_DBG_SHORT_TIERS) ? 5 : 2048, (c->opt.dbg & XB_DBG_SHORT_TIERS) ? 8 : 1 << 15};
     const bool blind = (size_t)n * tiers[1] <= budget;
     const size_t have = std::max<size_t>(std::min<size_t>(budget, (size_t)n * tiers[0]), blind ? (size_t)n * tiers[1] : 0) + (size_t)(1 << 15) * 64;
     const size_t n_lists = 2 * (size_t)n + 8;
@@ -239,7 +239,7 @@ int xb_assign_trace(xb_ctx *c, int method, int64_t *n_local) {
         c->g.main_ties = 1;   // methods.neargrid's stepping rule for everything the assignment traces
         box_max = c->box_max_tab ? c->box_max_tab : c->boxbuf + BB_REGMAX;
         {
-            ScopedTimer t(c, 0);
+            ScopedTimer t(c, XB_TIMER_ASSIGN);
             const int opt = 3;      // (k_ng_trace: one wave per 4x4x4 cube of start voxels, XCD-aware block order)
             const int tpb = 64;     // one wave per block: a finished wave frees its slot at once
             const bool slab_bricks = (g.x0 % 8 == 0) && (g.x1 % 8 == 0);
@@ -274,7 +274,7 @@ int xb_assign_trace(xb_ctx *c, int method, int64_t *n_local) {
                 }
                 int nwalk = 0;
                 if (fast_slab) {   // the persistent trace of the one-GPU path: no host wait before it
-                    ScopedTimer tw(c, 6);
+                    ScopedTimer t_trace(c, XB_TIMER_TRACE);
                     launch_persistent_trace(c, false, false, box_max, walk, c->has_vacuum ? 1 : 0, nullptr);
                 } else {
                 if (int rc = read_counter(c, CT_N_WALK, &nwalk)) return rc;
@@ -282,7 +282,7 @@ int xb_assign_trace(xb_ctx *c, int method, int64_t *n_local) {
                 }
                 if (nwalk) {
                     const long long waves = 8LL * nwalk;
-                    ScopedTimer tw(c, 6);
+                    ScopedTimer t_trace(c, XB_TIMER_TRACE);
                     const unsigned nblk = (unsigned)((waves + tpb / XB_WAVE - 1) / (tpb / XB_WAVE));
                     if (table_windowed(c)) {
                         // the lean kernel first: a trajectory that leaves the table window lands on a list (in `stage`, its
@@ -335,14 +335,14 @@ int xb_assign_trace(xb_ctx *c, int method, int64_t *n_local) {
         c->g.main_ties = 0;
     } else if (method == XB_METHOD_ONGRID) {
         c->zero_outside[0] = -1;   // (the pointer pass writes the labels of every plane, on a slab too)
-        // Host-driven ongrid (slabs, vacuum, tiny grids, option 7 = 0): the pointer of every voxel by k_og_masks -- its brick
+        // Host-driven ongrid (slabs, vacuum, grids below 16 voxels on an axis, XB_OPT_REGIONS without both bits): the pointer of every voxel by k_og_masks -- its brick
         // outputs go to scratch, nobody reads them -- then pointer jumping until every chain has reached its root.  (The
         // trapping regions of the pointer field are built by assign_ongrid_fused, one GPU without vacuum.)
         c->blab = nullptr;
         c->n_boxes = 0;
         c->box_voxels = 0;
         {
-            ScopedTimer t(c, 1);
+            ScopedTimer t(c, XB_TIMER_OG_MASKS);
             const int small = small_grid(g);
             const int nbr = ((g.nx + BRK - 1) / BRK) * ((g.ny + BRK - 1) / BRK) * ((g.nz + BRK - 1) / BRK);
             if (3LL * nbr > c->list_cap) return fail(XB_E_LIMIT, "xb_assign: scratch too small for the brick arrays of the pointer pass");
@@ -431,7 +431,7 @@ int xb_assign_finish(xb_ctx *c, const int64_t *max_idx_sorted, int64_t n_global)
 static bool fused_ok(const xb_ctx *c) {
     const Grid &g = c->g;
     // (round 4: any grid of at least 16 voxels per axis -- the brick lattice is ceil(n / 8), k_brick_masks PART)
-    return c->opt_boxes && c->opt_bricks && g.x0 == 0 && g.x1 == g.nx && !table_windowed(c) &&
+    return c->opt.boxes && c->opt.bricks && g.x0 == 0 && g.x1 == g.nx && !table_windowed(c) &&
            g.nx >= 16 && g.ny >= 16 && g.nz >= 16;
 }
 static int assign_neargrid_tail(xb_ctx *c, int64_t *n_maxima);
@@ -486,9 +486,9 @@ static int assign_neargrid_fused(xb_ctx *c, int64_t *n_maxima) {
     int *bpot = c->list + 5 * nbr;   // brick potentials of the region growth (k_grow_parent)
     int *bres = nullptr;   // per walk-list brick: the one maximum all its voxels ended on (k_ng_trace_g), for the edge sweep's uniformity
     c->box_max_tab = box_max;
-    // (debug switch 32: wait after every stage and say so -- finds the kernel that does not come back)
+    // (XB_DBG_STAGE_WAIT: wait after every stage and say so -- finds the kernel that does not come back)
     auto stage_done = [&](const char *what) {
-        if (c->opt_dbg & 32) {
+        if (c->opt.dbg & XB_DBG_STAGE_WAIT) {
             const hipError_t e = (hipStreamSynchronize)(c->stream);
             int h16[16] = {0};
             (void)hipMemcpy(h16, fs, sizeof h16, hipMemcpyDeviceToHost);
@@ -501,9 +501,9 @@ static int assign_neargrid_fused(xb_ctx *c, int64_t *n_maxima) {
     g.main_ties = 1;   // methods.neargrid's tie test (methods.py:324)
     const GridL gl = light(g);
     {   // brick masks + seeds
-        ScopedTimer t4(c, 4);
+        ScopedTimer t_growth(c, XB_TIMER_MASKS_GROWTH);
         {
-            ScopedTimer t5(c, 5);
+            ScopedTimer t_masks(c, XB_TIMER_BRICK_MASKS);
             launch_brick_masks(c, part, true, bmask, bmaxv, bpot);
         }
         stage_done("brick masks");
@@ -520,7 +520,7 @@ static int assign_neargrid_fused(xb_ctx *c, int64_t *n_maxima) {
     c->nbk[0] = nb0; c->nbk[1] = nb1; c->nbk[2] = nb2;
     const long long own = c->N;
     {   // region fill / notes, then the walkers of the uncertain bricks
-        ScopedTimer t0(c, 0);
+        ScopedTimer t_assign(c, XB_TIMER_ASSIGN);
         {
             int bits = 0;
             while ((1 << bits) < std::max(std::max(nb0, nb1), nb2)) bits++;
@@ -532,7 +532,7 @@ static int assign_neargrid_fused(xb_ctx *c, int64_t *n_maxima) {
                                                                                                   vac ? bpot : nullptr, c->vac_tol);
         }
         {   // pass B: records for the bricks of the walk list only
-            ScopedTimer t7(c, 7);
+            ScopedTimer t_records(c, XB_TIMER_BRICK_RECORDS);
             launch_brick_records(c, walk, fs + FS_N_WALK, nbr, nb1, nb2);
         }
         stage_done("walk list + records");
@@ -544,7 +544,7 @@ static int assign_neargrid_fused(xb_ctx *c, int64_t *n_maxima) {
             c->regions_pending = true;
         }
         {
-            ScopedTimer t6(c, 6);
+            ScopedTimer t_trace(c, XB_TIMER_TRACE);
             // (the lean walker needs nothing else the fused path does not already guarantee: whole-grid table window,
             // brick-label regions; without vacuum its walkers also leave bres)
             int *bres_buf = c->has_vacuum ? nullptr : c->list + 6 * nbr;
@@ -621,7 +621,7 @@ static int assign_neargrid_tail(xb_ctx *c, int64_t *n_maxima) {
                                                           c->has_vacuum ? 1 : 0);
             HIPCHK(hipGetLastError());
             // (what the wider window leaves is a subset of what it was given: the list's length stays on the device, n_listed bounds it)
-            if (c->opt_dbg & 4) {
+            if (c->opt.dbg & XB_DBG_EC_PASSES) {
                 int m2 = 0;
                 if (int rc2 = read_counter(c, CT_MID_LEFT, &m2)) return rc2;
                 fprintf(stderr, "[assign] %d walkers listed, %d left for the exact slow kernel after the %d-voxel window\n", n_listed, m2, XB_MID_K);
@@ -702,7 +702,7 @@ static int assign_ongrid_fused(xb_ctx *c, int64_t *n_maxima) {
     c->zero_outside[0] = -1;
     const GridL gl = light(g);
     {
-        ScopedTimer t(c, 1);
+        ScopedTimer t(c, XB_TIMER_OG_MASKS);
         const int small = small_grid(g);
         dim3 grid((g.nz + GT_Z - 1) / GT_Z, (g.ny + GT_Y - 1) / GT_Y, (g.nx + GT_X - 1) / GT_X);
         GridS gs;
@@ -715,7 +715,7 @@ static int assign_ongrid_fused(xb_ctx *c, int64_t *n_maxima) {
         }
     }
     {
-        ScopedTimer t4(c, 4);
+        ScopedTimer t_growth(c, XB_TIMER_MASKS_GROWTH);
         launch_region_growth(c, nb0, nb1, nb2, bmask, bmaxv, bpot, seed, buf0, buf1, box_max, box_first, true);
         HIPCHK(hipGetLastError());
     }
@@ -728,7 +728,7 @@ static int assign_ongrid_fused(xb_ctx *c, int64_t *n_maxima) {
     c->bres_last = nullptr;
     c->nbk[0] = nb0; c->nbk[1] = nb1; c->nbk[2] = nb2;
     {
-        ScopedTimer t0(c, 0);
+        ScopedTimer t_assign(c, XB_TIMER_ASSIGN);
         int bits = 0;
         while ((1 << bits) < std::max(std::max(nb0, nb1), nb2)) bits++;
         const unsigned n_codes = 1u << (3 * bits);

@@ -61,7 +61,6 @@ void xb_destroy(xb_ctx *c) {
     fmt_release(c);
     for (auto &t : c->tk)
         for (auto &p : t.pending) { hipEventDestroy(p.first); hipEventDestroy(p.second); }
-    for (auto &p : c->tk_merge.pending) { hipEventDestroy(p.first); hipEventDestroy(p.second); }
     free_grid(c);
     hipFree(c->counters); hipFree(c->counters64); hipFree(c->dsum); hipFree(c->dist_dev); hipFree(c->boxbuf);
     hipFree(c->walk_in); hipFree(c->walk_out2); hipFree(c->walk_res); hipFree(c->xbuf); hipFree(c->wbuf[0]); hipFree(c->wbuf[1]); hipFree(c->wk_in);

@@ -108,7 +108,7 @@ static int io_import_density(xb_ctx *c, const T *src, const int64_t st[3], doubl
             first = 4 * n4;      // (the up to three values behind the last whole group: the gather below)
             if (first == N) return XB_OK;
         }
-    if (first == 0 && sz != 1 && (sy == 1 || sx == 1) && c->opt_io_tiled) {
+    if (first == 0 && sz != 1 && (sy == 1 || sx == 1) && c->opt.io_tiled) {
         const bool fy = sy == 1;     // the source's fast axis is y (else x); o is the other one
         const int nf = fy ? g.ny : g.nx, no = fy ? g.nx : g.ny;
         const int tiles_f = (nf + IO_TILE - 1) / IO_TILE, tiles_z = (g.nz + IO_TILE - 1) / IO_TILE;

@@ -55,7 +55,7 @@ int xb_moment_sum(xb_ctx *c, const double lattice[9], const double *centres_cart
     G.tab = buf + o_tab; G.pbc_dev = buf; G.centres = buf + o_cen;
     G.nx = g.nx; G.ny = g.ny; G.nz = g.nz; G.nyz = g.nyz;
     {
-        ScopedTimer timer(c, 8);
+        ScopedTimer timer(c, XB_TIMER_MOMENTS);
         k_ms_tables<<<nblocks(3 * (long long)len), TPB, 0, c->stream>>>(g.nx, g.ny, g.nz, buf + 96, buf + o_tab);
         const unsigned blocks = nblocks((own + MS_PER_THREAD - 1) / MS_PER_THREAD);
         if (n <= MS_BINS) k_moment_sum_lds<<<blocks, TPB, 0, c->stream>>>(g, G, img, c->rho, c->labels, (int)n, buf + o_sum, dcn);

@@ -42,7 +42,7 @@ static int edge_find_launch(xb_ctx *c, bool *dilate_owned) {
     plane_range(g, all ? g.nx : c->halo - 2, xb_, npd);
     HIPCHK(hipMemsetAsync(c->counters + CT_N_EDGES, 0, sizeof(int), c->stream));
     {
-        ScopedTimer t(c, 2);
+        ScopedTimer t(c, XB_TIMER_EDGE_FIND);
         const GridL gl = light(g);
         const int small = small_grid(g);
         int *buni = nullptr;
@@ -124,7 +124,7 @@ int xb_edge_find(xb_ctx *c, int64_t *edges) {
     int n = 0;
     if (int rc = read_counter(c, CT_N_EDGES, &n)) return rc;
     if (dilate_owned && n) {  // the list holds every owned edge: dilate from it
-        ScopedTimer t(c, 2);
+        ScopedTimer t(c, XB_TIMER_EDGE_FIND);
         k_edge_dilate_list<<<nblocks(n), TPB, 0, c->stream>>>(light(g), c->known, c->list, n, nullptr);
         HIPCHK(hipGetLastError());
     }
@@ -279,7 +279,7 @@ static int refine_trace_impl(xb_ctx *c, int flag, int64_t *changed, int64_t *esc
         int wio_cap = 0;
         if (int rc = ensure_grad(c, false, false, false)) return rc;
         {
-            ScopedTimer t(c, 3);
+            ScopedTimer t(c, XB_TIMER_REFINE_TRACE);
             const unsigned char *brec = c->grad_cover == 1 ? c->brick_rec : nullptr;
             const int regions_ok = brec && c->regions_labels && !c->has_vacuum ? 1 : 0;
             const int *slab_regions = slab_regions_of(c);
@@ -476,10 +476,10 @@ static int edge_check_resolve(xb_ctx *c, int n, const int8_t *cls, int near_xa, 
         k_ec_first<<<(unsigned)std::min<long long>(nblocks(n), 4096), TPB, 0, c->stream>>>(g, c->known, pend_w, c->list, n, buf[0],
                                                                                          c->counters + CT_EC_SEEDS_A, cap);
         HIPCHK(hipGetLastError());
-        const int groups = std::max(1, std::min(256, c->opt_ec_groups));
+        const int groups = std::max(1, std::min(256, c->opt.ec_groups));
         // (round 5: the workgroups share out a long front through mailboxes -- k_ec_chase)
         int *share = nullptr;
-        if (c->opt_ec_share && groups >= 2) {
+        if (c->opt.ec_share && groups >= 2) {
             if (!c->ec_share) HIPCHK(hipMalloc(&c->ec_share, ec_share_bytes(256)));
             share = c->ec_share;
         }
@@ -492,7 +492,7 @@ static int edge_check_resolve(xb_ctx *c, int n, const int8_t *cls, int near_xa, 
                 HIPCHK(hipMemsetAsync(share, 0, ec_share_bytes(groups), c->stream));
             }
             k_ec_chase<<<groups, EC_CHASE_THREADS, 0, c->stream>>>(g, c->known, pend_w, buf[pass & 1], c->counters + slot_in, buf[1 - (pass & 1)], c->counters + slot_out,
-                                                                   cap, c->opt_ec_qcap, share);
+                                                                   cap, c->opt.ec_qcap, share);
             HIPCHK(hipGetLastError());
             // (with the first pass's overflow count also k_ec_first's own seed count: k_ec_chase clamps what it reads to the
             // list's capacity, so a list that was too small must fail HERE, not later as "undecided" -- ADVICE r4)
@@ -501,7 +501,7 @@ static int edge_check_resolve(xb_ctx *c, int n, const int8_t *cls, int near_xa, 
             if (int rc = read_counter(c, slot_out, &n_seeds)) return rc;
             if (n_seeds > cap || (pass == 0 && c->host_ints[HI_EC_SEEDS0] > cap)) return fail(XB_E_LIMIT, "xb_edge_check: seed list too small");
             if (share && c->host_ints[HI_EC_SHARE_ERR]) return fail(XB_E_STATE, "xb_edge_check: a reserved mailbox slot of the chase was never filled");
-            if (c->opt_dbg & 4) {
+            if (c->opt.dbg & XB_DBG_EC_PASSES) {
                 fprintf(stderr, "edge_check pass %d: %d overflowed (%d groups)\n", pass, n_seeds, groups);
 #ifdef XB_EC_PROBE
                     {
@@ -681,7 +681,7 @@ static int refine_iteration_fused(xb_ctx *c, int64_t *edges, int64_t *changed, b
     HIPCHK(hipMemsetAsync(fs + FS_N_EDGES, 0, 7 * sizeof(int), c->stream));   // edges, changed, escaped, overflows, deferred, listed tiles, relabelled list
     c->chg_n = -1;
     {
-        ScopedTimer t(c, 2);
+        ScopedTimer t(c, XB_TIMER_EDGE_FIND);
         const int small = small_grid(g);
         int *buni = nullptr;
         int ntiles_listed = 0;
@@ -703,7 +703,7 @@ static int refine_iteration_fused(xb_ctx *c, int64_t *edges, int64_t *changed, b
             k_edge_flag_tiled<<<grid, TPB, 0, c->stream>>>(gl, c->rho, c->labels, c->known, 0, g.nx, c->list, fs + FS_N_EDGES, small, buni,
                                                            c->grad_valid ? c->grad : nullptr, brec, c->has_vacuum ? 0 : 1);
         }
-        if (buni && c->opt_tile_dilate && g.nz % ET_Z == 0) k_edge_dilate_tiles<<<std::min(ntiles_listed, 4096), TPB, 0, c->stream>>>(gl, c->known, (const int *)c->stage, fs + FS_N_TILES);
+        if (buni && c->opt.tile_dilate && g.nz % ET_Z == 0) k_edge_dilate_tiles<<<std::min(ntiles_listed, 4096), TPB, 0, c->stream>>>(gl, c->known, (const int *)c->stage, fs + FS_N_TILES);
         else k_edge_dilate_list<<<nblocks(c->N / 16), TPB, 0, c->stream>>>(gl, c->known, c->list, 0, fs + FS_N_EDGES);
     }
     c->list_valid = false; c->chg_n = -1;
@@ -711,7 +711,7 @@ static int refine_iteration_fused(xb_ctx *c, int64_t *edges, int64_t *changed, b
     if (late_records) {
         // the records of the band bricks (k_masks.h), now that the flags say where the band is
         if (int rc = need_grad(c)) return rc;
-        ScopedTimer t(c, 4);
+        ScopedTimer t(c, XB_TIMER_MASKS_GROWTH);
         const int nb0 = (g.nx + 7) / 8, nb1 = (g.ny + 7) / 8, nb2 = (g.nz + 7) / 8, nbr = nb0 * nb1 * nb2;
         unsigned char *band = reinterpret_cast<unsigned char *>(c->blab_buf);   // (the bricks' region labels have served: scratch)
         HIPCHK(hipMemsetAsync(band, 0, (size_t)nbr, c->stream));
@@ -729,7 +729,7 @@ static int refine_iteration_fused(xb_ctx *c, int64_t *edges, int64_t *changed, b
     const unsigned char *brec = c->grad_cover == 1 ? c->brick_rec : nullptr;
     const int regions_ok = c->grad_cover == 1 && c->regions_labels && !c->has_vacuum ? 1 : 0;
     {
-        ScopedTimer t(c, 3);
+        ScopedTimer t(c, XB_TIMER_REFINE_TRACE);
         int *defer = (int *)c->stage;
         WalkerIO wl{};   // (no walkers on one GPU)
         constexpr int XB_RT_BLOCK = 128;   // (threads per workgroup of the retrace kernel: 64 / 128 / 256 measured 0.512 / 0.495 / 0.514 ms on the whole list)
@@ -779,7 +779,7 @@ static int refine_iteration_fused(xb_ctx *c, int64_t *edges, int64_t *changed, b
             HIPCHK(hipGetLastError());
             slow_list = list2;
             slow_n_dev = c->counters + CT_MID_LEFT;   // (the list's length stays on the device; novf bounds it)
-            if (c->opt_dbg & 4) {
+            if (c->opt.dbg & XB_DBG_EC_PASSES) {
                 int m2 = 0;
                 if (int rc = read_counter(c, CT_MID_LEFT, &m2)) return rc;
                 fprintf(stderr, "[refine] %d retraces listed, %d left for the exact slow kernel after the %d-voxel window\n", novf, m2, XB_MID_K);

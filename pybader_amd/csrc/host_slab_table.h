@@ -20,7 +20,7 @@ int xb_set_table_window(xb_ctx *c, int64_t margin) {
 }
 static bool slab_sparse_ok(const xb_ctx *c) {
     const Grid &g = c->g;
-    return c->opt_boxes && c->opt_bricks && table_windowed(c) && g.nx % BRK == 0 && g.ny % BRK == 0 && g.nz % BRK == 0 &&
+    return c->opt.boxes && c->opt.bricks && table_windowed(c) && g.nx % BRK == 0 && g.ny % BRK == 0 && g.nz % BRK == 0 &&
            g.x0 % BRK == 0 && g.x1 % BRK == 0 && g.ny >= 16 && g.nz >= 16 && 7LL * (c->N / (BRK * BRK * BRK)) <= c->N;
 }
 int xb_table_build(xb_ctx *c, int64_t *n_local_seeds) {
@@ -37,8 +37,8 @@ int xb_table_build(xb_ctx *c, int64_t *n_local_seeds) {
         HIPCHK(hipMemsetAsync(fs, 0, FS_TOTAL * sizeof(int), c->stream));
         g.main_ties = 1;
         {
-            ScopedTimer t4(c, 4);
-            ScopedTimer t5(c, 5);
+            ScopedTimer t_growth(c, XB_TIMER_MASKS_GROWTH);
+            ScopedTimer t_masks(c, XB_TIMER_BRICK_MASKS);
             launch_brick_masks(c, false, false, bmask, bmaxv, nullptr);
         }
         HIPCHK(hipGetLastError());
@@ -101,13 +101,13 @@ int xb_table_finish(xb_ctx *c, const int64_t *seeds, int64_t n_seeds, int64_t an
             *reclist = c->list + 5 * nbr;
         int *box_max = c->boxbuf + BB_REGMAX, *box_first = c->boxbuf + BB_REGFIRST;
         c->box_max_tab = box_max;
-        ScopedTimer t4(c, 4);
+        ScopedTimer t_growth(c, XB_TIMER_MASKS_GROWTH);
         launch_region_growth(c, nb0, nb1, nb2, bmask, bmaxv, nullptr, seed, buf0, buf1, box_max, box_first, false);
         c->blab = c->blab_buf;
         c->nbk[0] = nb0; c->nbk[1] = nb1; c->nbk[2] = nb2;
         launch_window_bricks(c, reclist, fs + FS_N_WALK, nullptr);
         {
-            ScopedTimer t7(c, 7);
+            ScopedTimer t_records(c, XB_TIMER_BRICK_RECORDS);
             g.main_ties = 1;
             launch_brick_records(c, reclist, fs + FS_N_WALK, nbr, nb1, nb2);
         }

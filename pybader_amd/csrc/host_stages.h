@@ -47,9 +47,9 @@ static void launch_brick_masks(xb_ctx *c, bool part, bool allow_diag, int *bmask
     const bool sym = sym_grid(g, gs);
     int mirror = 0;
     double mu_scale = 0.;
-    if (sym && c->opt_mirror) mirror_prefilter(g, mirror, mu_scale);
+    if (sym && c->opt.mirror) mirror_prefilter(g, mirror, mu_scale);
     // (an orthogonal lattice has a diagonal T_grad: exact zeros off the diagonal)
-    const bool diag = allow_diag && c->opt_mask_diag && g.T[1] == 0. && g.T[2] == 0. && g.T[3] == 0. && g.T[5] == 0. && g.T[6] == 0. && g.T[7] == 0.;
+    const bool diag = allow_diag && c->opt.mask_diag && g.T[1] == 0. && g.T[2] == 0. && g.T[3] == 0. && g.T[5] == 0. && g.T[6] == 0. && g.T[7] == 0.;
     auto launch = [&](auto kernel, const auto &gt) {
         kernel<<<grid, TPB, 0, c->stream>>>(gt, c->rho, small_grid(g), bmask, bmaxv, c->fs + FS_TIES, g.x0, mu_scale, mirror, bpot);
     };
@@ -107,7 +107,7 @@ static void launch_window_bricks(xb_ctx *c, int *list, int *count, const int *sk
 
 // The persistent trace of the walk list's bricks (k_ng_trace_g): workgroups of XB_TRACE_WAVES waves, one brick per pull
 // (per-XCD cursors over the list, its length on the device).  lean_ok: the lean walker, the own brick's records in LDS, when
-// the index products fit 24 bits (32-bit table offsets up to 2^27 window voxels); otherwise the generic walker (option 14 = 0:
+// the index products fit 24 bits (32-bit table offsets up to 2^27 window voxels); otherwise the generic walker (XB_CHECK_GENERIC_WALKER:
 // the tests' cross-check; planes or rows beyond 2^24 voxels), which tests every start voxel.  bres: per walk-list brick, did
 // all its voxels end on one maximum (the lean walker only).  A trajectory that leaves a table window lands on a list (in
 // `stage`, its length on the device) and is redone by the kernel that derives missing records from rho.  Returns whether the
@@ -115,7 +115,7 @@ static void launch_window_bricks(xb_ctx *c, int *list, int *count, const int *sk
 static bool launch_persistent_trace(xb_ctx *c, bool lean_ok, bool part, const int *box_max, const int *walk, int has_vacuum, int *bres) {
     const Grid &g = c->g;
     const int groups = std::max(1, c->trace_waves / XB_TRACE_WAVES);
-    const int lean = lean_ok && light(g).use24 && c->opt_lean ? ((long long)g.wlen * g.nyz <= (1LL << 27) ? 4 : 3) : 0;
+    const int lean = lean_ok && light(g).use24 && c->opt.lean ? ((long long)g.wlen * g.nyz <= (1LL << 27) ? 4 : 3) : 0;
     const bool window = table_windowed(c);
     int *ovf = window ? (int *)c->stage : c->ovf_list;
     const int ovf_cap = window ? (int)std::min<size_t>(c->stage_bytes / sizeof(int), 0x7fffffffu) : c->ovf_cap;

@@ -211,8 +211,8 @@ int xb_slab_assign_masks(xb_ctx *c, int rank, int nranks) {
     HIPCHK(hipMemsetAsync(fs, 0, FS_TOTAL * sizeof(int), c->stream));
     g.main_ties = 1;   // methods.py:324
     {
-        ScopedTimer t4(c, 4);
-        ScopedTimer t5(c, 5);
+        ScopedTimer t_growth(c, XB_TIMER_MASKS_GROWTH);
+        ScopedTimer t_masks(c, XB_TIMER_BRICK_MASKS);
         launch_brick_masks(c, false, true, bmask, bmaxv, bpot);
         k_slab_flag<<<1, 1, 0, c->stream>>>(fs, slab_flags(c), rank);
     }
@@ -312,7 +312,7 @@ int xb_slab_assign_trace(xb_ctx *c) {
     c->labels_zero_pending = false;   // every owned label is written, none is read (no vacuum; the halo planes are the peers')
     if (int rc = begin_assignment(c, c->counters + CT_N_MAX, CT_INTS(CT_N_MAX, CT_REDO), true)) return rc;
     {
-        ScopedTimer t4(c, 4);
+        ScopedTimer t_growth(c, XB_TIMER_MASKS_GROWTH);
         k_slab_any_flag<<<1, 1, 0, c->stream>>>(slab_flags(c), c->slab_nranks, fs);
         // every rank holds every brick's mask / maximum / potential now: the same seeding + growth as on one GPU (replicated)
         launch_region_growth(c, nb0, nb1, nb2, bmask, bmaxv, bpot, seed, buf0, buf1, box_max, box_first, true);
@@ -322,20 +322,20 @@ int xb_slab_assign_trace(xb_ctx *c) {
     c->walk = walk;
     c->nbk[0] = nb0; c->nbk[1] = nb1; c->nbk[2] = nb2;
     {
-        ScopedTimer t0(c, 0);
+        ScopedTimer t_assign(c, XB_TIMER_ASSIGN);
         // the window's bricks outside the regions get their records; the owned ones among them are traced
         const int per_plane = nb1 * nb2;
         launch_window_bricks(c, reclist, fs + FS_N_RECL, fs + FS_GROW_RETRY);
         k_brick_walk_list<<<(nbr + 16 * TPB - 1) / (16 * TPB), TPB, 0, c->stream>>>(nbr, (g.x0 / BRK) * per_plane, (g.x1 / BRK) * per_plane, c->blab, walk, fs + FS_N_WALK, fs + FS_GROW_RETRY);
         {
-            ScopedTimer t7(c, 7);
+            ScopedTimer t_records(c, XB_TIMER_BRICK_RECORDS);
             launch_brick_records(c, reclist, fs + FS_N_RECL, nbr, nb1, nb2);
         }
         k_note_certain_bricks<<<(nbr + 255) / 256, 256, 0, c->stream>>>(gl, nb0, nb1, nb2, (g.x0 / BRK) * per_plane, (g.x1 / BRK) * per_plane, c->blab,
                                                                       box_max, c->first, c->max_list, fs + FS_N_MAX, c->max_cap, fs + FS_GROW_RETRY);
         c->regions_pending = true;
         {
-            ScopedTimer tw(c, 6);
+            ScopedTimer t_trace(c, XB_TIMER_TRACE);
             launch_persistent_trace(c, true, false, box_max, walk, 0, nullptr);
         }
         k_slab_pack_table<<<1, 256, 0, c->stream>>>(slab_tables(c) + (size_t)c->slab_rank * XB_TAB_INTS, c->max_list, c->first, fs, c->counters + CT_N_OVF);
@@ -384,7 +384,7 @@ int xb_slab_assign_finish(xb_ctx *c, int64_t *n_maxima, int64_t *status) {
     c->n_boxes = h[FS_N_BOXES];
     c->box_voxels = (long long)h[FS_N_CERTAIN] * BRK * BRK * BRK;
     c->n_walk = h[FS_N_WALK];
-    if (c->opt_dbg & 16)
+    if (c->opt.dbg & XB_DBG_SLAB_STATS)
         fprintf(stderr, "[slab %d] bricks traced %d, with records %d, trajectories redone beyond the table window %d, regions %d\n", c->slab_rank,
                 h[FS_N_WALK], h[FS_N_RECL], h[FS_N_REDO], h[FS_N_BOXES]);
     numbering_done(c, h + FS_COUNT, h[FS_N_MAX], n_maxima);
@@ -409,7 +409,7 @@ int xb_slab_refine_pass(xb_ctx *c) {
     if (int rc = edge_find_launch(c, &dilate_owned)) return rc;
     const GridL gl = light(g);
     if (dilate_owned) {
-        ScopedTimer t(c, 2);
+        ScopedTimer t(c, XB_TIMER_EDGE_FIND);
         k_edge_dilate_list<<<2048, TPB, 0, c->stream>>>(gl, c->known, c->list, 0, c->counters + CT_N_EDGES);
     }
     c->g.main_ties = 0;
@@ -422,7 +422,7 @@ int xb_slab_refine_pass(xb_ctx *c) {
     HIPCHK(hipMemsetAsync(c->counters + CT_N_MAX, 0, CT_INTS(CT_N_MAX, CT_OG_MOVED) * sizeof(int), c->stream));
     HIPCHK(hipMemsetAsync(c->counters + CT_HALO_EDGES, 0, CT_INTS(CT_HALO_EDGES, CT_TILES_HALO) * sizeof(int), c->stream));
     {
-        ScopedTimer t(c, 3);
+        ScopedTimer t(c, XB_TIMER_REFINE_TRACE);
         const unsigned char *brec = c->grad_cover == 1 ? c->brick_rec : nullptr;
         const int regions_ok = brec && c->regions_labels && !c->has_vacuum ? 1 : 0;
         const int *slab_regions = slab_regions_of(c);
@@ -498,7 +498,7 @@ int xb_slab_refine_counts(xb_ctx *c, int64_t *local, int64_t *global) {
     long long loc[XB_XCNT], glo[XB_XCNT];
     for (int i = 0; i < XB_XCNT; i++) { loc[i] = h[i]; glo[i] = h[XB_XCNT + i]; }
     c->list_n = (int)loc[XB_XC_EDGES];
-    if (c->opt_dbg & 16) {
+    if (c->opt.dbg & XB_DBG_SLAB_STATS) {
         HIPCHK(hipMemcpyAsync(c->host_ints + HI_SLAB_DBG, c->counters + CT_DEFER, sizeof(int), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
         fprintf(stderr, "[slab %d] edges %lld, retraces redone from rho %d, exported %lld\n", c->slab_rank, loc[XB_XC_EDGES], c->host_ints[HI_SLAB_DBG], loc[XB_XC_ESCAPED]);

@@ -20,6 +20,7 @@ import numpy as np
 
 from ._lib import (XB_XC_CHANGED, XB_XC_EDGES, XB_XC_ESCAPED, XB_XC_LOST, XB_XC_MINE, XB_XC_ROUNDS, XB_XC_SLOW,
                    XB_XC_TRAVELLING)   # the entries of slab_refine_counts()
+from ._lib import XB_OPT_ASYNC_COMM
 
 
 def slab_ranges(nx, nranks):
@@ -192,7 +193,7 @@ class SlabRunner:
                   and not os.environ.get('XB_SLAB_HOST_DRIVEN'))
             self._step_vote = all(self.comm.allgather(bool(ok)))
             if self._step_vote and hasattr(self.be, 'set_option'):
-                self.be.set_option(24, 1)      # collectives are ordered on the stream: nothing waits for them on the host
+                self.be.set_option(XB_OPT_ASYNC_COMM, 1)      # collectives are ordered on the stream: nothing waits for them on the host
         return self._step_vote and not getattr(self, '_step_declined', False) and self.be.slab_supported(self.comm.size)
 
     def _guard(self, what):

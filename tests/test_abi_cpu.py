@@ -40,6 +40,47 @@ def test_slab_count_enum_and_binding_agree():
     assert entries == list(range(declared['XB_XC_COUNT'])) and declared['XB_XC_COUNT'] == 8
 
 
+def numbered_names(prefix):
+    """(the header's enumerators with this prefix, _lib's constants with it); every enumerator must state its value"""
+    hdr = open(os.path.join(ROOT, 'include', 'bader_hip.h')).read()
+    hdr = re.sub(r'/\*.*?\*/', '', hdr, flags=re.S)
+    names = [e.strip() for body in re.findall(r'enum\s*\{([^}]*)\}', hdr) for e in body.split(',') if e.strip().startswith(prefix)]
+    declared = {name: int(value) for name, value in (re.fullmatch(r'(\w+)\s*=\s*(\d+)', e).groups() for e in names)}   # (no match: no value stated)
+    assert len(declared) == len(names), 'no enumerator twice'
+    mirrored = {name: getattr(_lib, name) for name in dir(_lib) if name.startswith(prefix)}
+    return declared, mirrored
+
+
+@pytest.mark.parametrize('prefix', ['XB_OPT_', 'XB_REGIONS_', 'XB_CHECK_', 'XB_DBG_', 'XB_TIMER_', 'XB_DROP_'])
+def test_option_and_timer_enums_and_binding_agree(prefix):
+    """The option keys, their values and bits and the timer slots cross the ABI as plain integers: the header's enums and the
+    constants _lib.py mirrors name the same things with the same values, and none is missing on either side."""
+    declared, mirrored = numbered_names(prefix)
+    assert declared and declared == mirrored, set(declared.items()) ^ set(mirrored.items())
+
+
+def test_option_and_timer_values_are_frozen():
+    """bench.py and the tools' command lines pass these as numbers: no value moves."""
+    opt, _ = numbered_names('XB_OPT_')
+    assert sorted(opt.values()) == [1, 2, 3, 4, 5, 6, 17, 19, 24, 30] and len(opt) == 10
+    assert opt == {'XB_OPT_REGIONS': 1, 'XB_OPT_CROSS_CHECK': 2, 'XB_OPT_DEBUG': 3, 'XB_OPT_EC_GROUPS': 4, 'XB_OPT_EC_QCAP': 5,
+                   'XB_OPT_DROP_TABLE': 6, 'XB_OPT_KILL_LAUNCHES': 17, 'XB_OPT_SELF_EXCHANGE': 19, 'XB_OPT_ASYNC_COMM': 24,
+                   'XB_OPT_WEIGHT_NO_LABELS': 30}
+    check, _ = numbered_names('XB_CHECK_')
+    assert sorted(check.values()) == [1, 2, 4, 8, 16, 32, 64] and len(check) == 7
+    assert numbered_names('XB_REGIONS_')[0] == {'XB_REGIONS_BOXES': 1, 'XB_REGIONS_BRICKS': 2}
+    assert numbered_names('XB_DBG_')[0] == {'XB_DBG_EC_PASSES': 4, 'XB_DBG_SLAB_STATS': 16, 'XB_DBG_STAGE_WAIT': 32,
+                                           'XB_DBG_SHORT_TIERS': 64}
+    assert numbered_names('XB_DROP_')[0] == {'XB_DROP_TABLE_AND_MAXIMA': 2}
+    timer, _ = numbered_names('XB_TIMER_')
+    assert timer.pop('XB_TIMER_COUNT') == 11 and sorted(timer.values()) == list(range(11)) and len(timer) == 11
+    # slots 0 to 7 in the order of the benchmark's stage names; TRACE and OG_MASKS are the timers it keeps on in its timed region
+    stages = ['ASSIGN', 'OG_MASKS', 'EDGE_FIND', 'REFINE_TRACE', 'MASKS_GROWTH', 'BRICK_MASKS', 'TRACE', 'BRICK_RECORDS']
+    assert [getattr(_lib, 'XB_TIMER_' + name) for name in stages] == list(range(8))
+    assert _lib.XB_TIMER_TRACE == 6 and _lib.XB_TIMER_OG_MASKS == 1
+    assert (_lib.XB_TIMER_MOMENTS, _lib.XB_TIMER_ADJACENCY, _lib.XB_TIMER_MERGE) == (8, 9, 10)
+
+
 def test_no_gpu_fails_loudly(lib):
     if lib.xb_device_count() > 0:
         pytest.skip('a GPU is present')

@@ -95,7 +95,8 @@ def test_header_declares_and_lib_binds_the_three_entries():
     assert callable(_lib.Context.adjacency) and callable(_lib.Context.adjacency_release)
     assert 2 <= AJ_DENSE and AJ_DENSE * (AJ_DENSE - 1) // 2 * 15 * 8 <= 4 << 20, 'the largest dense table fits the L2 of an XCD'
     src = open(os.path.join(ROOT, 'pybader_amd', 'csrc', 'bader_hip.hip')).read()
-    assert re.search(r'which < 0 \|\| which > 9\b', src) and 'TimedKernel tk[10]' in src
+    assert re.search(r'which < 0 \|\| which >= XB_TIMER_COUNT\b', src) and 'TimedKernel tk[XB_TIMER_COUNT]' in src
+    assert 0 <= _lib.XB_TIMER_ADJACENCY < _lib.XB_TIMER_COUNT, "xb_adjacency's timer is one of the slots the bounds check admits"
 
 
 def test_bader_has_the_flag_and_it_is_off():

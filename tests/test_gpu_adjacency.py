@@ -279,12 +279,12 @@ def test_error_codes_and_bookkeeping():
         same(c.adjacency(-dirs, n), reference_adjacency(rho, lab, n, -dirs))
         # fetch with a short capacity, then with enough
         before = c.memory_stats()
-        c.enable_timing(only=[9])
+        c.enable_timing(only=[_lib.XB_TIMER_ADJACENCY])
         c.kernel_time_reset()
         pairs, facets, saddle, sfacet = c.adjacency(dirs, n)
-        ms, launches = c.kernel_time(9)
+        ms, launches = c.kernel_time(_lib.XB_TIMER_ADJACENCY)
         assert launches >= 1 and ms > 0.0
-        assert c.kernel_time(8) == (0.0, 0)
+        assert c.kernel_time(_lib.XB_TIMER_MOMENTS) == (0.0, 0)
         c.enable_timing(False)
         p = len(pairs)
         assert p == 3

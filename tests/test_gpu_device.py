@@ -92,8 +92,8 @@ def layouts(shape, np_dtype, seed):
 @pytest.mark.parametrize('shape', SHAPES)
 def test_import_is_exact(ctx, shape, np_dtype):
     ctx.set_grid(shape, np.zeros(27), np.zeros(9))
-    for gather_only in (0, 64):                                  # the LDS tile, then the plain gather, on permuted layouts
-        ctx.set_option(2, gather_only)
+    for gather_only in (0, _lib.XB_CHECK_IO_GATHER):             # the LDS tile, then the plain gather, on permuted layouts
+        ctx.set_option(_lib.XB_OPT_CROSS_CHECK, gather_only)
         try:
             for name, arr, host in layouts(shape, np_dtype, seed=sum(shape)):
                 ctx.import_density(arr)
@@ -103,7 +103,7 @@ def test_import_is_exact(ctx, shape, np_dtype):
                 except AssertionError as e:
                     raise AssertionError(f'{name} {np.dtype(np_dtype).name} {shape} option {gather_only}: {e}') from None
         finally:
-            ctx.set_option(2, 0)
+            ctx.set_option(_lib.XB_OPT_CROSS_CHECK, 0)
 
 
 def test_import_of_an_unaligned_contiguous_float32_view(ctx):

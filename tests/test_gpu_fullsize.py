@@ -13,6 +13,8 @@ from conftest import load_golden
 from pybader_amd import _lib, synth
 from pybader_amd.interface import distance_matrix, gradient_transform
 
+REGIONS_ON = _lib.XB_REGIONS_BOXES | _lib.XB_REGIONS_BRICKS   # the default of XB_OPT_REGIONS; 0: plain full trajectories
+
 pytestmark = pytest.mark.gpu
 
 
@@ -181,13 +183,13 @@ def test_768_eight_slabs_equal_one_gpu():
 @pytest.mark.parametrize('size,lattice', [(256, synth.CUBIC6), (192, synth.TRICLINIC), (512, synth.CUBIC6)])
 def test_trapping_regions_do_not_change_the_map(size, lattice):
     """The trapping-region early exit (brick masks + growth) is exact by construction; check it anyway against the plain
-    full-trajectory trace (option 1 = 0: records for every voxel, no regions) at sizes the CPU oracle cannot reach."""
+    full-trajectory trace (XB_OPT_REGIONS = 0: records for every voxel, no regions) at sizes the CPU oracle cannot reach."""
     ctx = _lib.Context(0)
     shape = (size,) * 3
-    ctx.set_option(1, 0)                      # plain tracing
+    ctx.set_option(_lib.XB_OPT_REGIONS, 0)             # plain tracing
     n0, max0, lab0 = run(ctx, shape, lattice)
     assert ctx.box_stats() == (0, 0)
-    ctx.set_option(1, 3)                      # trapping regions (the default)
+    ctx.set_option(_lib.XB_OPT_REGIONS, REGIONS_ON)    # trapping regions (the default)
     n2, max2, lab2 = run(ctx, shape, lattice)
     nb, nv2 = ctx.box_stats()
     assert nb == n2 and nv2 > 0.4 * size ** 3
@@ -304,8 +306,8 @@ def test_many_atoms_keep_their_trapping_regions():
     ctx.set_grid(shape, dm, tg)
     ctx.synth_density(lattice, atoms, synth.BACKGROUND)
     out = []
-    for opt in (0, 3):                        # plain tracing / cubes + brick growth
-        ctx.set_option(1, opt)
+    for opt in (0, REGIONS_ON):               # plain tracing / cubes + brick growth
+        ctx.set_option(_lib.XB_OPT_REGIONS, opt)
         ctx.vacuum_assign(None, 1.0)
         n = ctx.assign('neargrid')
         out.append((n, ctx.maxima(), ctx.download_labels(np.int32), ctx.box_stats()))
@@ -321,16 +323,16 @@ def test_many_atoms_keep_their_trapping_regions():
 def test_vacuum_at_scale_sparse_table_equals_full_table(method):
     """256^3 with half of the cell declared vacuum: the pipeline (brick masks, records for the walk-list / mixed bricks
     only, deferred from-rho retraces -- no region stop with vacuum) against plain full-trajectory tracing over a record for
-    every voxel (option 1 = 0); maps, maxima and refinement logs must agree."""
+    every voxel (XB_OPT_REGIONS = 0); maps, maxima and refinement logs must agree."""
     shape = (256,) * 3
     dm, tg = matrices(shape, synth.CUBIC6)
     ctx = _lib.Context(0)
     ctx.set_grid(shape, dm, tg)
     ctx.synth_density(synth.CUBIC6, synth.ATOMS8, synth.BACKGROUND)
     res = []
-    for boxes in (3, 0):
-        ctx.set_option(1, boxes)
-        ctx.set_option(6, 1)
+    for boxes in (REGIONS_ON, 0):
+        ctx.set_option(_lib.XB_OPT_REGIONS, boxes)
+        ctx.set_option(_lib.XB_OPT_DROP_TABLE, 1)
         vc, vv = ctx.vacuum_assign(0.03, 1.0)
         n = ctx.assign(method)
         pre = ctx.download_labels(np.int32)
@@ -364,8 +366,8 @@ def test_noisy_vacuum_keeps_the_atoms_regions():
     rho = np.ascontiguousarray(rho + np.where(low, 2e-3 * rng.random(shape), 0.0))
     ctx.upload_density(rho)
     out = []
-    for opt in (0, 3):
-        ctx.set_option(1, opt)
+    for opt in (0, REGIONS_ON):
+        ctx.set_option(_lib.XB_OPT_REGIONS, opt)
         ctx.vacuum_assign(None, 1.0)
         n = ctx.assign('neargrid')
         out.append((n, ctx.maxima(), ctx.download_labels(np.int32), ctx.box_stats()))
@@ -398,9 +400,9 @@ def test_mirror_prefilter_and_lean_walker_do_not_change_the_map(shape, lattice, 
         ctx.upload_density(rho)
     res = []
     for mirror, lean, diag in ((1, 1, 1), (0, 1, 1), (1, 0, 1), (0, 0, 1), (1, 1, 0)):
-        # option 2, the cross-check bits: 1 no mirror prefilter, 2 the generic walker, 4 the full T_grad . grad product
-        ctx.set_option(2, (0 if mirror else 1) | (0 if lean else 2) | (0 if diag else 4))
-        ctx.set_option(6, 1)
+        ctx.set_option(_lib.XB_OPT_CROSS_CHECK, (0 if mirror else _lib.XB_CHECK_NO_MIRROR) | (0 if lean else _lib.XB_CHECK_GENERIC_WALKER) |
+                       (0 if diag else _lib.XB_CHECK_FULL_TGRAD))
+        ctx.set_option(_lib.XB_OPT_DROP_TABLE, 1)
         ctx.vacuum_assign(None, 1.0)
         n = ctx.assign('neargrid')
         pre = ctx.download_labels(np.int32)
@@ -421,7 +423,7 @@ def test_mirror_prefilter_and_lean_walker_do_not_change_the_map(shape, lattice, 
                                                      ((128, 128, 128), synth.TRICLINIC, 0.0, 0.02), ((96, 96, 96), synth.CUBIC6, 3e-2, None),
                                                      ((64, 64, 64), synth.CUBIC6, 0.0, 0.05)])
 def test_tile_wise_dilation_leaves_the_same_flags(shape, lattice, noise, tol):
-    """k_edge_dilate_tiles (the dilation of refinement.py:385-404 from LDS tiles of the flags, option 25) against
+    """k_edge_dilate_tiles (the dilation of refinement.py:385-404 from LDS tiles of the flags; XB_CHECK_LIST_DILATE selects the other) against
     k_edge_dilate_list (27 byte gathers per edge voxel): the same `known` array after the first refinement iteration, the
     same log and map after three -- smooth, rough, with vacuum (uniform vacuum tiles are on the list too), a z extent that
     is not a whole number of tiles."""
@@ -435,8 +437,8 @@ def test_tile_wise_dilation_leaves_the_same_flags(shape, lattice, noise, tol):
         ctx.upload_density(rho)
     res = []
     for tiled in (1, 0):
-        ctx.set_option(2, 0 if tiled else 8)      # cross-check bit 8: the dilation from the edge list
-        ctx.set_option(6, 1)
+        ctx.set_option(_lib.XB_OPT_CROSS_CHECK, 0 if tiled else _lib.XB_CHECK_LIST_DILATE)   # the dilation from the edge list
+        ctx.set_option(_lib.XB_OPT_DROP_TABLE, 1)
         ctx.vacuum_assign(tol, 1.0)
         n = ctx.assign('neargrid')
         log1 = ctx.refine('all', 1)
@@ -463,8 +465,8 @@ def test_growth_that_outlasts_its_schedule_is_repeated_with_the_long_one():
     n0 = ctx.assign('neargrid')
     want, boxes = ctx.download_labels(np.int32), ctx.box_stats()
     assert ctx.growth_stats() == (0, 6)
-    ctx.set_option(17, 1)
-    ctx.set_option(6, 1)
+    ctx.set_option(_lib.XB_OPT_KILL_LAUNCHES, 1)
+    ctx.set_option(_lib.XB_OPT_DROP_TABLE, 1)
     ctx.vacuum_assign(None, 1.0)
     n1 = ctx.assign('neargrid')
     assert ctx.growth_stats()[0] == 1 and ctx.growth_stats()[1] > 6
@@ -478,7 +480,7 @@ def test_brick_uniformity_left_by_the_walkers_equals_the_label_scan():
     """The group trace leaves, per walk-list brick, the one maximum all its 512 voxels ended on (LDS min / max of the
     walkers' results), which replaces k_label_uniform_list's pass over the labels for the edge sweep.  Checked where it
     shows: the edge sweep's flags -- `known` after the first refinement iteration must equal the flags of a run whose
-    uniformity came from the label scan (the generic walker, option 14 = 0, keeps the scan)."""
+    uniformity came from the label scan (the generic walker, XB_CHECK_GENERIC_WALKER, keeps the scan)."""
     shape = (192, 192, 192)
     ctx = _lib.Context(0)
     dm, tg = matrices(shape, synth.TRICLINIC)
@@ -486,8 +488,8 @@ def test_brick_uniformity_left_by_the_walkers_equals_the_label_scan():
     ctx.synth_density(synth.TRICLINIC, synth.ATOMS8, synth.BACKGROUND)
     res = []
     for lean in (1, 0):
-        ctx.set_option(2, 0 if lean else 2)       # cross-check bit 2: the generic walker
-        ctx.set_option(6, 1)
+        ctx.set_option(_lib.XB_OPT_CROSS_CHECK, 0 if lean else _lib.XB_CHECK_GENERIC_WALKER)
+        ctx.set_option(_lib.XB_OPT_DROP_TABLE, 1)
         ctx.vacuum_assign(None, 1.0)
         n = ctx.assign('neargrid')
         log = ctx.refine('all', 1)
@@ -508,7 +510,7 @@ def test_host_waits_of_one_gpu_steps():
     ctx.vacuum_assign(None, 1.0)
     ctx.assign('neargrid')                    # (first call: allocations)
     for method, want_assign in (('neargrid', 1), ('ongrid', 1)):
-        ctx.set_option(6, 1)
+        ctx.set_option(_lib.XB_OPT_DROP_TABLE, 1)
         ctx.vacuum_assign(None, 1.0)
         w0 = ctx.host_waits()
         ctx.assign(method)

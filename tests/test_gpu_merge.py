@@ -90,14 +90,14 @@ def test_another_n_reuses_the_buffer_and_release_frees_it():
         c.upload_density(big[0])
         c.upload_labels(small[1])
         before = c.memory_stats()
-        c.enable_timing(only=[10])
+        c.enable_timing(only=[_lib.XB_TIMER_MERGE])
         c.kernel_time_reset()
         for rho, lab, n, dirs, max_idx, per_tol in (small, big, small, big):
             c.upload_labels(lab)
             for tname in ('mid', 'inf'):
                 same(c.merge_basins(dirs, max_idx, per_tol[tname][0]), per_tol[tname][1], f'n {n} {tname}')
-        ms, launches = c.kernel_time(10)
-        assert launches >= 8 and ms > 0.0 and c.kernel_time(9) == (0.0, 0)
+        ms, launches = c.kernel_time(_lib.XB_TIMER_MERGE)
+        assert launches >= 8 and ms > 0.0 and c.kernel_time(_lib.XB_TIMER_ADJACENCY) == (0.0, 0)
         c.enable_timing(False)
         held = c.memory_stats()
         assert held[2] - before[2] == 44 * big[2] and held[0] - before[0] == held[2] - before[2], '44 bytes per label, counted'

@@ -287,12 +287,12 @@ def test_error_codes_and_bookkeeping():
         assert not mo.any() and not vo.any()
         # the context works on
         before = c.memory_stats()
-        c.enable_timing(only=[8])
+        c.enable_timing(only=[_lib.XB_TIMER_MOMENTS])
         c.kernel_time_reset()
         got, volume = c.moment_sum(lat, cen, VV)
         _, _, _, s, cnt, mag = reference(shape, None, lname, n)
         check(got, volume, s, cnt, mag, 'after the refused calls')
-        ms, launches = c.kernel_time(8)
+        ms, launches = c.kernel_time(_lib.XB_TIMER_MOMENTS)
         assert launches == 1 and ms > 0.0
         c.enable_timing(False)
         big = MS_BINS + 1000

@@ -184,7 +184,7 @@ def test_contexts_sharing_the_card_at_the_same_time():
             c.set_grid(shape, g['dist_mat'], g['T_grad'])
             c.synth_density(g['lattice'], g['atoms'], float(g['background']))
             for _ in range(3):
-                c.set_option(6, 1)
+                c.set_option(_lib.XB_OPT_DROP_TABLE, 1)
                 c.vacuum_assign(None, float(g['voxel_volume']))
                 c.assign('ongrid')
                 log = c.refine('changed', 2)
@@ -227,7 +227,7 @@ for name in ('c256_cubic', 'c128_tric'):
     c = _lib.Context(0)
     c.set_grid(tuple(int(s) for s in g['shape']), g['dist_mat'], g['T_grad'])
     c.synth_density(g['lattice'], g['atoms'], float(g['background']))
-    c.set_option(3, 4)
+    c.set_option(_lib.XB_OPT_DEBUG, _lib.XB_DBG_EC_PASSES)
     c.vacuum_assign(None, float(g['voxel_volume']))
     c.assign('ongrid')
     log = c.refine('changed', 2)
@@ -323,16 +323,16 @@ def test_edge_check_queue_overflow_hand_over(ctx, groups, qcap):
     """The chase kernel's LDS queues, shrunk to a few entries, spill into the overflow list that seeds
     the next launch: logs, map and flags must still equal the reference's (golden 'changed' run)."""
     g, rho = setup_case(ctx, 'c64_cubic')
-    ctx.set_option(4, groups)
-    ctx.set_option(5, qcap)
+    ctx.set_option(_lib.XB_OPT_EC_GROUPS, groups)
+    ctx.set_option(_lib.XB_OPT_EC_QCAP, qcap)
     try:
         ctx.upload_labels(g['ng_main'])
         log = ctx.refine('changed', -1)
         assert np.array_equal(np.array(log, np.int64).reshape(-1, 2), g['ng_changed_inf_log'])
         assert np.array_equal(ctx.download_labels(g['ng_changed_inf'].dtype), g['ng_changed_inf'])
     finally:
-        ctx.set_option(4, 256)
-        ctx.set_option(5, 6000)
+        ctx.set_option(_lib.XB_OPT_EC_GROUPS, 256)
+        ctx.set_option(_lib.XB_OPT_EC_QCAP, 6000)
 
 
 def test_atom_assign_matches_oracle(ctx):
@@ -705,7 +705,7 @@ def test_assign_refine_in_one_call_equals_the_two_calls(ctx, name, mode, iters):
     ctx.upload_density(rho)
     out = []
     for fused in (False, True):
-        ctx.set_option(6, 1)
+        ctx.set_option(_lib.XB_OPT_DROP_TABLE, 1)
         ctx.vacuum_assign(tol, 1.0)
         if fused:
             n, log = ctx.assign_refine('neargrid', mode, iters)
@@ -719,3 +719,36 @@ def test_assign_refine_in_one_call_equals_the_two_calls(ctx, name, mode, iters):
     assert a[0] == b[0] and np.array_equal(a[1], b[1]) and a[2] == b[2]
     assert np.array_equal(a[3], b[3])
     assert a[4] == b[4] and np.array_equal(a[5], b[5])
+
+
+def test_option_keys_and_timer_slots_are_checked_at_the_boundary():
+    """xb_set_option takes exactly the XB_OPT_* keys, each within its stated range, and xb_kernel_time exactly the slots
+    [0, XB_TIMER_COUNT); anything else is XB_E_ARG.  A context of its own: every switch ends where it started or goes with it."""
+    def refused(fn, *args):
+        with pytest.raises(_lib.BaderHipError) as e:
+            fn(*args)
+        assert e.value.code == _lib.XB_E_ARG, (args, e.value)
+
+    legal = {_lib.XB_OPT_REGIONS: _lib.XB_REGIONS_BOXES | _lib.XB_REGIONS_BRICKS, _lib.XB_OPT_CROSS_CHECK: 0, _lib.XB_OPT_DEBUG: 0,
+             _lib.XB_OPT_EC_GROUPS: 256, _lib.XB_OPT_EC_QCAP: 2, _lib.XB_OPT_DROP_TABLE: 1, _lib.XB_OPT_KILL_LAUNCHES: 6,
+             _lib.XB_OPT_SELF_EXCHANGE: 0, _lib.XB_OPT_ASYNC_COMM: 0, _lib.XB_OPT_WEIGHT_NO_LABELS: 0}
+    assert sorted(legal) == sorted(getattr(_lib, name) for name in dir(_lib) if name.startswith('XB_OPT_'))
+    c = _lib.Context(0)
+    try:
+        c.set_grid((8, 8, 8), np.zeros(27), np.zeros(9))
+        for key, value in legal.items():
+            c.set_option(key, value)
+        for key in range(41):
+            if key not in legal:
+                refused(c.set_option, key, 1)
+        refused(c.set_option, _lib.XB_OPT_EC_GROUPS, 0)
+        refused(c.set_option, _lib.XB_OPT_EC_GROUPS, 4097)
+        refused(c.set_option, _lib.XB_OPT_EC_QCAP, 1)
+        refused(c.set_option, _lib.XB_OPT_KILL_LAUNCHES, 0)
+        c.kernel_time_reset()
+        for k in range(_lib.XB_TIMER_COUNT):
+            assert c.kernel_time(k) == (0.0, 0), k
+        refused(c.kernel_time, _lib.XB_TIMER_COUNT)
+        refused(c.kernel_time, -1)
+    finally:
+        c.close()

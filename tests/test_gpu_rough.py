@@ -139,7 +139,7 @@ def test_slow_path_does_not_read_labels_nobody_wrote():
 
 def test_every_tier_of_the_slow_path_gives_the_same_map():
     """Round 6: the exact slow kernel runs in tiers of 64 / 2048 / 32768 path voxels and -- instead of failing the call as rounds 1-5
-    did -- a last one of 2^20.  With debug switch 64 the tiers hold 3 / 5 / 8 voxels, so that the walkers of a noisy density pass
+    did -- a last one of 2^20.  With XB_DBG_SHORT_TIERS the tiers hold 3 / 5 / 8 voxels, so that the walkers of a noisy density pass
     through every one of them, the last included; the assignment and the refinement must give what the default tiers give."""
     from pybader_amd import synth
     from pybader_amd.interface import distance_matrix, gradient_transform
@@ -147,9 +147,9 @@ def test_every_tier_of_the_slow_path_gives_the_same_map():
     vl = np.divide(synth.TRICLINIC, shape)
     dm, tg = distance_matrix(vl), gradient_transform(vl)
     res = []
-    for dbg in (0, 64):
+    for dbg in (0, _lib.XB_DBG_SHORT_TIERS):
         ctx = _lib.Context(0)
-        ctx.set_option(3, dbg)
+        ctx.set_option(_lib.XB_OPT_DEBUG, dbg)
         ctx.set_grid(shape, dm, tg)
         ctx.synth_density(synth.TRICLINIC, synth.ATOMS8, synth.BACKGROUND)
         rho = np.ascontiguousarray(ctx.download_density() + 1e-6 * np.random.default_rng(72).random(shape))

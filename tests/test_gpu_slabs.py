@@ -333,12 +333,12 @@ def test_rccl_transport_through_the_c_abi_single_rank():
     with pytest.raises(_lib.BaderHipError):
         ctx.comm_exchange_planes(0, [(0, 0, 1)], [])       # a send to myself is refused
     # the narrowed halo (round 3): 8 basins -> label planes travel as int8, packed before the group and widened behind it.
-    # One GPU can run that very code with itself as the peer (test switch 19): planes [3, 7) -> [40, 44), a second run
-    # [60, 62) -> [10, 12) in the same group, then the same with int32 on the wire (switch 18 off)
+    # One GPU can run that very code with itself as the peer (XB_OPT_SELF_EXCHANGE): planes [3, 7) -> [40, 44), a second run
+    # [60, 62) -> [10, 12) in the same group, then the same with int32 on the wire (XB_CHECK_WIDE_HALO)
     nyz = rho.shape[1] * rho.shape[2]
-    ctx.set_option(19, 1)
+    ctx.set_option(_lib.XB_OPT_SELF_EXCHANGE, 1)
     for narrow, width in ((1, 1), (0, 4)):
-        ctx.set_option(2, 0 if narrow else 16)      # cross-check bit 16: int32 label halos
+        ctx.set_option(_lib.XB_OPT_CROSS_CHECK, 0 if narrow else _lib.XB_CHECK_WIDE_HALO)   # int32 label halos
         ctx.upload_labels(before.astype(np.int8))   # (the wire width follows the uploaded dtype: bader_calc hands refine its int8 map)
         sent0 = ctx.comm_bytes_sent()
         ctx.comm_exchange_planes(0, [(0, 3, 7), (0, 60, 62)], [(0, 40, 44), (0, 10, 12)])
@@ -348,7 +348,7 @@ def test_rccl_transport_through_the_c_abi_single_rank():
         assert ctx.comm_bytes_sent() - sent0 == 6 * nyz * width
     # the wire width follows whoever wrote the labels last, not the last assignment's basin count -- a map with
     # more basins than the 8-basin assignment above, uploaded for a standalone refine, must cross the halo untruncated
-    ctx.set_option(2, 0)
+    ctx.set_option(_lib.XB_OPT_CROSS_CHECK, 0)
     many = (before.astype(np.int64) * 37 + (np.arange(before.size).reshape(before.shape) % 29)).astype(np.int32)   # labels 0..287
     assert many.max() > 127
     for up, width in ((many.astype(np.int16), 2), (many, 4)):
@@ -359,7 +359,7 @@ def test_rccl_transport_through_the_c_abi_single_rank():
         want[40:44], want[10:12] = many[3:7], many[60:62]
         assert np.array_equal(ctx.download_labels(np.int32), want)
         assert ctx.comm_bytes_sent() - sent0 == 6 * nyz * width
-    ctx.set_option(19, 0)
+    ctx.set_option(_lib.XB_OPT_SELF_EXCHANGE, 0)
     # RcclComm.gather_rows through the device collectives (one rank: what comes back is what went in): the single
     # collective for short contributions, the second one for long ones
     from pybader_amd import comm as pcomm
@@ -524,7 +524,7 @@ def test_device_driven_step_repeats_when_the_growth_outlasts_its_schedule():
     from pass A with the worst-case schedule.  Same map as always, one repeat per rank, two waits for the assignment."""
     g = load_golden('c64_cubic')
     rho = case_density(g)
-    pre, post, log, maxima, ch, vo, fb = run_slabs(4, g, rho, 'neargrid', 'changed', 2, 8, None, options=((17, 1),))
+    pre, post, log, maxima, ch, vo, fb = run_slabs(4, g, rho, 'neargrid', 'changed', 2, 8, None, options=((_lib.XB_OPT_KILL_LAUNCHES, 1),))
     assert run_slabs.last_device_steps == [1] * 4 and all(r == 1 for r, _ in run_slabs.last_growth)
     assert [a for a, _ in run_slabs.last_host_waits] == [2] * 4
     assert np.array_equal(pre, g['ng_F'].astype(np.int32)) and np.array_equal(post, g['ng_changed_2'].astype(np.int32))

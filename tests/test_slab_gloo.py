@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import load_golden
-from pybader_amd import slab
+from pybader_amd import _lib, slab
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -585,7 +585,7 @@ def test_device_driven_step_scheduling_with_a_mock_backend():
     assert runner.assign('neargrid') == 8 and runner.n_device_steps == 1
     one = [('masks', 0, 2), ('gather', 0, (0, 10)), ('gather', 1, (100, 10)), ('gather', 2, (200, 10)), ('gather', 3, (300, 10)), ('trace',),
            ('gather', 4, (400, 10)), ('finish',)]
-    assert calls == [('option', 24, 1)] + one + one
+    assert calls == [('option', _lib.XB_OPT_ASYNC_COMM, 1)] + one + one
     # a pass whose walkers were carried on in rounds 0 and 1 (bytes of glo[7]), none left: three rounds now, two next time
     del calls[:]
     be.counts = (np.array([50, 0, 7, 0, 0, 0, 0, 0x0101]), np.array([100, 0, 14, 0, 0, 0, 0, 0x0201]))

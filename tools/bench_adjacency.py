@@ -13,7 +13,7 @@ Three label maps at size^3, each from the neargrid assignment of a density gener
 Per case, warm-up first, then median / min / max of the repeats of
     adjacency_ms     xb_adjacency + xb_adjacency_fetch, host clock around the call (its host waits, the compaction's transfer
                      and the host sort are inside)
-    kernel_ms        the kernels of the same calls alone (timer 9 of xb_kernel_time, HIP events)
+    kernel_ms        the kernels of the same calls alone (XB_TIMER_ADJACENCY of xb_kernel_time, HIP events)
     charge_sum_ms    xb_charge_sum on the same labels, the same way: the yardstick, it streams 12 B per voxel once
 and ratio = kernel_ms / charge_sum_ms (medians), roofline_share = (24 B * voxels / kernel time) / --hbm-gbs: two passes.
 
@@ -112,9 +112,9 @@ def main():
         routes = [('', n)]
         if n <= AJ_DENSE:         # the same labels through the hash route: labels nobody carries past the dense limit
             routes.append(('_hash_route', AJ_DENSE + 1))
-        ctx.enable_timing(only=[9])
+        ctx.enable_timing(only=[_lib.XB_TIMER_ADJACENCY])
         for tag, m in routes:
-            wall, dev = timed(ctx, lambda: ctx.adjacency(dirs, m), a.warmup, a.repeats, a.limit, 'adjacency', timer=9)
+            wall, dev = timed(ctx, lambda: ctx.adjacency(dirs, m), a.warmup, a.repeats, a.limit, 'adjacency', timer=_lib.XB_TIMER_ADJACENCY)
             res['adjacency_ms' + tag], res['kernel_ms' + tag] = wall, dev
         ctx.enable_timing(False)
         res['charge_sum_ms'], _ = timed(ctx, lambda: ctx.charge_sum(vv, n), a.warmup, a.repeats, a.limit, 'charge_sum')

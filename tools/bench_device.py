@@ -57,11 +57,11 @@ def import_rates(ctx, n, repeats):
                  'ratio_to_copy': 1.0, 'GB_per_s': 2 * 8 * N / copy_ms / 1e6})
 
     def run(name, t, read_bytes, gather_only=False):
-        ctx.set_option(2, 64 if gather_only else 0)
+        ctx.set_option(_lib.XB_OPT_CROSS_CHECK, _lib.XB_CHECK_IO_GATHER if gather_only else 0)
         try:
             ms, lo, hi = event_ms(lambda: ctx.import_density(t), 3, repeats)
         finally:
-            ctx.set_option(2, 0)
+            ctx.set_option(_lib.XB_OPT_CROSS_CHECK, 0)
         rows.append({'path': name, 'ms': ms, 'min_ms': lo, 'max_ms': hi, 'ratio_to_copy': ms / copy_ms,
                      'GB_per_s': (read_bytes + 8 * N) / ms / 1e6})
 

@@ -14,8 +14,8 @@ The label maps of tools/bench_adjacency.py at size^3, each from the neargrid ass
 The maximum of a label is the Bader maximum of the highest density that carries it.  Per case, warm-up first, then median / min /
 max of the repeats of
     merge_ms             Context.merge_basins (xb_merge_basins + xb_merge_fetch), host clock around the call
-    merge_kernel_ms      the kernels of the same calls alone (timer 10 of xb_kernel_time, HIP events); per_round_ms = this / rounds
-    adjacency_kernel_ms  the kernels of xb_adjacency on the same labels (timer 9), measured in the same run
+    merge_kernel_ms      the kernels of the same calls alone (XB_TIMER_MERGE of xb_kernel_time, HIP events); per_round_ms = this / rounds
+    adjacency_kernel_ms  the kernels of xb_adjacency on the same labels (XB_TIMER_ADJACENCY), measured in the same run
     parent_route_ms      Context.adjacency + adjacency.persistence, host clock: what the library offered for the same
                          information before (the pair table, its download and host sort, the Python loop over the pairs)
 and rounds, survivors, merge_bytes (the method's device buffer) and pair_table_bytes.
@@ -116,18 +116,18 @@ def main():
                 top[owner[m]] = max_idx[m]
             max_idx, peak = top, None
         res['n_labels'] = int(n)
-        ctx.enable_timing(only=[10])
+        ctx.enable_timing(only=[_lib.XB_TIMER_MERGE])
         res['merge_ms'], res['merge_kernel_ms'] = timed(ctx, lambda: ctx.merge_basins(dirs, max_idx, a.tol), a.warmup, a.repeats,
-                                                        a.limit, 'merge_basins', timer=10)
+                                                        a.limit, 'merge_basins', timer=_lib.XB_TIMER_MERGE)
         root, rnd, pers, rounds, left, converged = ctx.merge_basins(dirs, max_idx, a.tol)
         res.update(rounds=rounds, survivors=left, converged=converged,
                    per_round_ms=res['merge_kernel_ms']['median'] / rounds)
         held = ctx.memory_stats()[2]
         ctx.merge_release()
         res['merge_bytes'] = int(held - ctx.memory_stats()[2])
-        ctx.enable_timing(only=[9])
+        ctx.enable_timing(only=[_lib.XB_TIMER_ADJACENCY])
         _, res['adjacency_kernel_ms'] = timed(ctx, lambda: ctx.adjacency(dirs, n), a.parent_warmup, a.parent_repeats, a.limit,
-                                              'adjacency', timer=9)
+                                              'adjacency', timer=_lib.XB_TIMER_ADJACENCY)
         ctx.enable_timing(False)
         if peak is None:
             peak = ctx.download_density().reshape(-1)[max_idx]

@@ -13,7 +13,7 @@ Three label maps at size^3, each the neargrid assignment of a density generated 
 Per case, warm-up first, then median / min / max of the repeats of
     moment_sum_ms    xb_moment_sum, host clock around the call (it returns with its results on the host: the transfer of
                      3 n centres in and 11 n numbers out is inside)
-    kernel_ms        the kernels of the same calls alone (timer 8 of xb_kernel_time, HIP events)
+    kernel_ms        the kernels of the same calls alone (XB_TIMER_MOMENTS of xb_kernel_time, HIP events)
     charge_sum_ms    xb_charge_sum on the same labels, the same way: the yardstick, it streams the same 12 B per voxel
 and ratio = kernel_ms / charge_sum_ms (medians), roofline_share = (12 B * voxels / kernel time) / --hbm-gbs.
 
@@ -106,9 +106,9 @@ def main():
         if n <= MS_BINS:        # the same labels through the global route: centres nobody carries past the bin limit
             routes.append(('_global_route', np.concatenate([centres, np.zeros((MS_BINS + 1 - n, 3))])))
         res = {'n_labels': int(n)}
-        ctx.enable_timing(only=[8])
+        ctx.enable_timing(only=[_lib.XB_TIMER_MOMENTS])
         for tag, cen in routes:
-            wall, dev = timed(ctx, lambda: ctx.moment_sum(lat, cen, vv), a.warmup, a.repeats, a.limit, 'moment_sum', timer=8)
+            wall, dev = timed(ctx, lambda: ctx.moment_sum(lat, cen, vv), a.warmup, a.repeats, a.limit, 'moment_sum', timer=_lib.XB_TIMER_MOMENTS)
             res['moment_sum_ms' + tag], res['kernel_ms' + tag] = wall, dev
         ctx.enable_timing(False)
         res['charge_sum_ms'], _ = timed(ctx, lambda: ctx.charge_sum(vv, n), a.warmup, a.repeats, a.limit, 'charge_sum')

@@ -29,7 +29,7 @@ ctx.set_grid(shape, distance_matrix(vl), gradient_transform(vl))
 ctx.synth_density(synth.CUBIC6, synth.ATOMS8, synth.BACKGROUND)
 out = (ctypes.c_ulonglong * 16)()
 for mirror in (1, 0):
-    ctx.set_option(2, 0 if mirror else 1)
+    ctx.set_option(_lib.XB_OPT_CROSS_CHECK, 0 if mirror else _lib.XB_CHECK_NO_MIRROR)
     raw.xb_debug_counts(out, 1)
     ctx.vacuum_assign(None, 1.0)
     ctx.assign('neargrid')

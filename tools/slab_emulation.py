@@ -77,7 +77,7 @@ def run(n, shape, g, halo, margin, steps, warmup, mode, iters):
         try:
             ctx = _lib.Context(0)
             if os.environ.get('XB_EMUL_DEBUG'):
-                ctx.set_option(3, 16)
+                ctx.set_option(_lib.XB_OPT_DEBUG, _lib.XB_DBG_SLAB_STATS)
             be = LockedBackend(ctx, {})
             comm = ThreadComm(sh, rank)
             runner = slab.SlabRunner(be, comm, shape, g['dist_mat'], g['T_grad'], halo=halo)
