@@ -339,6 +339,34 @@ int xb_weight_fetch(xb_ctx *c, int64_t *max_idx, double *charge, double *volume,
 int xb_weight_stats(xb_ctx *c, int64_t out[7]);
 /* frees the method's device buffers (25 N bytes, kept between calls while the grid stays) and the fetched results */
 int xb_weight_release(xb_ctx *c);
+/* ---- the Voronoi partition: every voxel to its nearest atom (`bader -c voronoi` in the Henkelman group's code; the geometric
+ * baseline next to the Bader charges, and a second atom map for xb_charge_sum, xb_moment_sum, xb_adjacency, xb_volume_mask) -- no
+ * counterpart in the reference ----
+ * WRITES the resident labels of the whole grid, as xb_upload_labels does, and invalidates everything that call invalidates (edge
+ * list, cached sums, the vacuum-by-tolerance mark, brick uniformity, the label width of the halos).  lattice[9]: the cell, a row per
+ * axis; atoms_cart[n][3]: Cartesian, already minus the voxel offset.  All of it is IEEE float64 without contraction: bit-defined.
+ *   position  of voxel (p0, p1, p2), as xb_moment_sum's and utils.surface_dist's (utils.py:357-359), left to right:
+ *             pc[j] = lat[j]*p0/nx;  pc[j] += lat[3+j]*p1/ny;  pc[j] += lat[6+j]*p2/nz
+ *   distance  for atom a and image x, y, z = -1..1, pbc[j] = (lat[j]*x + lat[3+j]*y) + lat[6+j]*z:
+ *             e[j] = pc[j] - (atom[a][j] + pbc[j]),  d2 = (e0*e0 + e1*e1) + e2*e2
+ *   label     D(a) = the minimum of d2 over the 27 images; the voxel's label is the a with the smallest D(a), TIES GO TO THE SMALLER
+ *             ATOM INDEX: the lexicographic minimum of (d2, a) over all 27 n pairs, which no order of the search changes.  Only
+ *             these 27 images of the positions as given are searched; atoms are not wrapped into the cell.
+ *   vacuum    with vac_tol not NaN a voxel with rho <= vac_tol gets -1, as xb_vacuum_assign decides it; with NaN the density is
+ *             not read at all (a context without one is accepted).
+ * One workgroup per 8 x 8 x 8 tile of voxels.  It keeps the images whose distance from the tile's centre is at most d_min + 2 R +
+ * slack (d_min the smallest such distance, R the tile's circumradius: no other image can be nearest, or tied for it, at any voxel of
+ * the tile; csrc/k_voronoi.h derives the slack), compacts them into LDS and lets every voxel search those.  A tile that keeps more
+ * than XB_VORONOI_CAND_MAX images searches all 27 n from global memory; XB_VORONOI_FULL_SEARCH in `flags` makes every tile do so:
+ * the second implementation, for tests and benchmarks -- both give the same labels.
+ *   stats     NULL, or {tiles answered from a candidate list, tiles answered by the full search, the largest number of images a
+ *             tile kept (it may exceed the cap; 0 with XB_VORONOI_FULL_SEARCH)}.  The call ends with a wait for the device.
+ * XB_E_STATE: no grid, a vacuum tolerance on a grid that has received no density yet, a context that holds a slab;
+ * XB_E_ARG: n < 1, a null lattice or atoms pointer, unknown flag bits, a lattice entry or coordinate that is not finite;
+ * XB_E_LIMIT: n > (2^31 - 1) / 27.  No timer slot: a caller times the call.  Its buffer is counted by xb_memory_stats. */
+enum { XB_VORONOI_FULL_SEARCH = 1, XB_VORONOI_CAND_MAX = 512 };
+int xb_voronoi_assign(xb_ctx *c, const double lattice[9], const double *atoms_cart, int64_t n, double vac_tol, int flags,
+                      int64_t stats[3]);
 /* utils.volume_assign (utils.py:404-421): labels[v] = swap[labels[v]] for labels >= 0 */
 int xb_volume_assign(xb_ctx *c, const int64_t *swap, int64_t n_swap);
 /* utils.atom_assign (utils.py:185-232): nearest atom of every maximum over the 27 periodic images (one

@@ -34,6 +34,9 @@ XB_OPT_KILL_LAUNCHES = 17
 XB_OPT_SELF_EXCHANGE = 19
 XB_OPT_ASYNC_COMM = 24
 XB_OPT_WEIGHT_NO_LABELS = 30
+# xb_voronoi_assign: the bit of `flags` that makes every tile search all images, and the candidates a tile's list holds
+XB_VORONOI_FULL_SEARCH = 1
+XB_VORONOI_CAND_MAX = 512
 
 # every symbol include/bader_hip.h declares: (restype, argtypes)
 _vp, _i64, _dbl, _int = C.c_void_p, C.c_int64, C.c_double, C.c_int
@@ -105,6 +108,7 @@ SYMBOLS = {
     'xb_weight_fetch': (_int, [_vp, _vp, _vp, _vp, _i64]),
     'xb_weight_stats': (_int, [_vp, _pi64]),
     'xb_weight_release': (_int, [_vp]),
+    'xb_voronoi_assign': (_int, [_vp, _pdbl, _pdbl, _i64, _dbl, _int, _pi64]),
     'xb_volume_assign': (_int, [_vp, _vp, _i64]),
     'xb_atom_assign': (_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp]),
     'xb_surface_distance': (_int, [_vp, _vp, _vp, _i64, _vp, _pi64]),
@@ -818,6 +822,20 @@ class Context:
         check(self.lib.xb_weight_stats(self.h, out))
         keys = ('levels', 'levels_batched', 'levels_tail', 'batches', 'voxels', 'peak_frontier', 'bytes')
         return dict(zip(keys, (int(v) for v in out)))
+
+    def voronoi_assign(self, lattice, atoms_cart, vac_tol=None, full_search=False, want_stats=True):
+        """the resident labels become the Voronoi partition: every voxel the index of its nearest atom over the 27 periodic
+        images, ties to the smaller index (xb_voronoi_assign; `lattice` the cell, a row per axis; `atoms_cart` [n, 3]); with
+        `vac_tol` voxels of the resident density at or below it get -1.  `full_search`: every tile searches all images (the
+        second implementation).  -> {'candidate_tiles', 'full_tiles', 'max_candidates'}, or None without `want_stats`"""
+        self.drop_label_token()
+        lat, at = _f64(lattice).reshape(9), _f64(atoms_cart).reshape(-1, 3)
+        tol = float('nan') if vac_tol is None else float(vac_tol)
+        st = (C.c_int64 * 3)()
+        check(self.lib.xb_voronoi_assign(self.h, lat.ctypes.data_as(_pdbl), at.ctypes.data_as(_pdbl), at.shape[0], tol,
+                                         XB_VORONOI_FULL_SEARCH if full_search else 0, st if want_stats else None))
+        if want_stats:
+            return dict(zip(('candidate_tiles', 'full_tiles', 'max_candidates'), (int(v) for v in st)))
 
     def volume_assign(self, swap):
         self.drop_label_token()

@@ -274,6 +274,23 @@ class Bader:
             rho_max = np.asarray(at[vox[:, 0], vox[:, 1], vox[:, 2]], dtype=np.float64)
             self.bader_persistence = persistence(b.pairs, b.saddle_density, rho_max)
 
+    voronoi_flag = False   # True: _run ends with voronoi_partition() (no other step changes)
+
+    def voronoi_partition(self):
+        """The Voronoi partition next to the Bader one (pybader_amd.voronoi: every voxel to its nearest atom) -- no counterpart
+        in the reference.  Sets voronoi_volumes (an atom map like atoms_volumes; vacuum_tol on the reference density marks -1),
+        voronoi_charge, voronoi_volume per atom (utils.charge_sum on that map; voronoi_spin with spin_bool) and voronoi_stats.
+        Atoms are atoms - voxel_offset, as in min_surface_distance.  It rewrites the device's label map, so it runs last."""
+        from .voronoi import voronoi_assign
+        atoms = self.atoms - self.voxel_offset
+        self.voronoi_volumes, self.voronoi_stats = voronoi_assign(self.reference, self.lattice, atoms, self.vacuum_tol)
+        n = self.atoms.shape[0]
+        self.voronoi_charge, self.voronoi_volume = np.zeros(n), np.zeros(n)
+        charge_sum(self.voronoi_charge, self.voronoi_volume, self.voxel_volume, self.density, self.voronoi_volumes)
+        if self.spin_bool:
+            self.voronoi_spin, self.voronoi_volume = np.zeros(n), np.zeros(n)
+            charge_sum(self.voronoi_spin, self.voronoi_volume, self.voxel_volume, self.spin, self.voronoi_volumes)
+
     persistence_tol = None   # a value: _run merges the Bader volumes below this persistence before their first use (None: no step changes)
 
     def merge_volumes(self):
@@ -318,6 +335,8 @@ class Bader:
             self.multipole_moments()
         if self.adjacency_flag:
             self.bond_surfaces()
+        if self.voronoi_flag:   # (last: it rewrites the device's label map)
+            self.voronoi_partition()
 
     def export_volumes(self):
         """The export loop of Bader.__call__ (interface.py:417-436): `export_mode` = ('volumes' | 'atoms', [numbers]),
