@@ -534,6 +534,10 @@ enum {
     XB_CHECK_NO_EC_SHARE = 32,    /* no front sharing in the edge_check chase: every workgroup keeps what it wakes */
     XB_CHECK_IO_GATHER = 64       /* xb_import_density gathers a permuted layout voxel by voxel instead of through the LDS tile */
 };
+/* One more bit of the same value: the lean walker and the lean retrace ask the brick label / brick byte on every step instead of
+ * reading the neighbour bits of the record in hand.  A macro, not an enumerator: tests/test_abi_cpu.py pins the enumerators above
+ * and their number (pybader_amd._lib mirrors it as CROSS_CHECK_BRICK_LOOKUP). */
+#define XB_CHECK_BRICK_LOOKUP 128
 /* value of XB_OPT_DEBUG (bits 1, 2 and 8 are not in use) */
 enum {
     XB_DBG_EC_PASSES = 4,         /* print the passes of edge_check and what the middle tier leaves for the exact slow kernel */

@@ -24,6 +24,7 @@ XB_REGIONS_BOXES, XB_REGIONS_BRICKS = 1, 2
 XB_OPT_CROSS_CHECK = 2
 (XB_CHECK_NO_MIRROR, XB_CHECK_GENERIC_WALKER, XB_CHECK_FULL_TGRAD, XB_CHECK_LIST_DILATE, XB_CHECK_WIDE_HALO,
  XB_CHECK_NO_EC_SHARE, XB_CHECK_IO_GATHER) = (1, 2, 4, 8, 16, 32, 64)
+CROSS_CHECK_BRICK_LOOKUP = 128   # the header's macro XB_CHECK_BRICK_LOOKUP, one more bit of XB_OPT_CROSS_CHECK (its enumerators are pinned)
 XB_OPT_DEBUG = 3
 XB_DBG_EC_PASSES, XB_DBG_SLAB_STATS, XB_DBG_STAGE_WAIT, XB_DBG_SHORT_TIERS = 4, 16, 32, 64
 XB_OPT_EC_GROUPS = 4

@@ -98,6 +98,7 @@ struct xb_ctx {
         int tile_dilate = 1;       // the dilation of the edge sweep tile by tile (k_edge_dilate_tiles) instead of from the edge list (tests compare)
         int narrow_halo = 1;       // label halos travel as dtype_calc(-n_maxima) (int8 / int16) instead of int32 (comm.h)
         int ec_share = 1;          // k_ec_chase: a long queue sheds its surplus into other workgroups' mailboxes (0: every workgroup keeps what it wakes; A/B, XB_CHECK_NO_EC_SHARE)
+        int nb_bits = 1;           // lean walker / lean retrace: "no records there" from the neighbour bits of the record in hand (0: the brick label / brick byte per step; tests compare, XB_CHECK_BRICK_LOOKUP)
         int io_tiled = 1;          // xb_import_density: permuted layouts through the LDS tile (0: the plain strided gather; tests and the benchmark compare)
         int dbg = 0;               // XB_OPT_DEBUG: XB_DBG_* bits
         int ec_groups = 256;       // XB_OPT_EC_GROUPS: workgroups of k_ec_chase (at most one per CU)
@@ -143,9 +144,13 @@ struct xb_ctx {
     int *blab = nullptr;        // brick labels of the trapping regions (inside `list`), or null
     int nbk[3] = {0, 0, 0};
     bool grad_valid = false;
+    bool grad_nb = false;      // every record of the resident table carries neighbour bits (bader_kernels.h) that match the bricks that hold
+                               // records now: set by the pass-B launches that write a whole-grid table of whole bricks (launch_brick_records),
+                               // cleared with grad_valid and by every other writer of records; nb_bits_ok() is what the launchers ask
     bool brick_max_valid = false;   // brick_rec bit 1 (the brick holds a 26-neighbour maximum) is right for the density on the card
     int grad_cover = 0;        // 0: the table holds a record for every voxel (of the window); 1: only for the bricks flagged in brick_rec
     unsigned char *brick_rec = nullptr;   // per 8^3 brick: its records exist (k_brick_records), nbr bytes inside blab_buf's allocation
+    unsigned long long *nb_tab = nullptr; // per 8^3 brick: the neighbour bits of its records by octant (k_nb_table), behind brick_rec
     void *xbuf = nullptr;      // the device-driven slab step's exchange blocks 3-5 (slab_step.h): tie flags, counters, maxima tables
     int slab_rank = 0, slab_nranks = 0, slab_stage = 0;
     void *wbuf[2] = {nullptr, nullptr};   // ... blocks 6 / 7: the walkers of a refinement pass and their results, one part per rank
@@ -354,6 +359,7 @@ int xb_set_option(xb_ctx *c, int key, int value) {
     switch (key) {
     case XB_OPT_REGIONS: c->opt.boxes = (value & XB_REGIONS_BOXES) != 0; c->opt.bricks = (value & XB_REGIONS_BRICKS) != 0; break;
     case XB_OPT_CROSS_CHECK:
+        if (!(ok = value >= 0 && value < 2 * XB_CHECK_BRICK_LOOKUP)) break;
         c->opt.mirror = !(value & XB_CHECK_NO_MIRROR);
         c->opt.lean = !(value & XB_CHECK_GENERIC_WALKER);
         c->opt.mask_diag = !(value & XB_CHECK_FULL_TGRAD);
@@ -361,11 +367,12 @@ int xb_set_option(xb_ctx *c, int key, int value) {
         c->opt.narrow_halo = !(value & XB_CHECK_WIDE_HALO);
         c->opt.ec_share = !(value & XB_CHECK_NO_EC_SHARE);
         c->opt.io_tiled = !(value & XB_CHECK_IO_GATHER);
+        c->opt.nb_bits = !(value & XB_CHECK_BRICK_LOOKUP);
         break;
     case XB_OPT_DEBUG: c->opt.dbg = value; break;
     case XB_OPT_EC_GROUPS: if ((ok = value >= 1 && value <= 4096)) c->opt.ec_groups = value; break;
     case XB_OPT_EC_QCAP: if ((ok = value >= 2 && value <= EC_Q)) c->opt.ec_qcap = value; break;
-    case XB_OPT_DROP_TABLE: c->grad_valid = false; if (value == XB_DROP_TABLE_AND_MAXIMA) c->brick_max_valid = false; break;   // (a refinement rebuilds the table)
+    case XB_OPT_DROP_TABLE: c->grad_valid = false; c->grad_nb = false; if (value == XB_DROP_TABLE_AND_MAXIMA) c->brick_max_valid = false; break;   // (a refinement rebuilds the table)
     case XB_OPT_KILL_LAUNCHES: if ((ok = value >= 1)) c->grow_kill_launches = value; break;
     case XB_OPT_SELF_EXCHANGE: c->opt.self_exchange = value != 0; break;
     case XB_OPT_ASYNC_COMM: c->opt.async_comm = value != 0; break;
@@ -404,7 +411,7 @@ int xb_memory_stats(xb_ctx *c, int64_t *bytes_total, int64_t *bytes_table, int64
                               (long long)c->mg_cap * MG_BYTES /* xb_merge_basins' per-label buffer */ +
                               (long long)c->vo_cap * 8 /* xb_voronoi_assign's buffer */;
     const long long fixed = 8 * N /* rho */ + 4 * N /* labels */ + (N + 16) /* known */ + 4 * N /* first */ + N /* st */ +
-                            2LL * c->max_cap * 4 + (long long)c->ovf_cap * 4 + c->blab_alloc * 5 + (long long)c->walk_cap * 3 * 80 +
+                            2LL * c->max_cap * 4 + (long long)c->ovf_cap * 4 + c->blab_alloc * 13 + (long long)c->walk_cap * 3 * 80 +
                             (1 << 22) /* boxbuf */;
     if (bytes_total) *bytes_total = fixed + table + scratch;
     if (bytes_table) *bytes_table = table;

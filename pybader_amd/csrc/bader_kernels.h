@@ -157,13 +157,15 @@ __device__ __forceinline__ bool ng_step(const double *__restrict__ rho, const Gr
 //                           not leave this voxel by a gradient step (max_grad < 1E-14)
 //               bits  6-10  the ongrid successor (methods.py:87-117) as (ix+1)*9+(iy+1)*3+(iz+1);
 //                           13 = the voxel itself, i.e. a 26-neighbour maximum
-//               bits 11-20  trapping-box id + 1 (0 = in no box), see k_box_scan
+//               bits 11-17  which neighbour bricks hold NO records (nb_* below): one bit per non-empty set of
+//                           crossed axes; 0 in every record of a windowed (slab) table and of make_rec_rho
+//               bits 18-20  0
 // `key` orders path voxels for the window test only (any fixed per-voxel function keeps that test
 // sound, see PathWindow); exact densities are never taken from it.
 struct __attribute__((aligned(32))) GradRec { double r0, r1, r2, key; };
 #define XB_STAY_CODE 63
 #define XB_OG_SELF 13
-#define XB_MAX_BOXES 1023
+#define XB_NOREC (-2147483647 - 1)   // brick label of a vacuum brick: no region, no records (k_brick_walk_list_morton)
 __device__ __forceinline__ GradRec fetch_rec(const GradRec *__restrict__ G, int l) {
     return *reinterpret_cast<const GradRec *>(reinterpret_cast<const char *>(G) + ((unsigned long long)(unsigned)l << 5));
 }
@@ -179,8 +181,50 @@ __device__ __forceinline__ int rec_slot(const GT &g, int l) {
 template <typename GT>
 __device__ __forceinline__ GradRec fetch_rec_w(const GT &g, const GradRec *__restrict__ G, int l) { return fetch_rec(G, rec_slot(g, l)); }
 
-__device__ __forceinline__ double pack_key(double rho, int code, int og) {
-    return __longlong_as_double((__double_as_longlong(rho) & ~0x1FFFFFLL) | (long long)(code | (og << 6)));
+// The neighbour bits of a record (key bits 11-17).  A move is at most two voxels long per axis (int_grad and the correction
+// are -1..1 each; an ongrid step is one voxel), so from a voxel of a whole 8-voxel brick at most ONE side per axis is
+// within reach: the low side from positions 0-1, the high side from 6-7 (nb_side; pass B takes < 4 for low).  That leaves
+// the 7 neighbour bricks given by the non-empty subsets (cx, cy, cz) of crossed axes; bit nb_index says that the brick
+// at that offset holds no records -- it belongs to a trapping region or is a vacuum brick --, so a walker that steps
+// into it knows without a lookup that its walk on the table ends there.  Pass B (k_brick_records) writes them.
+#define XB_KEY_BITS 21
+#define XB_NB_SHIFT 11
+constexpr __host__ __device__ int nb_side(int pos) { return pos < 4 ? -1 : 1; }
+constexpr __host__ __device__ int nb_index(int cx, int cy, int cz) { return cx + 2 * cy + 4 * cz - 1; }
+constexpr __host__ __device__ int key_low(int code, int og, int nb) { return code | (og << 6) | ((nb & 127) << XB_NB_SHIFT); }
+constexpr __host__ __device__ int low_code(int bits) { return bits & 63; }
+constexpr __host__ __device__ int low_og(int bits) { return (bits >> 6) & 31; }
+// does the record with these low key bits say "no records" for the brick across the axes (cx, cy, cz)?  (none crossed: the
+// own brick, whose records exist)
+constexpr __host__ __device__ bool low_nb_norec(int bits, int cx, int cy, int cz) {
+    return (cx | cy | cz) != 0 && ((bits >> (XB_NB_SHIFT + nb_index(cx, cy, cz))) & 1) != 0;
+}
+namespace nb_check {
+constexpr bool subsets_ok() {
+    for (int m = 1; m < 8; m++) {
+        const int cx = m & 1, cy = (m >> 1) & 1, cz = m >> 2;
+        if (nb_index(cx, cy, cz) != m - 1) return false;
+        for (int code = 0; code < 64; code += 21)
+            for (int og = 0; og < 27; og += 13) {
+                const int one = key_low(code, og, 1 << (m - 1)), rest = key_low(code, og, 127 & ~(1 << (m - 1)));
+                if (low_code(one) != code || low_og(one) != og || low_code(rest) != code || low_og(rest) != og) return false;
+                if (one >> XB_KEY_BITS || rest >> XB_KEY_BITS) return false;   // inside the bits key_floor rounds away
+                for (int k = 1; k < 8; k++) {   // exactly the subset's own bit answers
+                    if (low_nb_norec(one, k & 1, (k >> 1) & 1, k >> 2) != (k == m)) return false;
+                    if (low_nb_norec(rest, k & 1, (k >> 1) & 1, k >> 2) != (k != m)) return false;
+                }
+                if (low_nb_norec(one, 0, 0, 0) || low_nb_norec(key_low(code, og, 127), 0, 0, 0)) return false;
+            }
+    }
+    return true;
+}
+static_assert(subsets_ok(), "7 neighbour bits, one per subset of crossed axes, clear of the step code and the ongrid successor");
+static_assert(nb_side(0) == -1 && nb_side(1) == -1 && nb_side(3) == -1 && nb_side(4) == 1 && nb_side(6) == 1 && nb_side(7) == 1,
+              "the low side is within reach from positions 0-1 only, the high side from 6-7 only");
+static_assert(key_low(XB_STAY_CODE, 26, 127) == 0x3FEBF && key_low(63, 31, 127) < (1 << 18), "bits 18-20 stay 0");
+}
+__device__ __forceinline__ double pack_key(double rho, int code, int og, int nb = 0) {
+    return __longlong_as_double((__double_as_longlong(rho) & ~0x1FFFFFLL) | (long long)key_low(code, og, nb));
 }
 // the largest value with all-equal record bits that is <= every key pack_key can make of `rho` (round down on those bits)
 __device__ __forceinline__ double key_floor(double rho) {
@@ -188,9 +232,9 @@ __device__ __forceinline__ double key_floor(double rho) {
     return __longlong_as_double(b >= 0 ? (b & ~0x1FFFFFLL) : (b | 0x1FFFFFLL));
 }
 __device__ __forceinline__ int key_bits(double key) { return (int)(__double_as_longlong(key) & 0x1FFFFFLL); }
-__device__ __forceinline__ int key_code(double key) { return key_bits(key) & 63; }
-__device__ __forceinline__ int key_og(double key) { return (key_bits(key) >> 6) & 31; }
-__device__ __forceinline__ int key_box(double key) { return key_bits(key) >> 11; }
+__device__ __forceinline__ int key_code(double key) { return low_code(key_bits(key)); }
+__device__ __forceinline__ int key_og(double key) { return low_og(key_bits(key)); }
+static_assert((1 << XB_KEY_BITS) - 1 == 0x1FFFFF, "key_bits / key_floor / pack_key share one mask");
 
 // wrap q in [-n, 2n) into [0, n) with two unsigned minima
 __device__ __forceinline__ int wrap_u(int q, int n) {

@@ -8,14 +8,17 @@
 // (k_brick_records).
 static GridL light(const Grid &g);
 
-// per-brick arrays that outlive an assignment: blab_buf (nbr ints: region label per brick) and brick_rec (nbr bytes)
+// per-brick arrays that outlive an assignment: blab_buf (nbr ints: region label per brick), brick_rec (nbr bytes) and nb_tab
+// (nbr 8-byte words: pass B's neighbour bits per octant, k_nb_table)
 static int ensure_brick_bytes(xb_ctx *c, int nbr) {
     if (c->blab_alloc < nbr) {
-        hipFree(c->blab_buf); c->blab_buf = nullptr; c->blab_alloc = 0; c->brick_rec = nullptr; c->brick_max_valid = false;
-        if (c->grad_cover) { c->grad_cover = 0; c->grad_valid = false; }
-        HIPCHK(hipMalloc(&c->blab_buf, (size_t)nbr * sizeof(int) + (size_t)nbr + 16));
+        hipFree(c->blab_buf); c->blab_buf = nullptr; c->blab_alloc = 0; c->brick_rec = nullptr; c->nb_tab = nullptr; c->brick_max_valid = false;
+        if (c->grad_cover) { c->grad_cover = 0; c->grad_valid = false; c->grad_nb = false; }
+        const size_t rec_bytes = ((size_t)nbr + 16 + 7) & ~(size_t)7;   // (keeps nb_tab 8-byte aligned)
+        HIPCHK(hipMalloc(&c->blab_buf, (size_t)nbr * sizeof(int) + rec_bytes + (size_t)nbr * sizeof(unsigned long long)));
         c->blab_alloc = nbr;
         c->brick_rec = reinterpret_cast<unsigned char *>(c->blab_buf + nbr);
+        c->nb_tab = reinterpret_cast<unsigned long long *>(c->brick_rec + rec_bytes);
     }
     return XB_OK;
 }
@@ -588,7 +591,7 @@ static int assign_neargrid_tail(xb_ctx *c, int64_t *n_maxima) {
     if (h[FS_GROW_RETRY]) {   // the short kill schedule did not reach the fixpoint: once more, with the worst-case one from now on
         c->grow_kill_launches = 1 << 20;
         c->stat_grow_retries++;
-        c->grad_valid = false;
+        c->grad_valid = false; c->grad_nb = false;
         return assign_neargrid_fused(c, n_maxima);
     }
     if (h[FS_TIES] == 0) c->grad_rule = 2;
@@ -719,7 +722,7 @@ static int assign_ongrid_fused(xb_ctx *c, int64_t *n_maxima) {
         launch_region_growth(c, nb0, nb1, nb2, bmask, bmaxv, bpot, seed, buf0, buf1, box_max, box_first, true);
         HIPCHK(hipGetLastError());
     }
-    c->grad_valid = false;          // (brick_rec is rewritten: bit 1 = holds a maximum, no records)
+    c->grad_valid = false; c->grad_nb = false;          // (brick_rec is rewritten: bit 1 = holds a maximum, no records)
     c->grad_cover = 0;
     c->brick_max_valid = true;
     c->blab = c->blab_buf;

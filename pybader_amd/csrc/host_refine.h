@@ -300,7 +300,8 @@ static int refine_trace_impl(xb_ctx *c, int flag, int64_t *changed, int64_t *esc
                 }
             }
             HIPCHK(hipMemsetAsync(c->counters + CT_DEFER, 0, sizeof(int), c->stream));
-            launch_refine_trace<2, false>(c, nblocks(n), TPB, c->list, n, nullptr, c->counters + CT_CHANGED, c->counters + CT_ESCAPED, c->ovf_list,
+            // (NB: `missing` from the neighbour bits of the record in hand -- a whole-grid table that vouches for them)
+            (brec && !slab && nb_bits_ok(c) ? launch_refine_trace<2, false, false, false, true> : launch_refine_trace<2, false>)(c, nblocks(n), TPB, c->list, n, nullptr, c->counters + CT_CHANGED, c->counters + CT_ESCAPED, c->ovf_list,
                                           c->counters + CT_N_OVF, c->ovf_cap, brec, defer, c->counters + CT_DEFER, regions_ok, slab_regions, WalkerIO{});
             if (brec || slab || table_windowed(c))
                 launch_refine_trace<2, true>(c, 512, TPB, defer, 0, c->counters + CT_DEFER, c->counters + CT_CHANGED, c->counters + CT_ESCAPED, c->ovf_list,
@@ -733,7 +734,8 @@ static int refine_iteration_fused(xb_ctx *c, int64_t *edges, int64_t *changed, b
         int *defer = (int *)c->stage;
         WalkerIO wl{};   // (no walkers on one GPU)
         constexpr int XB_RT_BLOCK = 128;   // (threads per workgroup of the retrace kernel: 64 / 128 / 256 measured 0.512 / 0.495 / 0.514 ms on the whole list)
-        launch_refine_trace<2, false>(c, (unsigned)((c->N / 16 + XB_RT_BLOCK - 1) / XB_RT_BLOCK), XB_RT_BLOCK, c->list, 0, fs + FS_N_EDGES,
+        // (NB: `missing` from the neighbour bits of the record in hand -- a whole-grid table that vouches for them)
+        (brec && nb_bits_ok(c) ? launch_refine_trace<2, false, false, false, true> : launch_refine_trace<2, false>)(c, (unsigned)((c->N / 16 + XB_RT_BLOCK - 1) / XB_RT_BLOCK), XB_RT_BLOCK, c->list, 0, fs + FS_N_EDGES,
                                       fs + FS_CHANGED, fs + FS_ESCAPED, c->ovf_list, fs + FS_R_OVF, c->ovf_cap, brec, defer, fs + FS_R_DEFER,
                                       regions_ok, nullptr, wl);
         if (c->grad_cover == 1 && !regions_ok)   // the few retraces whose walk goes on through a brick without records (count on the
@@ -893,7 +895,7 @@ int xb_assign_refine(xb_ctx *c, int method, int mode, int64_t iters, int64_t *n_
             if (int rc2 = assign_neargrid_tail(c, n_maxima)) return rc2;
             return xb_refine(c, mode, iters, log, log_capacity, n_iters);
         }
-        c->grad_valid = false;   // the ordinary way, from the start: the assignment rewrites every label
+        c->grad_valid = false; c->grad_nb = false;   // the ordinary way, from the start: the assignment rewrites every label
         c->first_clean = false;
         c->buni_valid = false; c->regions_labels = false;
         if (n_iters) *n_iters = 0;

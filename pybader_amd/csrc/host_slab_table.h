@@ -5,7 +5,7 @@
 int xb_set_table_window(xb_ctx *c, int64_t margin) {
     NEED_GRID("xb_set_table_window");
     Grid &g = c->g;
-    c->grad_valid = false;
+    c->grad_valid = false; c->grad_nb = false;
     c->table_stage = 0;
     const int own = g.x1 - g.x0;
     if (margin < 0 || own == g.nx) { g.wx0 = 0; g.wlen = g.nx; c->table_margin = -1; g.wbase = 0; return XB_OK; }

@@ -59,11 +59,22 @@ static void launch_brick_masks(xb_ctx *c, bool part, bool allow_diag, int *bmask
 }
 
 // Pass B (k_brick_records): the 32-byte records of the listed bricks (list[0 .. *n_dev)), or of every brick whose
-// brick_rec byte asks for them (list null)
+// brick_rec byte asks for them (list null).  Every caller writes ALL the records the table is then said to hold -- the walk
+// list of an assignment after k_grow_finish has cleared the brick bytes, or every flagged brick -- never some bricks next to
+// older ones.  So a launch over a whole-grid table of whole bricks can mark in every record which neighbour bricks hold none
+// (grad_nb; a list must then be the bricks with blab <= 0 that are no vacuum bricks: the walk list), and every other launch --
+// a slab's window, a grid that cuts its last bricks -- writes zeros there and says so.
+static bool nb_bits_ok(const xb_ctx *c) { return c->grad_valid && c->grad_nb && c->opt.nb_bits; }
 static void launch_brick_records(xb_ctx *c, const int *list, const int *n_dev, int nbr, int nb1, int nb2) {
     const Grid &g = c->g;
+    const bool part = g.nx % BRK || g.ny % BRK || g.nz % BRK;
+    const bool mark = !table_windowed(c) && g.x0 == 0 && g.x1 == g.nx && !part && (!list || c->blab) && c->nb_tab;
+    c->grad_nb = mark;
+    if (mark)   // (the bricks that hold records are known: the labels after the walk list was made, or the flags)
+        k_nb_table<<<(nbr + 255) / 256, 256, 0, c->stream>>>(nbr / (nb1 * nb2), nb1, nb2, list ? c->blab : nullptr, c->brick_rec, c->nb_tab);
     auto launch = [&](auto kernel, const auto &gt) {
-        kernel<<<4096, TPB, 0, c->stream>>>(gt, c->rho, c->grad, list, n_dev, nbr, nb1, nb2, c->brick_rec, small_grid(g));
+        kernel<<<4096, TPB, 0, c->stream>>>(gt, c->rho, c->grad, list, n_dev, nbr, nb1, nb2, c->brick_rec, small_grid(g),
+                                            mark ? c->nb_tab : nullptr);
     };
     GridS gs;
     if (sym_grid(g, gs)) launch(k_brick_records<GridS>, gs);
@@ -119,7 +130,10 @@ static bool launch_persistent_trace(xb_ctx *c, bool lean_ok, bool part, const in
     const bool window = table_windowed(c);
     int *ovf = window ? (int *)c->stage : c->ovf_list;
     const int ovf_cap = window ? (int)std::min<size_t>(c->stage_bytes / sizeof(int), 0x7fffffffu) : c->ovf_cap;
+    // (the neighbour bits: whole bricks, the whole grid, and a table that vouches for them -- else the brick label per step)
+    const bool nb = lean && !window && !part && nb_bits_ok(c);
     auto kernel = !lean ? k_ng_trace_g<2, 0>
+                : nb ? (lean == 4 ? k_ng_trace_g<2, 4, false, false, true> : k_ng_trace_g<2, 3, false, false, true>)
                 : window ? (lean == 4 ? k_ng_trace_g<2, 4, true> : k_ng_trace_g<2, 3, true>)
                 : part ? (lean == 4 ? k_ng_trace_g<2, 4, false, true> : k_ng_trace_g<2, 3, false, true>)
                 : (lean == 4 ? k_ng_trace_g<2, 4> : k_ng_trace_g<2, 3>);
@@ -178,11 +192,11 @@ static void numbering_done(xb_ctx *c, const int *sorted, int nmax, int64_t *n_ma
 
 // k_refine_trace with what every retrace passes alike: the table, labels / known, the density and distances of the from-rho
 // form, the step bound.  (C++ linkage: the host parts are included inside an extern "C" block)
-extern "C++" template <int K, bool RHO, bool RESUME = false, bool EXPORT = false>
+extern "C++" template <int K, bool RHO, bool RESUME = false, bool EXPORT = false, bool NB = false>
 static void launch_refine_trace(xb_ctx *c, unsigned grid, int block, const int *list, int n_host, const int *n_dev, int *changed, int *escaped,
                                 int *ovf_list, int *ovf_count, int ovf_cap, const unsigned char *brec, int *defer_list, int *defer_count,
                                 int regions_ok, const int *region_blab, const WalkerIO &wio) {
-    k_refine_trace<K, RHO, RESUME, EXPORT><<<grid, block, 0, c->stream>>>(light(c->g), c->grad, c->labels, c->known, list, n_host, n_dev, changed,
+    k_refine_trace<K, RHO, RESUME, EXPORT, NB><<<grid, block, 0, c->stream>>>(light(c->g), c->grad, c->labels, c->known, list, n_host, n_dev, changed,
                                                                            escaped, ovf_list, ovf_count, ovf_cap, trace_maxsteps(c->g), c->rho,
                                                                            c->dist_dev, brec, defer_list, defer_count, regions_ok, region_blab, wio);
 }

@@ -678,7 +678,12 @@ struct WalkerIO {
 // EXPORT (slabs, device-driven step): the lean instantiation hands a retrace that leaves the valid planes over as a walker
 // itself (it holds the whole state) instead of deferring it to the from-rho instantiation, which walked it again from its
 // start only to export it at the same voxel.
-template <int K, bool RHO, bool RESUME = false, bool EXPORT = false>
+// NB (round 7; the lean retrace on a whole-grid table of whole bricks whose records carry valid neighbour bits, bader_kernels.h):
+// `missing` -- the brick of q holds no records -- is read off the record in hand instead of the brick byte: two gathers per
+// step (record, flag) instead of three.  Everything downstream of `missing` is the same.  The record of a missing q, which nobody
+// ever wrote, is still gathered: leaving it out puts the gather behind a divergent branch, which cost more than the cold lines
+// (measured at 512^3: 0.503 ms with the brick byte, 0.52-0.54 without that gather, 0.48 with it).
+template <int K, bool RHO, bool RESUME = false, bool EXPORT = false, bool NB = false>
 __global__ __launch_bounds__(TPB) void k_refine_trace(GridL g, const GradRec *__restrict__ G, int *labels,
                                                       int8_t *known, const int *__restrict__ list, int n_host,
                                                       const int *n_dev, int *changed, int *escaped, int *ovf_list,
@@ -688,6 +693,7 @@ __global__ __launch_bounds__(TPB) void k_refine_trace(GridL g, const GradRec *__
                                                       int *defer_count, int regions_ok, const int *__restrict__ region_blab,
                                                       WalkerIO wio) {
     static_assert(!RESUME || (RHO && K == 2), "walkers are carried on by the from-rho kernel");
+    static_assert(!NB || (K == 2 && !RHO && !RESUME && !EXPORT), "neighbour bits: the lean retrace of one GPU");
     const int n = n_dev ? *n_dev : n_host;   // the list length may live on the device: the grid strides over it
     int n_ch = 0, n_es = 0;
   // (XCD k retraces the k-th contiguous eighth of the list, which is in tile order: xcd_range)
@@ -787,9 +793,15 @@ __global__ __launch_bounds__(TPB) void k_refine_trace(GridL g, const GradRec *__
                 // the record is gathered speculatively, together with the flag and the brick byte: asking the brick byte
                 // first saved the gathers of never-written records (most of this kernel's HBM traffic) but cost more in
                 // dependent latency than it saved (0.49 -> 0.55 ms)
-                GradRec nr = fetch_rec(G, in_win ? rec_slot(g, lq) : 0);   // (outside the window: any valid slot, the value is not used)
+                // (NB: `rec` is a record of the table -- the start voxel's was tested, every later one was not missing --, and the
+                // wrapped brick coordinates differ exactly where the move, at most two voxels long, crossed a face: on an axis of
+                // ONE brick it comes back into the own brick, whose records exist)
+                const bool nb_missing = NB && low_nb_norec(key_bits(rec.key), (px >> 3) != (qx >> 3), (py >> 3) != (qy >> 3), (pz >> 3) != (qz >> 3));
+                GradRec nr;
+                if (!NB) nr = fetch_rec(G, in_win ? rec_slot(g, lq) : 0);   // (outside the window: any valid slot, the value is not used)
+                else nr = fetch_rec(G, lq);   // (for a missing q too: see above)
                 const int8_t kq = known[ok_plane ? lq : lp];
-                const bool missing = !(in_win && rec_exists(brick_rec, g, qx, qy, qz));
+                const bool missing = NB ? nb_missing : !(in_win && rec_exists(brick_rec, g, qx, qy, qz));
                 // slabs (region_blab: the brick labels of the trapping regions, the same on every rank): a retrace that
                 // enters a region ends in it with the region's label -- it no longer glides along a dividing surface for
                 // tens of planes, so a narrow label halo is enough and the remote path queries become rare

@@ -447,6 +447,37 @@ __global__ __launch_bounds__(TPB) void k_brick_masks(GT g, const double *__restr
     }
 }
 
+// The neighbour bits of pass B's records (bader_kernels.h, nb_index), per brick: byte o of tab[b] holds the 7 bits of the voxels in
+// octant o = (x >= 4) * 4 + (y >= 4) * 2 + (z >= 4) of brick b -- the side within reach is the same for all of them.  Which bricks
+// hold records must be final when this runs: with `blab` the bricks of the walk list do (label <= 0 and no vacuum brick; pass B
+// sets their brick_rec flags only while it writes them), otherwise the bricks whose brick_rec flag is set.  The periodic wrap is
+// by true brick index: on a lattice two bricks wide the low and the high neighbour are one brick.
+__global__ void k_nb_table(int nb0, int nb1, int nb2, const int *__restrict__ blab, const unsigned char *__restrict__ brick_rec,
+                           unsigned long long *__restrict__ tab) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= nb0 * nb1 * nb2) return;
+    const int b0 = b / (nb1 * nb2), b1 = (b / nb2) % nb1, b2 = b % nb2;
+    unsigned m27 = 0;   // bit t: the neighbour at offset (t / 9 - 1, (t / 3) % 3 - 1, t % 3 - 1) holds no records
+#pragma unroll
+    for (int t = 0; t < 27; t++) {
+        const int nbk = (wrapi(b0 + t / 9 - 1, nb0) * nb1 + wrapi(b1 + (t / 3) % 3 - 1, nb1)) * nb2 + wrapi(b2 + t % 3 - 1, nb2);
+        const bool has = blab ? (blab[nbk] <= 0 && blab[nbk] != XB_NOREC) : (brick_rec[nbk] & 1) != 0;
+        m27 |= has ? 0u : 1u << t;
+    }
+    unsigned long long w = 0;
+#pragma unroll
+    for (int o = 0; o < 8; o++) {   // offset index per axis: 0 low, 1 the own brick, 2 high
+        const int s0 = nb_side((o >> 2) * 4) + 1, s1 = nb_side(((o >> 1) & 1) * 4) + 1, s2 = nb_side((o & 1) * 4) + 1;
+#pragma unroll
+        for (int m = 1; m < 8; m++) {
+            const int cx = m & 1, cy = (m >> 1) & 1, cz = m >> 2;
+            const unsigned no = (m27 >> ((cx ? s0 : 1) * 9 + (cy ? s1 : 1) * 3 + (cz ? s2 : 1))) & 1u;
+            w |= (unsigned long long)no << (8 * o + nb_index(cx, cy, cz));
+        }
+    }
+    tab[b] = w;
+}
+
 // pass B: the records of the voxels of the listed bricks.  One workgroup per brick and turn: the 10^3 haloed brick
 // goes through LDS, every thread derives two records (k_grad_field's arithmetic).  The brick list is either the walk
 // list (`walk`, length *n_list on the device) or, with walk == nullptr, every brick whose brick_rec flag is already
@@ -465,8 +496,10 @@ __global__ __launch_bounds__(TPB) void k_brick_masks(GT g, const double *__restr
 template <typename GT>
 __global__ __launch_bounds__(TPB, 4) void k_brick_records(GT g, const double *__restrict__ rho, GradRec *__restrict__ G,
                                                        const int *__restrict__ walk, const int *n_list, int nbr, int nb1, int nb2,
-                                                       unsigned char *brick_rec, int small) {
+                                                       unsigned char *brick_rec, int small, const unsigned long long *__restrict__ nb_tab) {
     __shared__ double tile[10][10][BR_ROW];
+    // nb_tab (a whole-grid table of whole bricks, else null): the records carry their neighbour bits (bader_kernels.h, nb_index),
+    // which k_nb_table has laid out per brick and octant -- one scalar load per brick here, nothing per voxel but a shift.
     const int n = walk ? *n_list : nbr;
     int goff[4], loff[4];   // halo element e = threadIdx.x + j * TPB of the 10^3 tile: offset from the corner voxel (no wrap), slot in the tile
 #pragma unroll
@@ -480,6 +513,7 @@ __global__ __launch_bounds__(TPB, 4) void k_brick_records(GT g, const double *__
     for (int item = xr.begin; item < xr.end; item += xr.step) {
         const int b = walk ? walk[item] : item;
         if (!walk && !(brick_rec[b] & 1)) continue;   // uniform per block
+        const unsigned long long nbw = nb_tab ? nb_tab[b] : 0ull;   // (uniform: the 7 bits of each of the brick's 8 octants)
         const int b0 = b / (nb1 * nb2), b1 = (b / nb2) % nb1, b2 = b % nb2;
         const int x0 = b0 * 8, y0 = b1 * 8, z0 = b2 * 8;
         // the haloed brick lies inside the grid: no periodic wrap anywhere (block uniform)
@@ -545,7 +579,7 @@ __global__ __launch_bounds__(TPB, 4) void k_brick_records(GT g, const double *__
                 o.r2 = d2 - (double)i2;
                 code = (i0 + 1) | ((i1 + 1) << 2) | ((i2 + 1) << 4);
             }
-            o.key = pack_key(c, code, og);
+            o.key = pack_key(c, code, og, (int)(nbw >> (8 * (((tx >> 2) << 2) | ((ty >> 2) << 1) | (tz >> 2)))) & 127);
             // (a brick the grid cuts: only its voxels inside the grid have a record)
             if (inner || (x0 + tx < g.nx && y0 + ty < g.ny && z0 + tz < g.nz)) G[rec_slot(g, vbase + (tx * g.ny + ty) * g.nz + tz)] = o;
         }

@@ -140,7 +140,7 @@ __device__ __forceinline__ int compact3(unsigned x) {   // every third bit of x,
 // largest density as a float in integer order) says which bricks these are; they stay off the list and their brick label
 // becomes XB_NOREC: "no records here" -- a walker that steps into one (downhill across the tolerance: not excluded) is handed
 // to the exact slow kernel, which works from rho.  The float is compared with a margin that covers its rounding.
-#define XB_NOREC (-2147483647 - 1)
+// (XB_NOREC itself: bader_kernels.h -- pass B reads it too)
 __device__ __forceinline__ bool brick_is_vacuum(const int *__restrict__ bpot, int b, double vac_tol) {
     if (!bpot) return false;
     const int p = bpot[b];
@@ -208,8 +208,7 @@ __device__ __forceinline__ void ng_walk_wave(const GridL &g, const GradRec *__re
         if (lab0 != -1) {
             px = sx; py = sy; pz = sz;
             lp = v;
-            // trapping regions: brick labels (grids made of whole 8^3 bricks) or box ids in the keys
-            if (b <= 0) b = key_box(rec.key);
+            // trapping regions: brick labels
             if (b > 0) result = box_max[b - 1];  // starts inside a trapping region: ends at its maximum
             else { w.init(v, rec.key); moving = true; }
         }
@@ -242,7 +241,7 @@ __device__ __forceinline__ void ng_walk_wave(const GridL &g, const GradRec *__re
                 GradRec nr = fetch_rec(G, in_win ? rec_slot(g, lq) : 0);  // issued before the brick label: both in flight (outside the window: any valid slot)
                 const int bl = blab ? blab[((qx >> 3) * nb1 + (qy >> 3)) * nb2 + (qz >> 3)] : 0;
                 if (WIN && !in_win && bl <= 0) nr = make_rec_rho(g, rho, gc, qx, qy, qz);  // outside the window: from rho
-                const int b = bl > 0 ? bl : key_box(nr.key);
+                const int b = bl > 0 ? bl : 0;
                 if (bl == XB_NOREC) {  // a vacuum brick (k_brick_walk_list_morton): no records -- the exact slow kernel works from rho
                     result = -2;
                     moving = false;
@@ -271,7 +270,7 @@ __device__ __forceinline__ void ng_walk_wave(const GridL &g, const GradRec *__re
 // ---------------------------------------------------------------------------------------------
 // The lean walker of the single-GPU persistent trace.  Same trajectory, same exits and the same results as
 // ng_walk_wave<2, false> -- tests/test_gpu_parity.py runs both -- for the case that kernel is launched in: the table
-// window is the whole grid, trapping regions are brick labels (no box ids in the keys), nx * ny and nz below 2^24.
+// window is the whole grid, trapping regions are brick labels, nx * ny and nz below 2^24.
 // What differs is the instruction stream of a step (round 2: ~100 VALU + 48 SALU per wave-step, 87 % of the kernel's
 // time in VALU issue):
 //   * the gradient move is computed for every moving lane, straight-line; the rare ongrid step (a voxel without a
@@ -281,6 +280,11 @@ __device__ __forceinline__ void ng_walk_wave(const GridL &g, const GradRec *__re
 //     at the back-edge), linear and brick indices by 24-bit multiply-adds (the generic form compiles to the
 //     quarter-rate v_mad_u64_u32), the periodic wrap is one v_min3_u32 of (q, q + n, q - n);
 //   * no window / table-cover tests.
+// NB (round 7; a whole-grid table of whole bricks whose records carry valid neighbour bits, bader_kernels.h): the record in hand
+// says whether the brick the move enters holds records.  It does: the one gather, no brick-label load.  It does not: no gather
+// at all (the slot was never written; those gathers went all the way to HBM) -- the lane leaves the loop and only then loads
+// its brick label, to tell a trapping region from a vacuum brick.  Without NB (cut bricks, slabs, XB_CHECK_BRICK_LOOKUP): the
+// record gather and the brick-label load of every step that leaves the own brick, in flight together.
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ int wrap3(int q, int n) {   // q in [-n, 2n) -> [0, n)
     return (int)min(min((unsigned)q, (unsigned)(q + n)), (unsigned)(q - n));
@@ -312,13 +316,14 @@ __device__ __forceinline__ GradRec fetch_rec_o(const GradRec *__restrict__ G, in
 // (48 KB of LDS: three workgroups per compute unit), **4 x 1 1.135**, 4 x 2 1.56, 2 x 1 1.45 (the last two lose occupancy to LDS).
 constexpr int XB_TRACE_WAVES = 4;
 __shared__ GradRec xb_s_rec[512];   // the records of the brick a workgroup of the group trace walks (16 KB)
-template <bool OFF32, bool CACHE, bool WINDOW = false>
+template <bool OFF32, bool CACHE, bool WINDOW = false, bool NB = false>
 __device__ __forceinline__ int ng_walk_lean(const GridL &g, const GradRec *__restrict__ G, const int *__restrict__ box_max,
                                              const int *__restrict__ blab, int nb1, int nb2, int sx, int sy, int sz,
                                              int *labels, int *first, int *max_list, int *max_count, int max_cap,
                                              int *ovf_list, int *ovf_count, int ovf_cap, int maxsteps, bool has_vacuum) {
     // every start voxel is valid: the walk list holds whole bricks, and the lanes of a brick the grid cuts start from its
     // voxels inside the grid (k_ng_trace_g PART)
+    static_assert(!NB || (CACHE && !WINDOW), "neighbour bits: the whole-grid table of the group trace");
     const int v = lin24(g, sx, sy, sz);
     const int lab0 = has_vacuum ? labels[v] : 0;   // without vacuum `labels` is write-only here
     const int ox8 = sx & ~7, oy8 = sy & ~7, oz8 = sz & ~7;   // origin of the own brick
@@ -332,6 +337,7 @@ __device__ __forceinline__ int ng_walk_lean(const GridL &g, const GradRec *__res
     // 2.6 M with 3, 2.3 K / 1.2 M with 4; the headline pays 1.5 % / 3 % of the trace for a wider one, so 2 it is and the slow path
     // got its tiers instead: host_assign.h run_slow.)
     int i0 = v, i1 = -1;
+    bool norec = false;   // NB: left the loop on arrival in a brick without records
     double k0 = rec.key, k1 = -1.7976931348623157e308, m_old = -1.7976931348623157e308;
 #ifdef XB_DEBUG_COUNT
     int dbg_lane_steps = 0;
@@ -348,6 +354,8 @@ __device__ __forceinline__ int ng_walk_lean(const GridL &g, const GradRec *__res
         const double t0 = dr0 + rec.r0, t1 = dr1 + rec.r1, t2 = dr2 + rec.r2;
         const int id0 = rha_cs(t0), id1 = rha_cs(t1), id2 = rha_cs(t2);
         const int m0 = (bits & 3) + id0 - 1, m1 = ((bits >> 2) & 3) + id1 - 1, m2 = ((bits >> 4) & 3) + id2 - 1;
+        // NB: the axes on which the move leaves the brick of p (before the wrap: -1 and n are other bricks than 0 and n - 1)
+        int cross = NB ? (((px ^ (px + m0)) >> 3) != 0) | ((((py ^ (py + m1)) >> 3) != 0) << 1) | ((((pz ^ (pz + m2)) >> 3) != 0) << 2) : 0;
         px += m0; py += m1; pz += m2;
         dr0 = t0 - (double)id0; dr1 = t1 - (double)id1; dr2 = t2 - (double)id2;
         // the periodic wrap only for the waves that touch the faces of the grid
@@ -364,9 +372,11 @@ __device__ __forceinline__ int ng_walk_lean(const GridL &g, const GradRec *__res
                 og_offsets(og, ox, oy, oz);
                 at_max = og == XB_OG_SELF;   // break_flag: p is the maximum
                 dr0 = dr1 = dr2 = 0.;
-                px = wrap3(wrap3(px - m0, g.nx) + ox, g.nx);
-                py = wrap3(wrap3(py - m1, g.ny) + oy, g.ny);
-                pz = wrap3(wrap3(pz - m2, g.nz) + oz, g.nz);
+                const int ux = wrap3(px - m0, g.nx), uy = wrap3(py - m1, g.ny), uz = wrap3(pz - m2, g.nz);   // p again
+                if (NB) cross = (((ux ^ (ux + ox)) >> 3) != 0) | ((((uy ^ (uy + oy)) >> 3) != 0) << 1) | ((((uz ^ (uz + oz)) >> 3) != 0) << 2);
+                px = wrap3(ux + ox, g.nx);
+                py = wrap3(uy + oy, g.ny);
+                pz = wrap3(uz + oz, g.nz);
                 lq = lin24(g, px, py, pz);   // (== i0 at a maximum)
             }
         }
@@ -374,8 +384,11 @@ __device__ __forceinline__ int ng_walk_lean(const GridL &g, const GradRec *__res
         int bl = 0;
         const bool own = CACHE && (unsigned)((px ^ ox8) | (py ^ oy8) | (pz ^ oz8)) < 8u;
         const bool in_win = !WINDOW || own || plane_in_window(g, px);
+        if (NB) norec = cross != 0 && ((bits >> (XB_NB_SHIFT - 1) >> cross) & 1) != 0;   // (bit nb_index = cross - 1)
         if (own) rec = xb_s_rec[((px & 7) << 6) | ((py & 7) << 3) | (pz & 7)];
-        else {
+        else if (NB) {
+            if (!norec) rec = fetch_rec_o<OFF32>(G, lq);
+        } else {
             rec = fetch_rec_o<OFF32>(G, WINDOW ? (in_win ? rec_slot(g, lq) : 0) : lq);   // (outside the window: any valid slot, the value is not used)
             const unsigned bidx = (unsigned)mad24(mad24(px >> 3, nb1, py >> 3), nb2, pz >> 3);
             bl = *reinterpret_cast<const int *>(reinterpret_cast<const char *>(blab) + (bidx << 2));
@@ -387,6 +400,7 @@ __device__ __forceinline__ int ng_walk_lean(const GridL &g, const GradRec *__res
         // arrived inside a trapping region (q cannot be an old path voxel: the trajectory would have stopped there
         // already); membership undecidable from the window: exact slow kernel (ongrid moves are appended without a
         // membership test, methods.py:513-521)
+        if (NB && norec) break;   // a trapping region or a vacuum brick: which of them is asked after the loop
         const bool arrived = bl > 0 && !at_max;
         const bool undecided = (!og_move && rec.key <= m_old) || steps > maxsteps || (WINDOW && !in_win) || bl == XB_NOREC;   // (a vacuum brick: no records)
         if (arrived) result = box_max[bl - 1];
@@ -396,6 +410,11 @@ __device__ __forceinline__ int ng_walk_lean(const GridL &g, const GradRec *__res
         m_old = max_raw(m_old, k1);
         i1 = i0; k1 = k0;
         i0 = lq; k0 = rec.key;
+    }
+    if (NB && norec) {   // (px, py, pz) is the voxel arrived at
+        const unsigned bidx = (unsigned)mad24(mad24(px >> 3, nb1, py >> 3), nb2, pz >> 3);
+        const int bl = *reinterpret_cast<const int *>(reinterpret_cast<const char *>(blab) + (bidx << 2));
+        result = bl > 0 ? box_max[bl - 1] : -2;   // (XB_NOREC, a vacuum brick: the exact slow kernel works from rho)
     }
 #ifdef XB_DEBUG_COUNT
     if (xb_dbg_steps) xb_dbg_steps[v] = (signed char)min(dbg_lane_steps, 127);   // tools/walk_lengths.py
@@ -498,10 +517,10 @@ __device__ __forceinline__ int xcc_id() {
 // different unit.  The trace is bound by exactly that: L2 requests x L2 latency / misses in flight per compute unit
 // (profiles/r5_final_pmc_sq_512_neargrid.txt: 9.1e7 L2 requests x 370 cycles = 50 requests in flight per compute unit on
 // average, TCP_PENDING_STALL 55 % of the kernel; DESIGN.md 4.3 has what round 6 measured around that bound).
-// LEAN 0: the generic walker ng_walk_wave (tests every start voxel, box ids in the keys, table windows); LEAN 3 / 4: the lean
+// LEAN 0: the generic walker ng_walk_wave (tests every start voxel, table windows); LEAN 3 / 4: the lean
 // walker (4: 32-bit table offsets), the brick's 512 records copied into LDS (16 KB) before the waves start (see ng_walk_lean).
 // CH: items per pull (8: one brick).
-template <int K, int LEAN, bool WINDOW = false, bool PART = false>
+template <int K, int LEAN, bool WINDOW = false, bool PART = false, bool NB = false>
 __global__ __launch_bounds__(XB_WAVE * XB_TRACE_WAVES, 8) void k_ng_trace_g(GridL g, const GradRec *__restrict__ G, const int *__restrict__ box_max,
                                                        const int *__restrict__ blab, int nb1, int nb2,
                                                        const int *__restrict__ walk, int *fs, int *labels, int *first,
@@ -514,6 +533,7 @@ __global__ __launch_bounds__(XB_WAVE * XB_TRACE_WAVES, 8) void k_ng_trace_g(Grid
     // at 512^3), no cross-lane operations.
     __shared__ int s_w[8], s_mixed;
     constexpr bool CACHE = LEAN >= 3;
+    static_assert(!NB || (CACHE && !WINDOW && !PART), "neighbour bits: whole bricks, the whole grid (a cut brick narrower than 5 voxels reaches both sides of an axis)");
     int prev_brick = -1;
 #ifdef XB_DEBUG_COUNT   // time probes (tools/trace_probe.py): where do the waves of the persistent trace spend their cycles?
     const long long pr_t0 = clock64();
@@ -596,7 +616,7 @@ __global__ __launch_bounds__(XB_WAVE * XB_TRACE_WAVES, 8) void k_ng_trace_g(Grid
 #ifdef XB_DEBUG_COUNT
                     const long long pr_c = clock64();
 #endif
-                    const int res = ng_walk_lean<LEAN == 4, CACHE, WINDOW>(g, G, box_max, blab, nb1, nb2, sx, sy, sz, labels, first, max_list, &fs[FS_N_MAX],
+                    const int res = ng_walk_lean<LEAN == 4, CACHE, WINDOW, NB>(g, G, box_max, blab, nb1, nb2, sx, sy, sz, labels, first, max_list, &fs[FS_N_MAX],
                                                                 max_cap, ovf_list, &fs[FS_N_OVF], ovf_cap, maxsteps, has_vacuum != 0);
 #ifdef XB_DEBUG_COUNT
                     pr_walk += clock64() - pr_c;

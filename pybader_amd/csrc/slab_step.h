@@ -370,12 +370,12 @@ int xb_slab_assign_finish(xb_ctx *c, int64_t *n_maxima, int64_t *status) {
     if (h[FS_GROW_RETRY]) {
         c->grow_kill_launches = 1 << 20;
         c->stat_grow_retries++;
-        c->grad_valid = false;
+        c->grad_valid = false; c->grad_nb = false;
         if (status) *status = 1;
         return XB_OK;
     }
     if (!h[FS_SORT_OK]) {
-        c->grad_valid = false;
+        c->grad_valid = false; c->grad_nb = false;
         if (status) *status = 2;
         return XB_OK;
     }
