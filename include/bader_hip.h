@@ -367,6 +367,56 @@ int xb_weight_release(xb_ctx *c);
 enum { XB_VORONOI_FULL_SEARCH = 1, XB_VORONOI_CAND_MAX = 512 };
 int xb_voronoi_assign(xb_ctx *c, const double lattice[9], const double *atoms_cart, int64_t n, double vac_tol, int flags,
                       int64_t stats[3]);
+/* ---- critical points of the density and the bond graph they define (the core of a QTAIM analysis: nuclear, bond, ring and cage
+ * points; which atoms a bond path joins and rho at the bond point) -- no counterpart in the reference ----
+ * Reads the resident density rho of the whole grid (xb_critical_bonds the resident labels too); nothing resident is written.  The
+ * points are the PIECEWISE-LINEAR critical points of rho on the Freudenthal (Kuhn) triangulation of the periodic voxel lattice:
+ * combinatorial, integer-exact, and on a grid with every axis >= 4 they satisfy minima - sum ring + sum bond - maxima == 0 (the
+ * Euler characteristic of the 3-torus) for ANY field, noise and plateaus included.
+ *   order     lin is the C-order index, key() the total order of xb_adjacency;  u < v ("u is below v") iff key(rho[u]) < key(rho[v]),
+ *             or the keys are equal and lin(u) < lin(v)
+ *   offsets   d_0 .. d_6 = (0,0,1) (0,1,0) (0,1,1) (1,0,0) (1,0,1) (1,1,0) (1,1,1),  d_{7+k} = -d_k;  u_k = v + d_k, wrapped on every axis
+ *   masks     bit k of L(v) is set iff u_k is below v -- strictly: a neighbour that wraps onto v itself leaves its bit clear;
+ *             U(v) = ~L(v) & 0x3fff
+ *   link      bits a and b are adjacent iff d_b - d_a, as an integer vector without wrapping, is one of the 14 offsets: 36 edges and
+ *             24 triangles, a triangulated sphere.  c(M) = the number of connected components of the set bits of M (at most 6)
+ *   kind      L == 0: a minimum (cage point);  U == 0: a maximum (nuclear point);  otherwise ring = c(L) - 1 is the multiplicity of
+ *             the voxel as a 1-saddle and bond = c(U) - 1 as a 2-saddle; regular when both are 0.  A voxel may be both (on noise)
+ *   counts    counts[XB_CRITICAL_*] = {maxima, bond voxels, sum of bond, ring voxels, sum of ring, minima};  with every axis >= 4:
+ *             minima - sum ring + sum bond - maxima == 0.  Below 4 the wrapped neighbours coincide; the definition stands as
+ *             written, the identity is not claimed
+ *   vacuum    with vac_tol not NaN a voxel with rho[v] <= vac_tol is neither counted nor listed; its density still enters its
+ *             neighbours' masks.  The identity is not promised then
+ *   list      one record per non-regular voxel, ascending in lin: (lin, L, ring, bond), ring = bond = 0 for the two extrema.  Never
+ *             cut short: xb_critical_points returns its length, xb_critical_fetch wants that capacity
+ *   table     xb_critical_lut: out[L] = ring | bond << 4 for every L, 0 for L == 0 and L == 0x3fff; host only, needs no GPU
+ * The maxima use the 14-neighbour test: a superset of the 26-neighbour maxima of xb_assign.
+ *   bonds     xb_critical_bonds(n) works on the list of the last xb_critical_points call of this context (any writer of the density
+ *             discards it) and the resident labels.  For every listed voxel v with bond > 0 and every component of U(v): its TOP is
+ *             the greatest neighbour of the component in the order above, its basin labels[top].  D(v) = the distinct basins in
+ *             [0, n) (labels < 0 and >= n count for nothing).  Every unordered pair a < b of D(v) gains one saddle; per pair:
+ *             saddles, the count;  rho_b, the maximum of rho[v] under key();  voxel, the smallest lin among its bond voxels with that
+ *             key.  A bond voxel with exactly one basin in D(v) counts towards same_basin: its bond path returns to the basin it
+ *             left, through a periodic image or inside a noisy basin.  Pairs ascending in (a, b).  Integers and maxima of existing
+ *             bits only.
+ * One streaming pass: a workgroup stages the keys of an 8 x 8 x 32 tile and its halo in LDS, 14 ordered comparisons per voxel, one
+ * byte of the table (global memory); a wave of regular voxels leaves after one ballot.  XB_CRITICAL_FLOOD in `flags` counts the
+ * components by a flood fill in registers instead: the second implementation, same results.  The records are compacted on the
+ * device -- into a list of N / 64 + 4096 records that a call with more grows to the number its own counter found before it runs
+ * again -- and sorted on the host; a second kernel over the listed bond voxels emits the tops' labels, the host reduces per pair.
+ * XB_E_STATE: no grid, no density (bonds: no labels, no list) on this grid yet, a context that holds a slab (fetch: no result);
+ * XB_E_ARG: a null pointer, unknown flag bits, n < 1, capacity below the length in a fetch.  No timer slot: a caller times the
+ * calls.  The list and the table are counted by xb_memory_stats and freed by xb_critical_release. */
+enum { XB_CRITICAL_FLOOD = 1 };
+enum { XB_CRITICAL_MAXIMA = 0, XB_CRITICAL_BOND_VOXELS = 1, XB_CRITICAL_BOND_SUM = 2, XB_CRITICAL_RING_VOXELS = 3,
+       XB_CRITICAL_RING_SUM = 4, XB_CRITICAL_MINIMA = 5, XB_CRITICAL_COUNTS = 6 };
+enum { XB_CRITICAL_FULL = 16383 /* 0x3fff: every neighbour below */, XB_CRITICAL_LUT_SIZE = 16384 };
+int xb_critical_lut(uint8_t out[16384]);
+int xb_critical_points(xb_ctx *c, double vac_tol, int flags, int64_t counts[6], int64_t *n_list);
+int xb_critical_fetch(xb_ctx *c, int64_t *lin, uint16_t *lower_mask, uint8_t *ring, uint8_t *bond, int64_t capacity);
+int xb_critical_bonds(xb_ctx *c, int64_t n, int64_t *n_pairs, int64_t *same_basin);
+int xb_critical_bonds_fetch(xb_ctx *c, int32_t *a, int32_t *b, int64_t *saddles, double *rho_b, int64_t *voxel, int64_t capacity);
+int xb_critical_release(xb_ctx *c);
 /* utils.volume_assign (utils.py:404-421): labels[v] = swap[labels[v]] for labels >= 0 */
 int xb_volume_assign(xb_ctx *c, const int64_t *swap, int64_t n_swap);
 /* utils.atom_assign (utils.py:185-232): nearest atom of every maximum over the 27 periodic images (one

@@ -38,6 +38,13 @@ XB_OPT_WEIGHT_NO_LABELS = 30
 # xb_voronoi_assign: the bit of `flags` that makes every tile search all images, and the candidates a tile's list holds
 XB_VORONOI_FULL_SEARCH = 1
 XB_VORONOI_CAND_MAX = 512
+# xb_critical_points: the bit of `flags` that counts components by flood fill instead of the table; the entries of counts[];
+# the lower mask of a maximum and the size of xb_critical_lut's table
+XB_CRITICAL_FLOOD = 1
+(XB_CRITICAL_MAXIMA, XB_CRITICAL_BOND_VOXELS, XB_CRITICAL_BOND_SUM, XB_CRITICAL_RING_VOXELS, XB_CRITICAL_RING_SUM,
+ XB_CRITICAL_MINIMA, XB_CRITICAL_COUNTS) = range(7)
+XB_CRITICAL_FULL = 0x3fff
+XB_CRITICAL_LUT_SIZE = 16384
 
 # every symbol include/bader_hip.h declares: (restype, argtypes)
 _vp, _i64, _dbl, _int = C.c_void_p, C.c_int64, C.c_double, C.c_int
@@ -110,6 +117,12 @@ SYMBOLS = {
     'xb_weight_stats': (_int, [_vp, _pi64]),
     'xb_weight_release': (_int, [_vp]),
     'xb_voronoi_assign': (_int, [_vp, _pdbl, _pdbl, _i64, _dbl, _int, _pi64]),
+    'xb_critical_lut': (_int, [_vp]),
+    'xb_critical_points': (_int, [_vp, _dbl, _int, _pi64, _pi64]),
+    'xb_critical_fetch': (_int, [_vp, _vp, _vp, _vp, _vp, _i64]),
+    'xb_critical_bonds': (_int, [_vp, _i64, _pi64, _pi64]),
+    'xb_critical_bonds_fetch': (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64]),
+    'xb_critical_release': (_int, [_vp]),
     'xb_volume_assign': (_int, [_vp, _vp, _i64]),
     'xb_atom_assign': (_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp]),
     'xb_surface_distance': (_int, [_vp, _vp, _vp, _i64, _vp, _pi64]),
@@ -838,6 +851,35 @@ class Context:
         if want_stats:
             return dict(zip(('candidate_tiles', 'full_tiles', 'max_candidates'), (int(v) for v in st)))
 
+    def critical_points(self, vac_tol=None, flood=False):
+        """the piecewise-linear critical points of the resident density (xb_critical_points; `vac_tol`: voxels at or below it are
+        neither counted nor listed; `flood`: components by flood fill instead of the table, the second implementation) ->
+        (counts int64[6] indexed by XB_CRITICAL_*, lin int64[P] ascending, lower_mask uint16[P], ring uint8[P], bond uint8[P])"""
+        tol = float('nan') if vac_tol is None else float(vac_tol)
+        counts, n = np.zeros(XB_CRITICAL_COUNTS, np.int64), C.c_int64()
+        check(self.lib.xb_critical_points(self.h, tol, XB_CRITICAL_FLOOD if flood else 0, counts.ctypes.data_as(_pi64), C.byref(n)))
+        p = int(n.value)
+        lin, mask = np.zeros(p, np.int64), np.zeros(p, np.uint16)
+        ring, bond = np.zeros(p, np.uint8), np.zeros(p, np.uint8)
+        check(self.lib.xb_critical_fetch(self.h, _ptr(lin), _ptr(mask), _ptr(ring), _ptr(bond), p))
+        return counts, lin, mask, ring, bond
+
+    def critical_bonds(self, n):
+        """the bond graph of the last critical_points call on the resident labels 0 .. n - 1 (xb_critical_bonds) ->
+        (pairs int32[P, 2] ascending with a < b, saddles int64[P], rho_b f64[P], voxel int64[P], same_basin)"""
+        np_, same = C.c_int64(), C.c_int64()
+        check(self.lib.xb_critical_bonds(self.h, int(n), C.byref(np_), C.byref(same)))
+        p = int(np_.value)
+        a, b = np.zeros(p, np.int32), np.zeros(p, np.int32)
+        saddles, rho_b, voxel = np.zeros(p, np.int64), np.zeros(p, np.float64), np.zeros(p, np.int64)
+        check(self.lib.xb_critical_bonds_fetch(self.h, _ptr(a), _ptr(b), _ptr(saddles), _ptr(rho_b), _ptr(voxel), p))
+        return np.stack([a, b], axis=1), saddles, rho_b, voxel, int(same.value)
+
+    def critical_release(self):
+        """free the record list and the table of xb_critical_points (kept between calls while the grid's shape stays) and the
+        fetched results"""
+        check(self.lib.xb_critical_release(self.h))
+
     def volume_assign(self, swap):
         self.drop_label_token()
         sw = np.ascontiguousarray(swap, dtype=np.int64)
@@ -1079,6 +1121,13 @@ class Context:
 
     def sync(self):
         check(self.lib.xb_sync(self.h))
+
+
+def critical_lut():
+    """xb_critical_lut: ring | bond << 4 for each of the 16 384 lower masks (host only: needs the library, not a GPU)"""
+    out = np.zeros(XB_CRITICAL_LUT_SIZE, np.uint8)
+    check(load().xb_critical_lut(_ptr(out)))
+    return out
 
 
 def atom_assign(bader_max_cart, atoms_cart, lattice):

@@ -274,6 +274,31 @@ class Bader:
             rho_max = np.asarray(at[vox[:, 0], vox[:, 1], vox[:, 2]], dtype=np.float64)
             self.bader_persistence = persistence(b.pairs, b.saddle_density, rho_max)
 
+    critical_flag = False   # True: _run ends with critical_analysis() (no other step changes)
+
+    def critical_analysis(self):
+        """The critical points of the reference density and the bond graphs they define (pybader_amd.critical) -- no counterpart
+        in the reference.  Sets critical_points (a critical.CriticalPoints), critical_counts [6] (maxima, bond voxels, sum of
+        bond, ring voxels, sum of ring, minima), critical_voxels [P, 3], critical_kinds [P] (critical.NUCLEAR | BOND | RING |
+        CAGE bits) and critical_positions [P, 3] (Cartesian, voxel_offset added); vacuum_tol keeps vacuum voxels out of them.
+        From atoms_volumes: atoms_bond_graph (a critical.BondGraph), atoms_bonds [B, 2] (the pairs of atoms a bond path joins),
+        atoms_bond_saddles [B], atoms_bond_density [B] (rho at the highest bond point) and atoms_bond_position [B, 3].  From
+        bader_volumes, unless speed_flag dropped the map: bader_bond_graph and bader_bonds.  With adjacency_flag set as well,
+        atoms_bond_density and atoms_bond_position stay bond_surfaces()'s (it runs after this; they match its atoms_adjacency);
+        the bond graph's own are in atoms_bond_graph."""
+        from .critical import bond_graph, critical_points, positions
+        cp = critical_points(self.reference, self.vacuum_tol)
+        self.critical_points = cp
+        self.critical_counts, self.critical_voxels, self.critical_kinds = cp.counts, cp.voxels, cp.kinds
+        self.critical_positions = positions(cp.voxels, cp.shape, self.lattice) + self.voxel_offset
+        g = bond_graph(self.reference, self.atoms_volumes, self.atoms.shape[0], self.vacuum_tol)
+        self.atoms_bond_graph = g
+        self.atoms_bonds, self.atoms_bond_saddles, self.atoms_bond_density = g.pairs, g.saddles, g.rho_b
+        self.atoms_bond_position = positions(g.voxels, g.shape, self.lattice) + self.voxel_offset
+        if hasattr(self, 'bader_volumes'):
+            self.bader_bond_graph = bond_graph(self.reference, self.bader_volumes, self.bader_maxima.shape[0], self.vacuum_tol)
+            self.bader_bonds = self.bader_bond_graph.pairs
+
     voronoi_flag = False   # True: _run ends with voronoi_partition() (no other step changes)
 
     def voronoi_partition(self):
@@ -333,6 +358,8 @@ class Bader:
             self.weight_charges()
         if self.multipole_flag:
             self.multipole_moments()
+        if self.critical_flag:   # (before bond_surfaces, whose atoms_bond_density / atoms_bond_position win when both are set)
+            self.critical_analysis()
         if self.adjacency_flag:
             self.bond_surfaces()
         if self.voronoi_flag:   # (last: it rewrites the device's label map)
