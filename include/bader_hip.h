@@ -417,6 +417,57 @@ int xb_critical_fetch(xb_ctx *c, int64_t *lin, uint16_t *lower_mask, uint8_t *ri
 int xb_critical_bonds(xb_ctx *c, int64_t n, int64_t *n_pairs, int64_t *same_basin);
 int xb_critical_bonds_fetch(xb_ctx *c, int32_t *a, int32_t *b, int64_t *saddles, double *rho_b, int64_t *voxel, int64_t capacity);
 int xb_critical_release(xb_ctx *c);
+/* ---- the Laplacian and the Hessian of the density: as a field, summed per label, and at listed voxels (the sign of the Laplacian
+ * and the ellipticity at a bond point; L(Omega), the integral of the Laplacian over a basin, which vanishes over an exact zero-flux
+ * basin and is the figure of merit AIM codes print next to the charge) -- no counterpart in the reference ----
+ * All three calls read the resident density rho of the whole grid (xb_laplacian_sum the resident labels too); nothing resident is
+ * written.  lattice[9]: the cell, a row per axis.  The stencil is the compact second-order one on 19 points: the voxel, its six
+ * axis neighbours and its twelve edge neighbours, every coordinate wrapped.
+ *   geometry  A[i][j] = lattice[3*i+j] / n_i (the voxel lattice, one row per axis; n_0 n_1 n_2 = nx ny nz);  M = the inverse of A,
+ *             so that dp_i / dr_alpha = M[alpha][i] for the voxel coordinate p and the Cartesian r;  G = M^T M.  In this order:
+ *               C[i][a] = A[i+1][a+1]*A[i+2][a+2] - A[i+1][a+2]*A[i+2][a+1]        (the cofactors; indices mod 3)
+ *               det     = (A[0][0]*C[0][0] + A[0][1]*C[0][1]) + A[0][2]*C[0][2]
+ *               M[a][i] = C[i][a] / det
+ *               G[i][j] = (M[0][i]*M[0][j] + M[1][i]*M[1][j]) + M[2][i]*M[2][j]
+ *   voxel     rho(+i) is the periodic neighbour along axis i, rho(+i+j) the periodic edge neighbour, c = rho(p):
+ *               d_ii = (rho(+i) - c) + (rho(-i) - c)
+ *               d_ij = (rho(+i+j) - rho(+i-j)) - (rho(-i+j) - rho(-i-j))           for ij in 01, 02, 12 (the 1/4 is in the coefficient)
+ *               g_i  = rho(+i) - rho(-i)                                           (the 1/2 is in the coefficient)
+ *   values    every sum left-associated in the term order k = 00, 11, 22, 01, 02, 12:  ((((x_0 + x_1) + x_2) + x_3) + x_4) + x_5
+ *               Laplacian           sum w_k d_k,        w_ii = G[i][i],  w_ij = 0.5 * G[i][j]
+ *               Hessian ab          sum h_ab,k d_k,     h_ab,ii = M[a][i]*M[b][i],  h_ab,ij = 0.25 * (M[a][i]*M[b][j] + M[a][j]*M[b][i]),
+ *                                   ab in xx, xy, xz, yy, yz, zz
+ *               gradient a          ((t_a0*g_0) + t_a1*g_1) + t_a2*g_2,  t_ai = 0.5 * M[a][i]
+ *   coeffs    xb_stencil_coeffs(lattice, nx, ny, nz, out): out[0..8] = t[3*a+i], out[9..14] = w_k, out[15..50] = h[6*ab+k].  Host only,
+ *             needs no GPU.  XB_E_ARG: a null pointer, an axis below 1, a determinant that is exactly 0 or not finite.
+ * The library is built without contraction, so every value above is the same bits wherever it is formed.  Every coefficient takes
+ * part, zero ones included: an orthogonal cell has no definition of its own.  A constant field gives exactly 0.  An axis of one or
+ * two voxels needs no special case: the wrapped neighbours coincide.  Second-order accuracy; a fourth-order stencil and any
+ * smoothing of noisy data are out of scope.
+ *   field     xb_laplacian_field: the Laplacian of every voxel, N doubles in C order, into out_host (host memory) or out_dev (device
+ *             memory of the context's device that does not overlap the resident density) -- exactly one of the two is non-null.  The
+ *             call returns when the result is written.
+ *   sums      xb_laplacian_sum: over the voxels of every label a with 0 <= a < n (labels < 0 and >= n are skipped):  sum[a] = the sum
+ *             of the Laplacian times voxel_volume (L of the basin),  abs_sum[a] = the sum of its magnitude times voxel_volume,
+ *             volume[a] = the voxel count times voxel_volume.  The terms are bit-defined; the order of the sums is free (float
+ *             atomics, as xb_charge_sum).  n <= 256 labels sum in LDS bins per block, more in global memory; waves that hold one
+ *             label add once per wave.
+ *   points    xb_stencil_points: for each of the m linear C-order indices lin[i] ten doubles out[10*i ..]: rho, the gradient x y z,
+ *             the Hessian xx xy xz yy yz zz.  m == 0 writes nothing (lin and out may then be null).
+ * XB_STENCIL_GATHER in `flags` (field and sums) reads the 19 values from global memory, one thread per voxel, instead of staging
+ * 8 x 8 x 32 tiles with their halo in LDS: the second implementation, same bits for the field.
+ * XB_E_STATE: no grid, no density (sums: no labels) on this grid yet, a context that holds a slab;  XB_E_ARG: a null pointer, both or
+ * neither output of the field, unknown flag bits, n < 1, m < 0, an index outside [0, N), a lattice xb_stencil_coeffs refuses, a
+ * device output that is not N doubles of device memory;  XB_E_LIMIT: n above 2^31 - 1.  No option key, no timer slot: a caller
+ * times the calls.  The sums' device buffer (24 n bytes) is kept while the grid stays and counted by xb_memory_stats; the field
+ * for a host output goes through the context's scratch. */
+enum { XB_STENCIL_GATHER = 1 };
+enum { XB_STENCIL_COEFFS = 51, XB_STENCIL_POINT_VALUES = 10 };
+int xb_stencil_coeffs(const double lattice[9], int64_t nx, int64_t ny, int64_t nz, double out[XB_STENCIL_COEFFS]);
+int xb_laplacian_field(xb_ctx *c, const double lattice[9], int flags, double *out_host, void *out_dev);
+int xb_laplacian_sum(xb_ctx *c, const double lattice[9], int64_t n, double voxel_volume, int flags, double *sum, double *abs_sum,
+                     double *volume);
+int xb_stencil_points(xb_ctx *c, const double lattice[9], const int64_t *lin, int64_t m, double *out /* m*10 */);
 /* utils.volume_assign (utils.py:404-421): labels[v] = swap[labels[v]] for labels >= 0 */
 int xb_volume_assign(xb_ctx *c, const int64_t *swap, int64_t n_swap);
 /* utils.atom_assign (utils.py:185-232): nearest atom of every maximum over the 27 periodic images (one

@@ -45,6 +45,11 @@ XB_CRITICAL_FLOOD = 1
  XB_CRITICAL_MINIMA, XB_CRITICAL_COUNTS) = range(7)
 XB_CRITICAL_FULL = 0x3fff
 XB_CRITICAL_LUT_SIZE = 16384
+# xb_laplacian_field / xb_laplacian_sum: the bit of `flags` that reads the 19 values from global memory instead of staging tiles;
+# the doubles xb_stencil_coeffs writes and the doubles per voxel of xb_stencil_points
+XB_STENCIL_GATHER = 1
+XB_STENCIL_COEFFS = 51
+XB_STENCIL_POINT_VALUES = 10
 
 # every symbol include/bader_hip.h declares: (restype, argtypes)
 _vp, _i64, _dbl, _int = C.c_void_p, C.c_int64, C.c_double, C.c_int
@@ -123,6 +128,10 @@ SYMBOLS = {
     'xb_critical_bonds': (_int, [_vp, _i64, _pi64, _pi64]),
     'xb_critical_bonds_fetch': (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64]),
     'xb_critical_release': (_int, [_vp]),
+    'xb_stencil_coeffs': (_int, [_pdbl, _i64, _i64, _i64, _pdbl]),
+    'xb_laplacian_field': (_int, [_vp, _pdbl, _int, _vp, _vp]),
+    'xb_laplacian_sum': (_int, [_vp, _pdbl, _i64, _dbl, _int, _pdbl, _pdbl, _pdbl]),
+    'xb_stencil_points': (_int, [_vp, _pdbl, _vp, _i64, _vp]),
     'xb_volume_assign': (_int, [_vp, _vp, _i64]),
     'xb_atom_assign': (_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp]),
     'xb_surface_distance': (_int, [_vp, _vp, _vp, _i64, _vp, _pi64]),
@@ -880,6 +889,40 @@ class Context:
         fetched results"""
         check(self.lib.xb_critical_release(self.h))
 
+    def laplacian_field(self, lattice, gather=False, on_device=False, out=None):
+        """the Laplacian of the resident density at every voxel (xb_laplacian_field; `lattice` the cell, a row per axis;
+        `gather`: one thread per voxel reading global memory instead of tiles in LDS, the second implementation) -> f64 of the
+        grid's shape: a host array, or with `on_device` a device.DeviceArray (`out`: one to write into instead of a new one)"""
+        lat = _f64(lattice).reshape(9)
+        flags = XB_STENCIL_GATHER if gather else 0
+        if on_device or out is not None:
+            from . import device
+            if out is None:
+                out = device.DeviceArray(self, self.shape or (0,), np.float64)
+            d, _ = self._flat('laplacian_field', out, {np.dtype(np.float64): 64}, True)
+            check(self.lib.xb_laplacian_field(self.h, lat.ctypes.data_as(_pdbl), flags, None, C.c_void_p(d.ptr)))
+            return out
+        out = np.empty(self.shape or (0,), np.float64)
+        check(self.lib.xb_laplacian_field(self.h, lat.ctypes.data_as(_pdbl), flags, _ptr(out), None))
+        return out
+
+    def laplacian_sum(self, lattice, n, voxel_volume, gather=False):
+        """the Laplacian of the resident density summed over the voxels of each resident label 0 .. n - 1 (xb_laplacian_sum) ->
+        (sum f64[n], sum of magnitudes f64[n], volume f64[n]), each multiplied once by voxel_volume"""
+        lat, n = _f64(lattice).reshape(9), int(n)
+        s, m, vo = (np.zeros(max(n, 0), np.float64) for _ in range(3))
+        check(self.lib.xb_laplacian_sum(self.h, lat.ctypes.data_as(_pdbl), n, float(voxel_volume), XB_STENCIL_GATHER if gather else 0,
+                                        s.ctypes.data_as(_pdbl), m.ctypes.data_as(_pdbl), vo.ctypes.data_as(_pdbl)))
+        return s, m, vo
+
+    def stencil_points(self, lattice, lin):
+        """rho, its gradient (x y z) and its Hessian (xx xy xz yy yz zz) of the resident density at the linear C-order voxel
+        indices `lin` (xb_stencil_points) -> f64[m, 10]"""
+        lat, idx = _f64(lattice).reshape(9), np.ascontiguousarray(lin, dtype=np.int64).reshape(-1)
+        out = np.zeros((idx.shape[0], XB_STENCIL_POINT_VALUES), np.float64)
+        check(self.lib.xb_stencil_points(self.h, lat.ctypes.data_as(_pdbl), _ptr(idx), idx.shape[0], _ptr(out)))
+        return out
+
     def volume_assign(self, swap):
         self.drop_label_token()
         sw = np.ascontiguousarray(swap, dtype=np.int64)
@@ -1128,6 +1171,16 @@ def critical_lut():
     out = np.zeros(XB_CRITICAL_LUT_SIZE, np.uint8)
     check(load().xb_critical_lut(_ptr(out)))
     return out
+
+
+def stencil_coeffs(lattice, shape):
+    """xb_stencil_coeffs: the 51 coefficients of the stencil for the cell `lattice` (a row per axis) on a grid of `shape` ->
+    (t f64[3, 3] gradient, w f64[6] Laplacian, h f64[6, 6] Hessian); host only: needs the library, not a GPU"""
+    lat = _f64(lattice).reshape(9)
+    out = np.zeros(XB_STENCIL_COEFFS, np.float64)
+    nx, ny, nz = (int(s) for s in shape)
+    check(load().xb_stencil_coeffs(lat.ctypes.data_as(_pdbl), nx, ny, nz, out.ctypes.data_as(_pdbl)))
+    return out[:9].reshape(3, 3), out[9:15], out[15:].reshape(6, 6)
 
 
 def atom_assign(bader_max_cart, atoms_cart, lattice):

@@ -37,6 +37,7 @@ static void adjacency_free(xb_ctx *c);
 static void merge_free(xb_ctx *c);
 static void voronoi_free(xb_ctx *c);
 static void critical_free(xb_ctx *c);
+static void stencil_free(xb_ctx *c);
 static void free_grid(xb_ctx *c) {
     weight_free(c);
     moments_free(c);
@@ -44,6 +45,7 @@ static void free_grid(xb_ctx *c) {
     merge_free(c);
     voronoi_free(c);
     critical_free(c);
+    stencil_free(c);
     c->have_rho = c->have_labels = false;
     hipFree(c->rho); hipFree(c->grad); hipFree(c->labels); hipFree(c->known); hipFree(c->first); hipFree(c->list);
     hipFree(c->st); hipFree(c->stage); hipFree(c->ec_pend); c->ec_pend = nullptr; hipFree(c->ec_share); c->ec_share = nullptr; hipFree(c->ec_pflag); c->ec_pflag = nullptr; hipFree(c->max_list); hipFree(c->max_aux); hipFree(c->ovf_list);

@@ -299,6 +299,31 @@ class Bader:
             self.bader_bond_graph = bond_graph(self.reference, self.bader_volumes, self.bader_maxima.shape[0], self.vacuum_tol)
             self.bader_bonds = self.bader_bond_graph.pairs
 
+    laplacian_flag = False   # True: _run ends with laplacian_analysis() (no other step changes)
+
+    def laplacian_analysis(self):
+        """The Laplacian of the reference density per basin, and the Hessian at the critical points (pybader_amd.laplacian) -- no
+        counterpart in the reference.  Sets atoms_laplacian [n] (L = the integral of the Laplacian over the atom's basin: zero
+        for an exact zero-flux basin, the figure of merit of the integration) and atoms_laplacian_abs [n] (the integral of its
+        magnitude, the scale L is read against); bader_laplacian and bader_laplacian_abs per Bader volume unless speed_flag
+        dropped the map.  With critical_flag set as well (critical_analysis() runs before this): critical_properties (a
+        laplacian.PointProperties at critical_points.lin), critical_laplacian [P], critical_hessian [P, 3, 3],
+        critical_eigenvalues [P, 3] (ascending), critical_ellipticity [P]; and at the bond points atoms_bond_graph.voxels
+        atoms_bond_laplacian [B] (negative: shared-shell, positive: closed-shell interaction) and atoms_bond_ellipticity [B]."""
+        from .laplacian import basin_laplacian, point_properties
+        self.atoms_laplacian, self.atoms_laplacian_abs, _ = basin_laplacian(
+            self.reference, self.atoms_volumes, self.lattice, self.atoms.shape[0], self.voxel_volume)
+        if hasattr(self, 'bader_volumes'):
+            self.bader_laplacian, self.bader_laplacian_abs, _ = basin_laplacian(
+                self.reference, self.bader_volumes, self.lattice, self.bader_maxima.shape[0], self.voxel_volume)
+        if self.critical_flag:
+            p = point_properties(self.reference, self.lattice, self.critical_points.lin)
+            self.critical_properties = p
+            self.critical_laplacian, self.critical_hessian = p.laplacian, p.hessian
+            self.critical_eigenvalues, self.critical_ellipticity = p.eigenvalues, p.ellipticity
+            b = point_properties(self.reference, self.lattice, self.atoms_bond_graph.voxels)
+            self.atoms_bond_laplacian, self.atoms_bond_ellipticity = b.laplacian, b.ellipticity
+
     voronoi_flag = False   # True: _run ends with voronoi_partition() (no other step changes)
 
     def voronoi_partition(self):
@@ -360,6 +385,8 @@ class Bader:
             self.multipole_moments()
         if self.critical_flag:   # (before bond_surfaces, whose atoms_bond_density / atoms_bond_position win when both are set)
             self.critical_analysis()
+        if self.laplacian_flag:   # (after critical_analysis, whose points it reads when both are set)
+            self.laplacian_analysis()
         if self.adjacency_flag:
             self.bond_surfaces()
         if self.voronoi_flag:   # (last: it rewrites the device's label map)
