@@ -425,6 +425,7 @@ class Context:
         shape = tuple(int(s) for s in shape)
         if shape != getattr(self, 'shape', None):
             self.drop_label_token()     # (another grid: no host array equals the device labels any more)
+            self.resident_density = None    # (nor is any array's content the device density: xb_set_grid drops it with the shape)
         x0, x1 = (0, shape[0]) if x_range is None else x_range
         sh = np.array(shape, dtype=np.int64)
         dm, tg = _f64(dist_mat).reshape(27), _f64(T_grad).reshape(9)

@@ -8,9 +8,9 @@ numpy operations, in the same order, as the reference (they are inputs of every 
 bit-identical)."""
 import numpy as np
 
-from . import device
+from . import _lib, device
 from .thread_handlers import assign_to_atoms, bader_calc, bader_calc_refine, dtype_calc, refine, surface_distance
-from .utils import charge_sum, resident, vacuum_assign
+from .utils import charge_sum, ensure_density, resident, vacuum_assign
 
 
 def distance_matrix(voxel_lattice):
@@ -270,8 +270,14 @@ class Bader:
                 raise RuntimeError('bond_surfaces: set adjacency_flag before bader_calc(), which then keeps the maxima\'s voxels')
             b = adjacency(self.reference, self.bader_volumes, self.lattice, vox.shape[0], self.voxel_offset)
             self.bader_adjacency = b
-            at = device.to_host(self.reference) if device.is_device_array(self.reference) else np.asarray(self.reference)
-            rho_max = np.asarray(at[vox[:, 0], vox[:, 1], vox[:, 2]], dtype=np.float64)
+            if device.is_device_array(self.reference):
+                # (any strides, float32 or float64: read from the resident copy adjacency() has just made or found)
+                ctx = _lib.default_context()
+                ensure_density(ctx, self.reference)
+                rho_max = np.ascontiguousarray(ctx.stencil_points(self.lattice, np.ravel_multi_index(tuple(vox.T), self.grid_shape))[:, 0])
+            else:
+                at = np.asarray(self.reference)
+                rho_max = np.asarray(at[vox[:, 0], vox[:, 1], vox[:, 2]], dtype=np.float64)
             self.bader_persistence = persistence(b.pairs, b.saddle_density, rho_max)
 
     critical_flag = False   # True: _run ends with critical_analysis() (no other step changes)

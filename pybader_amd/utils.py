@@ -22,7 +22,9 @@ def dtype_calc(max_val):
 # holds the array still for a while says so with `resident(density)`: inside that block the array is uploaded
 # once, is read-only (an in-place edit raises instead of being missed) and is recognised by identity (address,
 # shape, strides).  The token lives in the Context, and every route that rewrites the device density (upload,
-# CHGCAR text parse -- also a failed one --, synthetic generator) clears it.
+# CHGCAR text parse -- also a failed one --, synthetic generator) clears it; so does a change of the grid's shape,
+# which drops the device density (a call that reads no density, such as volume_assign on a map of another shape,
+# changes the grid without uploading one).
 def _identity(a):
     return (a.ctypes.data, a.shape, a.strides)
 

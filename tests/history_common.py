@@ -1,0 +1,526 @@
+"""Shared by tests/test_history_cpu.py and tests/test_gpu_history.py: the inputs, the expectation of every public call and the
+comparison of a result with it, for tests that run the calls one after another on one context.
+
+Every expectation comes from what the feature's own test file imports (the oracle, or that file's numpy restatement) and every
+comparison is the one that file makes: `==` (or equal bits) where it compares so, its rounding bound with its arguments elsewhere.
+Nothing is restated a second time and no tolerance is new.  Expectations are memoised on (kind, grid, the inputs the kind reads).
+
+    GRIDS, density(grid, name), labels(grid, name), n_of(grid, name)   the inputs
+    KINDS                                                               call kind -> (reads the density, reads the map)
+    expect(kind, grid, dname, mname)                                    what the call must return
+    check(kind, got, (grid, dname, mname))                              None, or a message naming the kind and the first difference
+    walk(seed, steps)                                                   the seeded step list of test_seeded_walks (pure Python)"""
+import functools
+import math
+import random
+
+import numpy as np
+
+import oracle
+from oracle_context import OracleContext
+from pybader_amd import synth
+from pybader_amd.adjacency import active_directions
+from pybader_amd.interface import distance_matrix, gradient_transform
+from pybader_amd.weight import voronoi_weights
+from rough_common import own_map, rank_labels
+from test_adjacency_cpu import reference_adjacency
+from test_critical_cpu import noise_labels, reference_bonds, reference_points
+from test_gpu_sums import bound as sum_bound_any_order
+from test_gpu_sums import grouped as sum_grouped
+from test_gpu_sums import swapped
+from test_laplacian_cpu import cell_sum_bound, coefficients, restated_laplacian, restated_points
+from test_laplacian_cpu import grouped as lap_grouped
+from test_laplacian_cpu import sum_bound as lap_sum_bound
+from test_merge_cpu import maxima_of, reference_merge
+from test_multipole_cpu import VV, reference_terms
+from test_multipole_cpu import bound as moment_bound
+from test_multipole_cpu import grouped as moment_grouped
+from test_voronoi_cpu import reference_labels
+from test_weight_cpu import restate
+
+# G1: no whole 8^3 bricks, one partial 8 x 8 x 32 tile in z.  G2: two axes below a brick, z one voxel past a tile.  G3: larger
+# than G1 along x, smaller along y and z: G1 -> G2 -> G3 -> G1 makes every buffer kept "while the shape stays" shrink and regrow.
+GRIDS = {'G1': (24, 20, 28), 'G2': (9, 7, 33), 'G3': (40, 12, 16)}
+ORDER = ('G1', 'G2', 'G3')
+LAT = synth.TRICLINIC
+# (frac_x, frac_y, frac_z, sigma, amplitude): three unequal atoms each, at different places
+ATOMS_A = np.array([[0.231, 0.269, 0.247, 0.42, 7.50], [0.773, 0.261, 0.739, 0.45, 5.00], [0.257, 0.743, 0.629, 0.37, 3.25]])
+ATOMS_B = np.array([[0.761, 0.738, 0.271, 0.36, 5.25], [0.243, 0.233, 0.757, 0.49, 8.00], [0.651, 0.247, 0.233, 0.40, 2.75]])
+SITES = {'A': np.ascontiguousarray(ATOMS_A[:, :3] @ LAT), 'B': np.ascontiguousarray(ATOMS_B[:, :3] @ LAT)}   # Cartesian
+SITES8 = synth.atoms_cartesian(synth.ATOMS8, LAT)      # surface_distance: a site for every label any map carries
+NOISE = 0.02            # amplitude of the hash noise on density N (G1): ripples that the merge removes
+VAC_TOL = 0.05          # vacuum tolerance of the calls that take one
+MERGE_TOL = 0.03
+SWAP = np.array([2, 0, 3, 1], np.int64)                 # volume_assign: labels >= 4 and -1 stay
+MASK_LABEL = 1
+N_POINTS = 24
+REFINE_MODE = ('changed', -1)
+
+
+def shape_of(grid):
+    return GRIDS[grid]
+
+
+@functools.lru_cache(maxsize=None)
+def geometry(grid):
+    vl = np.divide(LAT, GRIDS[grid])
+    return distance_matrix(vl), gradient_transform(vl)
+
+
+def voxel_volume(grid):
+    """the cell's volume over the voxel count, formed as weight.weight_sum forms it"""
+    return np.abs(np.dot(LAT[0], np.cross(*LAT[1:]))) / np.prod(GRIDS[grid])
+
+
+@functools.lru_cache(maxsize=None)
+def density(grid, dname):
+    """A, B: synthetic atoms.  N (G1): A + hash noise.  X32: X rounded to float32 (what a float32 device tensor of X holds).
+    Never written: the tests that edit a density in place work on a copy."""
+    if dname.endswith('+'):
+        rho = edited(density(grid, dname[:-1]).copy(), 'density')
+    elif dname.endswith('32'):
+        rho = density(grid, dname[:-2]).astype(np.float32).astype(np.float64)
+    elif dname == 'N':
+        rho = density(grid, 'A') + NOISE * synth.hash_noise(GRIDS[grid], 9)
+    else:
+        rho = synth.synth_density(GRIDS[grid], LAT, {'A': ATOMS_A, 'B': ATOMS_B}[dname])
+    rho = np.ascontiguousarray(rho)
+    rho.flags.writeable = False
+    return rho
+
+
+def densities(grid):
+    return ('A', 'B', 'N') if grid == 'G1' else ('A', 'B')
+
+
+@functools.lru_cache(maxsize=None)
+def bader(grid, dname):
+    """the library-independent Bader partition of a density, as tests/soak_vs_oracle.py builds it: the own-trajectory map ranked
+    by first voxel, then the oracle's refinement of it"""
+    rho, (dm, tg) = density(grid, dname), geometry(grid)
+    shape = rho.shape
+    vol0 = np.zeros(shape, np.int32)
+    lab, maxima = rank_labels(own_map(rho, vol0, dm, tg, main_ties=True))
+    v, log = lab.astype(np.int32).copy(), []
+    oracle.refine('neargrid', REFINE_MODE, rho, v, dm, tg, 1, log=log)
+    vox = np.stack(np.unravel_index(maxima, shape), axis=1).astype(np.int64).reshape(-1, 3)
+    out = {'assign': lab.astype(np.int32), 'maxima': maxima, 'voxels': vox, 'refined': v, 'log': [tuple(int(x) for x in r) for r in log]}
+    for a in out.values():
+        if isinstance(a, np.ndarray):
+            a.flags.writeable = False
+    return out
+
+
+def maxima_cart(grid, dname='A'):
+    return np.dot(np.ascontiguousarray(np.divide(bader(grid, dname)['voxels'].astype(np.float64), GRIDS[grid])), LAT)
+
+
+def maps(grid):
+    return ('bader', 'atoms', 'noise', 'baderN') if grid == 'G1' else ('bader', 'atoms', 'noise')
+
+
+@functools.lru_cache(maxsize=None)
+def labels(grid, mname):
+    """bader: the refined Bader map of A.  atoms: its atom map.  noise: test_critical_cpu.noise_labels (labels -1 and >= n).
+    baderN (G1): the refined Bader map of the noisy density.  int32, never written."""
+    if mname.endswith('+'):
+        lab = edited(labels(grid, mname[:-1]).copy(), 'labels')
+    elif mname == 'bader':
+        lab = bader(grid, 'A')['refined']
+    elif mname == 'baderN':
+        lab = bader(grid, 'N')['refined']
+    elif mname == 'atoms':
+        ba, _ = oracle.atom_assign(maxima_cart(grid), SITES['A'], LAT)
+        lab = swapped(bader(grid, 'A')['refined'], ba)
+    else:
+        lab = noise_labels(GRIDS[grid])
+    lab = np.ascontiguousarray(lab, dtype=np.int32)
+    lab.flags.writeable = False
+    return lab
+
+
+def n_of(grid, mname):
+    """the number of labels a call on this map is told"""
+    mname = mname.rstrip('+')
+    if mname == 'noise':
+        return 5
+    if mname == 'atoms':
+        return 3
+    return int(bader(grid, 'N' if mname == 'baderN' else 'A')['maxima'].shape[0])
+
+
+def centres(grid, mname):
+    """moment_sum: a Cartesian centre per label"""
+    mname = mname.rstrip('+')
+    n = n_of(grid, mname)
+    if mname in ('bader', 'baderN'):
+        return maxima_cart(grid, 'N' if mname == 'baderN' else 'A')
+    return np.ascontiguousarray(np.resize(SITES8, (n, 3)))
+
+
+@functools.lru_cache(maxsize=None)
+def vacuum_map(grid, dname):
+    vol, _, _ = oracle.vacuum_assign(density(grid, dname), np.zeros(GRIDS[grid], np.int32), VAC_TOL, density(grid, dname), 1.0)
+    vol.flags.writeable = False
+    return vol
+
+
+def other(dname):
+    """the second field of the calls that take two: another density of the same grid"""
+    return 'B32' if dname == 'A32' else {'A': 'B', 'B': 'A', 'N': 'B'}.get(dname.rstrip('+'), 'A')
+
+
+@functools.lru_cache(maxsize=None)
+def alpha(grid):
+    return voronoi_weights(LAT / np.array(GRIDS[grid], dtype=np.float64)[:, None])
+
+
+@functools.lru_cache(maxsize=None)
+def directions(grid):
+    return active_directions(LAT / np.array(GRIDS[grid], dtype=np.float64)[:, None])[0]
+
+
+@functools.lru_cache(maxsize=None)
+def point_list(grid):
+    """point_properties: the corners of the grid and hashed voxels (repeats allowed)"""
+    n = int(np.prod(GRIDS[grid]))
+    return np.concatenate([[0, n - 1], np.floor(synth.hash_noise((N_POINTS - 2,), 17) * n).astype(np.int64)]).astype(np.int64)
+
+
+def cache_facet_areas(monkeypatch):
+    """weight.voronoi_areas is a pure host function of the voxel lattice that takes 0.2 s of Python; weight_sum, adjacency and
+    merge_basins each call it once per call.  For the duration of a test it is computed once per lattice (a copy per call, as
+    the function itself returns a fresh array): the calls under test and what they read on the device are untouched."""
+    from pybader_amd import adjacency, weight
+    plain, seen = weight.voronoi_areas, {}
+
+    def cached(voxel_lattice, who='voronoi_areas'):
+        key = (np.asarray(voxel_lattice, dtype=np.float64).tobytes(), who)
+        if key not in seen:
+            seen[key] = plain(voxel_lattice, who)
+        return seen[key].copy()
+    monkeypatch.setattr(weight, 'voronoi_areas', cached)
+    monkeypatch.setattr(adjacency, 'voronoi_areas', cached)
+
+
+# ---- the call kinds: name -> (reads the density, reads the map) --------------------------------------------------------------
+KINDS = {
+    'vacuum_assign': (True, False), 'bader_calc': (True, False), 'refine': (True, False), 'bader_calc_refine': (True, False),
+    'assign_to_atoms': (False, True), 'surface_distance': (False, True), 'charge_sum': (True, True), 'volume_mask': (True, True),
+    'volume_assign': (False, True),
+    'weight_own': (True, False), 'weight_other': (True, False), 'weight_vacuum': (True, False),
+    'moment_sum': (True, True), 'adjacency': (True, True), 'merge': (True, True),
+    'voronoi': (True, False), 'voronoi_full': (True, False), 'voronoi_vacuum': (True, False), 'voronoi_full_vacuum': (True, False),
+    'critical': (True, False), 'critical_flood': (True, False), 'critical_vacuum': (True, False), 'critical_flood_vacuum': (True, False),
+    'bond_graph': (True, True),
+    'laplacian': (True, False), 'laplacian_gather': (True, False), 'basin_laplacian': (True, True), 'point_properties': (True, False),
+}
+# surface_distance takes the density and its result does not depend on it (the edge voxels are the map's).
+# voronoi_assign without a tolerance reads no density: its second input is the atom set, which goes with the density's name
+LABEL_WRITERS = ('voronoi', 'voronoi_full', 'voronoi_vacuum', 'voronoi_full_vacuum', 'volume_assign')
+
+
+def sites_of(dname):
+    return SITES['B' if dname.startswith('B') else 'A']
+
+
+def map_for(kind, mname):
+    """the map a call of this kind gets when the step names `mname`: surface_distance indexes its eight sites by label, so the
+    noisy density's Bader map (hundreds of labels) is replaced by the atom map there"""
+    return 'atoms' + '+' * mname.endswith('+') if kind == 'surface_distance' and mname.startswith('baderN') else mname
+
+
+def maxima_for(grid, mname):
+    """assign_to_atoms: the Cartesian maxima that go with the map (the noisy density's for its own Bader map)"""
+    return maxima_cart(grid, 'N' if mname.startswith('baderN') else 'A')
+
+
+def _key(kind, grid, dname, mname):
+    reads_d, reads_m = KINDS[kind]
+    mname = map_for(kind, mname)
+    if kind in ('voronoi', 'voronoi_full'):
+        dname = 'B' if dname.startswith('B') else 'A'
+    return kind, grid, dname if reads_d else None, mname if reads_m else None
+
+
+def expect(kind, grid, dname, mname):
+    return _expect(*_key(kind, grid, dname, mname))
+
+
+@functools.lru_cache(maxsize=None)
+def _laplacian(grid, dname):
+    lap = restated_laplacian(density(grid, dname), LAT)
+    lap.flags.writeable = False
+    return lap
+
+
+@functools.lru_cache(maxsize=None)
+def _expect(kind, grid, dname, mname):
+    shape = GRIDS[grid]
+    rho = density(grid, dname) if dname is not None else None
+    lab = labels(grid, mname) if mname is not None else None
+    n = n_of(grid, mname) if mname is not None else None
+    if kind == 'vacuum_assign':
+        vol = vacuum_map(grid, dname)
+        x = rho[vol == -1]
+        return vol, math.fsum(x), int(x.size), math.fsum(np.abs(x))
+    if kind == 'bader_calc':
+        b = bader(grid, dname)
+        return b['voxels'], b['assign']
+    if kind == 'refine':
+        b = bader(grid, dname)
+        return b['refined'], b['log']
+    if kind == 'bader_calc_refine':
+        b = bader(grid, dname)
+        return b['voxels'], b['refined'], b['log']
+    if kind == 'assign_to_atoms':
+        ba, bd = oracle.atom_assign(maxima_for(grid, mname), SITES['A'], LAT)
+        return ba, bd, swapped(lab, ba)
+    if kind == 'surface_distance':
+        ref = OracleContext()
+        ref.set_grid(shape, *geometry(grid))
+        ref.upload_density(density(grid, 'A'))
+        ref.upload_labels(lab)
+        return ref.surface_distance(LAT, SITES8)
+    if kind == 'charge_sum':
+        return sum_grouped(rho, lab, n)
+    if kind == 'volume_mask':
+        return (np.where(lab == MASK_LABEL, rho, 0.0),)
+    if kind == 'volume_assign':
+        return (swapped(lab, SWAP),)
+    if kind.startswith('weight_'):
+        q = rho if kind != 'weight_other' else density(grid, other(dname))
+        m, A, V, _ = restate(rho, q, alpha(grid), vacuum_map(grid, dname) if kind == 'weight_vacuum' else None)
+        return np.stack(np.unravel_index(m, shape), axis=1).astype(np.int64).reshape(-1, 3), A, V
+    if kind == 'moment_sum':
+        terms, _, label = reference_terms(rho, lab, LAT, centres(grid, mname))
+        return moment_grouped(terms, label, n)
+    if kind == 'adjacency':
+        return reference_adjacency(rho, lab, n, directions(grid))
+    if kind == 'merge':
+        idx = maxima_of(rho, lab, n)
+        want = reference_merge(rho, lab, n, directions(grid), idx, MERGE_TOL, 64)
+        survivors = np.flatnonzero(want['merge_round'] < 0)
+        return want, swapped(lab, np.searchsorted(survivors, want['root']))
+    if kind.startswith('voronoi'):
+        want = reference_labels(shape, LAT, sites_of(dname))
+        return (np.where(rho <= VAC_TOL, -1, want) if kind.endswith('vacuum') else want,)
+    if kind.startswith('critical'):
+        return reference_points(rho, VAC_TOL if kind.endswith('vacuum') else None)
+    if kind == 'bond_graph':
+        return reference_bonds(rho, lab, n)
+    if kind in ('laplacian', 'laplacian_gather'):
+        return (_laplacian(grid, dname),)
+    if kind == 'basin_laplacian':
+        return lap_grouped(_laplacian(grid, dname), lab, n)
+    if kind == 'point_properties':
+        lin = point_list(grid)
+        return restated_points(rho, LAT, lin), _laplacian(grid, dname).reshape(-1)[lin]
+    raise KeyError(kind)
+
+
+# ---- comparison ------------------------------------------------------------------------------------------------------------------
+def _first(name, got, want, bits=False):
+    """None when the two arrays are equal (in bits for floats when asked), else where they first differ"""
+    got, want = np.asarray(got), np.asarray(want)
+    if got.shape != want.shape:
+        return f'{name}: shape {got.shape}, expected {want.shape}'
+    if bits:
+        got, want = np.ascontiguousarray(got, np.float64).view(np.uint64), np.ascontiguousarray(want, np.float64).view(np.uint64)
+    diff = got != want
+    if not diff.any():
+        return None
+    at = tuple(int(i) for i in np.argwhere(diff)[0]) if diff.ndim else ()
+    g, w = np.asarray(got)[at], np.asarray(want)[at]
+    return f'{name}: {int(diff.sum())} of {diff.size} differ, first at {list(at)}: got {g!r}, expected {w!r}'
+
+
+def _within(name, got, want, lim):
+    got, want, lim = np.asarray(got, np.float64), np.asarray(want, np.float64), np.asarray(lim, np.float64)
+    if got.shape != want.shape:
+        return f'{name}: shape {got.shape}, expected {want.shape}'
+    err = np.abs(got - want)
+    bad = ~(err <= lim)
+    if not bad.any():
+        return None
+    at = tuple(int(i) for i in np.argwhere(bad)[0])
+    return f'{name}: {int(bad.sum())} of {bad.size} beyond the bound, first at {list(at)}: got {got[at]!r}, expected {want[at]!r}, bound {np.broadcast_to(lim, err.shape)[at]:.3e}'
+
+
+def _compare(kind, got, want, grid, dname, mname):
+    """-> the first complaint, or None.  Each branch compares as the feature's own GPU test does."""
+    if kind == 'vacuum_assign':                                   # test_gpu_sums.test_vacuum_assign
+        vol, charge, volume = got
+        wmap, s, cnt, mag = want
+        return (_first('map', vol, wmap) or _first('volume', volume, float(cnt) * VV)
+                or _within('charge', [charge], [s * VV], sum_bound_any_order(cnt, mag, VV)))
+    if kind == 'bader_calc':                                      # soak_vs_oracle: ==
+        return _first('maxima', got[0], want[0]) or _first('map', got[1], want[1])
+    if kind == 'refine':
+        return _first('map', got[0], want[0]) or (None if list(got[1]) == list(want[1]) else f'log: got {got[1]}, expected {want[1]}')
+    if kind == 'bader_calc_refine':
+        return (_first('maxima', got[0], want[0]) or _first('map', got[1], want[1])
+                or (None if list(got[2]) == list(want[2]) else f'log: got {got[2]}, expected {want[2]}'))
+    if kind == 'assign_to_atoms':                                 # test_gpu_parity: atom_assign ==, the swapped map ==
+        return _first('bader_atoms', got[0], want[0]) or _first('bader_distance', got[1], want[1]) or _first('map', got[2], want[2])
+    if kind == 'surface_distance':                                # test_gpu_sums.test_surface_distance, on the squared distances
+        d2, edges = want
+        if got is None:
+            return None if edges == 0 else f'no edges found, expected {edges}'
+        fin = np.isfinite(d2)
+        g2 = np.asarray(got) ** 2
+        msg = _first('atoms without an edge voxel', got[~fin], np.zeros(int((~fin).sum())))
+        return msg or _within('squared distance', g2[fin], d2[fin], 1e-12 * np.abs(d2[fin]) + 1e-12 * np.abs(LAT).max() ** 2)
+    if kind == 'charge_sum':                                      # test_gpu_sums.test_charge_sum
+        s, cnt, mag = want
+        return (_first('volume', got[1], cnt.astype(np.float64) * VV)
+                or _within('charge', got[0], s * VV, sum_bound_any_order(cnt, mag, VV))
+                or _first('labels nobody carries', got[0][cnt == 0], np.zeros(int((cnt == 0).sum()))))
+    if kind in ('volume_mask', 'laplacian', 'laplacian_gather'):  # equal bits
+        return _first('field', got[0], want[0], bits=True)
+    if kind == 'volume_assign' or kind.startswith('voronoi'):
+        return _first('map', got[0], want[0])
+    if kind.startswith('weight_'):                                # test_gpu_weight.same
+        vv = voxel_volume(grid)
+        return _first('maxima', got[0], want[0]) or _first('charge', got[1], want[1] * vv, True) or _first('volume', got[2], want[2] * vv, True)
+    if kind == 'moment_sum':                                      # test_gpu_multipole.check
+        s, cnt, mag = want
+        return (_first('volume', got[1], cnt.astype(np.float64) * VV) or _within('moments', got[0], s * VV, moment_bound(cnt, mag, VV))
+                or _first('labels nobody carries', got[0][cnt == 0], np.zeros((int((cnt == 0).sum()), 10))))
+    if kind == 'adjacency':                                       # test_adjacency_cpu.same
+        return (_first('pairs', got[0], want[0]) or _first('facets', got[1], want[1]) or _first('saddle', got[2], want[2], True)
+                or _first('saddle facet', got[3], want[3]))
+    if kind == 'merge':                                           # test_gpu_merge.same, and the applied map
+        w, wmap = want
+        root, rnd, pers, rounds, converged, applied = got
+        return (_first('root', root, w['root']) or _first('merge_round', rnd, w['merge_round'])
+                or _first('merge_persistence', pers, w['merge_persistence'], True)
+                or _first('rounds, converged', [rounds, int(converged)], [w['rounds'], int(w['converged'])])
+                or _first('applied map', applied, wmap))
+    if kind.startswith('critical'):                               # test_gpu_critical.same_points
+        for name, g, w in zip(('counts', 'lin', 'masks', 'ring', 'bond'), got, want):
+            msg = _first(name, g, w)
+            if msg:
+                return msg
+        return None
+    if kind == 'bond_graph':                                      # test_gpu_critical.same_bonds
+        return (_first('pairs', got[0], want[0]) or _first('saddles', got[1], want[1]) or _first('rho_b', got[2], want[2], True)
+                or _first('voxel', got[3], want[3]) or _first('same_basin', [got[4]], [want[4]]))
+    if kind == 'basin_laplacian':                                 # test_gpu_laplacian.check_sums; the cell's zero where no voxel is left out
+        s, cnt, mag = want
+        lim = lap_sum_bound(cnt, mag)
+        msg = (_first('volume', got[2], cnt.astype(np.float64) * VV) or _within('L', got[0], s * VV, lim)
+               or _within('L_abs', got[1], mag * VV, lim))
+        if msg is None and int(cnt.sum()) == int(np.prod(GRIDS[grid])):
+            _, w6, _ = coefficients(LAT, GRIDS[grid])
+            msg = _within('L summed over the cell', [np.sum(got[0])], [0.0], cell_sum_bound(density(grid, dname), w6) * VV)
+        return msg
+    if kind == 'point_properties':                                # test_gpu_laplacian: equal bits
+        return _first('the ten values', got[0], want[0], True) or _first('laplacian', got[1], want[1], True)
+    raise KeyError(kind)
+
+
+def check(kind, got, inputs):
+    """inputs = (grid, density name, map name).  -> None, or a message that names the kind and the first differing element"""
+    grid, dname, mname = inputs
+    msg = _compare(kind, got, expect(kind, grid, dname, mname), grid, dname, mname)
+    return None if msg is None else f'{kind} on {grid} density {dname} map {mname}: {msg}'
+
+
+def as_result(kind, want, grid):
+    """an expectation in the form of the call's result: what check() reports on when handed another input's expectation"""
+    if kind == 'vacuum_assign':
+        return want[0], want[1] * VV, float(want[2]) * VV
+    if kind == 'surface_distance':
+        d2, edges = want
+        out = np.zeros(d2.shape[0])
+        out[np.isfinite(d2)] = d2[np.isfinite(d2)] ** .5
+        return None if edges == 0 else out
+    if kind == 'charge_sum':
+        return want[0] * VV, want[1].astype(np.float64) * VV
+    if kind.startswith('weight_'):
+        return want[0], want[1] * voxel_volume(grid), want[2] * voxel_volume(grid)
+    if kind == 'moment_sum':
+        return want[0] * VV, want[1].astype(np.float64) * VV
+    if kind == 'merge':
+        w, wmap = want
+        return w['root'], w['merge_round'], w['merge_persistence'], w['rounds'], w['converged'], wmap
+    if kind == 'basin_laplacian':
+        return want[0] * VV, want[2] * VV, want[1].astype(np.float64) * VV
+    return want
+
+
+# ---- the seeded walks ------------------------------------------------------------------------------------------------------------
+EVENTS = ('shape', 'resident', 'mutate', 'fail')
+FAILURES = ('density of another shape', 'label map of another shape', 'n < 1', 'non-float device dtype')
+
+
+def walk(seed, steps=80):
+    """-> a list of steps, each a dict with 'op':
+
+        call      kind, grid, dname, mname: one checked call
+        enter / leave   dname: utils.resident() of that density of the current grid
+        grid      grid: the next calls run there (in the order G1 -> G2 -> G3 -> G1, and by direct jumps), also inside resident()
+        mutate    what ('density' | 'labels'), kind, dname, mname: outside resident(), the same host object goes into two calls
+                  of `kind` with an in-place edit between them; both are checked
+        fail      how (one of FAILURES), then kind, dname, mname of the checked call that follows the refused one
+
+    Pure Python on the seed: the same list on every machine.  Every step is executable as it stands: no test leaves one out."""
+    rng = random.Random(seed)
+    kinds = list(KINDS)
+    grid, inside, out = 'G1', None, []
+    # the kinds whose result shows an edit of a corner block on every input (tests/test_history_cpu.py asserts it for the steps
+    # drawn): the block lies in the tails, where the sparse results -- surfaces, saddles, bond points -- need not pass
+    reads_d = [k for k in kinds if KINDS[k][0] and k not in ('voronoi', 'voronoi_full', 'adjacency', 'merge', 'critical_vacuum',
+                                                             'critical_flood_vacuum')]
+    reads_m = [k for k in kinds if KINDS[k][1] and k not in ('surface_distance', 'merge', 'bond_graph')]
+    queue = []
+    while len(out) < steps:
+        r = rng.random()
+        if not queue:
+            queue = kinds[:]
+            rng.shuffle(queue)
+        pick = lambda: (rng.choice(densities(grid)), rng.choice(maps(grid)))
+        if r < 0.64:
+            d, m = pick()
+            out.append({'op': 'call', 'kind': queue.pop(), 'grid': grid, 'dname': d, 'mname': m})
+        elif r < 0.72:
+            if inside is None:
+                inside = rng.choice(('A', 'B'))
+                out.append({'op': 'enter', 'grid': grid, 'dname': inside})
+            else:
+                out.append({'op': 'leave', 'grid': grid, 'dname': inside})
+                inside = None
+        elif r < 0.82:        # (also inside resident(): the pinned array then belongs to another grid until the walk returns)
+            if rng.random() < 0.6:
+                grid = ORDER[(ORDER.index(grid) + 1) % 3]
+            else:
+                grid = rng.choice([g for g in ORDER if g != grid])
+            out.append({'op': 'grid', 'grid': grid})
+        elif r < 0.91:
+            if inside is not None:
+                out.append({'op': 'leave', 'grid': grid, 'dname': inside})
+                inside = None
+            what = rng.choice(('density', 'labels'))
+            d, m = pick()
+            out.append({'op': 'mutate', 'what': what, 'kind': rng.choice(reads_d if what == 'density' else reads_m),
+                        'grid': grid, 'dname': d, 'mname': m})
+        else:
+            d, m = pick()
+            out.append({'op': 'fail', 'how': rng.choice(FAILURES), 'kind': queue.pop(), 'grid': grid, 'dname': d, 'mname': m})
+    if inside is not None:
+        out.append({'op': 'leave', 'grid': grid, 'dname': inside})
+    return out
+
+
+SEEDS = (11, 23, 47)
+
+
+def edited(a, what):
+    """the in-place edit of a walk's 'mutate' step, on a writable copy the test owns: a constant added to a corner block of a
+    density, a corner block of a label map relabelled"""
+    if what == 'density':
+        a[:4, :3, :5] += 0.75
+    else:
+        a[:4, :3, :5] = 1
+    return a

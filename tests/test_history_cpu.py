@@ -1,0 +1,120 @@
+"""The check of the check for tests/test_gpu_history.py (no GPU): the inputs of tests/history_common.py tell a stale upload from a
+fresh one for every call kind, the seeded walks reach every kind and every event, no generated step is left out, and the
+oracle-built maps are converged."""
+import collections
+
+import numpy as np
+import pytest
+
+import history_common as H
+import oracle
+
+
+@pytest.mark.parametrize('grid', list(H.GRIDS))
+def test_every_kind_tells_the_two_inputs_apart(grid):
+    """the expectation for (B, atoms) handed to check() as the result of the call on (A, bader) is reported, for every kind: a
+    call that read the density or the map of the call before it cannot pass.  The kinds that read only one of the two are told
+    apart by that one alone, so the same holds for each input singly where the kind reads it."""
+    for kind, (reads_d, reads_m) in H.KINDS.items():
+        mine = ('A', 'bader')
+        assert H.check(kind, H.as_result(kind, H.expect(kind, grid, *mine), grid), (grid,) + mine) is None, kind
+        others = [('B', 'atoms')] + ([('B', 'bader')] if reads_d else []) + ([('A', 'atoms'), ('A', 'noise')] if reads_m else [])
+        for other in others:
+            msg = H.check(kind, H.as_result(kind, H.expect(kind, grid, *other), grid), (grid,) + mine)
+            assert msg is not None and msg.startswith(f'{kind} on {grid} density A map bader: '), (kind, other, msg)
+
+
+def test_the_float32_density_is_told_from_the_float64_one():
+    """setting 4 of the pair matrix computes its expectations from A32.astype(float64): they differ from A's wherever the kind
+    returns a float, so a device import that is not the tensor's content cannot pass"""
+    for kind in ('charge_sum', 'volume_mask', 'weight_own', 'moment_sum', 'laplacian', 'basin_laplacian', 'point_properties'):
+        got = H.as_result(kind, H.expect(kind, 'G1', 'A32', 'bader'), 'G1')
+        assert H.check(kind, got, ('G1', 'A', 'bader')) is not None, kind
+
+
+def test_the_walks_reach_every_kind_and_every_event_and_leave_no_step_out():
+    calls, events, total, runnable = collections.Counter(), collections.Counter(), 0, 0
+    for seed in H.SEEDS:
+        steps = H.walk(seed)
+        assert steps == H.walk(seed), 'the walk is a function of its seed'
+        assert 75 <= len(steps) <= 90, len(steps)
+        grid, inside = 'G1', False
+        for s in steps:
+            total += 1
+            op = s['op']
+            assert op in ('call', 'enter', 'leave', 'grid', 'mutate', 'fail'), op
+            if op == 'grid':
+                assert s['grid'] in H.GRIDS and s['grid'] != grid
+                grid = s['grid']
+                events['shape'] += 1
+            else:
+                assert s['grid'] == grid
+            if op in ('call', 'mutate', 'fail'):
+                assert s['kind'] in H.KINDS and s['dname'] in H.densities(grid) and s['mname'] in H.maps(grid), s
+                calls[s['kind']] += 2 if op == 'mutate' else 1
+            if op == 'enter':
+                assert not inside and s['dname'] in ('A', 'B')
+                inside = True
+                events['resident'] += 1
+            if op == 'leave':
+                assert inside
+                inside = False
+            if op == 'mutate':
+                assert not inside, 'an in-place edit belongs outside resident()'
+                reads_d, reads_m = H.KINDS[s['kind']]
+                assert reads_d if s['what'] == 'density' else reads_m
+                events['mutate'] += 1
+            if op == 'fail':
+                assert s['how'] in H.FAILURES
+                events['fail'] += 1
+            runnable += 1                       # (nothing above let a step through without a branch that runs it)
+        assert not inside, 'every walk leaves resident() at its end'
+    assert set(calls) == set(H.KINDS) and min(calls.values()) >= 5, sorted(calls.items(), key=lambda kv: kv[1])[:5]
+    assert set(events) == set(H.EVENTS) and min(events.values()) >= 3, events
+    assert (total - runnable) / total == 0.0
+
+
+def test_the_edits_of_the_walks_show_in_the_expectation():
+    """every 'mutate' step: the expectation after the edit, taken for the result before it, is reported"""
+    seen = 0
+    for seed in H.SEEDS:
+        for s in H.walk(seed):
+            if s['op'] != 'mutate':
+                continue
+            kind, grid, d, m = s['kind'], s['grid'], s['dname'], H.map_for(s['kind'], s['mname'])
+            d2, m2 = (d + '+', m) if s['what'] == 'density' else (d, m + '+')
+            after = H.as_result(kind, H.expect(kind, grid, d2, m2), grid)
+            assert H.check(kind, after, (grid, d2, m2)) is None, s
+            assert H.check(kind, after, (grid, d, m)) is not None, s
+            seen += 1
+    assert seen >= 3
+
+
+def test_the_oracle_built_maps_are_converged():
+    """one more refinement of each Bader map changes nothing: the parity of the README applies to them"""
+    for grid in H.GRIDS:
+        for dname in H.densities(grid):
+            b = H.bader(grid, dname)
+            v, log = b['refined'].copy(), []
+            oracle.refine('neargrid', H.REFINE_MODE, H.density(grid, dname), v, *H.geometry(grid), 1, log=log)
+            assert np.array_equal(v, b['refined']) and all(changed == 0 for _, changed in log), (grid, dname, log)
+            assert b['log'] == [] or b['log'][-1][1] == 0, (grid, dname, b['log'])
+
+
+def test_the_inputs_are_what_the_issue_asks_for():
+    assert any(s % 8 for s in H.GRIDS['G1']) and H.GRIDS['G1'][2] < 32
+    assert H.GRIDS['G2'][0] < 10 and H.GRIDS['G2'][1] < 8 and H.GRIDS['G2'][2] == 33
+    g1, g3 = H.GRIDS['G1'], H.GRIDS['G3']
+    assert g3[0] > g1[0] and g3[1] < g1[1] and g3[2] < g1[2]
+    assert len({int(np.prod(s)) for s in H.GRIDS.values()}) == 3
+    for grid in H.GRIDS:
+        noise = H.labels(grid, 'noise')
+        assert noise.min() == -1 and noise.max() >= H.n_of(grid, 'noise')
+        for m in H.maps(grid):
+            if m != 'baderN':
+                assert H.labels(grid, m).max() < len(H.SITES8)      # surface_distance indexes its sites by label
+        vac = H.vacuum_map(grid, 'A') == -1
+        assert 0 < vac.sum() < vac.size
+    # the merge has something to merge on the noisy density, and does not merge everything
+    want, _ = H.expect('merge', 'G1', 'N', 'baderN')
+    assert 1 < want['n_survivors'] < H.n_of('G1', 'baderN') and want['converged']
