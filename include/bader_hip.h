@@ -468,6 +468,73 @@ int xb_laplacian_field(xb_ctx *c, const double lattice[9], int flags, double *ou
 int xb_laplacian_sum(xb_ctx *c, const double lattice[9], int64_t n, double voxel_volume, int flags, double *sum, double *abs_sum,
                      double *volume);
 int xb_stencil_points(xb_ctx *c, const double lattice[9], const int64_t *lin, int64_t m, double *out /* m*10 */);
+/* ---- Hirshfeld (stockholder) charges from radial pro-atom tables, the promolecular density and the deformation density (the charge
+ * Critic2, Chargemol and Multiwfn print beside the Bader one: every voxel's density is shared among the atoms in proportion to what
+ * each FREE atom would put there, w_a(r) = rho0_a(|r - R_a|) / sum_b rho0_b(|r - R_b|): no surfaces, no maxima, no sensitivity to
+ * noise) -- no counterpart in the reference ----
+ * xb_hirshfeld_setup puts the cell, the atoms and the pro-atoms on the device; xb_hirshfeld_sum and xb_hirshfeld_field read the
+ * resident density of the whole grid and write nothing resident: not the density, not the labels, which they do not need at all.
+ * All of it is IEEE float64 without contraction: every value at a voxel is bit-defined.
+ *   pro-atoms S species; species s has a cutoff r_cut[s] > 0 and a table f[s][0..K] of K + 1 finite, non-negative doubles, K >= 1 the
+ *             same for all (tables[s * (K + 1) + k]).  f[s][k] is the free-atom density at r^2 = k * r_cut[s]^2 / K: the table is
+ *             uniform in r^2, so no square root enters a bit-defined value.  f[s][K] must be exactly 0: the interpolant reaches zero
+ *             continuously at the cutoff, and dropping an image beyond the cutoff drops an exact zero.  The host computes
+ *             rc2[s] = r_cut[s]*r_cut[s] and inv_h2[s] = K / rc2[s] once; these doubles are what the kernel uses.
+ *   position  of voxel (p0, p1, p2), as xb_voronoi_assign's:  pc[j] = lat[j]*p0/nx;  pc[j] += lat[3+j]*p1/ny;  pc[j] += lat[6+j]*p2/nz
+ *   image     (a, x, y, z) of atom a:  q[j] = atom[a][j] + ((lat[j]*x + lat[3+j]*y) + lat[6+j]*z);
+ *             e[j] = pc[j] - q[j],  d2 = (e0*e0 + e1*e1) + e2*e2
+ *   term      for an image of atom a with species s:  term = 0 when d2 >= rc2[s];  otherwise u = d2*inv_h2[s],
+ *             k = min((int)u, K - 1),  t = u - k,  term = f[s][k] + t*(f[s][k+1] - f[s][k])
+ *   list      the images (a, x, y, z) in CANONICAL ORDER: a ascending, then x, y, z ascending.  Per atom and axis i the shifts run over
+ *             lo_i .. hi_i, which covers every image with any voxel of the cell closer than r_cut[species[a]].  With M the inverse
+ *             of the lattice by cofactors, as xb_stencil_coeffs forms it with A = the lattice itself
+ *               C[i][b] = A[i+1][b+1]*A[i+2][b+2] - A[i+1][b+2]*A[i+2][b+1],  det = (A[0][0]*C[0][0] + A[0][1]*C[0][1]) + A[0][2]*C[0][2],
+ *               M[b][i] = C[i][b] / det                                         (indices mod 3)
+ *             the atom's fractional coordinate, the reciprocal of the cell's height h_i = |det| / |a_j x a_k|, and the range are
+ *               f_i  = (atom[a][0]*M[0][i] + atom[a][1]*M[1][i]) + atom[a][2]*M[2][i]
+ *               g_i  = sqrt((M[0][i]*M[0][i] + M[1][i]*M[1][i]) + M[2][i]*M[2][i])            (= 1 / h_i)
+ *               rho_i = r_cut[s]*g_i,   m_i = 2^-20 * ((1 + |f_i|) + rho_i)                    (the margin for the rounding of f and rho)
+ *               lo_i = floor((-rho_i - f_i) - m_i),   hi_i = ceil(((1 + rho_i) - f_i) + m_i)
+ *             Atoms are taken as given, not wrapped: an atom outside the cell only shifts its range.  A wider range adds zero terms
+ *             only -- every term is >= +0 and x + 0.0 == x -- so NO RESULT DEPENDS ON THE RANGE.
+ *   voxel     P(v) = the left-to-right running sum of all terms in list order;  p_a(v) = the same sum over atom a's images only,
+ *             started from 0;  w_a = p_a / P,  term_a = rho(v) * w_a.  A voxel with P == 0 belongs to nobody.
+ *   results   charge[a] = voxel_volume * sum_v term_a;  volume[a] = voxel_volume * sum_{v: P > 0} w_a;
+ *             rest = {voxel_volume * sum_{v: P == 0} rho, voxel_volume * #{v: P == 0}};  the fields are P (XB_HIRSHFELD_PROMOLECULE)
+ *             and rho - P (XB_HIRSHFELD_DEFORMATION), N doubles in C order.  The order of the sums over voxels is free (float
+ *             atomics, as xb_charge_sum); everything per voxel is bit-defined.
+ * xb_hirshfeld_images: HOST ONLY, needs no GPU.  Writes the canonical list (a, x, y, z as int32 quadruples) into out_images, which
+ *             holds `capacity` quadruples, and its length into out_count; with out_images null only the length.
+ * xb_hirshfeld_setup: species[n] in [0, n_species); tables[n_species * (knots + 1)]; knots = K.  Builds the list, q, the position
+ *             table and the tables (as pairs f[k], f[k+1] - f[k]) in ONE device buffer of the context, grown on demand and counted by
+ *             xb_memory_stats.  The setup belongs to the grid's SHAPE: it survives density and label uploads and every other call; an
+ *             xb_set_grid that changes the shape drops it (the two calls below then answer XB_E_STATE); a call refused for its arguments
+ *             leaves an earlier setup as it was, a new one replaces it; xb_hirshfeld_release frees it.
+ * xb_hirshfeld_sum: charge[n], volume[n], rest[2] as above for the resident density (upload another, the spin, and call again: the
+ *             setup is reused).  stats: NULL, or {tiles answered from a candidate list, tiles answered by the full search, the largest
+ *             number of images a tile kept (it may exceed the cap; 0 with XB_HIRSHFELD_FULL_SEARCH)}.
+ * xb_hirshfeld_field: mode XB_HIRSHFELD_PROMOLECULE or XB_HIRSHFELD_DEFORMATION into out_host (host memory) or out_dev (device memory
+ *             of the context's device that overlaps neither the resident density nor the setup) -- exactly one of the two is
+ *             non-null.  The promolecule reads no density: a context without one is accepted.
+ * One workgroup per 8 x 8 x 8 tile of voxels.  It keeps the images within r_cut[s] + R + slack of the tile's centre (R the tile's
+ * circumradius; csrc/k_hirshfeld.h derives the slack), compacts them IN LIST ORDER into LDS and lets every voxel run over those.  A
+ * tile that keeps more than XB_HIRSHFELD_CAND_MAX images runs over the whole list from global memory; XB_HIRSHFELD_FULL_SEARCH in
+ * `flags` makes every tile do so: the second implementation, for tests and benchmarks -- both give the same bits.
+ * XB_E_STATE: no grid, no setup for this grid's shape, no density where it is read, a context that holds a slab;
+ * XB_E_ARG: a null pointer (a null context included, in all five calls), n < 1, n_species < 1, knots < 1, a species index outside [0, n_species), a lattice entry or coordinate
+ * that is not finite, a determinant that is exactly 0 (or not finite), r_cut not finite or <= 0, a table value that is negative or not
+ * finite, f[s][K] != 0, unknown flag bits, an unknown mode, both or neither output of the field, a device output that is not N doubles
+ * of device memory, a capacity below the list's length;  XB_E_LIMIT: an image list longer than 2^31 - 1 (or a shift beyond 2^30), more
+ * than 2^26 table entries.  No option key, no timer slot: a caller times the calls.  Every error is found before any launch. */
+enum { XB_HIRSHFELD_FULL_SEARCH = 1, XB_HIRSHFELD_CAND_MAX = 256 };
+enum { XB_HIRSHFELD_PROMOLECULE = 0, XB_HIRSHFELD_DEFORMATION = 1 };
+int xb_hirshfeld_images(const double lattice[9], const double *atoms_cart, const int32_t *species, int64_t n, const double *r_cut,
+                        int64_t n_species, int64_t *out_count, int32_t *out_images, int64_t capacity);
+int xb_hirshfeld_setup(xb_ctx *c, const double lattice[9], const double *atoms_cart, const int32_t *species, int64_t n,
+                       const double *tables, const double *r_cut, int64_t n_species, int64_t knots);
+int xb_hirshfeld_release(xb_ctx *c);
+int xb_hirshfeld_sum(xb_ctx *c, double voxel_volume, int flags, double *charge, double *volume, double rest[2], int64_t stats[3]);
+int xb_hirshfeld_field(xb_ctx *c, int mode, int flags, double *out_host, void *out_dev);
 /* utils.volume_assign (utils.py:404-421): labels[v] = swap[labels[v]] for labels >= 0 */
 int xb_volume_assign(xb_ctx *c, const int64_t *swap, int64_t n_swap);
 /* utils.atom_assign (utils.py:185-232): nearest atom of every maximum over the 27 periodic images (one

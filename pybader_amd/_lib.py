@@ -50,6 +50,11 @@ XB_CRITICAL_LUT_SIZE = 16384
 XB_STENCIL_GATHER = 1
 XB_STENCIL_COEFFS = 51
 XB_STENCIL_POINT_VALUES = 10
+# xb_hirshfeld_sum / xb_hirshfeld_field: the bit of `flags` that makes every tile run over the whole image list, the candidates a
+# tile's list holds, and the two modes of the field
+XB_HIRSHFELD_FULL_SEARCH = 1
+XB_HIRSHFELD_CAND_MAX = 256
+XB_HIRSHFELD_PROMOLECULE, XB_HIRSHFELD_DEFORMATION = 0, 1
 
 # every symbol include/bader_hip.h declares: (restype, argtypes)
 _vp, _i64, _dbl, _int = C.c_void_p, C.c_int64, C.c_double, C.c_int
@@ -132,6 +137,11 @@ SYMBOLS = {
     'xb_laplacian_field': (_int, [_vp, _pdbl, _int, _vp, _vp]),
     'xb_laplacian_sum': (_int, [_vp, _pdbl, _i64, _dbl, _int, _pdbl, _pdbl, _pdbl]),
     'xb_stencil_points': (_int, [_vp, _pdbl, _vp, _i64, _vp]),
+    'xb_hirshfeld_images': (_int, [_pdbl, _pdbl, _vp, _i64, _pdbl, _i64, _pi64, _vp, _i64]),
+    'xb_hirshfeld_setup': (_int, [_vp, _pdbl, _pdbl, _vp, _i64, _pdbl, _pdbl, _i64, _i64]),
+    'xb_hirshfeld_release': (_int, [_vp]),
+    'xb_hirshfeld_sum': (_int, [_vp, _dbl, _int, _pdbl, _pdbl, _pdbl, _pi64]),
+    'xb_hirshfeld_field': (_int, [_vp, _int, _int, _vp, _vp]),
     'xb_volume_assign': (_int, [_vp, _vp, _i64]),
     'xb_atom_assign': (_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp]),
     'xb_surface_distance': (_int, [_vp, _vp, _vp, _i64, _vp, _pi64]),
@@ -400,6 +410,8 @@ class Context:
         self.resident_labels = None
         self._labels_host = None
         self.n_maxima = 0
+        self.hirshfeld_key = None   # hirshfeld._setup(): what the library's Hirshfeld setup was made from
+        self._hirshfeld_atoms = 0
 
     def drop_label_token(self):
         """the device labels are about to change (or be replaced): no host array equals them any more"""
@@ -425,6 +437,7 @@ class Context:
         shape = tuple(int(s) for s in shape)
         if shape != getattr(self, 'shape', None):
             self.drop_label_token()     # (another grid: no host array equals the device labels any more)
+            self.hirshfeld_key = None   # (nor does the library keep a Hirshfeld setup over a change of shape)
             self.resident_density = None    # (nor is any array's content the device density: xb_set_grid drops it with the shape)
         x0, x1 = (0, shape[0]) if x_range is None else x_range
         sh = np.array(shape, dtype=np.int64)
@@ -924,6 +937,52 @@ class Context:
         check(self.lib.xb_stencil_points(self.h, lat.ctypes.data_as(_pdbl), _ptr(idx), idx.shape[0], _ptr(out)))
         return out
 
+    def hirshfeld_setup(self, lattice, atoms_cart, species, tables, r_cut):
+        """the cell, the atoms and the pro-atoms of the Hirshfeld calls go to the device (xb_hirshfeld_setup; `lattice` the cell, a
+        row per axis; `atoms_cart` [n, 3]; `species` int[n]; `tables` f64[S, K + 1] uniform in r^2 with a last column of zeros;
+        `r_cut` f64[S]).  The setup stays until the grid's shape changes or hirshfeld_release()."""
+        lat, at = _f64(lattice).reshape(9), _f64(atoms_cart).reshape(-1, 3)
+        sp = np.ascontiguousarray(species, dtype=np.int32).reshape(-1)
+        tab, rc = _f64(tables), _f64(r_cut).reshape(-1)
+        self.hirshfeld_key = None   # (whatever hirshfeld._setup remembered is no longer what the library holds)
+        if tab.ndim != 2 or tab.shape[0] != rc.shape[0] or sp.shape[0] != at.shape[0]:
+            raise ValueError(f'hirshfeld_setup: tables {tab.shape}, r_cut {rc.shape}, species {sp.shape}, atoms {at.shape} do not fit')
+        check(self.lib.xb_hirshfeld_setup(self.h, lat.ctypes.data_as(_pdbl), at.ctypes.data_as(_pdbl), _ptr(sp), at.shape[0],
+                                          tab.ctypes.data_as(_pdbl), rc.ctypes.data_as(_pdbl), rc.shape[0], tab.shape[1] - 1))
+        self._hirshfeld_atoms = at.shape[0]
+
+    def hirshfeld_release(self):
+        """free the setup of hirshfeld_setup (kept while the grid's shape stays)"""
+        self.hirshfeld_key = None
+        check(self.lib.xb_hirshfeld_release(self.h))
+
+    def hirshfeld_sum(self, voxel_volume, full_search=False):
+        """Hirshfeld charge and volume of every atom of the setup for the resident density (xb_hirshfeld_sum) ->
+        (charge f64[n], volume f64[n], rest f64[2]: charge and volume of the voxels no pro-atom reaches,
+        {'candidate_tiles', 'full_tiles', 'max_candidates'})"""
+        n = int(getattr(self, '_hirshfeld_atoms', 0))
+        charge, volume, rest = np.zeros(max(n, 1)), np.zeros(max(n, 1)), np.zeros(2)
+        st = (C.c_int64 * 3)()
+        check(self.lib.xb_hirshfeld_sum(self.h, float(voxel_volume), XB_HIRSHFELD_FULL_SEARCH if full_search else 0,
+                                        charge.ctypes.data_as(_pdbl), volume.ctypes.data_as(_pdbl), rest.ctypes.data_as(_pdbl), st))
+        return charge[:n], volume[:n], rest, dict(zip(('candidate_tiles', 'full_tiles', 'max_candidates'), (int(v) for v in st)))
+
+    def hirshfeld_field(self, mode, full_search=False, on_device=False, out=None):
+        """the promolecular density (mode XB_HIRSHFELD_PROMOLECULE) or the deformation density rho - P of the resident density
+        (XB_HIRSHFELD_DEFORMATION) at every voxel (xb_hirshfeld_field) -> f64 of the grid's shape: a host array, or with
+        `on_device` a device.DeviceArray (`out`: one to write into instead of a new one)"""
+        flags = XB_HIRSHFELD_FULL_SEARCH if full_search else 0
+        if on_device or out is not None:
+            from . import device
+            if out is None:
+                out = device.DeviceArray(self, self.shape or (0,), np.float64)
+            d, _ = self._flat('hirshfeld_field', out, {np.dtype(np.float64): 64}, True)
+            check(self.lib.xb_hirshfeld_field(self.h, int(mode), flags, None, C.c_void_p(d.ptr)))
+            return out
+        out = np.empty(self.shape or (0,), np.float64)
+        check(self.lib.xb_hirshfeld_field(self.h, int(mode), flags, _ptr(out), None))
+        return out
+
     def volume_assign(self, swap):
         self.drop_label_token()
         sw = np.ascontiguousarray(swap, dtype=np.int64)
@@ -1171,6 +1230,22 @@ def critical_lut():
     """xb_critical_lut: ring | bond << 4 for each of the 16 384 lower masks (host only: needs the library, not a GPU)"""
     out = np.zeros(XB_CRITICAL_LUT_SIZE, np.uint8)
     check(load().xb_critical_lut(_ptr(out)))
+    return out
+
+
+def hirshfeld_images(lattice, atoms_cart, species, r_cut):
+    """xb_hirshfeld_images: the canonical image list of the Hirshfeld calls for the cell `lattice` (a row per axis), the atoms
+    [n, 3], their species int[n] and the cutoffs f64[S] -> int32[m, 4] rows (atom, x, y, z) (host only: needs the library, not a
+    GPU)"""
+    lat, at = _f64(lattice).reshape(9), _f64(atoms_cart).reshape(-1, 3)
+    sp, rc = np.ascontiguousarray(species, dtype=np.int32).reshape(-1), _f64(r_cut).reshape(-1)
+    if sp.shape[0] != at.shape[0]:
+        raise ValueError(f'hirshfeld_images: {sp.shape[0]} species for {at.shape[0]} atoms')
+    lib, m = load(), C.c_int64()
+    args = (lat.ctypes.data_as(_pdbl), at.ctypes.data_as(_pdbl), _ptr(sp), at.shape[0], rc.ctypes.data_as(_pdbl), rc.shape[0])
+    check(lib.xb_hirshfeld_images(*args, C.byref(m), None, 0))
+    out = np.zeros((int(m.value), 4), np.int32)
+    check(lib.xb_hirshfeld_images(*args, C.byref(m), _ptr(out), out.shape[0]))
     return out
 
 

@@ -38,6 +38,7 @@ static void merge_free(xb_ctx *c);
 static void voronoi_free(xb_ctx *c);
 static void critical_free(xb_ctx *c);
 static void stencil_free(xb_ctx *c);
+static void hirshfeld_free(xb_ctx *c);
 static void free_grid(xb_ctx *c) {
     weight_free(c);
     moments_free(c);
@@ -46,6 +47,7 @@ static void free_grid(xb_ctx *c) {
     voronoi_free(c);
     critical_free(c);
     stencil_free(c);
+    hirshfeld_free(c);
     c->have_rho = c->have_labels = false;
     hipFree(c->rho); hipFree(c->grad); hipFree(c->labels); hipFree(c->known); hipFree(c->first); hipFree(c->list);
     hipFree(c->st); hipFree(c->stage); hipFree(c->ec_pend); c->ec_pend = nullptr; hipFree(c->ec_share); c->ec_share = nullptr; hipFree(c->ec_pflag); c->ec_pflag = nullptr; hipFree(c->max_list); hipFree(c->max_aux); hipFree(c->ovf_list);
@@ -181,7 +183,7 @@ int xb_set_grid(xb_ctx *c, const int64_t shape[3], const double dist_mat[27], co
     }
     c->zero_outside[0] = -1;
     Grid &g = c->g;
-    if (g.nx != (int)shape[0] || g.ny != (int)shape[1] || g.nz != (int)shape[2]) { c->grad_valid = false; c->grad_nb = false; c->brick_max_valid = false; c->have_rho = c->have_labels = false; adjacency_free(c); merge_free(c); critical_free(c); }
+    if (g.nx != (int)shape[0] || g.ny != (int)shape[1] || g.nz != (int)shape[2]) { c->grad_valid = false; c->grad_nb = false; c->brick_max_valid = false; c->have_rho = c->have_labels = false; adjacency_free(c); merge_free(c); critical_free(c); c->hs_have = false; }
     if (dist_mat && !T_grad) return fail(XB_E_ARG, "xb_set_grid: dist_mat without T_grad");
     g.nx = (int)shape[0]; g.ny = (int)shape[1]; g.nz = (int)shape[2];
     g.nyz = g.ny * g.nz;

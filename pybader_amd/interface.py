@@ -330,6 +330,31 @@ class Bader:
             b = point_properties(self.reference, self.lattice, self.atoms_bond_graph.voxels)
             self.atoms_bond_laplacian, self.atoms_bond_ellipticity = b.laplacian, b.ellipticity
 
+    hirshfeld_flag = False    # True: _run runs hirshfeld_analysis() before voronoi_partition() (no other step changes)
+    hirshfeld_field = False   # ... and True: it keeps the deformation density as well
+    proatoms = None           # a hirshfeld.ProAtoms: the free atoms hirshfeld_analysis() weighs with
+    species = None            # int[n]: the row of `proatoms` each atom takes
+
+    def hirshfeld_analysis(self):
+        """Hirshfeld (stockholder) charges next to the Bader ones (pybader_amd.hirshfeld) -- no counterpart in the reference.
+        Needs `proatoms` (a hirshfeld.ProAtoms) and `species` (int[n]).  Sets hirshfeld_charge, hirshfeld_volume per atom (on the
+        charge density, as the Bader sums), hirshfeld_rest (charge and volume of the voxels no pro-atom reaches) and
+        hirshfeld_stats; hirshfeld_spin with spin_bool, from a second sum on the spin density with the same setup; and, only with
+        hirshfeld_field, hirshfeld_deformation (rho - the promolecular density: a host array for a host density, a device array
+        for a device one).  Atoms are atoms - voxel_offset, as in min_surface_distance.  It reads the density alone and rewrites
+        nothing, so its place in _run is free."""
+        from .hirshfeld import deformation_density, hirshfeld_charges
+        if self.proatoms is None or self.species is None:
+            raise ValueError('hirshfeld_analysis: set proatoms (a hirshfeld.ProAtoms) and species (int[n_atoms])')
+        atoms = self.atoms - self.voxel_offset
+        args = (self.lattice, atoms, self.species, self.proatoms)
+        self.hirshfeld_charge, self.hirshfeld_volume, self.hirshfeld_rest, self.hirshfeld_stats = hirshfeld_charges(
+            self.density, *args, self.voxel_volume)
+        if self.hirshfeld_field:
+            self.hirshfeld_deformation = deformation_density(self.density, *args)
+        if self.spin_bool:
+            self.hirshfeld_spin, _, _, _ = hirshfeld_charges(self.spin, *args, self.voxel_volume)
+
     voronoi_flag = False   # True: _run ends with voronoi_partition() (no other step changes)
 
     def voronoi_partition(self):
@@ -395,6 +420,8 @@ class Bader:
             self.laplacian_analysis()
         if self.adjacency_flag:
             self.bond_surfaces()
+        if self.hirshfeld_flag:   # (it reads the density alone: its place is free)
+            self.hirshfeld_analysis()
         if self.voronoi_flag:   # (last: it rewrites the device's label map)
             self.voronoi_partition()
 
