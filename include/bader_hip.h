@@ -706,6 +706,9 @@ enum {
  * reading the neighbour bits of the record in hand.  A macro, not an enumerator: tests/test_abi_cpu.py pins the enumerators above
  * and their number (pybader_amd._lib mirrors it as CROSS_CHECK_BRICK_LOOKUP). */
 #define XB_CHECK_BRICK_LOOKUP 128
+/* ... and one more: the edge sweep of the listed tiles voxel by voxel (k_edge_flag_listed) with the dilation in a kernel of its
+ * own, instead of by row bit masks with the dilation fused in (k_edge_sweep_bits).  CROSS_CHECK_VOXEL_SWEEP in pybader_amd._lib. */
+#define XB_CHECK_VOXEL_SWEEP 256
 /* value of XB_OPT_DEBUG (bits 1, 2 and 8 are not in use) */
 enum {
     XB_DBG_EC_PASSES = 4,         /* print the passes of edge_check and what the middle tier leaves for the exact slow kernel */
@@ -739,6 +742,10 @@ int xb_slow_path_stats(xb_ctx *c, int64_t *assign_total, int64_t *refine_total);
 /* retraces redone by the from-rho kernel since the context was created (their walk went on through a brick whose
  * records the sparse table does not hold) */
 int xb_deferred_stats(xb_ctx *c, int64_t *refine_total);
+/* edge sweeps launched since the context was created: by row bit masks (no vacuum, the whole grid, whole 4 x 8 x 64 tiles and
+ * at least 16 x 16 x 80 voxels, no table whose brick bytes flag every brick as a possible maximum's, fewer maxima in the last assignment than one per 8 bricks), and by the per-voxel kernels
+ * (everything else, and everything under XB_CHECK_VOXEL_SWEEP) */
+int xb_sweep_stats(xb_ctx *c, int64_t *bit_sweeps, int64_t *voxel_sweeps);
 /* region growth: assignments repeated because the scheduled kill launches (XB_OPT_KILL_LAUNCHES; 6 after a chase) did not reach the
  * fixpoint, and the schedule this context uses now (raised to the worst case by the first repeat) */
 int xb_growth_stats(xb_ctx *c, int64_t *retries, int64_t *kill_launches);

@@ -25,6 +25,7 @@ XB_OPT_CROSS_CHECK = 2
 (XB_CHECK_NO_MIRROR, XB_CHECK_GENERIC_WALKER, XB_CHECK_FULL_TGRAD, XB_CHECK_LIST_DILATE, XB_CHECK_WIDE_HALO,
  XB_CHECK_NO_EC_SHARE, XB_CHECK_IO_GATHER) = (1, 2, 4, 8, 16, 32, 64)
 CROSS_CHECK_BRICK_LOOKUP = 128   # the header's macro XB_CHECK_BRICK_LOOKUP, one more bit of XB_OPT_CROSS_CHECK (its enumerators are pinned)
+CROSS_CHECK_VOXEL_SWEEP = 256    # XB_CHECK_VOXEL_SWEEP, likewise: the per-voxel edge sweep + the dilation kernel instead of row bit masks
 XB_OPT_DEBUG = 3
 XB_DBG_EC_PASSES, XB_DBG_SLAB_STATS, XB_DBG_STAGE_WAIT, XB_DBG_SHORT_TIERS = 4, 16, 32, 64
 XB_OPT_EC_GROUPS = 4
@@ -171,6 +172,7 @@ SYMBOLS = {
     'xb_brick_labels': (_int, [_vp, _vp, _i64, _pi64]),
     'xb_slow_path_stats': (_int, [_vp, _pi64, _pi64]),
     'xb_deferred_stats': (_int, [_vp, _pi64]),
+    'xb_sweep_stats': (_int, [_vp, _pi64, _pi64]),
     'xb_growth_stats': (_int, [_vp, _pi64, _pi64]),
     'xb_comm_unique_id': (_int, [_vp]),
     'xb_comm_init': (_int, [_vp, _int, _int, _vp]),
@@ -1221,6 +1223,12 @@ class Context:
         a = C.c_int64()
         check(self.lib.xb_deferred_stats(self.h, C.byref(a)))
         return a.value
+
+    def sweep_stats(self):
+        """(edge sweeps launched by row bit masks, by the per-voxel kernels) since the context was made"""
+        a, b = C.c_int64(), C.c_int64()
+        check(self.lib.xb_sweep_stats(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     def sync(self):
         check(self.lib.xb_sync(self.h))

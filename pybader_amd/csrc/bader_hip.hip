@@ -103,6 +103,7 @@ struct xb_ctx {
         int narrow_halo = 1;       // label halos travel as dtype_calc(-n_maxima) (int8 / int16) instead of int32 (comm.h)
         int ec_share = 1;          // k_ec_chase: a long queue sheds its surplus into other workgroups' mailboxes (0: every workgroup keeps what it wakes; A/B, XB_CHECK_NO_EC_SHARE)
         int nb_bits = 1;           // lean walker / lean retrace: "no records there" from the neighbour bits of the record in hand (0: the brick label / brick byte per step; tests compare, XB_CHECK_BRICK_LOOKUP)
+        int bit_sweep = 1;         // edge sweep of the listed tiles: row bit masks with the dilation fused in (k_edge_sweep_bits); 0: k_edge_flag_listed + k_edge_dilate_tiles (tests compare, XB_CHECK_VOXEL_SWEEP)
         int io_tiled = 1;          // xb_import_density: permuted layouts through the LDS tile (0: the plain strided gather; tests and the benchmark compare)
         int dbg = 0;               // XB_OPT_DEBUG: XB_DBG_* bits
         int ec_groups = 256;       // XB_OPT_EC_GROUPS: workgroups of k_ec_chase (at most one per CU)
@@ -143,6 +144,7 @@ struct xb_ctx {
     void *walk_in = nullptr, *walk_out2 = nullptr, *walk_res = nullptr;   // xb_walkers_continue: incoming walkers, re-exported ones, results
     long long walk_cap = 0;
     long long stat_deferred = 0;   // retraces redone by the from-rho kernel (sparse table)
+    long long stat_bit_sweeps = 0, stat_voxel_sweeps = 0;   // edge sweeps launched by row bit masks / by the per-voxel kernels
     long long stat_ovf_assign = 0, stat_ovf_refine = 0;   // trajectories handed to the exact slow kernel
     int *bres_last = nullptr;   // the fused neargrid assignment's per-brick trace results (inside `list`), or null
     int *blab = nullptr;        // brick labels of the trapping regions (inside `list`), or null
@@ -152,6 +154,7 @@ struct xb_ctx {
                                // records now: set by the pass-B launches that write a whole-grid table of whole bricks (launch_brick_records),
                                // cleared with grad_valid and by every other writer of records; nb_bits_ok() is what the launchers ask
     bool brick_max_valid = false;   // brick_rec bit 1 (the brick holds a 26-neighbour maximum) is right for the density on the card
+    bool brick_max_blanket = false; // brick_rec bit 1 is set on EVERY flagged brick (nothing is known about the maxima), not only where a maximum was found.  Owned by the writers of bit 1: ensure_grad's two tables for given labels set it; pass A (launch_brick_masks: every neargrid assignment, slabs and windowed tables too) and the ongrid masks (k_og_masks, whose flags the late records of refine_iteration_fused keep) clear it
     int grad_cover = 0;        // 0: the table holds a record for every voxel (of the window); 1: only for the bricks flagged in brick_rec
     unsigned char *brick_rec = nullptr;   // per 8^3 brick: its records exist (k_brick_records), nbr bytes inside blab_buf's allocation
     unsigned long long *nb_tab = nullptr; // per 8^3 brick: the neighbour bits of its records by octant (k_nb_table), behind brick_rec
@@ -388,7 +391,7 @@ int xb_set_option(xb_ctx *c, int key, int value) {
     switch (key) {
     case XB_OPT_REGIONS: c->opt.boxes = (value & XB_REGIONS_BOXES) != 0; c->opt.bricks = (value & XB_REGIONS_BRICKS) != 0; break;
     case XB_OPT_CROSS_CHECK:
-        if (!(ok = value >= 0 && value < 2 * XB_CHECK_BRICK_LOOKUP)) break;
+        if (!(ok = value >= 0 && value < 2 * XB_CHECK_VOXEL_SWEEP)) break;
         c->opt.mirror = !(value & XB_CHECK_NO_MIRROR);
         c->opt.lean = !(value & XB_CHECK_GENERIC_WALKER);
         c->opt.mask_diag = !(value & XB_CHECK_FULL_TGRAD);
@@ -397,6 +400,7 @@ int xb_set_option(xb_ctx *c, int key, int value) {
         c->opt.ec_share = !(value & XB_CHECK_NO_EC_SHARE);
         c->opt.io_tiled = !(value & XB_CHECK_IO_GATHER);
         c->opt.nb_bits = !(value & XB_CHECK_BRICK_LOOKUP);
+        c->opt.bit_sweep = !(value & XB_CHECK_VOXEL_SWEEP);
         break;
     case XB_OPT_DEBUG: c->opt.dbg = value; break;
     case XB_OPT_EC_GROUPS: if ((ok = value >= 1 && value <= 4096)) c->opt.ec_groups = value; break;
@@ -420,6 +424,12 @@ int xb_growth_stats(xb_ctx *c, int64_t *retries, int64_t *kill_launches) {
 int xb_deferred_stats(xb_ctx *c, int64_t *refine_total) {
     if (!c) return fail(XB_E_ARG, "null ctx");
     if (refine_total) *refine_total = c->stat_deferred;
+    return XB_OK;
+}
+int xb_sweep_stats(xb_ctx *c, int64_t *bit_sweeps, int64_t *voxel_sweeps) {
+    if (!c) return fail(XB_E_ARG, "null ctx");
+    if (bit_sweeps) *bit_sweeps = c->stat_bit_sweeps;
+    if (voxel_sweeps) *voxel_sweeps = c->stat_voxel_sweeps;
     return XB_OK;
 }
 int xb_slow_path_stats(xb_ctx *c, int64_t *assign_total, int64_t *refine_total) {

@@ -55,6 +55,7 @@ static int ensure_grad(xb_ctx *c, bool force, bool boxes, bool main_rule) {
         HIPCHK(hipGetLastError());
         c->grad_valid = true;
         c->grad_cover = 1;
+        c->brick_max_blanket = true;
         c->grad_rule = main_rule ? 1 : 0;
         c->regions_labels = false;
         c->blab = nullptr;
@@ -78,6 +79,7 @@ static int ensure_grad(xb_ctx *c, bool force, bool boxes, bool main_rule) {
     }
     c->grad_valid = true;
     c->grad_cover = 1;
+    c->brick_max_blanket = true;
     c->grad_rule = main_rule ? 1 : 0;   // (no tie count on this route: a refinement under the other rule rebuilds the records)
     c->window_ties = true;
     c->n_boxes = 0;
@@ -725,6 +727,7 @@ static int assign_ongrid_fused(xb_ctx *c, int64_t *n_maxima) {
     c->grad_valid = false; c->grad_nb = false;          // (brick_rec is rewritten: bit 1 = holds a maximum, no records)
     c->grad_cover = 0;
     c->brick_max_valid = true;
+    c->brick_max_blanket = false;
     c->blab = c->blab_buf;
     c->regions_neargrid = false;   // (closed under the pointer moves only: the refinement's retraces must not stop on them)
     c->walk = walk;

@@ -28,6 +28,33 @@ static int *launch_brick_uniformity(xb_ctx *c, const GridL &gl, int b_off, int c
     return buni + nbr;
 }
 
+// The sweep of the listed tiles by row bit masks (k_edge_sweep_bits: flags, dilation and list in one kernel) instead of
+// k_edge_flag_listed + k_edge_dilate_tiles: no vacuum, the whole grid, whole 4 x 8 x 64 tiles, a tile list to run over, and the
+// maximum exception rare (the two cases below).
+// XB_CHECK_VOXEL_SWEEP keeps the per-voxel kernels (tests compare); xb_sweep_stats counts the sweeps of either form.
+// Not with a table whose brick bytes flag EVERY brick as one that may hold a maximum (ensure_grad for given labels): every edge
+// voxel then asks its record, which the per-voxel kernel does with all 256 threads at once and the bit form row by row --
+// refine('all', 1) on uploaded labels at 512^3: edge_find stage 0.47 ms per voxel, 0.70 by bits (1.41 on one wave).
+static bool sweep_bits_ok(const xb_ctx *c, const int *buni) {
+    const Grid &g = c->g;
+    if (c->grad_valid && c->grad_cover == 1 && c->brick_max_blanket) return false;
+    // Nor where the last assignment this context completed found maxima in most bricks (a noisy density: 1.6 M maxima in the
+    // 262 144 bricks of 512^3).  The maximum exception is then the common case, and the bit form tests the 3 960 voxels of a
+    // tile's ring for it where the per-voxel kernel tests its own 2 048: edge_find 1.89 -> 3.76 ms on that density.  A tile and
+    // its ring touch 60 bricks, so from one maximum per 8 bricks on a listed tile meets several flagged bricks as a rule; the
+    // smooth densities hold 8 ... 216 maxima.  The count is the host's from the last numbering (the sweep of a queued step is
+    // launched before its own assignment is known: no wait is added); a stale count changes the kernel, never the flags.
+    const long long nbr = (long long)((g.nx + 7) / 8) * ((g.ny + 7) / 8) * ((g.nz + 7) / 8);
+    if (8 * (long long)c->maxima_sorted.size() >= nbr) return false;
+    return c->opt.bit_sweep && c->opt.tile_dilate && buni && !c->has_vacuum && g.x0 == 0 && g.x1 == g.nx && g.nx % ET_X == 0 &&
+           g.ny % ET_Y == 0 && g.nz % ET_Z == 0 && !small_grid(g);
+}
+static void launch_sweep_bits(xb_ctx *c, const GridL &gl, int ntiles, int *edge_count, const GradRec *G, const unsigned char *brec,
+                              const int *tiles, const int *n_tiles) {
+    k_edge_sweep_bits<<<std::min(ntiles, 2048), TPB, 0, c->stream>>>(gl, c->rho, c->labels, c->known, c->list, edge_count, G, brec, tiles, n_tiles);
+    c->stat_bit_sweeps++;
+}
+
 // the sweep's launches; the edge count stays on the device (CT_N_EDGES).  *dilate_owned: the owned edges still have to
 // dilate from the list (k_edge_dilate_list over CT_N_EDGES entries)
 static int edge_find_launch(xb_ctx *c, bool *dilate_owned) {
@@ -62,6 +89,20 @@ static int edge_find_launch(xb_ctx *c, bool *dilate_owned) {
         }
         const GradRec *G = c->grad_valid ? c->grad : nullptr;
         const unsigned char *brec = c->grad_valid && c->grad_cover == 1 ? c->brick_rec : nullptr;
+        if (whole && sweep_bits_ok(c, buni)) {
+            // flags preset to "known", the tiles that are not of one label with their surroundings listed, and those swept with the
+            // dilation in the same kernel: nothing is left to dilate from the list
+            const int ntiles = (g.nz / ET_Z) * (g.ny / ET_Y) * (g.nx / ET_X);
+            int *tiles = (int *)c->stage;
+            HIPCHK(hipMemsetAsync(c->known, 2, (size_t)c->N, c->stream));
+            HIPCHK(hipMemsetAsync(c->counters + CT_TILES_OWN, 0, sizeof(int), c->stream));
+            k_edge_tile_list<<<(ntiles + TPB - 1) / TPB, TPB, 0, c->stream>>>(gl, buni, tiles, c->counters + CT_TILES_OWN, 0, g.nx / ET_X);
+            launch_sweep_bits(c, gl, ntiles, c->counters + CT_N_EDGES, G, brec, tiles, c->counters + CT_TILES_OWN);
+            HIPCHK(hipGetLastError());
+            *dilate_owned = false;
+            return XB_OK;
+        }
+        c->stat_voxel_sweeps++;
         if (whole || all) {
             dim3 grid((g.nz + ET_Z - 1) / ET_Z, (g.ny + ET_Y - 1) / ET_Y, (np + ET_X - 1) / ET_X);
             k_edge_flag_tiled<<<grid, TPB, 0, c->stream>>>(gl, c->rho, c->labels, c->known, xa, np, c->list,
@@ -681,6 +722,7 @@ static int refine_iteration_fused(xb_ctx *c, int64_t *edges, int64_t *changed, b
     static_assert(FS_N_CHGLIST == FS_N_EDGES + 6, "one memset clears the refinement's counters");
     HIPCHK(hipMemsetAsync(fs + FS_N_EDGES, 0, 7 * sizeof(int), c->stream));   // edges, changed, escaped, overflows, deferred, listed tiles, relabelled list
     c->chg_n = -1;
+    bool bits = false;   // the sweep by row bit masks (sweep_bits_ok)
     {
         ScopedTimer t(c, XB_TIMER_EDGE_FIND);
         const int small = small_grid(g);
@@ -697,16 +739,22 @@ static int refine_iteration_fused(xb_ctx *c, int64_t *edges, int64_t *changed, b
             HIPCHK(hipMemsetAsync(c->known, 2, (size_t)c->N, c->stream));
             k_edge_tile_list<<<(ntiles + TPB - 1) / TPB, TPB, 0, c->stream>>>(gl, buni, tiles, fs + FS_N_TILES, 0, (g.nx + ET_X - 1) / ET_X,
                                                                               c->pending_assign ? fs : nullptr);
-            k_edge_flag_listed<<<std::min(ntiles, 2048), TPB, 0, c->stream>>>(gl, c->rho, c->labels, c->known, c->list, fs + FS_N_EDGES, small,
-                                                           c->grad_valid ? c->grad : nullptr, brec, c->has_vacuum ? 0 : 1, tiles, fs + FS_N_TILES);
+            if ((bits = sweep_bits_ok(c, buni)))
+                launch_sweep_bits(c, gl, ntiles, fs + FS_N_EDGES, c->grad_valid ? c->grad : nullptr, brec, tiles, fs + FS_N_TILES);
+            else
+                k_edge_flag_listed<<<std::min(ntiles, 2048), TPB, 0, c->stream>>>(gl, c->rho, c->labels, c->known, c->list, fs + FS_N_EDGES, small,
+                                                               c->grad_valid ? c->grad : nullptr, brec, c->has_vacuum ? 0 : 1, tiles, fs + FS_N_TILES);
         } else {
             dim3 grid((g.nz + ET_Z - 1) / ET_Z, (g.ny + ET_Y - 1) / ET_Y, (g.nx + ET_X - 1) / ET_X);
             k_edge_flag_tiled<<<grid, TPB, 0, c->stream>>>(gl, c->rho, c->labels, c->known, 0, g.nx, c->list, fs + FS_N_EDGES, small, buni,
                                                            c->grad_valid ? c->grad : nullptr, brec, c->has_vacuum ? 0 : 1);
         }
-        if (buni && c->opt.tile_dilate && g.nz % ET_Z == 0) k_edge_dilate_tiles<<<std::min(ntiles_listed, 4096), TPB, 0, c->stream>>>(gl, c->known, (const int *)c->stage, fs + FS_N_TILES);
-        else k_edge_dilate_list<<<nblocks(c->N / 16), TPB, 0, c->stream>>>(gl, c->known, c->list, 0, fs + FS_N_EDGES);
+        if (!bits) {   // (k_edge_sweep_bits dilated as it went)
+            if (buni && c->opt.tile_dilate && g.nz % ET_Z == 0) k_edge_dilate_tiles<<<std::min(ntiles_listed, 4096), TPB, 0, c->stream>>>(gl, c->known, (const int *)c->stage, fs + FS_N_TILES);
+            else k_edge_dilate_list<<<nblocks(c->N / 16), TPB, 0, c->stream>>>(gl, c->known, c->list, 0, fs + FS_N_EDGES);
+        }
     }
+    if (!bits) c->stat_voxel_sweeps++;
     c->list_valid = false; c->chg_n = -1;
     c->buni_valid = false;
     if (late_records) {

@@ -56,6 +56,7 @@ static void launch_brick_masks(xb_ctx *c, bool part, bool allow_diag, int *bmask
     if (!sym) launch(part ? k_brick_masks<Grid, 1, false, true> : k_brick_masks<Grid, 1, false>, g);
     else if (part) launch(diag ? k_brick_masks<GridS, 1, true, true> : k_brick_masks<GridS, 1, false, true>, gs);
     else launch(diag ? k_brick_masks<GridS, 1, true> : k_brick_masks<GridS, 1, false>, gs);
+    c->brick_max_blanket = false;   // (pass A flags the bricks that hold a maximum, and only those)
 }
 
 // Pass B (k_brick_records): the 32-byte records of the listed bricks (list[0 .. *n_dev)), or of every brick whose

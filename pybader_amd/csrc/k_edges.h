@@ -545,6 +545,308 @@ __global__ __launch_bounds__(TPB) void k_edge_flag_listed(GridL g, const double 
     }
 }
 
+// The sweep of the listed tiles with ROW BIT MASKS, flags and dilation in one kernel (whole grid of whole tiles, no vacuum).
+// "Some neighbour carries another label" needs no label values, only equalities, and along a row of 64 voxels an equality is
+// one ballot.  A row (x, y) of the tile plus a two-voxel halo holds 68 z-positions p = (z - z0) mod 68: 0..63 the tile's own,
+// 64 / 65 = z0 + 64 / z0 + 65, 66 / 67 = z0 - 2 / z0 - 1, so that "the next voxel in z" is p + 1 mod 68 everywhere that counts.
+// A mask is a 64-bit word for p < 64 and a nibble for p = 64..67:
+//   Z (x,y)[p] = l(p) == l(p + 1)            T(x,y) = Z & rotl(Z): z-1, z, z+1 of the row carry one label
+//   Cy(x,y)[p] = l(x,y,p) == l(x,y+1,p)      Cx(x,y)[p] = l(x,y,p) == l(x+1,y,p)
+//   P (x,y) = T(x,y-1) & T(x,y) & T(x,y+1) & Cy(x,y-1) & Cy(x,y)                 the 9 voxels around (y, p) in plane x
+//   uniform(x,y) = P(x-1,y) & P(x,y) & P(x+1,y) & Cx(x-1,y) & Cx(x,y)            the 27-box; edge = ~uniform
+// (refinement.py:357-372 without vacuum).  The edge masks are needed one voxel round the tile (6 x 10 rows, p = 67 and 64 too):
+// the dilation (refinement.py:385-404) of the tile's 32 rows is the OR over the nine rows around of E | E << 1 | E >> 1.
+//   staging   wave w loads planes 2w, 2w + 1 of the 8 x 12 rows (lane = z, every load in flight, values stay in registers)
+//             and stores them to LDS; 384 halo values and 180 brick bytes by thread
+//   phase 1   wave w: Z, Cy, Cx of its 24 rows as ballots (the z-shifted row and plane 2w + 2 from LDS), parked with
+//             lane = row; lanes < 24 add the four halo positions, form T and P (the rows y +- 1 are lanes +- 1) and store
+//             P and Cx: 2.3 KB
+//   phase 2   wave 0, lane = one of the 60 ring rows: edge, dilation (rows y +- 1 / x +- 1 are lanes +- 1 / +- 10), the
+//             tile's edge count by a wave scan and ONE atomic.  The maximum exception, where a tile has candidates for it:
+//             the rows go to all four waves through LDS (lane = z, eight rows' record words in flight), two more barriers
+//   phase 3   wave w, lane = z: the flags and the list entries of the 8 rows of plane w
+// Three barriers per tile (five with the exception); the labels' LDS is not reused before the third.
+#define EB_X (ET_X + 4)
+#define EB_Y (ET_Y + 4)
+#define EB_P (ET_Z + 4)
+#define EB_ROWS (EB_X * EB_Y)
+#define EB_RING ((ET_X + 2) * (ET_Y + 2))
+typedef unsigned long long eb_mask;
+__device__ __forceinline__ eb_mask eb_ballot(bool b) { return __builtin_amdgcn_ballot_w64(b); }
+__device__ __forceinline__ void eb_park(unsigned &lo, unsigned &hi, eb_mask m, bool here) {   // the wave-uniform m into one lane of (lo, hi)
+    lo = here ? (unsigned)m : lo;
+    hi = here ? (unsigned)(m >> 32) : hi;
+}
+__device__ __forceinline__ unsigned eb_eq4(const int4 &a, const int4 &b) {
+    return (a.x == b.x ? 1u : 0u) | (a.y == b.y ? 2u : 0u) | (a.z == b.z ? 4u : 0u) | (a.w == b.w ? 8u : 0u);
+}
+// refinement.py:374-383 for one edge candidate without vacuum: the 27-point density test (the caller has asked the record first)
+__device__ __forceinline__ bool eb_is_max(const GridL &g, const double *__restrict__ rho, int x, int y, int z) {
+    const int v = (x * g.ny + y) * g.nz + z;
+    const double c = rho[v];
+    bool is_max = true;
+#pragma unroll 1
+    for (int dx = -1; dx < 2; dx++) {
+        const int X = wrapi(x + dx, g.nx);
+#pragma unroll 1
+        for (int dy = -1; dy < 2; dy++) {
+            const int Y = wrapi(y + dy, g.ny);
+#pragma unroll
+            for (int dz = -1; dz < 2; dz++)
+                if (rho[(X * g.ny + Y) * g.nz + wrapi(z + dz, g.nz)] > c) is_max = false;
+        }
+    }
+    return is_max;
+}
+__global__ __launch_bounds__(TPB) void k_edge_sweep_bits(GridL g, const double *__restrict__ rho, const int *__restrict__ labels,
+                                                         int8_t *__restrict__ known, int *__restrict__ list, int *list_count,
+                                                         const GradRec *__restrict__ G, const unsigned char *__restrict__ brick_rec,
+                                                         const int *__restrict__ tiles, const int *n_tiles) {
+    static_assert(ET_Z == XB_WAVE && TPB == 4 * XB_WAVE && EB_X == 8 && EB_ROWS == 4 * 24 && ET_X == 4 && ET_Y == 8, "tile shape");
+    // (a row of 68 ints is 17 x 16 bytes: lane = z reads are consecutive, the 16-byte halo reads with lane = row fall on odd strides)
+    __shared__ __attribute__((aligned(16))) int tile[EB_ROWS][EB_P];
+    __shared__ eb_mask sP[EB_ROWS], sCx[EB_ROWS], sE[ET_X * ET_Y], sNear[ET_X * ET_Y];
+    __shared__ unsigned sHi[EB_ROWS];   // bits 0-3: P at p = 64..67, bits 4-7: Cx there
+    __shared__ int sOff[ET_X * ET_Y];
+    __shared__ eb_mask sQ[2], sRE[EB_RING], sRC[EB_RING];   // the maximum exception across the waves: ring rows with candidates (tile / halo
+    __shared__ unsigned sREh[EB_RING], sRCh[EB_RING];       // positions), the rows' edge masks and their candidates
+    __shared__ unsigned char sB[ET_X + 2][3][12];   // brick bytes: ring plane, brick row y0/8 - 1 .. + 1, brick z0/8 - 1 .. + 8
+    const int n = *n_tiles;
+    const int ntz = g.nz / ET_Z, nty = g.ny / ET_Y, nb1 = g.ny >> 3, nb2 = g.nz >> 3;
+    const int n_xcd = (gridDim.x % 8 == 0) ? 8 : 1;   // (an eighth of the list per XCD, as in k_edge_flag_listed)
+    const int part = (n + n_xcd - 1) / n_xcd, part0 = (int)(blockIdx.x % n_xcd) * part, part1 = min(n, part0 + part);
+#pragma unroll 1
+    for (int item = part0 + blockIdx.x / n_xcd; item < part1; item += gridDim.x / n_xcd) {   // (uniform per block)
+        // (salt: always 0, but opaque to the compiler -- what derives from the thread index then counts as loop variant, and the
+        // row addresses and lane predicates of all phases are not carried, and spilled, across iterations; see edge_tile)
+        int salt = 0;
+        asm volatile("" : "+v"(salt));
+        const int tid = (int)threadIdx.x + salt, lane = tid % XB_WAVE, wv = __builtin_amdgcn_readfirstlane(tid / XB_WAVE);
+        const unsigned entry = (unsigned)tiles[item];
+        const int t = (int)(entry & 0x7fffffffu);
+        const int tx0 = (t / (ntz * nty)) * ET_X, y0 = ((t / ntz) % nty) * ET_Y, z0 = (t % ntz) * ET_Z;
+        if (entry & 0x80000000u) {   // uniform vacuum (not with the labels this kernel is launched on): flags 0
+            for (int i = tid; i < ET_X * ET_Y * ET_Z; i += TPB)
+                known[((size_t)(tx0 + i / (ET_Z * ET_Y)) * g.ny + y0 + (i / ET_Z) % ET_Y) * g.nz + z0 + i % ET_Z] = 0;
+            continue;
+        }
+        // ---- staging
+        int a[24];
+        {
+            int yoff[EB_Y];
+#pragma unroll
+            for (int ey = 0; ey < EB_Y; ey++) yoff[ey] = wrap_u(y0 - 2 + ey, g.ny) * g.nz + z0;
+#pragma unroll
+            for (int e = 0; e < 2; e++) {
+                const int *plane = labels + (size_t)wrap_u(tx0 - 2 + 2 * wv + e, g.nx) * g.nyz;
+#pragma unroll
+                for (int ey = 0; ey < EB_Y; ey++) a[e * EB_Y + ey] = plane[yoff[ey] + lane];
+            }
+            int hv[2] = {0, 0};
+#pragma unroll
+            for (int k = 0; k < 2; k++) {
+                const int i = tid + k * TPB;
+                if (i < 4 * EB_ROWS) {
+                    const int row = i >> 2, q = i & 3;
+                    const int X = wrap_u(tx0 - 2 + row / EB_Y, g.nx), Y = wrap_u(y0 - 2 + row % EB_Y, g.ny);
+                    const int Z = wrap_u(q < 2 ? z0 + ET_Z + q : z0 - 4 + q, g.nz);
+                    hv[k] = labels[((size_t)X * g.ny + Y) * g.nz + Z];
+                }
+            }
+            int bv = 3;   // (no brick bytes: every brick may hold a maximum, a record exists wherever there is a table)
+            const int bi = tid - (TPB - (ET_X + 2) * 30);
+            if (bi >= 0 && brick_rec) {
+                const int X = wrap_u(tx0 - 1 + bi / 30, g.nx);
+                bv = brick_rec[((X >> 3) * nb1 + wrap_u((y0 >> 3) - 1 + (bi / 10) % 3, nb1)) * nb2 + wrap_u((z0 >> 3) - 1 + bi % 10, nb2)];
+            }
+#pragma unroll
+            for (int j = 0; j < 24; j++) tile[24 * wv + j][lane] = a[j];
+#pragma unroll
+            for (int k = 0; k < 2; k++) {
+                const int i = tid + k * TPB;
+                if (i < 4 * EB_ROWS) tile[i >> 2][ET_Z + (i & 3)] = hv[k];
+            }
+            if (bi >= 0) sB[bi / 30][(bi / 10) % 3][bi % 10] = (unsigned char)bv;
+        }
+        __syncthreads();
+        // ---- phase 1: the row masks.  A wave holds whole planes, so the y part of P is scalar algebra on the ballots: with
+        // Q(y) = Z(y-1) & Z(y) & Z(y+1) & Cy(y-1) & Cy(y), P = Q & rotl(Q) (a voxel with its 9-box of one label has the
+        // three voxels below it in z equal as well, so the rotated Cy terms take nothing away).  Two masks parked per row.
+        {
+            unsigned ql = 0, qh = 0, xl = 0, xh = 0;
+#pragma unroll
+            for (int e = 0; e < 2; e++) {
+                const int r0 = 24 * wv + EB_Y * e;
+                int b[EB_Y], nx[EB_Y];   // the row one voxel on in z; the same row of the next wave's first plane
+#pragma unroll
+                for (int ey = 0; ey < EB_Y; ey++) b[ey] = tile[r0 + ey][lane + 1];
+                if (e == 1) {   // (wave 3: a clamped row, for a Cx of plane 7 that nobody reads)
+#pragma unroll
+                    for (int ey = 0; ey < EB_Y; ey++) nx[ey] = tile[min(r0 + EB_Y + ey, EB_ROWS - 1)][lane];
+                }
+                eb_mask zm = 0, zc = eb_ballot(a[EB_Y * e] == b[0]), ym = 0;
+#pragma unroll
+                for (int ey = 0; ey < EB_Y; ey++) {
+                    const int j = EB_Y * e + ey;
+                    const eb_mask zp = ey + 1 < EB_Y ? eb_ballot(a[j + 1] == b[ey + 1]) : 0ull;
+                    const eb_mask yc = ey + 1 < EB_Y ? eb_ballot(a[j] == a[j + 1]) : 0ull;
+                    const eb_mask cx = eb_ballot(a[j] == (e == 0 ? a[j + EB_Y] : nx[ey]));
+                    const bool here = lane == j;
+                    eb_park(ql, qh, zm & zc & zp & ym & yc, here);   // (rows y0 - 2 and y0 + 9: 0, nobody reads them)
+                    eb_park(xl, xh, cx, here);
+                    zm = zc; zc = zp; ym = yc;
+                    // (a row's masks parked before the next row's compares: left alone the compiler sinks all 48 selects behind
+                    // the last compare and spills the ballots they wait for -- ~110 v_writelane / v_readlane pairs instead of ~10
+                    // and three workgroups per CU instead of five.  It is a fence for this compiler, not for correctness: after a
+                    // toolchain change look at `python tools/isa.py k_edge_sweep_bits` with and without it)
+                    asm volatile("" : "+v"(ql), "+v"(qh), "+v"(xl), "+v"(xh));
+                }
+            }
+            const eb_mask Q = ((eb_mask)qh << 32) | ql, Cx = ((eb_mask)xh << 32) | xl;
+            // the four halo positions, lane = row (lanes >= 24 compute on a clamped row and store nothing)
+            const int r = min(24 * wv + lane, EB_ROWS - 1);
+            const int4 h = *reinterpret_cast<const int4 *>(&tile[r][ET_Z]);
+            const int4 hy = *reinterpret_cast<const int4 *>(&tile[min(r + 1, EB_ROWS - 1)][ET_Z]);
+            const int4 hx = *reinterpret_cast<const int4 *>(&tile[min(r + EB_Y, EB_ROWS - 1)][ET_Z]);
+            const int first = tile[r][0];
+            const unsigned Zh = (h.x == h.y ? 1u : 0u) | (h.y == h.z ? 2u : 0u) | (h.z == h.w ? 4u : 0u) | (h.w == first ? 8u : 0u);
+            const unsigned Cyh = (r % EB_Y != EB_Y - 1) ? eb_eq4(h, hy) : 0u, Cxh = (r + EB_Y < EB_ROWS) ? eb_eq4(h, hx) : 0u;
+            const unsigned pk = Zh | (Cyh << 4);
+            const unsigned pkm = __shfl_up(pk, 1), pkp = __shfl_down(pk, 1);   // (rows y - 1, y + 1 of the plane)
+            const unsigned Qh = pkm & pk & pkp & (pkm >> 4) & (pk >> 4) & 15u;
+            if (lane < 24) {
+                sP[r] = Q & ((Q << 1) | (Qh >> 3));
+                sCx[r] = Cx;
+                sHi[r] = (Qh & ((Qh << 1) | (unsigned)(Q >> 63)) & 15u) | (Cxh << 4);
+            }
+        }
+        __syncthreads();
+        // ---- phase 2: wave 0, lane = ring row (x0 - 1 + rx, y0 - 1 + ry).  Where an edge meets an 8-voxel run of a brick that
+        // may hold a maximum (rare with the flags of an assignment; every mixed brick with a table built for given labels) the
+        // rows go through LDS to all four waves for the maximum exception, and wave 0 finishes behind two more barriers.
+        const bool ring = lane < EB_RING;
+        const int rl = min(lane, EB_RING - 1), rx = rl / (ET_Y + 2), ry = rl % (ET_Y + 2);
+        eb_mask E = 0;
+        unsigned Eh = 0;
+        // dilation, the tile's edge count and what phase 3 reads (wave 0, all its lanes)
+        auto finish = [&]() {
+            // along z in the row, then rows y +- 1 (lanes +- 1), then planes x +- 1 (lanes +- 10)
+            const eb_mask D = E | (E << 1) | (E >> 1) | (eb_mask)((Eh >> 3) & 1u) | ((eb_mask)(Eh & 1u) << 63);
+            const eb_mask Dy = __shfl_up(D, 1) | D | __shfl_down(D, 1);
+            const eb_mask Dn = __shfl_up(Dy, ET_Y + 2) | Dy | __shfl_down(Dy, ET_Y + 2);
+            const bool own = ring && rx >= 1 && rx <= ET_X && ry >= 1 && ry <= ET_Y;
+            const int cnt = own ? __popcll(E) : 0;
+            int incl = cnt;
+#pragma unroll
+            for (int o = 1; o < XB_WAVE; o <<= 1) {
+                const int up = __shfl_up(incl, o);
+                if (lane >= o) incl += up;
+            }
+            const int total = __shfl(incl, XB_WAVE - 1);
+            int base = 0;
+            if (total) {
+                if (lane == 0) base = atomicAdd(list_count, total);
+                base = __shfl(base, 0);
+            }
+            if (own) {
+                const int row = (rx - 1) * ET_Y + ry - 1;
+                sE[row] = E; sNear[row] = Dn; sOff[row] = base + incl - cnt;
+            }
+        };
+        if (wv == 0) {
+            const int r = (rx + 1) * EB_Y + ry + 1;
+            const unsigned hm = sHi[r - EB_Y], h0 = sHi[r], hp = sHi[r + EB_Y];
+            E = ring ? ~(sP[r - EB_Y] & sP[r] & sP[r + EB_Y] & sCx[r - EB_Y] & sCx[r]) : 0ull;
+            Eh = ring ? ~(hm & h0 & hp & (hm >> 4) & (h0 >> 4)) & 9u : 0u;   // p = 64 (z0 + 64) and p = 67 (z0 - 1)
+            const unsigned char *bb = sB[rx][ry == 0 ? 0 : (ry == ET_Y + 1 ? 2 : 1)];
+            eb_mask F = 0;
+#pragma unroll
+            for (int k = 0; k < 8; k++)
+                if (bb[k + 1] & 2) F |= 0xFFull << (8 * k);
+            const unsigned Fh = ((bb[9] >> 1) & 1u) | (((bb[0] >> 1) & 1u) << 3);
+            const eb_mask qa = eb_ballot((E & F) != 0), qb = eb_ballot((Eh & Fh) != 0);
+            if (lane == 0) { sQ[0] = qa; sQ[1] = qb; }
+            if (qa | qb) {
+                if (ring) { sRE[lane] = E; sREh[lane] = Eh; sRC[lane] = E & F; sRCh[lane] = Eh & Fh; }
+            } else
+                finish();
+        }
+        __syncthreads();
+        if (sQ[0] | sQ[1]) {   // (uniform per block)
+            // Wave w takes the ring rows w, w + 4, ... (lane = z), eight rows at a time so that their record words are in flight
+            // together; wave 3 first takes the two halo positions of every row (lane = ring row) in one go.
+            eb_mask qa = sQ[0] & (0x1111111111111111ull << wv);
+            qa = ((eb_mask)(unsigned)__builtin_amdgcn_readfirstlane((int)(qa >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)qa);
+            if (wv == 3 && sQ[1]) {
+                const unsigned ch = ring ? sRCh[rl] : 0u;
+                const unsigned char *sb = sB[rx][ry == 0 ? 0 : (ry == ET_Y + 1 ? 2 : 1)];
+                const int X = wrap_u(tx0 - 1 + rx, g.nx), Y = wrap_u(y0 - 1 + ry, g.ny);
+                int Z[2], kw[2];
+                bool act[2], usek[2];
+#pragma unroll
+                for (int i = 0; i < 2; i++) {   // p = 64 (z0 + 64, brick run 9) and p = 67 (z0 - 1, brick run 0)
+                    Z[i] = wrap_u(i == 0 ? z0 + ET_Z : z0 - 1, g.nz);
+                    act[i] = (ch >> (3 * i)) & 1u;
+                    usek[i] = G && act[i] && (sb[i == 0 ? 9 : 0] & 1) && plane_in_window(g, X);
+                    const int slot = usek[i] ? rec_slot(g, (X * g.ny + Y) * g.nz + Z[i]) : 0;
+                    kw[i] = G ? reinterpret_cast<const int *>(G)[(size_t)(unsigned)slot * 8 + 6] : 0;
+                }
+                unsigned clear = 0;
+#pragma unroll
+                for (int i = 0; i < 2; i++) {
+                    bool m = act[i] && !(usek[i] && low_og(kw[i] & 0x1FFFFF) != XB_OG_SELF);
+                    if (m) m = eb_is_max(g, rho, X, Y, Z[i]);
+                    if (m) clear |= 1u << (3 * i);
+                }
+                if (clear) sREh[rl] &= ~clear;   // (a lane's own word; the rows' waves write sRE only)
+            }
+            while (qa) {   // (wave-uniform)
+                int src[8], X[8], Y[8], kw[8];
+                bool act[8], usek[8];
+#pragma unroll
+                for (int i = 0; i < 8; i++) {
+                    src[i] = -1;
+                    if (qa) { src[i] = __ffsll((long long)qa) - 1; qa &= qa - 1; }
+                    const int sr = max(src[i], 0), sx = sr / (ET_Y + 2), sy = sr % (ET_Y + 2);
+                    const eb_mask c = sRC[sr];
+                    const unsigned char *sb = sB[sx][sy == 0 ? 0 : (sy == ET_Y + 1 ? 2 : 1)];
+                    X[i] = wrap_u(tx0 - 1 + sx, g.nx); Y[i] = wrap_u(y0 - 1 + sy, g.ny);
+                    act[i] = src[i] >= 0 && ((c >> lane) & 1ull);
+                    usek[i] = G && act[i] && (sb[1 + (lane >> 3)] & 1) && plane_in_window(g, X[i]);
+                    // (the low word of the key holds the ongrid successor; slot 0 for the lanes that do not ask)
+                    const int slot = usek[i] ? rec_slot(g, (X[i] * g.ny + Y[i]) * g.nz + z0 + lane) : 0;
+                    kw[i] = G ? reinterpret_cast<const int *>(G)[(size_t)(unsigned)slot * 8 + 6] : 0;
+                }
+#pragma unroll
+                for (int i = 0; i < 8; i++) {
+                    // a record whose ongrid successor is another voxel: not a maximum; else the 27-point density test
+                    bool m = act[i] && !(usek[i] && low_og(kw[i] & 0x1FFFFF) != XB_OG_SELF);
+                    if (m) m = eb_is_max(g, rho, X[i], Y[i], z0 + lane);
+                    const eb_mask mm = eb_ballot(m);
+                    if (lane == 0 && src[i] >= 0 && mm) sRE[src[i]] &= ~mm;   // (the row belongs to this wave alone)
+                }
+            }
+            __syncthreads();
+            if (wv == 0) {
+                E = ring ? sRE[rl] : 0ull;
+                Eh = ring ? sREh[rl] : 0u;
+                finish();
+            }
+            __syncthreads();
+        }
+        // ---- phase 3: flags and list, lane = z, wave w the 8 rows of plane tx0 + w
+#pragma unroll
+        for (int ty = 0; ty < ET_Y; ty++) {
+            const int row = wv * ET_Y + ty;
+            const eb_mask E = sE[row], N = sNear[row];
+            const int v = ((tx0 + wv) * g.ny + y0 + ty) * g.nz + z0 + lane;
+            const bool e = (E >> lane) & 1ull;
+            known[v] = e ? (int8_t)-2 : (((N >> lane) & 1ull) ? (int8_t)-1 : (int8_t)2);
+            if (e) list[sOff[row] + __popcll(E & ((1ull << lane) - 1ull))] = v;
+        }
+    }
+}
+
 // The retraces leave known == -2 on exactly the start voxels they relabelled, all of them entries of the edge list: the list of
 // the next edge_check is a pass over that list (round 4) instead of a sweep of the whole grid for the flag and a host wait.
 // (n_changed: the retrace pass's count of relabelled voxels -- none, the usual case after a neargrid assignment: nothing to list)
