@@ -468,6 +468,65 @@ int xb_laplacian_field(xb_ctx *c, const double lattice[9], int flags, double *ou
 int xb_laplacian_sum(xb_ctx *c, const double lattice[9], int64_t n, double voxel_volume, int flags, double *sum, double *abs_sum,
                      double *volume);
 int xb_stencil_points(xb_ctx *c, const double lattice[9], const int64_t *lin, int64_t m, double *out /* m*10 */);
+/* ---- the NCI index (Johnson et al. 2010; what NCIPLOT, Multiwfn and Critic2 print): the reduced density gradient s and
+ * sign(lambda2) rho at every voxel, the sums over the low-s, low-rho region per label split into attractive, van der Waals and
+ * repulsive parts, and the s against sign(lambda2) rho histogram -- no counterpart in the reference ----
+ * All three calls read the resident density rho of the whole grid (xb_nci_sum the resident labels too); nothing resident is
+ * written.  lattice[9]: the cell, a row per axis.
+ *   voxel     c = rho(p), the gradient g_x g_y g_z and the Hessian H_xx H_xy H_xz H_yy H_yz H_zz are EXACTLY the ten values of
+ *             xb_stencil_points: the coefficients of xb_stencil_coeffs, the operations in the order written in the block above.
+ *             Then, in this order:
+ *               g2 = (gx*gx + gy*gy) + gz*gz
+ *               I1 = (Hxx + Hyy) + Hzz
+ *               I2 = ((Hxx*Hyy - Hxy*Hxy) + (Hxx*Hzz - Hxz*Hxz)) + (Hyy*Hzz - Hyz*Hyz)
+ *               I3 = (Hxx*(Hyy*Hzz - Hyz*Hyz) - Hxy*(Hxy*Hzz - Hyz*Hxz)) + Hxz*(Hxy*Hyz - Hyy*Hxz)
+ *   sigma     the sign of lambda2, the middle eigenvalue of H, without an eigen-solve.  The characteristic polynomial
+ *             lambda^3 - I1 lambda^2 + I2 lambda - I3 of a symmetric matrix has real roots, so Descartes' rule is exact:
+ *               p = the number of sign changes in (1, -I1, I2, -I3), zeros skipped;  z = the number of trailing zeros of that
+ *               sequence;  neg = 3 - p - z;  sigma = +1 if p >= 2, -1 if neg >= 2, else 0.
+ *             The computed invariants are taken as they are (a NaN counts as a zero); p + z <= 3 for any sequence, so sigma is an
+ *             integer defined for every input.  A constant field gives 0.  Only the COUNT of signs enters: a rounding error in I3
+ *             can flip sigma only where lambda2 itself is at rounding level.
+ *   fields    where rho > 0:  x = sigma * rho (bit-defined),  s = sqrt(g2) / (C * (rho * cbrt(rho))),  C = XB_NCI_C = 2 (3 pi^2)^(1/3);
+ *             where rho <= 0 (or NaN):  s = +inf, x = 0; such a voxel is in no region and no bin.  s is the only value here that is
+ *             not bit-defined (sqrt and cbrt are library functions); nothing below uses it.
+ *   s < e     for a threshold e on s the host forms  a = C*e,  a2 = a*a,  T(e) = (a2*a2)*a2;  per voxel  r2 = rho*rho,  r4 = r2*r2,
+ *             r8 = r4*r4,  q = (g2*g2)*g2.  "s < e" MEANS  q < T(e)*r8:  multiplications and one comparison.  Denormal products take
+ *             part as they are: nothing is flushed to zero.
+ *   bins      edges e_0 < ... < e_m put a voxel into bin k = (the number of j with T(e_j)*r8 <= q) - 1; outside 0 .. m - 1 it is
+ *             not counted.  (A binary search gives the same k: the products are monotone in T.)  x goes into its bins the same
+ *             way, straight against its edges: k = (the number of j with xe_j <= x) - 1.
+ *   region    rho > 0  and  s < s_cut (as above)  and  rho < rho_cut.  Its classes:  0 attractive, x < -rho_split;  1 van der Waals,
+ *             -rho_split <= x <= rho_split;  2 repulsive, x > rho_split.  s is dimensionless when density and lattice share a length
+ *             unit; rho_cut and rho_split are in the density's units.
+ *   field     xb_nci_field: s and x of every voxel, N doubles each in C order, into s_host and x_host (host memory) or s_dev and
+ *             x_dev (device memory of the context's device; neither overlaps the resident density or the other) -- either both
+ *             host pointers or both device pointers are non-null.  The call returns when the result is written.
+ *   sums      xb_nci_sum: over the voxels of the region that carry a label a with 0 <= a < n (labels < 0 and >= n are skipped), per
+ *             key 3*a + class:  count[key] = the voxel count,  charge[key] = the sum of rho times voxel_volume,  charge2[key] = the
+ *             sum of r2 = rho*rho times voxel_volume; 3 n entries each.  The terms are bit-defined; the order of the sums is free
+ *             (float atomics, as xb_laplacian_sum).  n <= 85 labels (3 n <= 256 keys) sum in LDS bins per block, more in global
+ *             memory; waves that hold one key add once per wave.
+ *   hist      xb_nci_hist: counts[ks * n_x + kx] = the number of voxels with rho > 0 in bin ks of s_edges[0 .. n_s] and bin kx of
+ *             x_edges[0 .. n_x]: exact integers.  n_s * n_x <= XB_NCI_HIST_LDS_BINS bins are counted in LDS per block, more in
+ *             global memory.
+ * XB_STENCIL_GATHER in `flags` reads the 19 values from global memory, one thread per voxel, instead of staging 8 x 8 x 32 tiles
+ * with their halo in LDS: the second implementation of all three, same bits (s included: the same functions on the same bits).
+ * XB_E_STATE: no grid, no density (sums: no labels) on this grid yet, a context that holds a slab;  XB_E_ARG: a null pointer, host
+ * and device outputs of the field mixed or incomplete, unknown flag bits, n < 1, n_s < 1 or n_x < 1, a threshold (s_cut, rho_cut,
+ * rho_split) that is not finite or negative, an edge that is not finite, s edges below 0, edges that do not increase strictly, a
+ * lattice xb_stencil_coeffs refuses, a device output that is not N doubles of device memory;  XB_E_LIMIT: n above (2^31 - 1) / 3,
+ * n_s, n_x or n_s * n_x above XB_NCI_BINS_MAX.  No option key, no timer slot: a caller times the calls.  The device buffer of the
+ * sums (72 n bytes) and of the histogram (8 (n_s + n_x + 2 + n_s n_x) bytes) is one, kept while the grid stays and counted by
+ * xb_memory_stats; the field for host outputs goes through the context's scratch and a temporary buffer of N doubles. */
+#define XB_NCI_C 0x1.8bfd4dd6882cbp+2 /* 2 (3 pi^2)^(1/3) = 6.187335452560272, the nearest double */
+enum { XB_NCI_ATTRACTIVE = 0, XB_NCI_VDW = 1, XB_NCI_REPULSIVE = 2, XB_NCI_CLASSES = 3 };
+enum { XB_NCI_HIST_LDS_BINS = 1024, XB_NCI_BINS_MAX = 16777216 };
+int xb_nci_field(xb_ctx *c, const double lattice[9], int flags, double *s_host, double *x_host, void *s_dev, void *x_dev);
+int xb_nci_sum(xb_ctx *c, const double lattice[9], int64_t n, double voxel_volume, double s_cut, double rho_cut, double rho_split,
+               int flags, int64_t *count, double *charge, double *charge2);
+int xb_nci_hist(xb_ctx *c, const double lattice[9], const double *s_edges, int64_t n_s, const double *x_edges, int64_t n_x, int flags,
+                int64_t *counts);
 /* ---- Hirshfeld (stockholder) charges from radial pro-atom tables, the promolecular density and the deformation density (the charge
  * Critic2, Chargemol and Multiwfn print beside the Bader one: every voxel's density is shared among the atoms in proportion to what
  * each FREE atom would put there, w_a(r) = rho0_a(|r - R_a|) / sum_b rho0_b(|r - R_b|): no surfaces, no maxima, no sensitivity to

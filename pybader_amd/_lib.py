@@ -51,6 +51,12 @@ XB_CRITICAL_LUT_SIZE = 16384
 XB_STENCIL_GATHER = 1
 XB_STENCIL_COEFFS = 51
 XB_STENCIL_POINT_VALUES = 10
+# xb_nci_field / xb_nci_sum / xb_nci_hist: C = 2 (3 pi^2)^(1/3) of the reduced gradient (the header's macro XB_NCI_C, the same
+# double), the classes of the region, the bins up to which a block counts in LDS and the most bins a histogram may have
+NCI_C = float.fromhex('0x1.8bfd4dd6882cbp+2')
+XB_NCI_ATTRACTIVE, XB_NCI_VDW, XB_NCI_REPULSIVE, XB_NCI_CLASSES = range(4)
+XB_NCI_HIST_LDS_BINS = 1024
+XB_NCI_BINS_MAX = 1 << 24
 # xb_hirshfeld_sum / xb_hirshfeld_field: the bit of `flags` that makes every tile run over the whole image list, the candidates a
 # tile's list holds, and the two modes of the field
 XB_HIRSHFELD_FULL_SEARCH = 1
@@ -138,6 +144,9 @@ SYMBOLS = {
     'xb_laplacian_field': (_int, [_vp, _pdbl, _int, _vp, _vp]),
     'xb_laplacian_sum': (_int, [_vp, _pdbl, _i64, _dbl, _int, _pdbl, _pdbl, _pdbl]),
     'xb_stencil_points': (_int, [_vp, _pdbl, _vp, _i64, _vp]),
+    'xb_nci_field': (_int, [_vp, _pdbl, _int, _vp, _vp, _vp, _vp]),
+    'xb_nci_sum': (_int, [_vp, _pdbl, _i64, _dbl, _dbl, _dbl, _dbl, _int, _pi64, _pdbl, _pdbl]),
+    'xb_nci_hist': (_int, [_vp, _pdbl, _pdbl, _i64, _pdbl, _i64, _int, _pi64]),
     'xb_hirshfeld_images': (_int, [_pdbl, _pdbl, _vp, _i64, _pdbl, _i64, _pi64, _vp, _i64]),
     'xb_hirshfeld_setup': (_int, [_vp, _pdbl, _pdbl, _vp, _i64, _pdbl, _pdbl, _i64, _i64]),
     'xb_hirshfeld_release': (_int, [_vp]),
@@ -938,6 +947,49 @@ class Context:
         out = np.zeros((idx.shape[0], XB_STENCIL_POINT_VALUES), np.float64)
         check(self.lib.xb_stencil_points(self.h, lat.ctypes.data_as(_pdbl), _ptr(idx), idx.shape[0], _ptr(out)))
         return out
+
+    def nci_field(self, lattice, gather=False, on_device=False, out=None):
+        """the reduced density gradient s and sign(lambda2) rho of the resident density at every voxel (xb_nci_field; `lattice`
+        the cell, a row per axis; `gather`: the second implementation, as in laplacian_field) -> (s, x), f64 of the grid's shape
+        each: host arrays, or with `on_device` two device.DeviceArray (`out`: a pair to write into instead of new ones)"""
+        lat = _f64(lattice).reshape(9)
+        flags = XB_STENCIL_GATHER if gather else 0
+        if on_device or out is not None:
+            from . import device
+            if out is None:
+                out = [device.DeviceArray(self, self.shape or (0,), np.float64) for _ in range(2)]
+            ptr = [C.c_void_p(self._flat('nci_field', o, {np.dtype(np.float64): 64}, True)[0].ptr) for o in out]
+            check(self.lib.xb_nci_field(self.h, lat.ctypes.data_as(_pdbl), flags, None, None, ptr[0], ptr[1]))
+            return out[0], out[1]
+        s, x = np.empty(self.shape or (0,), np.float64), np.empty(self.shape or (0,), np.float64)
+        check(self.lib.xb_nci_field(self.h, lat.ctypes.data_as(_pdbl), flags, _ptr(s), _ptr(x), None, None))
+        return s, x
+
+    def nci_sum(self, lattice, n, voxel_volume, s_cut, rho_cut, rho_split, gather=False):
+        """the NCI region (rho > 0, s < s_cut, rho < rho_cut) of the resident density summed over the voxels of each resident
+        label 0 .. n - 1 and each class (attractive, van der Waals, repulsive by sign(lambda2) rho against rho_split)
+        (xb_nci_sum) -> (count i64[n, 3], charge f64[n, 3], charge2 f64[n, 3]): the voxel count, the sums of rho and of rho^2,
+        the sums multiplied once by voxel_volume"""
+        lat, n = _f64(lattice).reshape(9), int(n)
+        count = np.zeros((max(n, 0), 3), np.int64)
+        charge, charge2 = np.zeros((max(n, 0), 3), np.float64), np.zeros((max(n, 0), 3), np.float64)
+        check(self.lib.xb_nci_sum(self.h, lat.ctypes.data_as(_pdbl), n, float(voxel_volume), float(s_cut), float(rho_cut),
+                                  float(rho_split), XB_STENCIL_GATHER if gather else 0, count.ctypes.data_as(_pi64),
+                                  charge.ctypes.data_as(_pdbl), charge2.ctypes.data_as(_pdbl)))
+        return count, charge, charge2
+
+    def nci_hist(self, lattice, s_edges, x_edges, gather=False):
+        """the histogram of the resident density's voxels with rho > 0 over the bins of s (edges `s_edges` f64[n_s + 1]) and of
+        sign(lambda2) rho (`x_edges` f64[n_x + 1]) (xb_nci_hist) -> i64[n_s, n_x], exact"""
+        lat = _f64(lattice).reshape(9)
+        se, xe = (np.ascontiguousarray(e, dtype=np.float64).reshape(-1) for e in (s_edges, x_edges))
+        n_s, n_x = se.shape[0] - 1, xe.shape[0] - 1
+        # (a refused bin count never reaches the allocation of its counts)
+        ok = 1 <= n_s <= XB_NCI_BINS_MAX and 1 <= n_x <= XB_NCI_BINS_MAX and n_s * n_x <= XB_NCI_BINS_MAX
+        counts = np.zeros((n_s, n_x) if ok else (1, 1), np.int64)
+        check(self.lib.xb_nci_hist(self.h, lat.ctypes.data_as(_pdbl), se.ctypes.data_as(_pdbl), n_s, xe.ctypes.data_as(_pdbl), n_x,
+                                   XB_STENCIL_GATHER if gather else 0, counts.ctypes.data_as(_pi64)))
+        return counts
 
     def hirshfeld_setup(self, lattice, atoms_cart, species, tables, r_cut):
         """the cell, the atoms and the pro-atoms of the Hirshfeld calls go to the device (xb_hirshfeld_setup; `lattice` the cell, a

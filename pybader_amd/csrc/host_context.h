@@ -38,6 +38,7 @@ static void merge_free(xb_ctx *c);
 static void voronoi_free(xb_ctx *c);
 static void critical_free(xb_ctx *c);
 static void stencil_free(xb_ctx *c);
+static void nci_free(xb_ctx *c);
 static void hirshfeld_free(xb_ctx *c);
 static void free_grid(xb_ctx *c) {
     weight_free(c);
@@ -47,6 +48,7 @@ static void free_grid(xb_ctx *c) {
     voronoi_free(c);
     critical_free(c);
     stencil_free(c);
+    nci_free(c);
     hirshfeld_free(c);
     c->have_rho = c->have_labels = false;
     hipFree(c->rho); hipFree(c->grad); hipFree(c->labels); hipFree(c->known); hipFree(c->first); hipFree(c->list);

@@ -145,10 +145,10 @@ __device__ __forceinline__ void st_wave_add(const Sink &S, int a, double s, doub
     for (int o = 32; o > 0; o >>= 1) { s += __shfl_xor(s, o); m += __shfl_xor(m, o); }
     if ((int)(threadIdx.x % XB_WAVE) == leader) S.add(a, s, m, c);
 }
-// one step of a wave (all lanes call it): this lane's voxel has label a in [0, n), or a = -1 for nothing, and the Laplacian v
+// one step of a wave (all lanes call it): this lane's voxel has the key a >= 0, or a = -1 for nothing, and adds s to the first sum
+// of its key and m to the second; both must be zero where a = -1
 template <class Sink>
-__device__ __forceinline__ void st_step(const Sink &S, StAcc &A, int a, double v) {
-    const double s = a >= 0 ? v : 0., m = a >= 0 ? fabs(v) : 0.;
+__device__ __forceinline__ void st_step2(const Sink &S, StAcc &A, int a, double s, double m) {
     const unsigned long long act = __ballot(a >= 0);
     if (!act) return;
     const int la = __shfl(a, __ffsll((long long)act) - 1);
@@ -174,6 +174,11 @@ __device__ __forceinline__ void st_step(const Sink &S, StAcc &A, int a, double v
         else if (mine) S.add(a, s, m, 1u);
         todo &= ~grp;
     }
+}
+// the Laplacian's step: label a in [0, n) or -1, the sums of v and of its magnitude
+template <class Sink>
+__device__ __forceinline__ void st_step(const Sink &S, StAcc &A, int a, double v) {
+    st_step2(S, A, a, a >= 0 ? v : 0., a >= 0 ? fabs(v) : 0.);
 }
 template <class Sink>
 __device__ __forceinline__ void st_finish(const Sink &S, StAcc &A) {

@@ -330,6 +330,25 @@ class Bader:
             b = point_properties(self.reference, self.lattice, self.atoms_bond_graph.voxels)
             self.atoms_bond_laplacian, self.atoms_bond_ellipticity = b.laplacian, b.ellipticity
 
+    nci_flag = False            # True: _run runs nci_analysis() after laplacian_analysis() (no other step changes)
+    nci_s_cut = 0.5             # the NCI region: s below this,
+    nci_rho_cut = 0.05          # ... the reference density below this (its units; 0.05 e / bohr^3: see pybader_amd.nci for e / A^3)
+    nci_rho_split = 0.01        # |sign(lambda2) rho| up to which a voxel of the region counts as van der Waals
+
+    def nci_analysis(self):
+        """The non-covalent interaction regions of the reference density per atom (pybader_amd.nci) -- no counterpart in the
+        reference.  The region is rho > 0, s < nci_s_cut, rho < nci_rho_cut; its classes by sign(lambda2) rho against
+        nci_rho_split are attractive, van der Waals and repulsive.  From atoms_volumes: atoms_nci_count [n, 3] (voxels),
+        atoms_nci_volume [n, 3] and atoms_nci_charge [n, 3] (the integral of the reference density).  With critical_flag set as
+        well (critical_analysis() runs before this): atoms_bond_nci [B], for every bond voxel atoms_bond_graph.voxel the class
+        of the region it lies in (0, 1, 2), or -1 outside the region."""
+        from .nci import bond_classes, nci_regions
+        cuts = (self.nci_s_cut, self.nci_rho_cut, self.nci_rho_split)
+        r = nci_regions(self.reference, self.atoms_volumes, self.lattice, self.atoms.shape[0], self.voxel_volume, *cuts)
+        self.atoms_nci_count, self.atoms_nci_volume, self.atoms_nci_charge = r.count, r.volume, r.charge
+        if self.critical_flag:
+            self.atoms_bond_nci = bond_classes(self.reference, self.lattice, self.atoms_bond_graph.voxel, *cuts)
+
     hirshfeld_flag = False    # True: _run runs hirshfeld_analysis() before voronoi_partition() (no other step changes)
     hirshfeld_field = False   # ... and True: it keeps the deformation density as well
     proatoms = None           # a hirshfeld.ProAtoms: the free atoms hirshfeld_analysis() weighs with
@@ -418,6 +437,8 @@ class Bader:
             self.critical_analysis()
         if self.laplacian_flag:   # (after critical_analysis, whose points it reads when both are set)
             self.laplacian_analysis()
+        if self.nci_flag:   # (after critical_analysis, whose bond voxels it reads when both are set; it reads atoms_volumes)
+            self.nci_analysis()
         if self.adjacency_flag:
             self.bond_surfaces()
         if self.hirshfeld_flag:   # (it reads the density alone: its place is free)
