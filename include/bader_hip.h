@@ -527,6 +527,86 @@ int xb_nci_sum(xb_ctx *c, const double lattice[9], int64_t n, double voxel_volum
                int flags, int64_t *count, double *charge, double *charge2);
 int xb_nci_hist(xb_ctx *c, const double lattice[9], const double *s_edges, int64_t n_s, const double *x_edges, int64_t n_x, int flags,
                 int64_t *counts);
+/* ---- isosurfaces: marching tetrahedra on the Freudenthal (Kuhn) triangulation of the periodic voxel lattice (the 0.001 a.u.
+ * molecular surface with its area and volume, in total and per atom; the zero envelopes of the Laplacian; the s = 0.5 surface of
+ * the NCI index coloured by sign(lambda2) rho) -- no counterpart in the reference ----
+ * Reads a field f of the whole grid -- the resident density (field_dev null) or N doubles of device memory in C order -- and, with
+ * n_labels >= 1, the resident labels; nothing resident is written.  The triangulation is the one of the critical points above:
+ * 6 tetrahedra per cube, no ambiguous case, crack-free across tiles and the periodic boundary; connectivity is integers.
+ *   inside    inside(v) = f[v] >= level, a plain IEEE comparison: a NaN is outside, -0.0 and +0.0 are equal
+ *   edges     voxel v owns the 7 lattice edges (v, k), k = 0 .. 6, towards v + d_k (the positive seven offsets of the critical
+ *             points, every coordinate wrapped).  An edge CROSSES iff its two ends differ in inside().  The crossing edges are the
+ *             vertices; the id of a vertex is the rank of 7 lin(v) + k among them, ascending
+ *   vertex    a = f[v], b = f[v + d_k], t = (level - a) / (b - a): one division.  p_i = (double)v_i + (d_k,i ? t : 0), in voxel
+ *             coordinates in the frame of its OWNER v.  One expression on the same two values, built without contraction: every
+ *             triangle that uses the vertex sees the same bits.  With a colour field g (colour_dev, N doubles, or null):
+ *             colour = g[v] + t * (g[v + d_k] - g[v])
+ *   cube      cube v has the corners v + (cx, cy, cz), corner number 4 cx + 2 cy + cz.  Tetrahedron tau = 0 .. 5 is the path
+ *             P_0 = 0 -> P_1 = e_a -> P_2 = e_a + e_b -> P_3 = (1, 1, 1) for (a, b, c) the tau-th permutation of (0, 1, 2) in
+ *             lexicographic order; m = its inside bits (bit i: P_i).  Its edge P_lo P_hi (lo < hi) is the lattice edge
+ *             (v + P_lo, k) with d_k = P_hi - P_lo
+ *   triangles popcount(m) = 1 or 3: one triangle, on the three edges at the lone corner, the other ends ascending;  2 (inside i < j,
+ *             outside k < l): the quadrilateral ik il jl jk split along ik -- jl into (ik, il, jl) and (ik, jl, jk);  0 or 4: none.
+ *             The last two corners of a triangle are swapped where that makes its normal (q1 - q0) x (q2 - q0) in voxel
+ *             coordinates point from the inside corners to the outside ones, so every mesh edge is traversed once in each direction.
+ *             The triangles of the mesh ascend in (lin of the cube, tau, triangle within tau)
+ *   table     xb_isosurface_table: out[(16 tau + m) 8 + 0] = the number of triangles, out[.. + 1 + 3 t + j] = corner j of triangle t
+ *             as (owner corner of the cube) << 3 | k, 255 where unused; 768 bytes; host only, needs no GPU
+ *   per tri   three vertex ids (int64);  wrap (uint16): bit 3 corner + axis is set iff that corner's owner lies across the periodic
+ *             boundary from the cube along the axis -- the corner in the cube's frame is then vertex + n_axis;  cell (int64): lin of
+ *             the cube
+ *   area      the sum over the triangles of 0.5 sqrt((cx cx + cy cy) + cz cz), c = E1 x E2, E_j = (e_0 A[0][j] + e_1 A[1][j]) +
+ *             e_2 A[2][j] for e = q1 - q0 and q2 - q0, the corners q in the cube's frame, A the voxel lattice of the Laplacian block
+ *   volume    (|det A| / 6) times the sum over all tetrahedra of the inside fraction, det in the order of that block.  With u(a, b)
+ *             the crossing's distance from corner a on the edge towards b (t where a < b, 1 - t otherwise):
+ *               1 inside corner i, the others j < k < l:   (u(i,j) u(i,k)) u(i,l)
+ *               3 inside, outside o, the others j < k < l:  1 - (u(o,j) u(o,k)) u(o,l)
+ *               2 inside i < j, outside k < l:   (u(i,k) u(i,l) + (u(i,k) u(j,l)) (1 - u(i,l))) + (u(j,k) u(j,l)) (1 - u(i,k))
+ *                                                (the wedge as the tetrahedra (P_i ik il P_j), (P_j ik il jl), (P_j ik jl jk))
+ *               4: 1;  0: nothing
+ *   labels    with n_labels >= 1, volume_by_label[a] = (|det A| / 6) times the sum of fraction / popcount(m) over every inside
+ *             corner of every tetrahedron whose voxel carries label a (labels < 0 and >= n are skipped): a voxel whose 24
+ *             tetrahedra are all inside gets one voxel volume, as in xb_charge_sum
+ * The terms are bit-defined; the order of the sums is free (float atomics, as xb_laplacian_sum); LDS bins up to 256 labels.
+ * Axes below 4: the definition stands as written (wrapped neighbours coincide); watertightness is not claimed there.
+ * No smoothing, no vertex normals, no higher-order interpolation, no marching cubes.
+ *   calls     xb_isosurface runs the passes (count; offsets and a scan in kernels of their own -- no kernel waits for another
+ *             workgroup; emit) and keeps the mesh on the device: counts[0] = V, counts[1] = T.  It compares the emit pass's own
+ *             counters with the count pass (XB_E_STATE on a mismatch); the emit pass never writes beyond the counted capacities.
+ *             xb_isosurface_fetch copies into host arrays (on_device 0) or device arrays (on_device 1): vertices f64[3 V], colour
+ *             f64[V] (null: not wanted), triangles i64[3 T], wrap u16[T], cell i64[T], scalars = {area, volume},
+ *             volume_by_label f64[n_labels] (may be null when n_labels was 0).  It checks before it writes.
+ *             xb_isosurface_release frees the mesh.  Any writer of the density discards the kept result.
+ *   nci       xb_isosurface_nci_mask: s[v] = XB_ISO_NCI_RAISED wherever rho[v] >= rho_cut or s[v] is not below it (the +inf of a
+ *             voxel without density, a NaN), in place on N doubles of device memory (what NCIPLOT does before it draws
+ *             s = s_cut); rho is the resident density
+ * XB_ISO_GATHER in `flags` reads the eight corners from global memory, one thread per voxel, instead of staging 8 x 8 x 32 tiles
+ * with their halo in LDS: the second implementation, same results.
+ * XB_E_STATE: no grid, no density, no labels with n_labels >= 1, a context that holds a slab (fetch: no result);  XB_E_ARG: a null
+ * pointer, a field that is not N doubles of device memory or overlaps the scratch, field and colour overlapping without being one
+ * array, unknown flag bits, a level that is not finite, n_labels < 0, a lattice xb_stencil_coeffs refuses, capacity below the
+ * counts in a fetch, a colour asked of a mesh without;  XB_E_LIMIT: 7 N beyond the 64-bit range, n_labels above 2^31 - 1.  No
+ * option key, no timer slot.  Memory: the per-voxel words and the scan live in the context's scratch (already counted); the kept
+ * mesh is 24 V (+ 8 V with a colour) + 34 T bytes, each array at least one element, counted by xb_memory_stats.
+ *   streams   xb_isosurface reads the caller's arrays on the context's stream.  A field or colour that another stream produces (a
+ *             tensor made on a non-blocking stream) must be ordered first: xb_stream_wait(c, stream) makes the context's stream take
+ *             up its work after everything queued on `stream` so far (an event, no host wait).  pybader_amd does so for every device
+ *             field and colour it hands in.  xb_isosurface returns when the mesh is written: the caller may free its arrays then.
+ * xb_device_write copies host bytes into device memory of the context's device (the counterpart of xb_device_read) and returns when
+ * they are there.  The target is the caller's own memory: it must not be memory the context owns (the resident density handed out
+ * by xb_density_ptr, the labels, the scratch) -- the call invalidates nothing. */
+#define XB_ISO_NCI_RAISED 100.0
+enum { XB_ISO_GATHER = 1 };
+enum { XB_ISO_TABLE_SIZE = 768 };
+int xb_isosurface_table(uint8_t *out);
+int xb_isosurface(xb_ctx *c, const void *field_dev, const void *colour_dev, const double lattice[9], double level, int64_t n_labels,
+                  int flags, int64_t counts[2]);
+int xb_isosurface_fetch(xb_ctx *c, int on_device, void *vertices, void *colour, void *triangles, void *wrap, void *cell,
+                        int64_t cap_vertices, int64_t cap_triangles, double scalars[2], double *volume_by_label, int64_t cap_labels);
+int xb_isosurface_release(xb_ctx *c);
+int xb_isosurface_nci_mask(xb_ctx *c, void *s_dev, double rho_cut);
+int xb_stream_wait(xb_ctx *c, void *stream);
+int xb_device_write(xb_ctx *c, void *dev_ptr, const void *src_host, int64_t bytes);
 /* ---- Hirshfeld (stockholder) charges from radial pro-atom tables, the promolecular density and the deformation density (the charge
  * Critic2, Chargemol and Multiwfn print beside the Bader one: every voxel's density is shared among the atoms in proportion to what
  * each FREE atom would put there, w_a(r) = rho0_a(|r - R_a|) / sum_b rho0_b(|r - R_b|): no surfaces, no maxima, no sensitivity to

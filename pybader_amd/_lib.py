@@ -57,6 +57,11 @@ NCI_C = float.fromhex('0x1.8bfd4dd6882cbp+2')
 XB_NCI_ATTRACTIVE, XB_NCI_VDW, XB_NCI_REPULSIVE, XB_NCI_CLASSES = range(4)
 XB_NCI_HIST_LDS_BINS = 1024
 XB_NCI_BINS_MAX = 1 << 24
+# xb_isosurface: the bit of `flags` that reads the cube's corners from global memory instead of staging tiles; the bytes of
+# xb_isosurface_table; what xb_isosurface_nci_mask raises s to (the header's macro XB_ISO_NCI_RAISED)
+XB_ISO_GATHER = 1
+XB_ISO_TABLE_SIZE = 768
+ISO_NCI_RAISED = 100.0
 # xb_hirshfeld_sum / xb_hirshfeld_field: the bit of `flags` that makes every tile run over the whole image list, the candidates a
 # tile's list holds, and the two modes of the field
 XB_HIRSHFELD_FULL_SEARCH = 1
@@ -147,6 +152,13 @@ SYMBOLS = {
     'xb_nci_field': (_int, [_vp, _pdbl, _int, _vp, _vp, _vp, _vp]),
     'xb_nci_sum': (_int, [_vp, _pdbl, _i64, _dbl, _dbl, _dbl, _dbl, _int, _pi64, _pdbl, _pdbl]),
     'xb_nci_hist': (_int, [_vp, _pdbl, _pdbl, _i64, _pdbl, _i64, _int, _pi64]),
+    'xb_isosurface_table': (_int, [_vp]),
+    'xb_isosurface': (_int, [_vp, _vp, _vp, _pdbl, _dbl, _i64, _int, _pi64]),
+    'xb_isosurface_fetch': (_int, [_vp, _int, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _pdbl, _pdbl, _i64]),
+    'xb_isosurface_release': (_int, [_vp]),
+    'xb_isosurface_nci_mask': (_int, [_vp, _vp, _dbl]),
+    'xb_stream_wait': (_int, [_vp, _vp]),
+    'xb_device_write': (_int, [_vp, _vp, _vp, _i64]),
     'xb_hirshfeld_images': (_int, [_pdbl, _pdbl, _vp, _i64, _pdbl, _i64, _pi64, _vp, _i64]),
     'xb_hirshfeld_setup': (_int, [_vp, _pdbl, _pdbl, _vp, _i64, _pdbl, _pdbl, _i64, _i64]),
     'xb_hirshfeld_release': (_int, [_vp]),
@@ -991,6 +1003,58 @@ class Context:
                                    XB_STENCIL_GATHER if gather else 0, counts.ctypes.data_as(_pi64)))
         return counts
 
+    def _field_ptr(self, what, obj):
+        """the device pointer of a C-contiguous float64 device array of the grid's shape, or None for None; the context's stream
+        takes up its work after everything queued so far on the stream the array belongs to (xb_stream_wait)"""
+        if obj is None:
+            return None
+        d, stream = self._flat(what, obj, {np.dtype(np.float64): 64}, False)
+        check(self.lib.xb_stream_wait(self.h, stream))
+        return C.c_void_p(d.ptr)
+
+    def isosurface(self, lattice, level, field=None, colour=None, n=0, gather=False, fetch=True):
+        """marching tetrahedra on the resident density, or on `field` (a float64 device array of the grid's shape), at `level`
+        (xb_isosurface + xb_isosurface_fetch; `colour`: a float64 device array interpolated onto the vertices; `n`: the resident
+        labels 0 .. n - 1 share the inside volume; `gather`: the second implementation) -> (vertices f64[V, 3] in voxel
+        coordinates, colour f64[V] or None, triangles i64[T, 3], wrap u16[T], cells i64[T], area, volume, volume_by_label f64[n]).
+        The mesh stays on the device until isosurface_release or the next call; without `fetch` only (V, T) comes back."""
+        lat, n = _f64(lattice).reshape(9), int(n)
+        counts = np.zeros(2, np.int64)
+        check(self.lib.xb_isosurface(self.h, self._field_ptr('isosurface', field), self._field_ptr('isosurface', colour),
+                                     lat.ctypes.data_as(_pdbl), float(level), n, XB_ISO_GATHER if gather else 0, counts.ctypes.data_as(_pi64)))
+        if not fetch:
+            return int(counts[0]), int(counts[1])
+        return self.isosurface_fetch(int(counts[0]), int(counts[1]), colour is not None, n)
+
+    def isosurface_fetch(self, n_vertices, n_triangles, with_colour=False, n=0):
+        """the mesh of the last isosurface call into host arrays of the given capacities (xb_isosurface_fetch)"""
+        v, t = int(n_vertices), int(n_triangles)
+        vert, col = np.zeros((v, 3), np.float64), (np.zeros(v, np.float64) if with_colour else None)
+        tri, wrap, cell = np.zeros((t, 3), np.int64), np.zeros(t, np.uint16), np.zeros(t, np.int64)
+        sc, vbl = np.zeros(2, np.float64), np.zeros(max(int(n), 0), np.float64)
+        check(self.lib.xb_isosurface_fetch(self.h, 0, _ptr(vert), _ptr(col) if with_colour else None, _ptr(tri), _ptr(wrap), _ptr(cell), v, t,
+                                           sc.ctypes.data_as(_pdbl), vbl.ctypes.data_as(_pdbl), vbl.shape[0]))
+        return vert, col, tri, wrap, cell, float(sc[0]), float(sc[1]), vbl
+
+    def isosurface_release(self):
+        """free the mesh xb_isosurface keeps on the device"""
+        check(self.lib.xb_isosurface_release(self.h))
+
+    def isosurface_nci_mask(self, s, rho_cut):
+        """s := ISO_NCI_RAISED wherever the resident density is >= rho_cut or s is not below it, in place on the float64 device
+        array `s` (xb_isosurface_nci_mask)"""
+        d, stream = self._flat('isosurface_nci_mask', s, {np.dtype(np.float64): 64}, True)
+        check(self.lib.xb_stream_wait(self.h, stream))
+        check(self.lib.xb_isosurface_nci_mask(self.h, C.c_void_p(d.ptr), float(rho_cut)))
+
+    def device_copy(self, host):
+        """a new device.DeviceArray with the content of the host array `host` (xb_device_write)"""
+        from . import device
+        host = np.ascontiguousarray(host)
+        out = device.DeviceArray(self, host.shape, host.dtype)
+        check(self.lib.xb_device_write(self.h, C.c_void_p(out.ptr), _ptr(host), host.nbytes))
+        return out
+
     def hirshfeld_setup(self, lattice, atoms_cart, species, tables, r_cut):
         """the cell, the atoms and the pro-atoms of the Hirshfeld calls go to the device (xb_hirshfeld_setup; `lattice` the cell, a
         row per axis; `atoms_cart` [n, 3]; `species` int[n]; `tables` f64[S, K + 1] uniform in r^2 with a last column of zeros;
@@ -1291,6 +1355,14 @@ def critical_lut():
     out = np.zeros(XB_CRITICAL_LUT_SIZE, np.uint8)
     check(load().xb_critical_lut(_ptr(out)))
     return out
+
+
+def isosurface_table():
+    """xb_isosurface_table: uint8[6, 16, 8] -- per tetrahedron and inside mask the number of triangles and their corners as
+    (owner corner of the cube) << 3 | k, 255 where unused (host only: needs the library, not a GPU)"""
+    out = np.zeros(XB_ISO_TABLE_SIZE, np.uint8)
+    check(load().xb_isosurface_table(_ptr(out)))
+    return out.reshape(6, 16, 8)
 
 
 def hirshfeld_images(lattice, atoms_cart, species, r_cut):

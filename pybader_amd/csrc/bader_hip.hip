@@ -1,7 +1,7 @@
 // bader_hip.hip -- libbader_hip.so: HIP kernels + C ABI (include/bader_hip.h) for gfx950.  ONE translation unit:
-//   kernels    k_common.h k_masks.h k_fused.h k_trace.h k_ongrid.h k_edges.h k_sums.h k_text.h k_format.h (fmt_core.h) k_interop.h k_weight.h k_moments.h k_adjacency.h k_merge.h k_voronoi.h k_critical.h k_stencil.h k_nci.h k_hirshfeld.h
+//   kernels    k_common.h k_masks.h k_fused.h k_trace.h k_ongrid.h k_edges.h k_sums.h k_text.h k_format.h (fmt_core.h) k_interop.h k_weight.h k_moments.h k_adjacency.h k_merge.h k_voronoi.h k_critical.h k_stencil.h k_nci.h k_hirshfeld.h k_isosurface.h
 //   host side  this file (context struct, options, statistics, timing) + host_context.h (life cycle, transfers)
-//              + host_assign.h (the table outside an assignment, the assignments) + host_refine.h + host_sums.h + host_slab_table.h (host-driven slab calls) + host_interop.h (device arrays in and out) + host_weight.h (the weight method) + host_moments.h (moments per label) + host_adjacency.h (surfaces between labels) + host_merge.h (merging volumes by persistence) + host_voronoi.h (the nearest-atom partition) + host_critical.h (critical points and the bond graph) + host_stencil.h (the Laplacian and the Hessian of the density) + host_nci.h (the NCI index: reduced gradient, sign(lambda2) rho, region sums, histogram) + host_hirshfeld.h (Hirshfeld charges, the promolecular and the deformation density) + comm.h (RCCL through the ABI)
+//              + host_assign.h (the table outside an assignment, the assignments) + host_refine.h + host_sums.h + host_slab_table.h (host-driven slab calls) + host_interop.h (device arrays in and out) + host_weight.h (the weight method) + host_moments.h (moments per label) + host_adjacency.h (surfaces between labels) + host_merge.h (merging volumes by persistence) + host_voronoi.h (the nearest-atom partition) + host_critical.h (critical points and the bond graph) + host_stencil.h (the Laplacian and the Hessian of the density) + host_nci.h (the NCI index: reduced gradient, sign(lambda2) rho, region sums, histogram) + host_hirshfeld.h (Hirshfeld charges, the promolecular and the deformation density) + host_isosurface.h (isosurfaces by marching tetrahedra) + comm.h (RCCL through the ABI)
 //              + slab_step.h (the slab step with its control flow on the device)
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -shared (see pybader_amd/build.py).
 #include "bader_kernels.h"
@@ -44,6 +44,7 @@ static inline hipError_t xb_counted_sync(hipStream_t s) { xb_waits++; return (hi
 #include "k_stencil.h"
 #include "k_nci.h"
 #include "k_hirshfeld.h"
+#include "k_isosurface.h"
 
 // =============================================================================================
 // host side
@@ -270,6 +271,15 @@ struct xb_ctx {
     int64_t hs_n = 0;
     int hs_cus = 0;   // compute units of the device (sizes the sums' launch)
     HsGeom hs_geom{};
+    // xb_isosurface (host_isosurface.h): the mesh of the last call on the device (iso_v vertices, iso_t triangles, iso_bytes in
+    // all), its two scalars and the per-label volumes.  iso_have falls with every writer of the density
+    double *iso_vert = nullptr, *iso_col = nullptr;
+    long long *iso_tri = nullptr, *iso_cell = nullptr;
+    unsigned short *iso_wrap = nullptr;
+    size_t iso_v = 0, iso_t = 0, iso_bytes = 0;
+    bool iso_have = false;
+    double iso_area = 0., iso_volume = 0.;
+    std::vector<double> iso_vbl;
     // has anything been put into the density / the labels of this grid?  (xb_moment_sum refuses a grid without; set by every
     // call that writes them or hands their pointer out, cleared when the grid's shape changes)
     bool have_rho = false, have_labels = false;
@@ -389,6 +399,7 @@ const char *xb_last_error(void) { return g_err.c_str(); }
 #include "host_stencil.h"
 #include "host_nci.h"
 #include "host_hirshfeld.h"
+#include "host_isosurface.h"
 
 int xb_set_option(xb_ctx *c, int key, int value) {
     if (!c) return fail(XB_E_ARG, "null ctx");
@@ -457,7 +468,8 @@ int xb_memory_stats(xb_ctx *c, int64_t *bytes_total, int64_t *bytes_table, int64
                               (long long)c->cp_cap * 8 + (c->cp_lut ? XB_CRITICAL_LUT_SIZE : 0) /* xb_critical_points' list and table */ +
                               (long long)c->st_cap * 8 /* xb_laplacian_sum's buffer */ +
                               (long long)c->nci_cap * 8 /* xb_nci_sum's and xb_nci_hist's buffer */ +
-                              (long long)c->hs_cap * 8 /* xb_hirshfeld_setup's buffer */;
+                              (long long)c->hs_cap * 8 /* xb_hirshfeld_setup's buffer */ +
+                              (long long)c->iso_bytes /* xb_isosurface's mesh */;
     const long long fixed = 8 * N /* rho */ + 4 * N /* labels */ + (N + 16) /* known */ + 4 * N /* first */ + N /* st */ +
                             2LL * c->max_cap * 4 + (long long)c->ovf_cap * 4 + c->blab_alloc * 13 + (long long)c->walk_cap * 3 * 80 +
                             (1 << 22) /* boxbuf */;

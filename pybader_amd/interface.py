@@ -349,6 +349,18 @@ class Bader:
         if self.critical_flag:
             self.atoms_bond_nci = bond_classes(self.reference, self.lattice, self.atoms_bond_graph.voxel, *cuts)
 
+    isosurface_level = None   # a value: _run runs isosurface_analysis() after nci_analysis() (None: no step changes)
+
+    def isosurface_analysis(self):
+        """The envelope reference density == isosurface_level (pybader_amd.isosurface; 0.001 e / bohr^3 is the usual molecular
+        surface) -- no counterpart in the reference.  Sets isosurface (an isosurface.Mesh), isosurface_area, isosurface_volume
+        (the volume inside the envelope) and atoms_isosurface_volume [n] (that volume shared among the atoms of atoms_volumes:
+        AIMAll's Vol(0.001))."""
+        from .isosurface import isosurface
+        m = isosurface(self.reference, self.lattice, self.isosurface_level, volumes=self.atoms_volumes, n=self.atoms.shape[0])
+        self.isosurface, self.isosurface_area, self.isosurface_volume = m, m.area, m.volume
+        self.atoms_isosurface_volume = m.volume_by_label
+
     hirshfeld_flag = False    # True: _run runs hirshfeld_analysis() before voronoi_partition() (no other step changes)
     hirshfeld_field = False   # ... and True: it keeps the deformation density as well
     proatoms = None           # a hirshfeld.ProAtoms: the free atoms hirshfeld_analysis() weighs with
@@ -439,6 +451,8 @@ class Bader:
             self.laplacian_analysis()
         if self.nci_flag:   # (after critical_analysis, whose bond voxels it reads when both are set; it reads atoms_volumes)
             self.nci_analysis()
+        if self.isosurface_level is not None:   # (it reads the reference density and atoms_volumes and rewrites nothing)
+            self.isosurface_analysis()
         if self.adjacency_flag:
             self.bond_surfaces()
         if self.hirshfeld_flag:   # (it reads the density alone: its place is free)

@@ -16,6 +16,7 @@ through sqrt and cbrt.
     nci_fields(density, lattice)                                                     (s, x = sign(lambda2) rho)
     nci_regions(density, volumes, lattice, n, voxel_volume, s_cut, rho_cut, rho_split)   an NciRegions
     nci_histogram(density, lattice, s_edges, x_edges)                                int64[n_s, n_x]
+    nci_isosurface(density, lattice, s_cut, rho_cut)                                 the surface s = s_cut, an isosurface.Mesh
 
 Units: s is dimensionless when density and lattice share a length unit.  rho_cut and rho_split are in the density's units; the
 defaults S_CUT, RHO_CUT, RHO_SPLIT are the usual ones in atomic units (e / bohr^3).  For a density in e / Angstrom^3 multiply
@@ -132,6 +133,23 @@ def nci_histogram(density, lattice, s_edges, x_edges, gather=False):
     -> int64[n_s, n_x], exact"""
     ctx, _ = _resident(density)
     return ctx.nci_hist(lattice, s_edges, x_edges, gather)
+
+
+def nci_isosurface(density, lattice, s_cut=S_CUT, rho_cut=RHO_CUT, gather=False):
+    """The surface s = `s_cut` of the reduced gradient of `density` (host or device array), coloured by sign(lambda2) rho -- the
+    picture of the NCI index.  As NCIPLOT does, s is first raised to _lib.ISO_NCI_RAISED wherever rho >= `rho_cut` (and where it
+    is not below that value: the +inf of a voxel without density), so only the low-density surfaces remain.  Inside, in the sense
+    of isosurface.Mesh, is s >= s_cut: the normals point into the NCI region and `volume` is what lies outside it.  The two
+    fields are made, masked and read on the device, whichever side `density` lives on.  -> isosurface.Mesh"""
+    from .isosurface import Mesh
+    if not 0.0 <= float(s_cut) < _lib.ISO_NCI_RAISED:
+        raise ValueError(f'nci_isosurface: s_cut must lie in [0, {_lib.ISO_NCI_RAISED})')
+    ctx, shape = _resident(density)
+    s, x = ctx.nci_field(lattice, gather, on_device=True)
+    ctx.isosurface_nci_mask(s, rho_cut)
+    out = ctx.isosurface(lattice, s_cut, s, x, 0, gather)
+    ctx.isosurface_release()
+    return Mesh(shape, s_cut, lattice, *out)
 
 
 def bond_classes(density, lattice, lin, s_cut=S_CUT, rho_cut=RHO_CUT, rho_split=RHO_SPLIT):
