@@ -885,6 +885,10 @@ int xb_deferred_stats(xb_ctx *c, int64_t *refine_total);
  * at least 16 x 16 x 80 voxels, no table whose brick bytes flag every brick as a possible maximum's, fewer maxima in the last assignment than one per 8 bricks), and by the per-voxel kernels
  * (everything else, and everything under XB_CHECK_VOXEL_SWEEP) */
 int xb_sweep_stats(xb_ctx *c, int64_t *bit_sweeps, int64_t *voxel_sweeps);
+/* after xb_edge_find, while its edge list is valid (nothing has rewritten `known` since): the list as the sweep left it -- voxel
+ * indices, tile by tile in the order the tiles' workgroups arrived, by row and z inside a tile -- and how many tiles the sweep
+ * listed (-1: this edge_find swept without a tile list).  `capacity` in ints; *edges is set even where the list does not fit. */
+int xb_edge_list(xb_ctx *c, int32_t *out, int64_t capacity, int64_t *edges, int64_t *tiles_listed);
 /* region growth: assignments repeated because the scheduled kill launches (XB_OPT_KILL_LAUNCHES; 6 after a chase) did not reach the
  * fixpoint, and the schedule this context uses now (raised to the worst case by the first repeat) */
 int xb_growth_stats(xb_ctx *c, int64_t *retries, int64_t *kill_launches);

@@ -194,6 +194,7 @@ SYMBOLS = {
     'xb_slow_path_stats': (_int, [_vp, _pi64, _pi64]),
     'xb_deferred_stats': (_int, [_vp, _pi64]),
     'xb_sweep_stats': (_int, [_vp, _pi64, _pi64]),
+    'xb_edge_list': (_int, [_vp, _vp, _i64, _pi64, _pi64]),
     'xb_growth_stats': (_int, [_vp, _pi64, _pi64]),
     'xb_comm_unique_id': (_int, [_vp]),
     'xb_comm_init': (_int, [_vp, _int, _int, _vp]),
@@ -1345,6 +1346,15 @@ class Context:
         a, b = C.c_int64(), C.c_int64()
         check(self.lib.xb_sweep_stats(self.h, C.byref(a), C.byref(b)))
         return a.value, b.value
+
+    def edge_list(self):
+        """(the edge list the last edge_find() left, in the sweep's order; tiles the sweep listed, -1 without a tile list)"""
+        n, t = C.c_int64(), C.c_int64()
+        check(self.lib.xb_edge_list(self.h, None, 0, C.byref(n), C.byref(t)))
+        out = np.zeros(n.value, np.int32)
+        if n.value:
+            check(self.lib.xb_edge_list(self.h, _ptr(out), out.size, C.byref(n), C.byref(t)))
+        return out, t.value
 
     def sync(self):
         check(self.lib.xb_sync(self.h))

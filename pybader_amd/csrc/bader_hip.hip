@@ -211,6 +211,7 @@ struct xb_ctx {
     int chg_n = -1;            // >= 0: the upper half of `stage` lists the chg_n voxels the last retrace pass relabelled (all known == -2 voxels)
     int list_n = 0;            // entries of `list` that hold the owned known == -2 voxels ...
     bool list_valid = false;   // ... when this is set (by xb_edge_find)
+    bool tiles_listed = false; // the last edge_find swept a tile list whose length is in CT_TILES_OWN (xb_edge_list)
     unsigned timing = 0;   // bit k: timer k records its events (xb_enable_timing)
     TimedKernel tk[XB_TIMER_COUNT];
     long long n_alloc = 0;

@@ -68,6 +68,7 @@ static int edge_find_launch(xb_ctx *c, bool *dilate_owned) {
     plane_range(g, all ? g.nx : c->halo - 1, xa, np);
     plane_range(g, all ? g.nx : c->halo - 2, xb_, npd);
     HIPCHK(hipMemsetAsync(c->counters + CT_N_EDGES, 0, sizeof(int), c->stream));
+    c->tiles_listed = false;
     {
         ScopedTimer t(c, XB_TIMER_EDGE_FIND);
         const GridL gl = light(g);
@@ -99,6 +100,7 @@ static int edge_find_launch(xb_ctx *c, bool *dilate_owned) {
             k_edge_tile_list<<<(ntiles + TPB - 1) / TPB, TPB, 0, c->stream>>>(gl, buni, tiles, c->counters + CT_TILES_OWN, 0, g.nx / ET_X);
             launch_sweep_bits(c, gl, ntiles, c->counters + CT_N_EDGES, G, brec, tiles, c->counters + CT_TILES_OWN);
             HIPCHK(hipGetLastError());
+            c->tiles_listed = true;
             *dilate_owned = false;
             return XB_OK;
         }
@@ -173,6 +175,21 @@ int xb_edge_find(xb_ctx *c, int64_t *edges) {
     c->list_valid = true;
     if (edges) *edges = (int64_t)n;
     return XB_OK;
+}
+
+int xb_edge_list(xb_ctx *c, int32_t *out, int64_t capacity, int64_t *edges, int64_t *tiles_listed) {
+    NEED_GRID("xb_edge_list");
+    if (!c->list_valid) return fail(XB_E_STATE, "xb_edge_list: call xb_edge_find first (its list is gone once `known` is rewritten)");
+    if (edges) *edges = c->list_n;
+    if (tiles_listed) {
+        int nt = -1;
+        if (c->tiles_listed)
+            if (int rc = read_counter(c, CT_TILES_OWN, &nt)) return rc;
+        *tiles_listed = nt;
+    }
+    if (!out) return XB_OK;
+    if (capacity < c->list_n) return fail(XB_E_ARG, "xb_edge_list: %d edges, room for %lld", c->list_n, (long long)capacity);
+    return download_pinned(c, out, c->list, (size_t)c->list_n * sizeof(int));
 }
 
 static int compact(xb_ctx *c, int value, int *n_out) {

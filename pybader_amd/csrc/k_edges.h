@@ -562,15 +562,17 @@ __global__ __launch_bounds__(TPB) void k_edge_flag_listed(GridL g, const double 
 //             lane = row; lanes < 24 add the four halo positions, form T and P (the rows y +- 1 are lanes +- 1) and store
 //             P and Cx: 2.3 KB
 //   phase 2   wave 0, lane = one of the 60 ring rows: edge, dilation (rows y +- 1 / x +- 1 are lanes +- 1 / +- 10), the
-//             tile's edge count by a wave scan and ONE atomic.  The maximum exception, where a tile has candidates for it:
+//             tile's edge count by a wave scan (no atomic here: one per batch).  The maximum exception, where a tile has candidates for it:
 //             the rows go to all four waves through LDS (lane = z, eight rows' record words in flight), two more barriers
-//   phase 3   wave w, lane = z: the flags and the list entries of the 8 rows of plane w
-// Three barriers per tile (five with the exception); the labels' LDS is not reused before the third.
+//   phase 3   wave w, lane = z: the flags of the 8 rows of plane w; the list entries by batches of EB_BATCH tiles (below)
+// Three barriers per tile (five with the exception), one more per batch; the labels' LDS is not reused before the third.
+// 76 VGPRs, no scratch, 31.5 KB LDS (26 KB of it the label tile): five workgroups per CU.
 #define EB_X (ET_X + 4)
 #define EB_Y (ET_Y + 4)
 #define EB_P (ET_Z + 4)
 #define EB_ROWS (EB_X * EB_Y)
 #define EB_RING ((ET_X + 2) * (ET_Y + 2))
+#define EB_BATCH 4   // tiles a workgroup sweeps per list atomic
 typedef unsigned long long eb_mask;
 __device__ __forceinline__ eb_mask eb_ballot(bool b) { return __builtin_amdgcn_ballot_w64(b); }
 __device__ __forceinline__ void eb_park(unsigned &lo, unsigned &hi, eb_mask m, bool here) {   // the wave-uniform m into one lane of (lo, hi)
@@ -605,9 +607,9 @@ __global__ __launch_bounds__(TPB) void k_edge_sweep_bits(GridL g, const double *
     static_assert(ET_Z == XB_WAVE && TPB == 4 * XB_WAVE && EB_X == 8 && EB_ROWS == 4 * 24 && ET_X == 4 && ET_Y == 8, "tile shape");
     // (a row of 68 ints is 17 x 16 bytes: lane = z reads are consecutive, the 16-byte halo reads with lane = row fall on odd strides)
     __shared__ __attribute__((aligned(16))) int tile[EB_ROWS][EB_P];
-    __shared__ eb_mask sP[EB_ROWS], sCx[EB_ROWS], sE[ET_X * ET_Y], sNear[ET_X * ET_Y];
+    __shared__ eb_mask sP[EB_ROWS], sCx[EB_ROWS], sE[EB_BATCH][ET_X * ET_Y], sNear[ET_X * ET_Y];
     __shared__ unsigned sHi[EB_ROWS];   // bits 0-3: P at p = 64..67, bits 4-7: Cx there
-    __shared__ int sOff[ET_X * ET_Y];
+    __shared__ int sOff[EB_BATCH][ET_X * ET_Y], sTile[EB_BATCH], sBase;   // a batch's rows: offsets from the batch's list base; its tiles
     __shared__ eb_mask sQ[2], sRE[EB_RING], sRC[EB_RING];   // the maximum exception across the waves: ring rows with candidates (tile / halo
     __shared__ unsigned sREh[EB_RING], sRCh[EB_RING];       // positions), the rows' edge masks and their candidates
     __shared__ unsigned char sB[ET_X + 2][3][12];   // brick bytes: ring plane, brick row y0/8 - 1 .. + 1, brick z0/8 - 1 .. + 8
@@ -615,6 +617,29 @@ __global__ __launch_bounds__(TPB) void k_edge_sweep_bits(GridL g, const double *
     const int ntz = g.nz / ET_Z, nty = g.ny / ET_Y, nb1 = g.ny >> 3, nb2 = g.nz >> 3;
     const int n_xcd = (gridDim.x % 8 == 0) ? 8 : 1;   // (an eighth of the list per XCD, as in k_edge_flag_listed)
     const int part = (n + n_xcd - 1) / n_xcd, part0 = (int)(blockIdx.x % n_xcd) * part, part1 = min(n, part0 + part);
+    // The list space of EB_BATCH tiles is taken with ONE atomic: every listed tile's atomic on the one counter, 28 K of them in
+    // 0.3 ms at 512^3, is about what one address serves, whatever else the kernel does.  A tile's flags are written at once; its
+    // edge masks and its rows' offsets from the batch's base stay in LDS until the batch is full or the workgroup's tiles are
+    // done, then wave 0 takes the space and every wave writes the entries of its rows of each tile (one barrier more per batch).
+    int kt = 0, run = 0;   // tiles in the batch (uniform per block); their edges so far (wave 0)
+    auto flush = [&](int lane, int wv) {   // (behind phase 3's barrier; the next tile's phase 2 lies behind two more)
+        if (wv == 0 && lane == 0) sBase = run ? atomicAdd(list_count, run) : 0;
+        __syncthreads();
+        const int base = sBase;
+#pragma unroll 1
+        for (int k = 0; k < kt; k++) {
+            const int t = sTile[k];
+            const int tx0 = (t / (ntz * nty)) * ET_X, y0 = ((t / ntz) % nty) * ET_Y, z0 = (t % ntz) * ET_Z;
+#pragma unroll
+            for (int ty = 0; ty < ET_Y; ty++) {
+                const int row = wv * ET_Y + ty;
+                const eb_mask E = sE[k][row];
+                if ((E >> lane) & 1ull)
+                    list[base + sOff[k][row] + __popcll(E & ((1ull << lane) - 1ull))] = ((tx0 + wv) * g.ny + y0 + ty) * g.nz + z0 + lane;
+            }
+        }
+        kt = 0; run = 0;
+    };
 #pragma unroll 1
     for (int item = part0 + blockIdx.x / n_xcd; item < part1; item += gridDim.x / n_xcd) {   // (uniform per block)
         // (salt: always 0, but opaque to the compiler -- what derives from the thread index then counts as loop variant, and the
@@ -742,16 +767,12 @@ __global__ __launch_bounds__(TPB) void k_edge_sweep_bits(GridL g, const double *
                 const int up = __shfl_up(incl, o);
                 if (lane >= o) incl += up;
             }
-            const int total = __shfl(incl, XB_WAVE - 1);
-            int base = 0;
-            if (total) {
-                if (lane == 0) base = atomicAdd(list_count, total);
-                base = __shfl(base, 0);
-            }
             if (own) {
                 const int row = (rx - 1) * ET_Y + ry - 1;
-                sE[row] = E; sNear[row] = Dn; sOff[row] = base + incl - cnt;
+                sE[kt][row] = E; sNear[row] = Dn; sOff[kt][row] = run + incl - cnt;
             }
+            if (lane == 0) sTile[kt] = t;
+            run += __shfl(incl, XB_WAVE - 1);
         };
         if (wv == 0) {
             const int r = (rx + 1) * EB_Y + ry + 1;
@@ -838,12 +859,17 @@ __global__ __launch_bounds__(TPB) void k_edge_sweep_bits(GridL g, const double *
 #pragma unroll
         for (int ty = 0; ty < ET_Y; ty++) {
             const int row = wv * ET_Y + ty;
-            const eb_mask E = sE[row], N = sNear[row];
+            const eb_mask E = sE[kt][row], N = sNear[row];
             const int v = ((tx0 + wv) * g.ny + y0 + ty) * g.nz + z0 + lane;
-            const bool e = (E >> lane) & 1ull;
-            known[v] = e ? (int8_t)-2 : (((N >> lane) & 1ull) ? (int8_t)-1 : (int8_t)2);
-            if (e) list[sOff[row] + __popcll(E & ((1ull << lane) - 1ull))] = v;
+            known[v] = ((E >> lane) & 1ull) ? (int8_t)-2 : (((N >> lane) & 1ull) ? (int8_t)-1 : (int8_t)2);
         }
+        if (++kt == EB_BATCH) flush(lane, wv);
+    }
+    if (kt) {
+        int salt = 0;
+        asm volatile("" : "+v"(salt));
+        const int tid = (int)threadIdx.x + salt;
+        flush(tid % XB_WAVE, __builtin_amdgcn_readfirstlane(tid / XB_WAVE));
     }
 }
 
