@@ -607,6 +607,62 @@ int xb_isosurface_release(xb_ctx *c);
 int xb_isosurface_nci_mask(xb_ctx *c, void *s_dev, double rho_cut);
 int xb_stream_wait(xb_ctx *c, void *stream);
 int xb_device_write(xb_ctx *c, void *dev_ptr, const void *src_host, int64_t bytes);
+/* ---- connected regions: the components of a periodic voxel mask -- the islands of a level set, the pockets below it, the domains
+ * of the NCI region -- each with its seed, size, top and integrals (what NCIPLOT's, Critic2's and Multiwfn's domain analyses start
+ * from) -- no counterpart in the reference ----
+ * The calls read the resident density rho of the whole grid, a caller's field and (the shares) the resident labels; nothing resident
+ * is written, and the result can be computed while the labels stay resident.
+ *   adjacency   lin is the C-order index.  The offsets are those of the critical points and the isosurface: d_0 .. d_6 = (0,0,1)
+ *               (0,1,0) (0,1,1) (1,0,0) (1,0,1) (1,1,0) (1,1,1), d_{7+k} = -d_k.  u and v are adjacent iff u = wrap(v + d_k) for some k
+ *               and u != v.  On an axis of length 1 a neighbour that wraps onto v itself counts for nothing; on an axis of length 2
+ *               v + d and v - d are one voxel.  (1,-1,0) and its kin are NOT adjacent: the components of {field >= level} are the
+ *               pieces the marching-tetrahedra surface of xb_isosurface encloses.
+ *   members     XB_DOMAINS_ABOVE: field[v] >= level;  XB_DOMAINS_BELOW: field[v] < level -- field_dev (N doubles of device memory in C
+ *               order), or the resident density when it is NULL;  XB_DOMAINS_NCI: the region of the NCI block above (rho > 0, s < s_cut
+ *               as q < T(s_cut) r8, rho < rho_cut) on the resident density in the cell `lattice`, the operations of xb_nci_sum in their
+ *               order; field_dev must be NULL.  A NaN is outside in every mode.
+ *   components  those of the members under the adjacency.  A component's seed is its smallest lin; the components are numbered
+ *               0 .. m - 1 in ascending seed.  map[v] (int32) is the component of v, -1 outside.  The numbering is unique: no output
+ *               depends on a schedule.
+ *   sums        xb_regions_sums, per component, on the RESIDENT density: seed;  count, its voxels;  top, its greatest voxel in the
+ *               order of the critical points (key(rho), ties to the greater lin);  sum1 and sum2, the sums of rho and of rho*rho times
+ *               voxel_volume.  With rho_split not NaN (components of the NCI region only) also count3, sum1_3, sum2_3 [3 m]: the same
+ *               per class 3*i + k, the class of xb_nci_sum (x < -rho_split, between, x > rho_split); count is then the sum of the
+ *               three counts and sum1, sum2 the three partial sums added in class order before the one multiplication.  The terms
+ *               are bit-defined, the order of the sums is free (float atomics; a wave that holds one component adds once).
+ *   shares      xb_regions_shares: the triplets (component, label, count) with count > 0 over the members whose resident label a has
+ *               0 <= a < n, ascending in (component, label); xb_regions_shares_fetch copies them.  m * n <= XB_DOMAINS_SHARE_CELLS
+ *               cells are counted in a dense table on the device (in LDS per workgroup up to 1024 cells) whose non-empty cells
+ *               are compacted there; more, or XB_DOMAINS_SHARES_LIST in `flags`, lists the keys component * n + label of those
+ *               voxels and sorts and counts them on the host: the same triplets.
+ *   routes      the default labels 8 x 8 x 32 tiles by a union-find in LDS, joins the tiles' faces (the periodic wrap included) in
+ *               global memory and flattens; XB_DOMAINS_GLOBAL joins every member with its seven forward neighbours in global memory:
+ *               the second implementation, same map.  Both use one lock-free union that never waits for another wave: the roots are
+ *               the smaller lin, atomicMin makes the link and its return value alone says whether it did.  XB_DOMAINS_GATHER (NCI
+ *               mode) reads the predicate's 19 values from global memory instead of the staged tile, as XB_STENCIL_GATHER does.
+ *   times       XB_DOMAINS_TIMES in `flags` puts an event on the stream before the first launch and behind each stage;
+ *               xb_regions_times then gives the milliseconds of the last labelling: ms[0] membership and tile union-find (or
+ *               parent[v] = v), ms[1] the unions across the faces (or all of them), ms[2] the flatten, ms[3] the numbering
+ *               (its wait for the component count and the allocation of the seeds included).  XB_E_STATE without such a result.
+ * The map (4 N bytes) and the seeds (4 m bytes) stay on the device until xb_regions_release, counted by xb_memory_stats;
+ * xb_regions_fetch_map copies the map to host memory or, with on_device, to N int32 of device memory.  Every writer of the density
+ * and every change of the grid discards the result.
+ * XB_E_STATE: no grid, no density on this grid yet (shares: no labels), a context that holds a slab, sums, shares or a fetch without
+ * a result, classes asked of components that are not the NCI region's;  XB_E_ARG: a null pointer, an unknown mode or flag bits, a
+ * level that is NaN, a field in NCI mode, thresholds that are not finite or negative, a lattice xb_stencil_coeffs refuses, a field or
+ * destination that is not N elements of device memory, a capacity below the length, n < 1;  XB_E_LIMIT: N above 2^31 - 1. */
+enum { XB_DOMAINS_ABOVE = 0, XB_DOMAINS_BELOW = 1, XB_DOMAINS_NCI = 2 };
+enum { XB_DOMAINS_GLOBAL = 1, XB_DOMAINS_SHARES_LIST = 2, XB_DOMAINS_GATHER = 4, XB_DOMAINS_TIMES = 8 };
+enum { XB_DOMAINS_SHARE_CELLS = 16777216 };
+int xb_regions_label(xb_ctx *c, int mode, const void *field_dev, double level, const double lattice[9], double s_cut, double rho_cut,
+                     int flags, int64_t *m);
+int xb_regions_sums(xb_ctx *c, double voxel_volume, double rho_split, int64_t *seed, int64_t *count, int64_t *top, double *sum1,
+                    double *sum2, int64_t *count3, double *sum1_3, double *sum2_3, int64_t capacity);
+int xb_regions_shares(xb_ctx *c, int64_t n, int flags, int64_t *n_triplets);
+int xb_regions_shares_fetch(xb_ctx *c, int32_t *component, int32_t *label, int64_t *count, int64_t capacity);
+int xb_regions_fetch_map(xb_ctx *c, int on_device, void *map);
+int xb_regions_times(xb_ctx *c, double ms[4]);
+int xb_regions_release(xb_ctx *c);
 /* ---- Hirshfeld (stockholder) charges from radial pro-atom tables, the promolecular density and the deformation density (the charge
  * Critic2, Chargemol and Multiwfn print beside the Bader one: every voxel's density is shared among the atoms in proportion to what
  * each FREE atom would put there, w_a(r) = rho0_a(|r - R_a|) / sum_b rho0_b(|r - R_b|): no surfaces, no maxima, no sensitivity to

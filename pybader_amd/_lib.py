@@ -62,6 +62,16 @@ XB_NCI_BINS_MAX = 1 << 24
 XB_ISO_GATHER = 1
 XB_ISO_TABLE_SIZE = 768
 ISO_NCI_RAISED = 100.0
+# xb_regions_label: the modes, the bits of `flags` (the second route; the list route of xb_regions_shares; the NCI predicate's
+# values from global memory) and the cell count up to which the shares use a dense table
+XB_DOMAINS_ABOVE = 0
+XB_DOMAINS_BELOW = 1
+XB_DOMAINS_NCI = 2
+XB_DOMAINS_GLOBAL = 1
+XB_DOMAINS_SHARES_LIST = 2
+XB_DOMAINS_GATHER = 4
+XB_DOMAINS_TIMES = 8
+XB_DOMAINS_SHARE_CELLS = 1 << 24
 # xb_hirshfeld_sum / xb_hirshfeld_field: the bit of `flags` that makes every tile run over the whole image list, the candidates a
 # tile's list holds, and the two modes of the field
 XB_HIRSHFELD_FULL_SEARCH = 1
@@ -157,6 +167,13 @@ SYMBOLS = {
     'xb_isosurface_fetch': (_int, [_vp, _int, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _pdbl, _pdbl, _i64]),
     'xb_isosurface_release': (_int, [_vp]),
     'xb_isosurface_nci_mask': (_int, [_vp, _vp, _dbl]),
+    'xb_regions_label': (_int, [_vp, _int, _vp, _dbl, _pdbl, _dbl, _dbl, _int, _pi64]),
+    'xb_regions_sums': (_int, [_vp, _dbl, _dbl, _pi64, _pi64, _pi64, _pdbl, _pdbl, _pi64, _pdbl, _pdbl, _i64]),
+    'xb_regions_shares': (_int, [_vp, _i64, _int, _pi64]),
+    'xb_regions_shares_fetch': (_int, [_vp, _vp, _vp, _pi64, _i64]),
+    'xb_regions_fetch_map': (_int, [_vp, _int, _vp]),
+    'xb_regions_times': (_int, [_vp, _pdbl]),
+    'xb_regions_release': (_int, [_vp]),
     'xb_stream_wait': (_int, [_vp, _vp]),
     'xb_device_write': (_int, [_vp, _vp, _vp, _i64]),
     'xb_hirshfeld_images': (_int, [_pdbl, _pdbl, _vp, _i64, _pdbl, _i64, _pi64, _vp, _i64]),
@@ -1047,6 +1064,69 @@ class Context:
         d, stream = self._flat('isosurface_nci_mask', s, {np.dtype(np.float64): 64}, True)
         check(self.lib.xb_stream_wait(self.h, stream))
         check(self.lib.xb_isosurface_nci_mask(self.h, C.c_void_p(d.ptr), float(rho_cut)))
+
+    def regions_label(self, mode, field=None, level=0.0, lattice=None, s_cut=0.0, rho_cut=0.0, global_route=False, gather=False, times=False):
+        """the connected components of a mask of the grid under the Freudenthal adjacency (xb_regions_label).  `mode`:
+        XB_DOMAINS_ABOVE / XB_DOMAINS_BELOW (`field` >= / < `level`; `field` a float64 C-contiguous device array, None for the
+        resident density) or XB_DOMAINS_NCI (the NCI region of the resident density in the cell `lattice`).  `global_route`: the
+        second implementation; `gather`: the NCI predicate's values from global memory; `times`: the stages are timed with events
+        (regions_times).  -> m, the number of components; the map stays on the device until regions_release"""
+        lat = None if lattice is None else _f64(lattice).reshape(9)
+        flags = (XB_DOMAINS_GLOBAL if global_route else 0) | (XB_DOMAINS_GATHER if gather else 0) | (XB_DOMAINS_TIMES if times else 0)
+        m = C.c_int64(0)
+        check(self.lib.xb_regions_label(self.h, int(mode), self._field_ptr('regions_label', field), float(level),
+                                        None if lat is None else lat.ctypes.data_as(_pdbl), float(s_cut), float(rho_cut), flags, C.byref(m)))
+        return int(m.value)
+
+    def regions_sums(self, m, voxel_volume, rho_split=None):
+        """per component of the last regions_label, on the resident density (xb_regions_sums) -> (seed i64[m], count i64[m], top
+        i64[m], sum1 f64[m], sum2 f64[m]), and with `rho_split` (NCI components) also (count3 i64[m, 3], sum1_3 f64[m, 3], sum2_3
+        f64[m, 3]); the sums multiplied once by voxel_volume"""
+        m = int(m)
+        seed, count, top = (np.zeros(m, np.int64) for _ in range(3))
+        s1, s2 = np.zeros(m, np.float64), np.zeros(m, np.float64)
+        classes = rho_split is not None
+        c3, s13, s23 = np.zeros((m, 3), np.int64), np.zeros((m, 3), np.float64), np.zeros((m, 3), np.float64)
+        check(self.lib.xb_regions_sums(self.h, float(voxel_volume), float(rho_split) if classes else float('nan'), seed.ctypes.data_as(_pi64),
+                                       count.ctypes.data_as(_pi64), top.ctypes.data_as(_pi64), s1.ctypes.data_as(_pdbl), s2.ctypes.data_as(_pdbl),
+                                       c3.ctypes.data_as(_pi64) if classes else None, s13.ctypes.data_as(_pdbl) if classes else None,
+                                       s23.ctypes.data_as(_pdbl) if classes else None, m))
+        return (seed, count, top, s1, s2) + ((c3, s13, s23) if classes else ())
+
+    def regions_shares(self, n, force_list=False):
+        """the voxels of every component of the last regions_label per resident label 0 .. n - 1 (xb_regions_shares +
+        xb_regions_shares_fetch; `force_list`: the route of the large case) -> (component i32[t], label i32[t], count i64[t]),
+        ascending in (component, label), count > 0"""
+        nt = C.c_int64(0)
+        check(self.lib.xb_regions_shares(self.h, int(n), XB_DOMAINS_SHARES_LIST if force_list else 0, C.byref(nt)))
+        t = int(nt.value)
+        comp, lab, cnt = np.zeros(t, np.int32), np.zeros(t, np.int32), np.zeros(t, np.int64)
+        check(self.lib.xb_regions_shares_fetch(self.h, _ptr(comp), _ptr(lab), cnt.ctypes.data_as(_pi64), t))
+        return comp, lab, cnt
+
+    def regions_map(self, on_device=False):
+        """the component of every voxel, -1 outside (xb_regions_fetch_map) -> int32 of the grid's shape: a host array, or with
+        `on_device` a device.DeviceArray"""
+        if on_device:
+            from . import device
+            out = device.DeviceArray(self, self.shape or (0,), np.int32)
+            d, _ = self._flat('regions_map', out, {np.dtype(np.int32): 4}, True)
+            check(self.lib.xb_regions_fetch_map(self.h, 1, C.c_void_p(d.ptr)))
+            return out
+        out = np.empty(self.shape or (0,), np.int32)
+        check(self.lib.xb_regions_fetch_map(self.h, 0, _ptr(out)))
+        return out
+
+    def regions_times(self):
+        """milliseconds of the four stages of the last regions_label(..., times=True) (xb_regions_times) -> f64[4]: membership and
+        tile union-find, the unions in global memory, the flatten, the numbering"""
+        ms = np.zeros(4, np.float64)
+        check(self.lib.xb_regions_times(self.h, ms.ctypes.data_as(_pdbl)))
+        return ms
+
+    def regions_release(self):
+        """free the map and the seeds xb_regions_label keeps on the device"""
+        check(self.lib.xb_regions_release(self.h))
 
     def device_copy(self, host):
         """a new device.DeviceArray with the content of the host array `host` (xb_device_write)"""

@@ -1,7 +1,7 @@
 // bader_hip.hip -- libbader_hip.so: HIP kernels + C ABI (include/bader_hip.h) for gfx950.  ONE translation unit:
-//   kernels    k_common.h k_masks.h k_fused.h k_trace.h k_ongrid.h k_edges.h k_sums.h k_text.h k_format.h (fmt_core.h) k_interop.h k_weight.h k_moments.h k_adjacency.h k_merge.h k_voronoi.h k_critical.h k_stencil.h k_nci.h k_hirshfeld.h k_isosurface.h
+//   kernels    k_common.h k_masks.h k_fused.h k_trace.h k_ongrid.h k_edges.h k_sums.h k_text.h k_format.h (fmt_core.h) k_interop.h k_weight.h k_moments.h k_adjacency.h k_merge.h k_voronoi.h k_critical.h k_stencil.h k_nci.h k_hirshfeld.h k_isosurface.h k_regions.h
 //   host side  this file (context struct, options, statistics, timing) + host_context.h (life cycle, transfers)
-//              + host_assign.h (the table outside an assignment, the assignments) + host_refine.h + host_sums.h + host_slab_table.h (host-driven slab calls) + host_interop.h (device arrays in and out) + host_weight.h (the weight method) + host_moments.h (moments per label) + host_adjacency.h (surfaces between labels) + host_merge.h (merging volumes by persistence) + host_voronoi.h (the nearest-atom partition) + host_critical.h (critical points and the bond graph) + host_stencil.h (the Laplacian and the Hessian of the density) + host_nci.h (the NCI index: reduced gradient, sign(lambda2) rho, region sums, histogram) + host_hirshfeld.h (Hirshfeld charges, the promolecular and the deformation density) + host_isosurface.h (isosurfaces by marching tetrahedra) + comm.h (RCCL through the ABI)
+//              + host_assign.h (the table outside an assignment, the assignments) + host_refine.h + host_sums.h + host_slab_table.h (host-driven slab calls) + host_interop.h (device arrays in and out) + host_weight.h (the weight method) + host_moments.h (moments per label) + host_adjacency.h (surfaces between labels) + host_merge.h (merging volumes by persistence) + host_voronoi.h (the nearest-atom partition) + host_critical.h (critical points and the bond graph) + host_stencil.h (the Laplacian and the Hessian of the density) + host_nci.h (the NCI index: reduced gradient, sign(lambda2) rho, region sums, histogram) + host_hirshfeld.h (Hirshfeld charges, the promolecular and the deformation density) + host_isosurface.h (isosurfaces by marching tetrahedra) + host_regions.h (connected components of a mask: level-set islands, pockets, NCI domains) + comm.h (RCCL through the ABI)
 //              + slab_step.h (the slab step with its control flow on the device)
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -shared (see pybader_amd/build.py).
 #include "bader_kernels.h"
@@ -45,6 +45,7 @@ static inline hipError_t xb_counted_sync(hipStream_t s) { xb_waits++; return (hi
 #include "k_nci.h"
 #include "k_hirshfeld.h"
 #include "k_isosurface.h"
+#include "k_regions.h"
 
 // =============================================================================================
 // host side
@@ -281,6 +282,16 @@ struct xb_ctx {
     bool iso_have = false;
     double iso_area = 0., iso_volume = 0.;
     std::vector<double> iso_vbl;
+    // xb_regions_label (host_regions.h): the component of every voxel and the components' seeds on the device (rg_m components,
+    // rg_members voxels in them, rg_seed_cap seeds allocated), whether they are the NCI region's and the stencil they were made with; the last
+    // xb_regions_shares triplets.  rg_have falls with every writer of the density
+    int *rg_map = nullptr, *rg_seed = nullptr;
+    size_t rg_m = 0, rg_members = 0, rg_seed_cap = 0;
+    bool rg_have = false, rg_sh_have = false, rg_nci = false, rg_timed = false;
+    double rg_ms[4] = {0., 0., 0., 0.};   // XB_DOMAINS_TIMES: tile, link, flatten, numbering of the last labelling
+    StCoeffs rg_K{};
+    std::vector<int32_t> rg_sh_comp, rg_sh_lab;
+    std::vector<int64_t> rg_sh_cnt;
     // has anything been put into the density / the labels of this grid?  (xb_moment_sum refuses a grid without; set by every
     // call that writes them or hands their pointer out, cleared when the grid's shape changes)
     bool have_rho = false, have_labels = false;
@@ -401,6 +412,7 @@ const char *xb_last_error(void) { return g_err.c_str(); }
 #include "host_nci.h"
 #include "host_hirshfeld.h"
 #include "host_isosurface.h"
+#include "host_regions.h"
 
 int xb_set_option(xb_ctx *c, int key, int value) {
     if (!c) return fail(XB_E_ARG, "null ctx");
@@ -470,7 +482,8 @@ int xb_memory_stats(xb_ctx *c, int64_t *bytes_total, int64_t *bytes_table, int64
                               (long long)c->st_cap * 8 /* xb_laplacian_sum's buffer */ +
                               (long long)c->nci_cap * 8 /* xb_nci_sum's and xb_nci_hist's buffer */ +
                               (long long)c->hs_cap * 8 /* xb_hirshfeld_setup's buffer */ +
-                              (long long)c->iso_bytes /* xb_isosurface's mesh */;
+                              (long long)c->iso_bytes /* xb_isosurface's mesh */ +
+                              (long long)regions_bytes(c) /* xb_regions_label's map and seeds */;
     const long long fixed = 8 * N /* rho */ + 4 * N /* labels */ + (N + 16) /* known */ + 4 * N /* first */ + N /* st */ +
                             2LL * c->max_cap * 4 + (long long)c->ovf_cap * 4 + c->blab_alloc * 13 + (long long)c->walk_cap * 3 * 80 +
                             (1 << 22) /* boxbuf */;

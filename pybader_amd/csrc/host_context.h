@@ -41,6 +41,7 @@ static void stencil_free(xb_ctx *c);
 static void nci_free(xb_ctx *c);
 static void hirshfeld_free(xb_ctx *c);
 static void isosurface_free(xb_ctx *c);
+static void regions_free(xb_ctx *c);
 static void free_grid(xb_ctx *c) {
     weight_free(c);
     moments_free(c);
@@ -52,6 +53,7 @@ static void free_grid(xb_ctx *c) {
     nci_free(c);
     hirshfeld_free(c);
     isosurface_free(c);
+    regions_free(c);
     c->have_rho = c->have_labels = false;
     hipFree(c->rho); hipFree(c->grad); hipFree(c->labels); hipFree(c->known); hipFree(c->first); hipFree(c->list);
     hipFree(c->st); hipFree(c->stage); hipFree(c->ec_pend); c->ec_pend = nullptr; hipFree(c->ec_share); c->ec_share = nullptr; hipFree(c->ec_pflag); c->ec_pflag = nullptr; hipFree(c->max_list); hipFree(c->max_aux); hipFree(c->ovf_list);
@@ -187,7 +189,7 @@ int xb_set_grid(xb_ctx *c, const int64_t shape[3], const double dist_mat[27], co
     }
     c->zero_outside[0] = -1;
     Grid &g = c->g;
-    if (g.nx != (int)shape[0] || g.ny != (int)shape[1] || g.nz != (int)shape[2]) { c->grad_valid = false; c->grad_nb = false; c->brick_max_valid = false; c->have_rho = c->have_labels = false; adjacency_free(c); merge_free(c); critical_free(c); isosurface_free(c); c->hs_have = false; }
+    if (g.nx != (int)shape[0] || g.ny != (int)shape[1] || g.nz != (int)shape[2]) { c->grad_valid = false; c->grad_nb = false; c->brick_max_valid = false; c->have_rho = c->have_labels = false; adjacency_free(c); merge_free(c); critical_free(c); isosurface_free(c); regions_free(c); c->hs_have = false; }
     if (dist_mat && !T_grad) return fail(XB_E_ARG, "xb_set_grid: dist_mat without T_grad");
     g.nx = (int)shape[0]; g.ny = (int)shape[1]; g.nz = (int)shape[2];
     g.nyz = g.ny * g.nz;
@@ -347,7 +349,7 @@ static int staged_d2h(xb_ctx *c, void *dst_host, const void *src_dev, size_t byt
 int xb_upload_density(xb_ctx *c, const double *rho_host) {
     if (c) c->vac_by_tol = false;   // (the -1 labels no longer say "rho <= vac_tol" of the density on the card)
     NEED_GRID_THIN("xb_upload_density");
-    c->grad_valid = false; c->grad_nb = false; c->brick_max_valid = false; c->have_rho = true; c->cp_have = false; c->iso_have = false;
+    c->grad_valid = false; c->grad_nb = false; c->brick_max_valid = false; c->have_rho = true; c->cp_have = false; c->iso_have = false; c->rg_have = false;
     if (int rc = staged_h2d(c, c->rho, rho_host, c->N * sizeof(double))) return rc;
     HIPCHK(hipStreamSynchronize(c->stream));
     return XB_OK;
@@ -388,7 +390,7 @@ static int parse_text(xb_ctx *c, const char *who, const char *text, int64_t nbyt
                       int64_t *n_host) {
     if (!text || nbytes <= 0) return fail(XB_E_ARG, "%s: empty text", who);
     if (nbytes / (TPB * TXT_BYTES) >= (1LL << 31) - 2) return fail(XB_E_LIMIT, "%s: text too large", who);
-    c->grad_valid = false; c->grad_nb = false; c->brick_max_valid = false; c->have_rho = true; c->cp_have = false; c->iso_have = false;
+    c->grad_valid = false; c->grad_nb = false; c->brick_max_valid = false; c->have_rho = true; c->cp_have = false; c->iso_have = false; c->rg_have = false;
     static const double P10[23] = {1e0, 1e1, 1e2, 1e3, 1e4, 1e5, 1e6, 1e7, 1e8, 1e9, 1e10, 1e11,
                                    1e12, 1e13, 1e14, 1e15, 1e16, 1e17, 1e18, 1e19, 1e20, 1e21, 1e22};
     const int nblk = (int)((nbytes + TPB * TXT_BYTES - 1) / (TPB * TXT_BYTES));
@@ -490,7 +492,7 @@ int xb_synth_density(xb_ctx *c, const double lattice[9], const double *atoms5, i
     if (n_atoms < 0 || n_atoms > XB_SYNTH_ATOMS_MAX) return fail(XB_E_ARG, "xb_synth_density: bad atom count");
     if ((16 + 5 * (size_t)n_atoms) * sizeof(double) > c->stage_bytes)   // (never with need_scratch's floor)
         return fail(XB_E_LIMIT, "xb_synth_density: %lld atoms do not fit the scratch buffer", (long long)n_atoms);
-    c->grad_valid = false; c->grad_nb = false; c->brick_max_valid = false; c->have_rho = true; c->cp_have = false; c->iso_have = false;
+    c->grad_valid = false; c->grad_nb = false; c->brick_max_valid = false; c->have_rho = true; c->cp_have = false; c->iso_have = false; c->rg_have = false;
     double *tmp = (double *)c->stage;
     HIPCHK(hipMemcpyAsync(tmp, lattice, 9 * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(tmp + 16, atoms5, n_atoms * 5 * sizeof(double), hipMemcpyHostToDevice, c->stream));

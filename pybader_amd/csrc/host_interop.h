@@ -138,7 +138,7 @@ int xb_import_density(xb_ctx *c, const void *dev_ptr, int dtype, const int64_t s
     // from here on as xb_upload_density
     c->vac_by_tol = false;   // (the -1 labels no longer say "rho <= vac_tol" of the density on the card)
     NEED_GRID_THIN("xb_import_density");
-    c->grad_valid = false; c->grad_nb = false; c->brick_max_valid = false; c->have_rho = true; c->cp_have = false; c->iso_have = false;
+    c->grad_valid = false; c->grad_nb = false; c->brick_max_valid = false; c->have_rho = true; c->cp_have = false; c->iso_have = false; c->rg_have = false;
     const hipStream_t s = (hipStream_t)stream;
     if (int rc = io_after_caller(c, s)) return rc;
     if (int rc = dtype == XB_F32 ? io_import_density(c, (const float *)dev_ptr, stride, c->rho) : io_import_density(c, (const double *)dev_ptr, stride, c->rho)) return rc;

@@ -136,7 +136,7 @@ void *xb_labels_ptr(xb_ctx *c) {
 }
 void *xb_known_ptr(xb_ctx *c) { return c ? (void *)c->known : nullptr; }
 void *xb_density_ptr(xb_ctx *c) {
-    if (c) { c->have_rho = true; c->cp_have = false; c->iso_have = false; }   // (whoever holds the pointer may write it)
+    if (c) { c->have_rho = true; c->cp_have = false; c->iso_have = false; c->rg_have = false; }   // (whoever holds the pointer may write it)
     return c ? (void *)c->rho : nullptr;
 }
 int64_t xb_plane_elems(xb_ctx *c) { return c ? c->g.nyz : 0; }

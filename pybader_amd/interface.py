@@ -348,6 +348,25 @@ class Bader:
         self.atoms_nci_count, self.atoms_nci_volume, self.atoms_nci_charge = r.count, r.volume, r.charge
         if self.critical_flag:
             self.atoms_bond_nci = bond_classes(self.reference, self.lattice, self.atoms_bond_graph.voxel, *cuts)
+        if self.nci_domains_flag:
+            self.nci_domain_analysis()
+
+    def nci_domain_analysis(self):
+        """The connected domains of the NCI region (nci.nci_domains; runs inside nci_analysis() when nci_domains_flag is set).
+        Sets nci_domains (an nci.NciDomains) and, per domain, nci_domain_count [m, 3] (voxels per class), nci_domain_volume
+        [m, 3], nci_domain_charge [m, 3] (the integral of the reference density), nci_domain_kind [m] (the class of the domain's
+        top voxel), nci_domain_atoms [m, 2] (the two atoms of atoms_volumes that hold most of it, -1 where fewer) and
+        nci_domain_position [m, 3] (the Cartesian position of the top voxel, voxel_offset added)."""
+        from .critical import positions
+        from .nci import nci_domains
+        d = nci_domains(self.reference, self.lattice, self.atoms_volumes, self.atoms.shape[0], self.voxel_volume, self.nci_s_cut,
+                        self.nci_rho_cut, self.nci_rho_split)
+        self.nci_domains = d
+        self.nci_domain_count, self.nci_domain_volume, self.nci_domain_charge = d.count, d.volume, d.charge
+        self.nci_domain_kind, self.nci_domain_atoms = d.kind, d.atoms
+        self.nci_domain_position = positions(d.top, d.shape, self.lattice) + self.voxel_offset
+
+    nci_domains_flag = False    # True: nci_analysis() also splits the region into its connected domains (no other step changes)
 
     isosurface_level = None   # a value: _run runs isosurface_analysis() after nci_analysis() (None: no step changes)
 

@@ -17,6 +17,7 @@ through sqrt and cbrt.
     nci_regions(density, volumes, lattice, n, voxel_volume, s_cut, rho_cut, rho_split)   an NciRegions
     nci_histogram(density, lattice, s_edges, x_edges)                                int64[n_s, n_x]
     nci_isosurface(density, lattice, s_cut, rho_cut)                                 the surface s = s_cut, an isosurface.Mesh
+    nci_domains(density, lattice, volumes, n, voxel_volume, s_cut, rho_cut, rho_split)   the region's connected pieces, an NciDomains
 
 Units: s is dimensionless when density and lattice share a length unit.  rho_cut and rho_split are in the density's units; the
 defaults S_CUT, RHO_CUT, RHO_SPLIT are the usual ones in atomic units (e / bohr^3).  For a density in e / Angstrom^3 multiply
@@ -150,6 +151,58 @@ def nci_isosurface(density, lattice, s_cut=S_CUT, rho_cut=RHO_CUT, gather=False)
     out = ctx.isosurface(lattice, s_cut, s, x, 0, gather)
     ctx.isosurface_release()
     return Mesh(shape, s_cut, lattice, *out)
+
+
+class NciDomains:
+    """The connected pieces of the NCI region (rho > 0, s < s_cut, rho < rho_cut) under the adjacency of pybader_amd.regions,
+    numbered 0 .. m - 1 in ascending seed -- one per contact:
+
+    shape, m
+    labels     int32 of the grid's shape: the domain of every voxel, -1 outside the region (host array or device.DeviceArray,
+               as the density)
+    seed       int64[m]      the smallest linear C-order index of the domain;  voxel int64[m, 3]: the same as grid coordinates
+    count      int64[m, 3]   voxels per class (CLASSES: attractive, van der Waals, repulsive)
+    volume     f64[m, 3]     count * voxel_volume
+    charge     f64[m, 3]     the integral of rho per class;  charge2 f64[m, 3]: of rho^2
+    size       int64[m]      voxels in all;  total f64[m], total2 f64[m]: the integrals of rho and rho^2 over the whole domain
+    top        int64[m]      the domain's greatest voxel of rho in the order of critical.critical_points
+    kind       int8[m]       the class of `top` (point_classes): what the domain is called
+    shares     (domain, label, count) triplets against `volumes`;  atoms int64[m, 2]: the two labels with the largest counts
+    s_cut, rho_cut, rho_split   the thresholds they were made with"""
+
+    def __init__(self, shape, labels, seed, size, top, total, total2, count, charge, charge2, kind, shares, voxel_volume, s_cut, rho_cut,
+                 rho_split):
+        from .regions import atoms_from_shares
+        self.shape, self.m = tuple(int(s) for s in shape), int(seed.shape[0])
+        self.labels, self.seed, self.size, self.top, self.total, self.total2 = labels, seed, size, top, total, total2
+        self.count, self.charge, self.charge2, self.kind, self.shares = count, charge, charge2, kind, shares
+        self.voxel = np.stack(np.unravel_index(seed, self.shape), axis=1).astype(np.int64).reshape(-1, 3)
+        self.volume = count.astype(np.float64) * float(voxel_volume)
+        self.atoms = atoms_from_shares(self.m, shares)
+        self.s_cut, self.rho_cut, self.rho_split = float(s_cut), float(rho_cut), float(rho_split)
+
+    def __len__(self):
+        return self.m
+
+
+def nci_domains(density, lattice, volumes=None, n=0, voxel_volume=1.0, s_cut=S_CUT, rho_cut=RHO_CUT, rho_split=RHO_SPLIT, gather=False,
+                global_route=False, shares_list=False):
+    """The NCI region of `density` (host or device array) split into its connected domains, each summed per class; with a label
+    map `volumes` and n >= 1 also which labels 0 .. n - 1 every domain lies between.  `gather` reads the predicate's stencil from
+    global memory, `global_route` runs every union in global memory, `shares_list` counts the shares from a sorted key list: second
+    implementations, the same results.  -> NciDomains"""
+    from .regions import _shares
+    ctx, shape = _resident(density)
+    m = ctx.regions_label(_lib.XB_DOMAINS_NCI, None, 0.0, lattice, s_cut, rho_cut, global_route=global_route, gather=gather)
+    try:
+        labels = ctx.regions_map(on_device=device.is_device_array(density))
+        seed, size, top, total, total2, count, charge, charge2 = ctx.regions_sums(m, voxel_volume, rho_split)
+        shares = _shares(ctx, shape, volumes, n, shares_list, 'nci_domains')
+    finally:
+        ctx.regions_release()      # (the map does not outlive the call, whichever way it ends)
+    kind = point_classes(ctx.stencil_points(lattice, top), s_cut, rho_cut, rho_split) if m else np.zeros(0, np.int8)
+    return NciDomains(shape, labels, seed, size, top, total, total2, count, charge, charge2, kind, shares, voxel_volume, s_cut, rho_cut,
+                      rho_split)
 
 
 def bond_classes(density, lattice, lin, s_cut=S_CUT, rho_cut=RHO_CUT, rho_split=RHO_SPLIT):
