@@ -1,11 +1,12 @@
 // bader_hip.hip -- libbader_hip.so: HIP kernels + C ABI (include/bader_hip.h) for gfx950.  ONE translation unit:
 //   kernels    k_common.h k_masks.h k_fused.h k_trace.h k_ongrid.h k_edges.h k_sums.h k_text.h k_format.h (fmt_core.h) k_interop.h k_weight.h k_moments.h k_adjacency.h k_merge.h k_voronoi.h k_critical.h k_stencil.h k_nci.h k_hirshfeld.h k_isosurface.h k_regions.h
-//   host side  this file (context struct, options, statistics, timing) + host_context.h (life cycle, transfers)
+//   host side  this file (context struct, options, statistics, timing) + ctx_state.h (the cached-state flags and their invalidation events; plain C++) + host_context.h (life cycle, transfers)
 //              + host_assign.h (the table outside an assignment, the assignments) + host_refine.h + host_sums.h + host_slab_table.h (host-driven slab calls) + host_interop.h (device arrays in and out) + host_weight.h (the weight method) + host_moments.h (moments per label) + host_adjacency.h (surfaces between labels) + host_merge.h (merging volumes by persistence) + host_voronoi.h (the nearest-atom partition) + host_critical.h (critical points and the bond graph) + host_stencil.h (the Laplacian and the Hessian of the density) + host_nci.h (the NCI index: reduced gradient, sign(lambda2) rho, region sums, histogram) + host_hirshfeld.h (Hirshfeld charges, the promolecular and the deformation density) + host_isosurface.h (isosurfaces by marching tetrahedra) + host_regions.h (connected components of a mask: level-set islands, pockets, NCI domains) + comm.h (RCCL through the ABI)
 //              + slab_step.h (the slab step with its control flow on the device)
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -shared (see pybader_amd/build.py).
 #include "bader_kernels.h"
 #include "../../include/bader_hip.h"
+#include "ctx_state.h"
 
 #include <algorithm>
 #include <cmath>
@@ -74,7 +75,7 @@ struct TimedKernel {
 };
 
 namespace xbcomm { struct State; }
-struct xb_ctx {
+struct xb_ctx : CtxState {   // (ctx_state.h: the flags of the cached state and the events that drop them)
     int device = 0;
     xbcomm::State *comm = nullptr;   // RCCL transport (comm.h), one process per GPU
     struct FmtState *fmt = nullptr;  // density -> text writer between xb_format_begin and xb_format_end (host_format.h)
@@ -120,16 +121,11 @@ struct xb_ctx {
     unsigned long long *ec_pend = nullptr;  // edge_check's counter word per voxel (8 N bytes, allocated on first use)
     int8_t *ec_pflag = nullptr;             // ... and a flag byte per voxel, set on the processed voxels while their boxes are applied (zero otherwise)
     std::vector<int8_t> esc_complete;
-    bool has_vacuum = true;    // false only when volumes_init proved there is no -1 label
-    bool vac_by_tol = false;   // the -1 labels are exactly the voxels with rho <= vac_tol (xb_vacuum_assign wrote them, nobody since)
-    double vac_tol = 0.;
+    double vac_tol = 0.;       // xb_vacuum_assign's tolerance while vac_by_tol holds
     bool regions_pending = false;  // labels of certain bricks are written by the relabel pass
-    bool buni_valid = false;       // per-brick label uniformity (in `st`) matches the resident labels
-    bool buni_halo_safe = false;   // ... and marks every brick outside the owned planes that is not of a trapping region as mixed:
+    bool buni_halo_safe = false;   // buni_valid, and `st` marks every brick outside the owned planes that is not of a trapping region as mixed:
                                    // it stays right when the peers' halo planes arrive (slabs, xb_assign_finish)
     bool regions_neargrid = false; // the regions in `blab` are closed under NEARGRID moves (k_brick_masks); false: the ongrid pointer field's
-    bool regions_labels = false;   // the resident labels are the last neargrid assignment's (+ refinement): every voxel of a
-                                   // trapping-region brick (blab > 0) still carries the region's label
     int n_walk = 0;                // bricks on the walk list of the last assignment
     int *walk = nullptr;           // ... and where that list lives (inside `list`)
     int table_margin = -1;         // planes of table each side of the slab (slabs); -1: whole grid
@@ -152,11 +148,6 @@ struct xb_ctx {
     int *bres_last = nullptr;   // the fused neargrid assignment's per-brick trace results (inside `list`), or null
     int *blab = nullptr;        // brick labels of the trapping regions (inside `list`), or null
     int nbk[3] = {0, 0, 0};
-    bool grad_valid = false;
-    bool grad_nb = false;      // every record of the resident table carries neighbour bits (bader_kernels.h) that match the bricks that hold
-                               // records now: set by the pass-B launches that write a whole-grid table of whole bricks (launch_brick_records),
-                               // cleared with grad_valid and by every other writer of records; nb_bits_ok() is what the launchers ask
-    bool brick_max_valid = false;   // brick_rec bit 1 (the brick holds a 26-neighbour maximum) is right for the density on the card
     bool brick_max_blanket = false; // brick_rec bit 1 is set on EVERY flagged brick (nothing is known about the maxima), not only where a maximum was found.  Owned by the writers of bit 1: ensure_grad's two tables for given labels set it; pass A (launch_brick_masks: every neargrid assignment, slabs and windowed tables too) and the ongrid masks (k_og_masks, whose flags the late records of refine_iteration_fused keep) clear it
     int grad_cover = 0;        // 0: the table holds a record for every voxel (of the window); 1: only for the bricks flagged in brick_rec
     unsigned char *brick_rec = nullptr;   // per 8^3 brick: its records exist (k_brick_records), nbr bytes inside blab_buf's allocation
@@ -190,8 +181,6 @@ struct xb_ctx {
     int *fs = nullptr;         // state block of the device-side control flow (k_fused.h), inside `counters`
     int *blab_buf = nullptr;   // brick labels of the trapping regions (fused path), nbr ints
     long long blab_alloc = 0;
-    bool labels_zero_pending = false;   // volumes_init without vacuum: labels := 0 is owed (see xb_vacuum_assign)
-    int zero_outside[3] = {-1, -1, -1}; // slab (x0, x1, halo) for which every label outside the planes [x0-halo, x1+halo) is known to be 0
     static constexpr int trace_waves = 8192;   // waves of the persistent trace: 2048 workgroups of XB_TRACE_WAVES = 4, eight per compute unit
     unsigned long long *counters64 = nullptr;
     double *dsum = nullptr;
@@ -202,16 +191,9 @@ struct xb_ctx {
     char *pin = nullptr;       // pinned staging for the small host arrays a step uploads (pageable copies pin pages on the fly)
     size_t pin_bytes = 0;
     std::vector<int> maxima_sorted;  // global, label order
-    int label_wire = 4;        // bytes per label that hold EVERY resident label (1 / 2 / 4): what the narrowed halo may travel in.
-                               // Follows whoever wrote the labels last: an assignment (dtype_calc(-n_maxima)), an upload (its dtype),
-                               // volume_assign (the largest atom index) -- calls every rank of a slab run makes alike, so the
-                               // ranks agree on it (send / receive sizes).  Planes or voxels written from outside widen it only
-                               // if one of their labels does not fit; xb_label_wire lets a scheduler agree on the maximum
     std::vector<int> local_max, local_first;
     bool first_clean = false;
-    int chg_n = -1;            // >= 0: the upper half of `stage` lists the chg_n voxels the last retrace pass relabelled (all known == -2 voxels)
-    int list_n = 0;            // entries of `list` that hold the owned known == -2 voxels ...
-    bool list_valid = false;   // ... when this is set (by xb_edge_find)
+    int list_n = 0;            // entries of `list` that hold the owned known == -2 voxels while list_valid is set
     bool tiles_listed = false; // the last edge_find swept a tile list whose length is in CT_TILES_OWN (xb_edge_list)
     unsigned timing = 0;   // bit k: timer k records its events (xb_enable_timing)
     TimedKernel tk[XB_TIMER_COUNT];
@@ -254,7 +236,7 @@ struct xb_ctx {
     unsigned char *cp_lut = nullptr;
     unsigned long long *cp_list = nullptr;
     size_t cp_cap = 0, cp_n = 0, cp_bond_voxels = 0;
-    bool cp_have = false, cb_have = false;
+    bool cb_have = false;
     std::vector<unsigned long long> cp_rec;
     std::vector<int32_t> cb_a, cb_b;
     std::vector<int64_t> cb_saddles, cb_voxel;
@@ -279,7 +261,6 @@ struct xb_ctx {
     long long *iso_tri = nullptr, *iso_cell = nullptr;
     unsigned short *iso_wrap = nullptr;
     size_t iso_v = 0, iso_t = 0, iso_bytes = 0;
-    bool iso_have = false;
     double iso_area = 0., iso_volume = 0.;
     std::vector<double> iso_vbl;
     // xb_regions_label (host_regions.h): the component of every voxel and the components' seeds on the device (rg_m components,
@@ -287,14 +268,11 @@ struct xb_ctx {
     // xb_regions_shares triplets.  rg_have falls with every writer of the density
     int *rg_map = nullptr, *rg_seed = nullptr;
     size_t rg_m = 0, rg_members = 0, rg_seed_cap = 0;
-    bool rg_have = false, rg_sh_have = false, rg_nci = false, rg_timed = false;
+    bool rg_sh_have = false, rg_nci = false, rg_timed = false;
     double rg_ms[4] = {0., 0., 0., 0.};   // XB_DOMAINS_TIMES: tile, link, flatten, numbering of the last labelling
     StCoeffs rg_K{};
     std::vector<int32_t> rg_sh_comp, rg_sh_lab;
     std::vector<int64_t> rg_sh_cnt;
-    // has anything been put into the density / the labels of this grid?  (xb_moment_sum refuses a grid without; set by every
-    // call that writes them or hands their pointer out, cleared when the grid's shape changes)
-    bool have_rho = false, have_labels = false;
 };
 
 // utils.dtype_calc(-n) as a byte width (utils.py:25-37): the narrowest signed type for labels 0..n-1 and -1
@@ -434,7 +412,7 @@ int xb_set_option(xb_ctx *c, int key, int value) {
     case XB_OPT_DEBUG: c->opt.dbg = value; break;
     case XB_OPT_EC_GROUPS: if ((ok = value >= 1 && value <= 4096)) c->opt.ec_groups = value; break;
     case XB_OPT_EC_QCAP: if ((ok = value >= 2 && value <= EC_Q)) c->opt.ec_qcap = value; break;
-    case XB_OPT_DROP_TABLE: c->grad_valid = false; c->grad_nb = false; if (value == XB_DROP_TABLE_AND_MAXIMA) c->brick_max_valid = false; break;   // (a refinement rebuilds the table)
+    case XB_OPT_DROP_TABLE: if (value == XB_DROP_TABLE_AND_MAXIMA) drop_table_and_maxima(*c); else drop_table(*c); break;   // (a refinement rebuilds the table)
     case XB_OPT_KILL_LAUNCHES: if ((ok = value >= 1)) c->grow_kill_launches = value; break;
     case XB_OPT_SELF_EXCHANGE: c->opt.self_exchange = value != 0; break;
     case XB_OPT_ASYNC_COMM: c->opt.async_comm = value != 0; break;

@@ -13,7 +13,7 @@ static GridL light(const Grid &g);
 static int ensure_brick_bytes(xb_ctx *c, int nbr) {
     if (c->blab_alloc < nbr) {
         hipFree(c->blab_buf); c->blab_buf = nullptr; c->blab_alloc = 0; c->brick_rec = nullptr; c->nb_tab = nullptr; c->brick_max_valid = false;
-        if (c->grad_cover) { c->grad_cover = 0; c->grad_valid = false; c->grad_nb = false; }
+        if (c->grad_cover) { c->grad_cover = 0; drop_table(*c); }
         const size_t rec_bytes = ((size_t)nbr + 16 + 7) & ~(size_t)7;   // (keeps nb_tab 8-byte aligned)
         HIPCHK(hipMalloc(&c->blab_buf, (size_t)nbr * sizeof(int) + rec_bytes + (size_t)nbr * sizeof(unsigned long long)));
         c->blab_alloc = nbr;
@@ -408,7 +408,7 @@ int xb_assign_finish(xb_ctx *c, const int64_t *max_idx_sorted, int64_t n_global)
         k_set_rank<<<(unsigned)((n_global + 255) / 256), 256, 0, c->stream>>>(c->first, c->max_aux, (int)n_global);
         HIPCHK(hipGetLastError());
     }
-    c->buni_valid = false; c->regions_labels = false;
+    drop_label_marks(*c);
     const bool regions = c->regions_pending && c->blab;
     int buni = BUNI_NONE;
     if (regions && g.x1 - g.x0 == g.nx)   // one slab: the per-brick label uniformity edge_find wants comes for free
@@ -593,7 +593,7 @@ static int assign_neargrid_tail(xb_ctx *c, int64_t *n_maxima) {
     if (h[FS_GROW_RETRY]) {   // the short kill schedule did not reach the fixpoint: once more, with the worst-case one from now on
         c->grow_kill_launches = 1 << 20;
         c->stat_grow_retries++;
-        c->grad_valid = false; c->grad_nb = false;
+        drop_table(*c);
         return assign_neargrid_fused(c, n_maxima);
     }
     if (h[FS_TIES] == 0) c->grad_rule = 2;
@@ -724,7 +724,7 @@ static int assign_ongrid_fused(xb_ctx *c, int64_t *n_maxima) {
         launch_region_growth(c, nb0, nb1, nb2, bmask, bmaxv, bpot, seed, buf0, buf1, box_max, box_first, true);
         HIPCHK(hipGetLastError());
     }
-    c->grad_valid = false; c->grad_nb = false;          // (brick_rec is rewritten: bit 1 = holds a maximum, no records)
+    drop_table(*c);   // (brick_rec is rewritten: bit 1 = holds a maximum, no records)
     c->grad_cover = 0;
     c->brick_max_valid = true;
     c->brick_max_blanket = false;

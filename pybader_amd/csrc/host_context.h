@@ -60,7 +60,7 @@ static void free_grid(xb_ctx *c) {
     hipFree(c->blab_buf); c->blab_buf = nullptr; c->blab_alloc = 0; c->labels_zero_pending = false;
     hipFree(c->ec_buf); c->ec_buf = nullptr; c->ec_buf_cap = 0; c->grad_cap = 0; c->list_cap = 0;
     c->brick_rec = nullptr; c->nb_tab = nullptr; c->grad_cover = 0;
-    c->rho = nullptr; c->grad = nullptr; c->grad_valid = false; c->grad_nb = false; c->brick_max_valid = false; c->labels = nullptr; c->known = nullptr; c->first = nullptr; c->list = nullptr;
+    c->rho = nullptr; c->grad = nullptr; drop_table_and_maxima(*c); c->labels = nullptr; c->known = nullptr; c->first = nullptr; c->list = nullptr;
     c->st = nullptr; c->stage = nullptr; c->max_list = nullptr; c->max_aux = nullptr; c->ovf_list = nullptr;
     c->n_alloc = 0; c->stage_bytes = 0;
 }
@@ -119,7 +119,7 @@ static int need_scratch(xb_ctx *c) {
         hipFree(c->list); c->list = nullptr; c->list_cap = 0;
         HIPCHK(hipMalloc(&c->list, (size_t)list_want * sizeof(int)));
         c->list_cap = list_want;
-        c->list_valid = false; c->chg_n = -1; c->walk = nullptr; c->n_walk = 0;
+        drop_edge_lists(*c); c->walk = nullptr; c->n_walk = 0;
     }
     if (c->stage_bytes < stage_want) {
         HIPCHK(hipStreamSynchronize(c->stream));
@@ -137,7 +137,7 @@ static int need_grad(xb_ctx *c) {
     g.ntot = (int)c->N;
     if (c->grad_cap < want || c->grad_cap > 2 * want) {
         HIPCHK(hipStreamSynchronize(c->stream));
-        hipFree(c->grad); c->grad = nullptr; c->grad_cap = 0; c->grad_valid = false; c->grad_nb = false; c->brick_max_valid = false;
+        hipFree(c->grad); c->grad = nullptr; c->grad_cap = 0; drop_table_and_maxima(*c);
         HIPCHK(hipMalloc(&c->grad, (size_t)want * sizeof(GradRec)));
         c->grad_cap = want;
     }
@@ -189,19 +189,19 @@ int xb_set_grid(xb_ctx *c, const int64_t shape[3], const double dist_mat[27], co
     }
     c->zero_outside[0] = -1;
     Grid &g = c->g;
-    if (g.nx != (int)shape[0] || g.ny != (int)shape[1] || g.nz != (int)shape[2]) { c->grad_valid = false; c->grad_nb = false; c->brick_max_valid = false; c->have_rho = c->have_labels = false; adjacency_free(c); merge_free(c); critical_free(c); isosurface_free(c); regions_free(c); c->hs_have = false; }
+    if (g.nx != (int)shape[0] || g.ny != (int)shape[1] || g.nz != (int)shape[2]) { drop_table_and_maxima(*c); c->have_rho = c->have_labels = false; adjacency_free(c); merge_free(c); critical_free(c); isosurface_free(c); regions_free(c); c->hs_have = false; }
     if (dist_mat && !T_grad) return fail(XB_E_ARG, "xb_set_grid: dist_mat without T_grad");
     g.nx = (int)shape[0]; g.ny = (int)shape[1]; g.nz = (int)shape[2];
     g.nyz = g.ny * g.nz;
     g.x0 = (int)x0; g.x1 = (int)x1;
     if (dist_mat) {
-        if (memcmp(g.dist, dist_mat, sizeof g.dist) != 0) { c->grad_valid = false; c->grad_nb = false; c->brick_max_valid = false; }   // the tabulated ongrid successors depend on it
+        if (memcmp(g.dist, dist_mat, sizeof g.dist) != 0) drop_table_and_maxima(*c);   // the tabulated ongrid successors depend on it
         memcpy(g.dist, dist_mat, sizeof g.dist);
         HIPCHK(hipMemcpyAsync(c->dist_dev, dist_mat, sizeof g.dist, hipMemcpyHostToDevice, c->stream));
         HIPCHK(hipMemcpyAsync(c->dist_dev + 27, T_grad, sizeof g.T, hipMemcpyHostToDevice, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
     }
-    if (T_grad && memcmp(g.T, T_grad, sizeof g.T) != 0) { memcpy(g.T, T_grad, sizeof g.T); c->grad_valid = false; c->grad_nb = false; c->brick_max_valid = false; }
+    if (T_grad && memcmp(g.T, T_grad, sizeof g.T) != 0) { memcpy(g.T, T_grad, sizeof g.T); drop_table_and_maxima(*c); }
     c->N = N;
     c->thin = thin;
     c->halo = (x0 == 0 && x1 == shape[0]) ? g.nx : 0;
@@ -347,9 +347,9 @@ static int staged_d2h(xb_ctx *c, void *dst_host, const void *src_dev, size_t byt
 }
 
 int xb_upload_density(xb_ctx *c, const double *rho_host) {
-    if (c) c->vac_by_tol = false;   // (the -1 labels no longer say "rho <= vac_tol" of the density on the card)
+    if (c) vacuum_marks_unproven(*c);
     NEED_GRID_THIN("xb_upload_density");
-    c->grad_valid = false; c->grad_nb = false; c->brick_max_valid = false; c->have_rho = true; c->cp_have = false; c->iso_have = false; c->rg_have = false;
+    density_written(*c);
     if (int rc = staged_h2d(c, c->rho, rho_host, c->N * sizeof(double))) return rc;
     HIPCHK(hipStreamSynchronize(c->stream));
     return XB_OK;
@@ -390,7 +390,7 @@ static int parse_text(xb_ctx *c, const char *who, const char *text, int64_t nbyt
                       int64_t *n_host) {
     if (!text || nbytes <= 0) return fail(XB_E_ARG, "%s: empty text", who);
     if (nbytes / (TPB * TXT_BYTES) >= (1LL << 31) - 2) return fail(XB_E_LIMIT, "%s: text too large", who);
-    c->grad_valid = false; c->grad_nb = false; c->brick_max_valid = false; c->have_rho = true; c->cp_have = false; c->iso_have = false; c->rg_have = false;
+    density_written(*c);
     static const double P10[23] = {1e0, 1e1, 1e2, 1e3, 1e4, 1e5, 1e6, 1e7, 1e8, 1e9, 1e10, 1e11,
                                    1e12, 1e13, 1e14, 1e15, 1e16, 1e17, 1e18, 1e19, 1e20, 1e21, 1e22};
     const int nblk = (int)((nbytes + TPB * TXT_BYTES - 1) / (TPB * TXT_BYTES));
@@ -470,7 +470,7 @@ static int parse_text(xb_ctx *c, const char *who, const char *text, int64_t nbyt
 }  // extern "C++"
 int xb_parse_density_text(xb_ctx *c, const char *text, int64_t nbytes, double divisor, int64_t *n_tokens,
                           int64_t *n_host) {
-    if (c) c->vac_by_tol = false;   // (the -1 labels no longer say "rho <= vac_tol" of the density on the card)
+    if (c) vacuum_marks_unproven(*c);
     NEED_GRID("xb_parse_density_text");
     if (!(divisor == divisor) || divisor == 0.) return fail(XB_E_ARG, "xb_parse_density_text: bad divisor");
     const TxtFortran map{c->g.nx, c->g.ny, c->g.nz, divisor};
@@ -478,7 +478,7 @@ int xb_parse_density_text(xb_ctx *c, const char *text, int64_t nbytes, double di
 }
 int xb_parse_cube_text(xb_ctx *c, const char *text, int64_t nbytes, int64_t nval, int64_t pick, int accumulate,
                        double scale, int64_t *n_tokens, int64_t *n_host) {
-    if (c) c->vac_by_tol = false;   // (the -1 labels no longer say "rho <= vac_tol" of the density on the card)
+    if (c) vacuum_marks_unproven(*c);
     NEED_GRID("xb_parse_cube_text");
     if (nval < 1 || pick < 0 || pick >= nval) return fail(XB_E_ARG, "xb_parse_cube_text: bad nval %lld / pick %lld", (long long)nval, (long long)pick);
     if (nval > XB_INT_MAX / c->N) return fail(XB_E_LIMIT, "xb_parse_cube_text: %lld voxels x %lld values exceed %d numbers", (long long)c->N, (long long)nval, XB_INT_MAX);
@@ -487,12 +487,12 @@ int xb_parse_cube_text(xb_ctx *c, const char *text, int64_t nbytes, int64_t nval
 }
 
 int xb_synth_density(xb_ctx *c, const double lattice[9], const double *atoms5, int64_t n_atoms, double background) {
-    if (c) c->vac_by_tol = false;   // (the -1 labels no longer say "rho <= vac_tol" of the density on the card)
+    if (c) vacuum_marks_unproven(*c);
     NEED_GRID("xb_synth_density");
     if (n_atoms < 0 || n_atoms > XB_SYNTH_ATOMS_MAX) return fail(XB_E_ARG, "xb_synth_density: bad atom count");
     if ((16 + 5 * (size_t)n_atoms) * sizeof(double) > c->stage_bytes)   // (never with need_scratch's floor)
         return fail(XB_E_LIMIT, "xb_synth_density: %lld atoms do not fit the scratch buffer", (long long)n_atoms);
-    c->grad_valid = false; c->grad_nb = false; c->brick_max_valid = false; c->have_rho = true; c->cp_have = false; c->iso_have = false; c->rg_have = false;
+    density_written(*c);
     double *tmp = (double *)c->stage;
     HIPCHK(hipMemcpyAsync(tmp, lattice, 9 * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(tmp + 16, atoms5, n_atoms * 5 * sizeof(double), hipMemcpyHostToDevice, c->stream));
@@ -506,16 +506,9 @@ static size_t dtype_size(int dtype) { return (dtype == XB_I8 || dtype == XB_I16 
 
 int xb_upload_labels(xb_ctx *c, const void *labels_host, int dtype) {
     NEED_GRID_RAW_THIN("xb_upload_labels");
-    c->labels_zero_pending = false;   // every label is overwritten
-    c->zero_outside[0] = -1;
-    c->list_valid = false; c->chg_n = -1;
-    c->has_vacuum = true;
-    c->vac_by_tol = false;
-    c->buni_valid = false; c->regions_labels = false;
     const size_t sz = dtype_size(dtype);
     if (!sz) return fail(XB_E_ARG, "xb_upload_labels: bad dtype code %d", dtype);
-    c->label_wire = sz >= 4 ? 4 : (int)sz;   // what the caller's own dtype holds, the narrowed halo holds
-    c->have_labels = true;
+    labels_overwritten(*c, sz >= 4 ? 4 : (int)sz, true);   // (what the caller's own dtype holds, the narrowed halo holds; the vacuum is looked for below)
     if (dtype == XB_I32) {
         if (int rc = staged_h2d(c, c->labels, labels_host, c->N * 4)) return rc;
     } else {
@@ -561,7 +554,7 @@ int xb_download_labels(xb_ctx *c, void *labels_host, int dtype) {
             k_narrow<long long><<<nblocks(c->N), TPB, 0, c->stream>>>(c->labels, (long long *)dev_view, c->N);
         HIPCHK(hipGetLastError());
     } else {
-        c->chg_n = -1;   // (the narrowing goes through `stage`, whose upper half may list the changed voxels)
+        stage_clobbered(*c);   // (the narrowing goes through `stage`)
         const long long per = std::max<long long>(1, (long long)(c->stage_bytes / sz));
         for (long long o = 0; o < c->N; o += per) {
             const long long n = std::min(per, c->N - o);
@@ -577,7 +570,7 @@ int xb_download_labels(xb_ctx *c, void *labels_host, int dtype) {
 }
 int xb_upload_known(xb_ctx *c, const int8_t *known_host) {
     NEED_GRID("xb_upload_known");
-    c->list_valid = false; c->chg_n = -1;
+    drop_edge_lists(*c);
     HIPCHK(hipMemcpyAsync(c->known, known_host, c->N, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     return XB_OK;
@@ -591,7 +584,7 @@ int xb_download_known(xb_ctx *c, int8_t *known_host) {
 
 int xb_vacuum_assign(xb_ctx *c, double vac_tol, double voxel_volume, double *vac_charge, double *vac_volume) {
     NEED_GRID_RAW_THIN("xb_vacuum_assign");
-    c->buni_valid = false; c->regions_labels = false;
+    drop_label_marks(*c);
     c->label_wire = 1;   // every valid plane holds 0 / -1 from here on
     c->have_labels = true;
     c->labels_zero_pending = false;

@@ -250,7 +250,7 @@ int xb_hirshfeld_field(xb_ctx *c, int mode, int flags, double *out_host, void *o
         if (io_overlaps(lo, hi, c->hs_buf, c->hs_cap * 8)) return fail(XB_E_ARG, "xb_hirshfeld_field: the destination overlaps the setup");
     } else {
         if (c->stage_bytes < (size_t)c->N * sizeof(double)) return fail(XB_E_STATE, "xb_hirshfeld_field: the scratch buffer holds no whole grid");
-        c->chg_n = -1;   // (the upper half of `stage` may list the changed voxels)
+        stage_clobbered(*c);
         dst = (double *)c->stage;
     }
     const HsGeom &G = c->hs_geom;

@@ -136,9 +136,9 @@ int xb_import_density(xb_ctx *c, const void *dev_ptr, int dtype, const int64_t s
     if (int rc = io_check(c, "xb_import_density", dev_ptr, isz, shape, stride, &lo, &hi)) return rc;
     if (io_overlaps(lo, hi, c->rho, (size_t)c->N * 8)) return fail(XB_E_ARG, "xb_import_density: the source overlaps the resident density");
     // from here on as xb_upload_density
-    c->vac_by_tol = false;   // (the -1 labels no longer say "rho <= vac_tol" of the density on the card)
+    vacuum_marks_unproven(*c);
     NEED_GRID_THIN("xb_import_density");
-    c->grad_valid = false; c->grad_nb = false; c->brick_max_valid = false; c->have_rho = true; c->cp_have = false; c->iso_have = false; c->rg_have = false;
+    density_written(*c);
     const hipStream_t s = (hipStream_t)stream;
     if (int rc = io_after_caller(c, s)) return rc;
     if (int rc = dtype == XB_F32 ? io_import_density(c, (const float *)dev_ptr, stride, c->rho) : io_import_density(c, (const double *)dev_ptr, stride, c->rho)) return rc;
@@ -154,15 +154,7 @@ int xb_import_labels(xb_ctx *c, const void *dev_ptr, int dtype, void *stream) {
     uintptr_t lo, hi;
     if (int rc = io_check_flat(c, "xb_import_labels", dev_ptr, sz, &lo, &hi)) return rc;
     if (io_overlaps(lo, hi, c->labels, (size_t)c->N * 4)) return fail(XB_E_ARG, "xb_import_labels: the source overlaps the resident labels");
-    // from here on as xb_upload_labels
-    c->labels_zero_pending = false;   // every label is overwritten
-    c->zero_outside[0] = -1;
-    c->list_valid = false; c->chg_n = -1;
-    c->has_vacuum = true;
-    c->vac_by_tol = false;
-    c->buni_valid = false; c->regions_labels = false;
-    c->label_wire = sz >= 4 ? 4 : (int)sz;
-    c->have_labels = true;
+    labels_overwritten(*c, sz >= 4 ? 4 : (int)sz, true);   // from here on as xb_upload_labels
     const hipStream_t s = (hipStream_t)stream;
     if (int rc = io_after_caller(c, s)) return rc;
     if (dtype == XB_I32) HIPCHK(hipMemcpyAsync(c->labels, dev_ptr, (size_t)c->N * 4, hipMemcpyDeviceToDevice, c->stream));

@@ -55,7 +55,7 @@ int xb_isosurface(xb_ctx *c, const void *field_dev, const void *colour_dev, cons
     if (int rc = settle_labels(c)) return rc;
     HIPCHK(hipStreamSynchronize(c->stream));
     isosurface_free(c);
-    c->chg_n = -1;   // (the upper half of `stage` may list the changed voxels)
+    stage_clobbered(*c);
     const double *f = field_dev ? (const double *)field_dev : c->rho;
     const double *gcol = (const double *)colour_dev;
     unsigned int *word = reinterpret_cast<unsigned int *>(c->stage);

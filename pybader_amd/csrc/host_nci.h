@@ -51,7 +51,7 @@ int xb_nci_field(xb_ctx *c, const double lattice[9], int flags, double *s_host, 
     } else {
         if (c->stage_bytes < bytes) return fail(XB_E_STATE, "xb_nci_field: the scratch buffer holds no whole grid");
         HIPCHK(tmp.alloc((size_t)c->N));
-        c->chg_n = -1;   // (the upper half of `stage` may list the changed voxels)
+        stage_clobbered(*c);
         ds = (double *)c->stage;
         dx = tmp.p;
     }

@@ -162,7 +162,7 @@ int xb_edge_find(xb_ctx *c, int64_t *edges) {
     NEED_GRID("xb_edge_find");
     const Grid &g = c->g;
     bool dilate_owned = false;
-    c->chg_n = -1;   // `known` is rewritten: the changed-voxel list of an earlier retrace pass no longer describes it
+    stage_clobbered(*c);   // (`known` is rewritten)
     if (int rc = edge_find_launch(c, &dilate_owned)) return rc;
     int n = 0;
     if (int rc = read_counter(c, CT_N_EDGES, &n)) return rc;
@@ -212,7 +212,7 @@ int xb_escaped_paths(xb_ctx *c, int64_t max_len, int64_t *n_paths, int64_t *n_vo
     c->g.main_ties = 0;   // retraces follow refinement.py's rule
     int n = 0;
     if (int rc = compact(c, -6, &n)) return rc;
-    c->list_valid = false; c->chg_n = -1;
+    drop_edge_lists(*c);
     if (n) {
         if (max_len < 2 || max_len > (1 << 15)) return fail(XB_E_ARG, "xb_escaped_paths: max_len out of range");
         const int lmax = (int)max_len, chunk = (int)std::max<int64_t>(256, std::min<int64_t>(8192, (32LL << 20) / max_len));
@@ -291,8 +291,7 @@ static int voxel_io(xb_ctx *c, const int64_t *idx, int64_t n, int32_t *lab, int8
         if (e == hipSuccess) e = hipMemcpyAsync(dlab, lab, n * sizeof(int), hipMemcpyHostToDevice, c->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(dkn, kn, n, hipMemcpyHostToDevice, c->stream);
         if (e == hipSuccess) k_move_voxels<true><<<(unsigned)((n + 255) / 256), 256, 0, c->stream>>>(d, (int)n, c->labels, c->known, dlab, dkn);
-        c->list_valid = false; c->chg_n = -1;
-        c->buni_valid = false; c->regions_labels = false;
+        drop_edge_lists(*c); drop_label_marks(*c);
         c->zero_outside[0] = -1;
         // The halo's wire width is a value every rank must agree on (ncclSend / ncclRecv sizes): a scatter is a per-rank event
         // (only the ranks with parked retraces scatter), so it does NOT widen it -- the labels it writes are labels
@@ -325,7 +324,7 @@ static int refine_trace_impl(xb_ctx *c, int flag, int64_t *changed, int64_t *esc
     int n = 0;
     if (c->list_valid && flag == -2) n = c->list_n;
     else if (int rc = compact(c, flag, &n)) return rc;
-    c->list_valid = false; c->chg_n = -1;  // the retrace rewrites known
+    drop_edge_lists(*c);  // the retrace rewrites known
     c->buni_valid = false;  // ... and may relabel edge voxels; st is also edge_check's scratch
     c->walk_n_out = 0; c->walk_n_res = 0; c->walk_out_dev = nullptr;
     c->walk_host.clear(); c->res_host.clear();
@@ -482,7 +481,7 @@ int xb_walkers_apply(xb_ctx *c, const int64_t *results, int64_t n, int64_t *chan
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(c->host_ints, c->counters + CT_WALK_CHANGED, CT_INTS(CT_WALK_CHANGED, CT_WALK_STUCK) * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    c->list_valid = false; c->chg_n = -1; c->buni_valid = false;
+    drop_edge_lists(*c); c->buni_valid = false;
     if (changed) *changed = c->host_ints[0];
     if (stuck) *stuck = c->host_ints[1];
     return XB_OK;
@@ -636,8 +635,7 @@ int xb_edge_check(xb_ctx *c, int64_t *checked, int64_t *edges) {
     NEED_GRID("xb_edge_check");
     const Grid &g = c->g;
     const int chg_n = c->chg_n;   // (read before the invalidations below)
-    c->list_valid = false; c->chg_n = -1;
-    c->buni_valid = false;
+    drop_edge_lists(*c); c->buni_valid = false;
     if (g.x1 - g.x0 != g.nx) return fail(XB_E_STATE, "xb_edge_check: one slab only; slabs use xb_edge_check_local + xb_edge_check_global");
     int n = 0;
     bool listed = false;
@@ -666,7 +664,7 @@ int xb_edge_check(xb_ctx *c, int64_t *checked, int64_t *edges) {
 // (xb_edge_check_global).  Needs label AND known halos refreshed beforehand.
 int xb_edge_check_local(xb_ctx *c, int64_t *n_out) {
     NEED_GRID("xb_edge_check_local");
-    c->list_valid = false; c->chg_n = -1;
+    drop_edge_lists(*c);
     int n = 0;
     if (int rc = compact(c, -2, &n)) return rc;   // owned planes only
     if (n) {
@@ -691,8 +689,7 @@ int xb_edge_check_local_fetch(xb_ctx *c, int64_t *idx_out, int8_t *cls_out) {
 int xb_edge_check_global(xb_ctx *c, const int64_t *idx, const int8_t *cls, int64_t n, int64_t *checked, int64_t *edges) {
     NEED_GRID("xb_edge_check_global");
     const Grid &g = c->g;
-    c->list_valid = false; c->chg_n = -1;
-    c->buni_valid = false;
+    drop_edge_lists(*c); c->buni_valid = false;
     if (checked) *checked = 0;
     if (edges) *edges = 0;
     if (n < 0 || n > c->N) return fail(XB_E_ARG, "xb_edge_check_global: bad list length");
@@ -738,7 +735,7 @@ static int refine_iteration_fused(xb_ctx *c, int64_t *edges, int64_t *changed, b
     const GridL gl = light(g);
     static_assert(FS_N_CHGLIST == FS_N_EDGES + 6, "one memset clears the refinement's counters");
     HIPCHK(hipMemsetAsync(fs + FS_N_EDGES, 0, 7 * sizeof(int), c->stream));   // edges, changed, escaped, overflows, deferred, listed tiles, relabelled list
-    c->chg_n = -1;
+    stage_clobbered(*c);
     bool bits = false;   // the sweep by row bit masks (sweep_bits_ok)
     {
         ScopedTimer t(c, XB_TIMER_EDGE_FIND);
@@ -772,8 +769,7 @@ static int refine_iteration_fused(xb_ctx *c, int64_t *edges, int64_t *changed, b
         }
     }
     if (!bits) c->stat_voxel_sweeps++;
-    c->list_valid = false; c->chg_n = -1;
-    c->buni_valid = false;
+    drop_edge_lists(*c); c->buni_valid = false;
     if (late_records) {
         // the records of the band bricks (k_masks.h), now that the flags say where the band is
         if (int rc = need_grad(c)) return rc;
@@ -788,7 +784,7 @@ static int refine_iteration_fused(xb_ctx *c, int64_t *edges, int64_t *changed, b
         c->grad_valid = true;
         c->grad_cover = 1;
         c->grad_rule = 0;
-        c->regions_labels = false;
+        drop_label_marks(*c);   // (buni_valid fell after the sweep, above)
         c->blab = nullptr;
         c->table_stage = 0;
     }
@@ -865,7 +861,7 @@ int xb_refine(xb_ctx *c, int mode, int64_t iters, int64_t *log, int64_t log_capa
     const int rc = refine_impl(c, mode, iters, log, log_capacity, n_iters);
     // the changed-voxel list in `stage` is private to this call's iterations: a later xb_edge_check through the C ABI compacts
     // known == -2 itself instead of trusting a list that other calls (downloads through `stage`, xb_edge_find) may have clobbered
-    if (c) c->chg_n = -1;
+    if (c) stage_clobbered(*c);
     return rc;
 }
 static int refine_impl(xb_ctx *c, int mode, int64_t iters, int64_t *log, int64_t log_capacity, int64_t *n_iters) {
@@ -938,7 +934,7 @@ int xb_assign_refine(xb_ctx *c, int method, int mode, int64_t iters, int64_t *n_
         c->defer_wait = false;
         if (rc) { c->pending_assign = false; return rc; }
         rc = refine_impl(c, mode, iters, log, log_capacity, n_iters);
-        c->chg_n = -1;
+        stage_clobbered(*c);
         const bool redo = rc == XB_STEP_REDO || c->pending_assign;   // (pending still: the refinement returned before its first wait)
         const bool arrived = rc == XB_STEP_REDO;                     // the assignment's state block is on the host
         c->pending_assign = false;
@@ -954,15 +950,15 @@ int xb_assign_refine(xb_ctx *c, int method, int mode, int64_t iters, int64_t *n_
             // refinement as an ordinary call.  (Round 5: this used to repeat the assignment from the start -- 11.2 instead of 5.6 ms
             // per step on a 216-atom cell, whose 19 K undecidable walkers make every step end here.)
             c->grad_rule = 1;
-            c->buni_valid = false; c->regions_labels = false;
+            drop_label_marks(*c);
             c->regions_pending = true;
-            c->list_valid = false;
+            drop_edge_lists(*c);   // (chg_n fell after the refinement, above)
             if (int rc2 = assign_neargrid_tail(c, n_maxima)) return rc2;
             return xb_refine(c, mode, iters, log, log_capacity, n_iters);
         }
-        c->grad_valid = false; c->grad_nb = false;   // the ordinary way, from the start: the assignment rewrites every label
+        drop_table(*c);   // the ordinary way, from the start: the assignment rewrites every label
         c->first_clean = false;
-        c->buni_valid = false; c->regions_labels = false;
+        drop_label_marks(*c);
         if (n_iters) *n_iters = 0;
     }
     if (int rc = xb_assign(c, method, n_maxima)) return rc;

@@ -67,7 +67,7 @@ int xb_regions_label(xb_ctx *c, int mode, const void *field_dev, double level, c
     }
     HIPCHK(hipStreamSynchronize(c->stream));
     c->rg_have = false; c->rg_sh_have = false;
-    c->chg_n = -1;   // (the upper half of `stage` may list the changed voxels)
+    stage_clobbered(*c);
     if (!c->rg_map) HIPCHK(hipMalloc(&c->rg_map, (size_t)N * sizeof(int)));
     const double *f = field_dev ? (const double *)field_dev : c->rho;
     int *num = reinterpret_cast<int *>(c->stage);

@@ -5,7 +5,7 @@
 int xb_set_table_window(xb_ctx *c, int64_t margin) {
     NEED_GRID("xb_set_table_window");
     Grid &g = c->g;
-    c->grad_valid = false; c->grad_nb = false;
+    drop_table(*c);
     c->table_stage = 0;
     const int own = g.x1 - g.x0;
     if (margin < 0 || own == g.nx) { g.wx0 = 0; g.wlen = g.nx; c->table_margin = -1; g.wbase = 0; return XB_OK; }
@@ -136,7 +136,7 @@ void *xb_labels_ptr(xb_ctx *c) {
 }
 void *xb_known_ptr(xb_ctx *c) { return c ? (void *)c->known : nullptr; }
 void *xb_density_ptr(xb_ctx *c) {
-    if (c) { c->have_rho = true; c->cp_have = false; c->iso_have = false; c->rg_have = false; }   // (whoever holds the pointer may write it)
+    if (c) density_pointer_out(*c);   // (whoever holds the pointer may write it)
     return c ? (void *)c->rho : nullptr;
 }
 int64_t xb_plane_elems(xb_ctx *c) { return c ? c->g.nyz : 0; }
@@ -155,9 +155,9 @@ int xb_copy_planes(xb_ctx *c, int which, int to_device, void *host, int64_t xa, 
         c->zero_outside[0] = -1;
         c->label_wire = std::max(c->label_wire, labels_fit_wire((const int32_t *)host, (xb - xa) * c->g.nyz));
     }
-    if (to_device) { c->list_valid = false; c->chg_n = -1; c->has_vacuum = c->has_vacuum || c->g.x1 - c->g.x0 == c->g.nx;
+    if (to_device) { drop_edge_lists(*c); c->has_vacuum = c->has_vacuum || c->g.x1 - c->g.x0 == c->g.nx;
                      c->buni_valid = c->buni_valid && c->buni_halo_safe && c->g.x1 - c->g.x0 < c->g.nx;
-                     if (c->g.x1 - c->g.x0 == c->g.nx) c->regions_labels = false; }
+                     if (c->g.x1 - c->g.x0 == c->g.nx) drop_label_marks(*c); }   // (on the whole grid buni_valid fell on the line above)
     if (to_device) HIPCHK(hipMemcpyAsync(dev + off, host, bytes, hipMemcpyHostToDevice, c->stream));
     else HIPCHK(hipMemcpyAsync(host, dev + off, bytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));

@@ -31,10 +31,7 @@ static int begin_assignment(xb_ctx *c, int *counts, int n, bool invalidate) {
     }
     c->first_clean = false;
     c->regions_pending = false;
-    if (invalidate) {
-        c->buni_valid = false; c->regions_labels = false;
-        c->list_valid = false; c->chg_n = -1;
-    }
+    if (invalidate) { drop_label_marks(*c); drop_edge_lists(*c); }
     return XB_OK;
 }
 

@@ -80,7 +80,7 @@ int xb_laplacian_field(xb_ctx *c, const double lattice[9], int flags, double *ou
         if (io_overlaps(lo, hi, c->rho, (size_t)c->N * 8)) return fail(XB_E_ARG, "xb_laplacian_field: the destination overlaps the resident density");
     } else {
         if (c->stage_bytes < (size_t)c->N * sizeof(double)) return fail(XB_E_STATE, "xb_laplacian_field: the scratch buffer holds no whole grid");
-        c->chg_n = -1;   // (the upper half of `stage` may list the changed voxels)
+        stage_clobbered(*c);
         dst = (double *)c->stage;
     }
     if (flags & XB_STENCIL_GATHER) k_laplacian_field_gather<<<nblocks(c->N), TPB, 0, c->stream>>>(g.nx, g.ny, g.nz, c->rho, K, dst);

@@ -36,7 +36,7 @@ int xb_charge_sum(xb_ctx *c, double voxel_volume, int64_t n_labels, double *char
 int xb_volume_assign(xb_ctx *c, const int64_t *swap, int64_t n_swap) {
     NEED_GRID("xb_volume_assign");
     c->zero_outside[0] = -1;
-    c->buni_valid = false; c->regions_labels = false;
+    drop_label_marks(*c);
     if (n_swap <= 0) return XB_OK;
     if (n_swap > c->max_cap) return fail(XB_E_LIMIT, "xb_volume_assign: swap table too long");
     std::vector<int> s(n_swap);

@@ -40,15 +40,8 @@ int xb_voronoi_assign(xb_ctx *c, const double lattice[9], const double *atoms_ca
         HIPCHK(hipMalloc(&c->vo_buf, want * sizeof(double)));
         c->vo_cap = want;
     }
-    // from here on as xb_upload_labels: every label of the grid is overwritten
-    c->labels_zero_pending = false;
-    c->zero_outside[0] = -1;
-    c->list_valid = false; c->chg_n = -1;
-    c->has_vacuum = use_vac;
-    c->vac_by_tol = false;   // (the other labels are atoms, not the zeros an assignment expects next to its vacuum marks)
-    c->buni_valid = false; c->regions_labels = false;
-    c->label_wire = label_wire_for(n);
-    c->have_labels = true;
+    // every label of the grid is overwritten (vac_by_tol falls: the other labels are atoms, not the zeros an assignment expects next to its vacuum marks)
+    labels_overwritten(*c, label_wire_for(n), use_vac);
     double head[VO_HEAD] = {0.};
     VoGeom G;
     for (int x = -1; x < 2; x++)

@@ -66,7 +66,7 @@ static int weight_run(xb_ctx *c, const char *who, const WAlpha &al, double voxel
     const Grid &g = c->g;
     const long long N = c->N;
     double *S = c->w_S ? c->w_S : (double *)c->stage;
-    if (!c->w_S) c->chg_n = -1;   // (the upper half of `stage` may have listed the changed voxels)
+    if (!c->w_S) stage_clobbered(*c);   // (S goes into `stage`)
     const int *labels = (c->has_vacuum && !c->opt.weight_no_labels) ? c->labels : nullptr;
     HIPCHK(hipMemsetAsync(c->w_state, 0, WS_COUNT * sizeof(int), c->stream));
     const long long tiles = (long long)((g.nx + WT_X - 1) / WT_X) * ((g.ny + WT_Y - 1) / WT_Y) * ((g.nz + WT_Z - 1) / WT_Z);

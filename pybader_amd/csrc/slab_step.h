@@ -370,12 +370,12 @@ int xb_slab_assign_finish(xb_ctx *c, int64_t *n_maxima, int64_t *status) {
     if (h[FS_GROW_RETRY]) {
         c->grow_kill_launches = 1 << 20;
         c->stat_grow_retries++;
-        c->grad_valid = false; c->grad_nb = false;
+        drop_table(*c);
         if (status) *status = 1;
         return XB_OK;
     }
     if (!h[FS_SORT_OK]) {
-        c->grad_valid = false; c->grad_nb = false;
+        drop_table(*c);
         if (status) *status = 2;
         return XB_OK;
     }
@@ -413,8 +413,7 @@ int xb_slab_refine_pass(xb_ctx *c) {
         k_edge_dilate_list<<<2048, TPB, 0, c->stream>>>(gl, c->known, c->list, 0, c->counters + CT_N_EDGES);
     }
     c->g.main_ties = 0;
-    c->list_valid = false; c->chg_n = -1;
-    c->buni_valid = false;
+    drop_edge_lists(*c); c->buni_valid = false;
     c->walk_n_out = 0; c->walk_n_res = 0; c->walk_out_dev = nullptr;
     c->walk_host.clear(); c->res_host.clear();
     // everything but the sweep's edge count: overflows, changed, escaped ... deferred, the walker statistics (the sweep's own halo and tile counts are spent)
@@ -481,7 +480,7 @@ int xb_slab_walkers_round(xb_ctx *c, int src, int last) {
         c->walk_last = src;
     }
     HIPCHK(hipGetLastError());
-    c->list_valid = false; c->chg_n = -1; c->buni_valid = false;
+    drop_edge_lists(*c); c->buni_valid = false;
     return XB_OK;
 }
 
