@@ -192,6 +192,11 @@ int xb_refine_trace_escaped(xb_ctx *c, int64_t *changed, int64_t *escaped);
 int xb_escaped_paths(xb_ctx *c, int64_t max_len, int64_t *n_paths, int64_t *n_voxels);
 int xb_escaped_paths_fetch(xb_ctx *c, int64_t *starts, int64_t *offsets, int64_t *voxels, int8_t *complete);
 int xb_gather_voxels(xb_ctx *c, const int64_t *idx, int64_t n, int32_t *labels_out, int8_t *known_out);
+/* xb_scatter_voxels may write any voxel, so it invalidates what the context has cached of the labels: the edge and changed-voxel
+ * lists, the per-brick label marks of the last assignment (uniformity, the trapping regions' labels) and xb_vacuum_assign's
+ * promise that the -1 labels are exactly the voxels at or below its tolerance (the next assignment walks every brick again).  A
+ * negative label among the written ones makes the next assignment treat the grid as one with vacuum (-1 labels stay).  The
+ * halo's wire width grows only if a written label does not fit it (xb_label_wire).  The table and the density's results stay. */
 int xb_scatter_voxels(xb_ctx *c, const int64_t *idx, int64_t n, const int32_t *labels_in, const int8_t *known_in);
 /* slab scheduler, escaped retraces carried on by their next owner.  A retrace that leaves this rank's valid planes is
  * parked (known == -6) and exported as a walker: XB_WALKER_WORDS int64 holding its start voxel and label, the voxel it
@@ -765,13 +770,20 @@ int xb_table_finish(xb_ctx *c, const int64_t *seeds, int64_t n_seeds, int64_t an
 /* ---- slab halo planes (multi-GPU) -------------------------------------------------------- */
 /* Device pointers of the label / known arrays and the plane size in elements, so that the slab
  * scheduler can hand plane ranges to RCCL (ncclSend/ncclRecv) or any other transport.  On a slab, writes through
- * the label pointer must stay within the planes [x0 - halo, x1 + halo): the library keeps the rest zero. */
+ * the label pointer must stay within the planes [x0 - halo, x1 + halo): the library keeps the rest zero.
+ * The library does not see what is written through xb_labels_ptr / xb_density_ptr: keeping its cached state in step with such
+ * writes is the caller's responsibility (write whole planes with xb_copy_planes or voxels with xb_scatter_voxels where that matters). */
 void *xb_labels_ptr(xb_ctx *c);
 void *xb_known_ptr(xb_ctx *c);
 void *xb_density_ptr(xb_ctx *c);
 int64_t xb_plane_elems(xb_ctx *c);
 /* copy whole x-planes [xa,xb) of labels/known between host and device (halo transport over the
- * host / gloo; the RCCL transport works on the device pointers above) */
+ * host / gloo; the RCCL transport works on the device pointers above).  Label planes copied to the device invalidate the
+ * edge and changed-voxel lists and xb_vacuum_assign's promise about the -1 labels, as xb_scatter_voxels does.  On a context that
+ * holds the whole grid they also drop the per-brick label marks, and the next assignment treats the grid as one with vacuum
+ * whether the planes hold a -1 or not; on a slab the planes are taken to be halo planes of peers that ran the same assignment
+ * (the regions' labels stay; a negative label still brings the vacuum back).  Planes of `known` drop the lists and the
+ * uniformity marks.  Copies to the host invalidate nothing. */
 int xb_copy_planes(xb_ctx *c, int which /*0 labels,1 known*/, int to_device, void *host, int64_t xa, int64_t xb);
 /* Bytes per label (1 / 2 / 4) a label halo travels in (xb_comm_exchange_planes): the narrowest signed width that holds every
  * resident label -- the reference's own dtype_calc(-n_maxima) (thread_handlers.py:70-74, utils.py:25-37).  Sender and

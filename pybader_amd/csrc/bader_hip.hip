@@ -277,10 +277,11 @@ struct xb_ctx : CtxState {   // (ctx_state.h: the flags of the cached state and 
 
 // utils.dtype_calc(-n) as a byte width (utils.py:25-37): the narrowest signed type for labels 0..n-1 and -1
 static inline int label_wire_for(long long n) { return 2 * n <= 255 ? 1 : (2 * n <= 65535 ? 2 : 4); }
-// the narrowest signed width that holds each of n labels (host array)
-static inline int labels_fit_wire(const int32_t *lab, long long n) {
+// the narrowest signed width that holds each of n labels (host array); *any_negative: one of them is below 0
+static inline int labels_fit_wire(const int32_t *lab, long long n, bool *any_negative = nullptr) {
     int32_t lo = 0, hi = 0;
     for (long long i = 0; i < n; i++) { lo = std::min(lo, lab[i]); hi = std::max(hi, lab[i]); }
+    if (any_negative) *any_negative = lo < 0;
     return (lo >= -128 && hi <= 127) ? 1 : ((lo >= -32768 && hi <= 32767) ? 2 : 4);
 }
 static inline unsigned nblocks(long long n) { return (unsigned)((n + TPB - 1) / TPB); }

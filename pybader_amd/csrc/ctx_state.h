@@ -48,3 +48,20 @@ static inline void labels_overwritten(CtxState &s, int wire, bool has_vacuum) {
     s.has_vacuum = has_vacuum; s.vac_by_tol = false;
     s.label_wire = wire; s.have_labels = true;
 }
+// SOME labels are overwritten from outside an assignment (xb_scatter_voxels, label planes of xb_copy_planes, the results of
+// xb_walkers_apply): the -1 labels are no longer xb_vacuum_assign's alone, and a negative label among the written ones brings the
+// vacuum back.  `wire` bytes hold each written label: the resident width only grows (see label_wire).  `marks_kept`: which
+// label marks the writer vouches for -- LABEL_MARKS_NONE; LABEL_MARKS_REGIONS: the written labels are retrace results or a
+// slab's halo planes from peers that ran the same assignment, a region's brick keeps the region's label; LABEL_MARKS_BOTH:
+// halo planes that the uniformity marks do not cover either.  `owned_only`: every written voxel lies in the owned planes (what
+// zero_outside says of the others stays true)
+enum { LABEL_MARKS_NONE = 0, LABEL_MARKS_REGIONS = 1, LABEL_MARKS_BOTH = 2 };
+static inline void labels_patched(CtxState &s, int wire, bool any_negative, int marks_kept, bool owned_only) {
+    vacuum_marks_unproven(s);
+    if (any_negative) s.has_vacuum = true;
+    drop_edge_lists(s); s.have_labels = true;
+    if (!owned_only) s.zero_outside[0] = -1;
+    if (wire > s.label_wire) s.label_wire = wire;
+    if (marks_kept < LABEL_MARKS_BOTH) s.buni_valid = false;
+    if (marks_kept < LABEL_MARKS_REGIONS) s.regions_labels = false;
+}

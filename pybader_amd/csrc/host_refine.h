@@ -291,13 +291,14 @@ static int voxel_io(xb_ctx *c, const int64_t *idx, int64_t n, int32_t *lab, int8
         if (e == hipSuccess) e = hipMemcpyAsync(dlab, lab, n * sizeof(int), hipMemcpyHostToDevice, c->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(dkn, kn, n, hipMemcpyHostToDevice, c->stream);
         if (e == hipSuccess) k_move_voxels<true><<<(unsigned)((n + 255) / 256), 256, 0, c->stream>>>(d, (int)n, c->labels, c->known, dlab, dkn);
-        drop_edge_lists(*c); drop_label_marks(*c);
-        c->zero_outside[0] = -1;
         // The halo's wire width is a value every rank must agree on (ncclSend / ncclRecv sizes): a scatter is a per-rank event
         // (only the ranks with parked retraces scatter), so it does NOT widen it -- the labels it writes are labels
         // already present on the grid.  Only a label the resident width cannot hold widens it (raw API use); a scheduler then
         // agrees on the width with xb_label_wire before its next exchange (slab.py does).
-        c->label_wire = std::max(c->label_wire, labels_fit_wire(lab, n));
+        // Any voxel may be written: no label mark survives, the -1 labels are no longer xb_vacuum_assign's, a -1 brings the vacuum back.
+        bool any_negative = false;
+        const int wire = labels_fit_wire(lab, n, &any_negative);
+        labels_patched(*c, wire, any_negative, LABEL_MARKS_NONE, false);
     } else {
         if (e == hipSuccess) k_move_voxels<false><<<(unsigned)((n + 255) / 256), 256, 0, c->stream>>>(d, (int)n, c->labels, c->known, dlab, dkn);
         if (e == hipSuccess) e = hipMemcpyAsync(lab, dlab, n * sizeof(int), hipMemcpyDeviceToHost, c->stream);
@@ -467,10 +468,12 @@ int xb_walkers_apply(xb_ctx *c, const int64_t *results, int64_t n, int64_t *chan
     if (n > (1 << 28)) return fail(XB_E_LIMIT, "xb_walkers_apply: too many results");
     const Grid &g = c->g;
     std::vector<int> pairs(2 * (size_t)n);
+    int32_t lo = 0, hi = 0;   // the range of the labels that may be written (a stuck pair writes none)
     for (int64_t i = 0; i < n; i++) {
         const int64_t v = results[i] & 0xffffffffLL;
         if (v >= c->N) return fail(XB_E_ARG, "xb_walkers_apply: voxel out of range");
         pairs[2 * i] = (int)v; pairs[2 * i + 1] = (int)(results[i] >> 32);
+        if (pairs[2 * i + 1] != XB_WALKER_STUCK) { lo = std::min(lo, pairs[2 * i + 1]); hi = std::max(hi, pairs[2 * i + 1]); }
     }
     if (int rc = ensure_walker_bufs(c, n)) return rc;
     int *d = (int *)c->walk_res;    // (the results of the last xb_walkers_continue were fetched to the host already)
@@ -481,7 +484,10 @@ int xb_walkers_apply(xb_ctx *c, const int64_t *results, int64_t n, int64_t *chan
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(c->host_ints, c->counters + CT_WALK_CHANGED, CT_INTS(CT_WALK_CHANGED, CT_WALK_STUCK) * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    drop_edge_lists(*c); c->buni_valid = false;
+    // (owned voxels only; a pair is a retrace's result: a voxel of a region's brick gets the region's label, the resident width holds it
+    // -- only a label from outside a retrace widens it or brings a vacuum back, as in xb_scatter_voxels)
+    const int32_t span[2] = {lo, hi};
+    labels_patched(*c, labels_fit_wire(span, 2), lo < 0, LABEL_MARKS_REGIONS, true);
     if (changed) *changed = c->host_ints[0];
     if (stuck) *stuck = c->host_ints[1];
     return XB_OK;

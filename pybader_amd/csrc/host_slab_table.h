@@ -150,14 +150,18 @@ int xb_copy_planes(xb_ctx *c, int which, int to_device, void *host, int64_t xa, 
     // (a slab's halo planes come from peers that ran the same assignment: the regions' labels stay what they are)
     // (planes from outside: any label may arrive -- but the halo's wire width must stay a collectively agreed value, so it is
     // widened only when a label of these planes does not fit it: never for planes of peers that ran the same assignment)
+    // On the whole grid nothing is known of the planes: no label mark survives and the vacuum counts as back, -1 among them or not.
+    // (the -1 labels are no longer xb_vacuum_assign's either way: a plane may zero a voxel below the tolerance)
+    const bool whole = c->g.x1 - c->g.x0 == c->g.nx;
     if (to_device && which == 0) {
-        c->have_labels = true;
-        c->zero_outside[0] = -1;
-        c->label_wire = std::max(c->label_wire, labels_fit_wire((const int32_t *)host, (xb - xa) * c->g.nyz));
+        bool any_negative = false;
+        const int wire = labels_fit_wire((const int32_t *)host, (xb - xa) * c->g.nyz, &any_negative);
+        labels_patched(*c, wire, any_negative || whole, whole ? LABEL_MARKS_NONE : (c->buni_halo_safe ? LABEL_MARKS_BOTH : LABEL_MARKS_REGIONS), false);
+    } else if (to_device) {   // planes of `known`
+        drop_edge_lists(*c); c->has_vacuum = c->has_vacuum || whole;
+        c->buni_valid = c->buni_valid && c->buni_halo_safe && !whole;
+        if (whole) drop_label_marks(*c);
     }
-    if (to_device) { drop_edge_lists(*c); c->has_vacuum = c->has_vacuum || c->g.x1 - c->g.x0 == c->g.nx;
-                     c->buni_valid = c->buni_valid && c->buni_halo_safe && c->g.x1 - c->g.x0 < c->g.nx;
-                     if (c->g.x1 - c->g.x0 == c->g.nx) drop_label_marks(*c); }   // (on the whole grid buni_valid fell on the line above)
     if (to_device) HIPCHK(hipMemcpyAsync(dev + off, host, bytes, hipMemcpyHostToDevice, c->stream));
     else HIPCHK(hipMemcpyAsync(host, dev + off, bytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));

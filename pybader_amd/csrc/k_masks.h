@@ -430,7 +430,11 @@ __global__ __launch_bounds__(TPB) void k_brick_masks(GT g, const double *__restr
     static_assert(GT_X == 8, "eight x-positions per column");
     if (__any(any_tie) && threadIdx.x % XB_WAVE == 0) atomicAdd(tie_count, 1);  // only != 0 matters
     atomicOr(&s_mask[tz >> 3], mine);
-    if (bpot && col_in) {   // float order as signed-int order (a potential only steers the growth's guess: precision is irrelevant)
+    // float order as signed-int order.  For the growth a potential only steers the guess, but brick_is_vacuum (k_trace.h) takes a
+    // correctness decision from it: bpot must stay an image of the brick's OWN IN-GRID maximum (no halo, no wrapped plane) from
+    // which an upper bound follows -- the round-to-nearest float, whose error brick_is_vacuum's margin covers (FLT_MIN below the
+    // normal floats).  A maximum beyond FLT_MAX becomes +-inf and a NaN stays one: both make that test refuse (conservative).
+    if (bpot && col_in) {
         const int fi = __float_as_int((float)cmax);
         atomicMax(&s_pot[tz >> 3], fi >= 0 ? fi : fi ^ 0x7fffffff);
     }

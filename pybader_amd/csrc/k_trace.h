@@ -139,13 +139,17 @@ __device__ __forceinline__ int compact3(unsigned x) {   // every third bit of x,
 // of walkers that leave at once (1.4 + 0.4 ms of a 5.7 ms step at 512^3).  `bpot` (pass A's brick potentials: the brick's
 // largest density as a float in integer order) says which bricks these are; they stay off the list and their brick label
 // becomes XB_NOREC: "no records here" -- a walker that steps into one (downhill across the tolerance: not excluded) is handed
-// to the exact slow kernel, which works from rho.  The float is compared with a margin that covers its rounding.
+// to the exact slow kernel, which works from rho.  The float is compared with a margin that covers its rounding: 1e-6 of it
+// (2^-24 would do) while it is a normal float, and FLT_MIN where the brick's maximum m became a subnormal float or 0 (with or
+// without flushing |f - m| < FLT_MIN) -- so m <= f + margin for every m, and a brick is skipped only if every voxel of it lies
+// below the tolerance.  A brick of exact zeros is still skipped under any tolerance above FLT_MIN.  |m| > FLT_MAX gives
+// f = +-inf, a NaN gives NaN: the sum is +inf or NaN, the comparison false, the brick walked.
 // (XB_NOREC itself: bader_kernels.h -- pass B reads it too)
 __device__ __forceinline__ bool brick_is_vacuum(const int *__restrict__ bpot, int b, double vac_tol) {
     if (!bpot) return false;
     const int p = bpot[b];
     const double f = (double)__int_as_float(p >= 0 ? p : p ^ 0x7fffffff);
-    return f + fabs(f) * 1e-6 < vac_tol;
+    return f + fmax(fabs(f) * 1e-6, 1.1754943508222875e-38 /* FLT_MIN */) < vac_tol;
 }
 __global__ __launch_bounds__(TPB) void k_brick_walk_list_morton(int nb0, int nb1, int nb2, unsigned n_codes,
                                                                 int *blab, int *walk, int *n_walk, const int *skip,

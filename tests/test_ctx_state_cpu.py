@@ -15,7 +15,8 @@ FIELDS = ['grad_valid', 'grad_nb', 'brick_max_valid', 'buni_valid', 'regions_lab
           'vac_by_tol', 'label_wire', 'labels_zero_pending', 'zero_outside0', 'zero_outside1', 'zero_outside2', 'have_rho',
           'have_labels', 'cp_have', 'iso_have', 'rg_have']
 FUNCS = ['drop_table', 'drop_table_and_maxima', 'drop_edge_lists', 'stage_clobbered', 'drop_label_marks',
-         'drop_density_results', 'vacuum_marks_unproven', 'density_written', 'density_pointer_out', 'labels_overwritten']
+         'drop_density_results', 'vacuum_marks_unproven', 'density_written', 'density_pointer_out', 'labels_overwritten',
+         'labels_patched']
 
 SHIM = '#include "ctx_state.h"\n' + r'''
 static void load(CtxState &s, const int *v) {
@@ -34,7 +35,7 @@ static void store(const CtxState &s, int *v) {
 }
 extern "C" int n_fields(void) { return 19; }
 extern "C" void defaults(int *v) { store(CtxState{}, v); }
-extern "C" int apply(int fn, int wire, int has_vacuum, int *v) {
+extern "C" int apply(int fn, int wire, int has_vacuum, int marks_kept, int owned_only, int *v) {
     CtxState s;
     load(s, v);
     switch (fn) {
@@ -49,6 +50,7 @@ extern "C" int apply(int fn, int wire, int has_vacuum, int *v) {
     case 7: density_written(s); break;
     case 8: density_pointer_out(s); break;
     case 9: labels_overwritten(s, wire, has_vacuum != 0); break;
+    case 10: labels_patched(s, wire, has_vacuum != 0, marks_kept, owned_only != 0); break;
     default: return -1;
     }
     store(s, v);
@@ -66,8 +68,20 @@ LABEL_MARKS = {'buni_valid': False, 'regions_labels': False}
 RESULTS = {'cp_have': False, 'iso_have': False, 'rg_have': False}
 
 
-def expected(fn, wire, has_vacuum):
-    """the stores of each function: field -> new value"""
+def expected(fn, wire, has_vacuum, marks_kept=0, owned_only=False, start=None):
+    """the stores of each function: field -> new value (labels_patched: `has_vacuum` says that a written label is negative; its
+    stores of has_vacuum and label_wire depend on the state it finds, `start`)"""
+    if fn == 'labels_patched':
+        out = dict(EDGE_LISTS, vac_by_tol=False, have_labels=True, label_wire=max(wire, start['label_wire']))
+        if has_vacuum:
+            out['has_vacuum'] = True
+        if not owned_only:
+            out['zero_outside0'] = -1
+        if marks_kept < 2:     # LABEL_MARKS_BOTH
+            out['buni_valid'] = False
+        if marks_kept < 1:     # LABEL_MARKS_REGIONS
+            out['regions_labels'] = False
+        return out
     return {
         'drop_table': TABLE,
         'drop_table_and_maxima': TABLE_MAXIMA,
@@ -97,9 +111,9 @@ def state(tmp_path_factory):
     lib = C.CDLL(str(so))
     assert lib.n_fields() == len(FIELDS)
 
-    def run(fn, start, wire=0, has_vacuum=False):
+    def run(fn, start, wire=0, has_vacuum=False, marks_kept=0, owned_only=False):
         v = (C.c_int * len(FIELDS))(*[int(start[f]) for f in FIELDS])
-        assert lib.apply(-1 if fn is None else FUNCS.index(fn), wire, int(has_vacuum), v) == 0
+        assert lib.apply(-1 if fn is None else FUNCS.index(fn), wire, int(has_vacuum), int(marks_kept), int(owned_only), v) == 0
         return dict(zip(FIELDS, v))
     run.lib = lib
     return run
@@ -123,7 +137,7 @@ def test_the_shim_round_trips_every_field(state):
         assert state(None, start) == start
 
 
-CASES = [(fn, 0, False) for fn in FUNCS[:-1]] + [('labels_overwritten', w, hv) for w in (1, 2, 4) for hv in (False, True)]
+CASES = [(fn, 0, False) for fn in FUNCS[:-2]] + [('labels_overwritten', w, hv) for w in (1, 2, 4) for hv in (False, True)]
 
 
 @pytest.mark.parametrize('fn,wire,has_vacuum', CASES)
@@ -139,3 +153,30 @@ def test_each_function_changes_exactly_its_fields(state, fn, wire, has_vacuum):
     # (has_vacuum and label_wire take the arguments: VALID holds (2, true), INVALID (4, false))
     moved = {f for start in (VALID, INVALID) for f in FIELDS if state(fn, start, wire, has_vacuum)[f] != start[f]}
     assert moved == set(stores)
+
+
+PATCH_CASES = [(w, neg, marks, owned) for w in (1, 2, 4) for neg in (False, True) for marks in (0, 1, 2) for owned in (False, True)]
+
+
+@pytest.mark.parametrize('wire,any_negative,marks_kept,owned_only', PATCH_CASES)
+def test_labels_patched_changes_exactly_its_fields(state, wire, any_negative, marks_kept, owned_only):
+    """some labels written from outside an assignment (xb_scatter_voxels, label planes of xb_copy_planes, xb_walkers_apply): the
+    vacuum marks fall, a negative label brings the vacuum back and none takes it away, the wire width only grows, the label
+    marks fall unless the writer vouches for them, zero_outside falls unless only owned planes were written"""
+    text = open(HEADER).read()
+    assert 'LABEL_MARKS_NONE = 0, LABEL_MARKS_REGIONS = 1, LABEL_MARKS_BOTH = 2' in text
+    # (VALID: has_vacuum set, wire 2; INVALID: has_vacuum clear, wire 4; the third start has the vacuum proven absent at wire 1)
+    for start in (VALID, INVALID, dict(VALID, has_vacuum=0, label_wire=1)):
+        got = state('labels_patched', start, wire, any_negative, marks_kept, owned_only)
+        stores = expected('labels_patched', wire, any_negative, marks_kept, owned_only, start)
+        want = dict(start, **{f: int(x) for f, x in stores.items()})
+        assert got == want, {f: (start[f], got[f], want[f]) for f in FIELDS if got[f] != want[f]}
+        assert got['vac_by_tol'] == 0 and got['list_valid'] == 0 and got['chg_n'] == -1 and got['have_labels'] == 1
+        assert got['has_vacuum'] == int(bool(start['has_vacuum']) or any_negative)
+        assert got['label_wire'] == max(wire, start['label_wire'])
+    moved = {f for start in (VALID, INVALID, dict(VALID, has_vacuum=0, label_wire=1)) for f in FIELDS
+             if state('labels_patched', start, wire, any_negative, marks_kept, owned_only)[f] != start[f]}
+    named = {'list_valid', 'chg_n', 'vac_by_tol', 'have_labels'} | ({'has_vacuum'} if any_negative else set()) | \
+        ({'label_wire'} if wire > 1 else set()) | (set() if owned_only else {'zero_outside0'}) | \
+        ({'buni_valid'} if marks_kept < 2 else set()) | ({'regions_labels'} if marks_kept < 1 else set())
+    assert moved == named
