@@ -1,12 +1,13 @@
 // bader_hip.hip -- libbader_hip.so: HIP kernels + C ABI (include/bader_hip.h) for gfx950.  ONE translation unit:
 //   kernels    k_common.h k_masks.h k_fused.h k_trace.h k_ongrid.h k_edges.h k_sums.h k_text.h k_format.h (fmt_core.h) k_interop.h k_weight.h k_moments.h k_adjacency.h k_merge.h k_voronoi.h k_critical.h k_stencil.h k_nci.h k_hirshfeld.h k_isosurface.h k_regions.h
-//   host side  this file (context struct, options, statistics, timing) + ctx_state.h (the cached-state flags and their invalidation events; plain C++) + host_context.h (life cycle, transfers)
-//              + host_assign.h (the table outside an assignment, the assignments) + host_refine.h + host_sums.h + host_slab_table.h (host-driven slab calls) + host_interop.h (device arrays in and out) + host_weight.h (the weight method) + host_moments.h (moments per label) + host_adjacency.h (surfaces between labels) + host_merge.h (merging volumes by persistence) + host_voronoi.h (the nearest-atom partition) + host_critical.h (critical points and the bond graph) + host_stencil.h (the Laplacian and the Hessian of the density) + host_nci.h (the NCI index: reduced gradient, sign(lambda2) rho, region sums, histogram) + host_hirshfeld.h (Hirshfeld charges, the promolecular and the deformation density) + host_isosurface.h (isosurfaces by marching tetrahedra) + host_regions.h (connected components of a mask: level-set islands, pockets, NCI domains) + comm.h (RCCL through the ABI)
+//   host side  this file (context struct, options, statistics, timing) + ctx_state.h (the cached-state flags and their invalidation events; plain C++) + ctx_buffers.h (the device blocks the analyses keep, their table and their accounting; plain C++) + host_context.h (life cycle, transfers)
+//              + host_assign.h (the table outside an assignment, the assignments) + host_refine.h + host_sums.h + host_slab_table.h (host-driven slab calls) + host_interop.h (device arrays in and out) + host_weight.h (the weight method) + host_moments.h (moments per label) + host_adjacency.h (surfaces between labels) + host_merge.h (merging volumes by persistence) + host_voronoi.h (the nearest-atom partition) + host_critical.h (critical points and the bond graph) + host_stencil.h (the Laplacian and the Hessian of the density) + host_nci.h (the NCI index: reduced gradient, sign(lambda2) rho, region sums, histogram) + host_hirshfeld.h (Hirshfeld charges, the promolecular and the deformation density) + host_isosurface.h (isosurfaces by marching tetrahedra) + host_regions.h (connected components of a mask: level-set islands, pockets, NCI domains) + host_analyses.h (what the analyses forget with the grid or its shape, their release calls) + comm.h (RCCL through the ABI)
 //              + slab_step.h (the slab step with its control flow on the device)
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -shared (see pybader_amd/build.py).
 #include "bader_kernels.h"
 #include "../../include/bader_hip.h"
 #include "ctx_state.h"
+#include "ctx_buffers.h"
 
 #include <algorithm>
 #include <cmath>
@@ -75,7 +76,7 @@ struct TimedKernel {
 };
 
 namespace xbcomm { struct State; }
-struct xb_ctx : CtxState {   // (ctx_state.h: the flags of the cached state and the events that drop them)
+struct xb_ctx : CtxState, CtxBuffers {   // (ctx_state.h: the flags of the cached state and the events that drop them; ctx_buffers.h: the analyses' device blocks)
     int device = 0;
     xbcomm::State *comm = nullptr;   // RCCL transport (comm.h), one process per GPU
     struct FmtState *fmt = nullptr;  // density -> text writer between xb_format_begin and xb_format_end (host_format.h)
@@ -199,75 +200,45 @@ struct xb_ctx : CtxState {   // (ctx_state.h: the flags of the cached state and 
     TimedKernel tk[XB_TIMER_COUNT];
     long long n_alloc = 0;
     bool thin = false;         // an axis has fewer than 3 voxels: transfers, the vacuum sweep and the weight method only (NEED_GRID)
-    // the weight method (host_weight.h): accumulators, pending counts, the two work lists, S when `stage` cannot hold it, the
-    // level loop's state block; the last call's statistics and results
-    double *w_A = nullptr, *w_V = nullptr, *w_S = nullptr;
-    unsigned char *w_pending = nullptr;
-    int *w_list[2] = {nullptr, nullptr};
-    int *w_state = nullptr;
-    long long w_cap = 0;       // voxels the weight buffers hold (0: not allocated)
+    // the analyses' device buffers are the blocks of ctx_buffers.h (BLK_*); here: what each keeps of its last call on the host
+    // the weight method (host_weight.h): the last call's statistics and results
     long long w_stat[6] = {0, 0, 0, 0, 0, 0};
     bool w_have = false;
     std::vector<int64_t> w_idx;
     std::vector<double> w_charge, w_volume;
-    // xb_moment_sum (host_moments.h): its one buffer (image vectors, position table, centres, sums, counts) and its size in doubles
-    double *m_buf = nullptr;
-    size_t m_cap = 0;
-    // xb_adjacency (host_adjacency.h): the pair table (dense or hashed) and its size in bytes; the last call's pairs in key order
-    unsigned long long *aj_buf = nullptr;
-    size_t aj_bytes = 0;
+    // xb_adjacency (host_adjacency.h): the last call's pairs in key order
     bool aj_have = false;
     int aj_dirs = 0;
     std::vector<int32_t> aj_a, aj_b;
     std::vector<int64_t> aj_facets, aj_sfacet;
     std::vector<double> aj_saddle;
-    // xb_merge_basins (host_merge.h): the per-label buffer and the labels it holds; the last call's results
-    void *mg_buf = nullptr;
-    int64_t mg_cap = 0;
+    // xb_merge_basins (host_merge.h): the last call's results
     bool mg_have = false;
     std::vector<int32_t> mg_root, mg_round;
     std::vector<double> mg_pers;
-    // xb_voronoi_assign (host_voronoi.h): its one buffer (image vectors, position table, atoms, statistics) and its size in doubles
-    double *vo_buf = nullptr;
-    size_t vo_cap = 0;
-    // xb_critical_points / xb_critical_bonds (host_critical.h): the classification table and the record list on the device (cp_cap
-    // records allocated, cp_n in use); the last call's records sorted by voxel, and the last bond graph.  cp_have falls with every
-    // writer of the density
-    unsigned char *cp_lut = nullptr;
-    unsigned long long *cp_list = nullptr;
-    size_t cp_cap = 0, cp_n = 0, cp_bond_voxels = 0;
+    // xb_critical_points / xb_critical_bonds (host_critical.h): cp_n records of the list on the device are in use; the last call's
+    // records sorted by voxel, and the last bond graph.  cp_have falls with every writer of the density
+    size_t cp_n = 0, cp_bond_voxels = 0;
     bool cb_have = false;
     std::vector<unsigned long long> cp_rec;
     std::vector<int32_t> cb_a, cb_b;
     std::vector<int64_t> cb_saddles, cb_voxel;
     std::vector<double> cb_rho;
-    // xb_laplacian_sum (host_stencil.h): its result buffer (sums, sums of magnitudes, counts) and its size in 8-byte words
-    double *st_buf = nullptr;
-    size_t st_cap = 0;
-    // xb_nci_sum / xb_nci_hist (host_nci.h): their buffer (sums and counts; thresholds, edges and counts) and its size in 8-byte words
-    double *nci_buf = nullptr;
-    size_t nci_cap = 0;
-    // xb_hirshfeld_setup (host_hirshfeld.h): its one buffer (position table, pro-atom tables, image list, results) and its size in
-    // doubles; hs_have: the buffer holds a setup, made on the shape hs_geom records (xb_set_grid drops it with the shape)
-    double *hs_buf = nullptr;
-    size_t hs_cap = 0, hs_acc = 0;   // (hs_acc: where the results start)
+    // xb_hirshfeld_setup (host_hirshfeld.h): hs_have: its buffer holds a setup, made on the shape hs_geom records (xb_set_grid drops
+    // it with the shape)
+    size_t hs_acc = 0;   // (where the results start, in doubles)
     bool hs_have = false;
     int64_t hs_n = 0;
     int hs_cus = 0;   // compute units of the device (sizes the sums' launch)
     HsGeom hs_geom{};
-    // xb_isosurface (host_isosurface.h): the mesh of the last call on the device (iso_v vertices, iso_t triangles, iso_bytes in
-    // all), its two scalars and the per-label volumes.  iso_have falls with every writer of the density
-    double *iso_vert = nullptr, *iso_col = nullptr;
-    long long *iso_tri = nullptr, *iso_cell = nullptr;
-    unsigned short *iso_wrap = nullptr;
-    size_t iso_v = 0, iso_t = 0, iso_bytes = 0;
+    // xb_isosurface (host_isosurface.h): the mesh of the last call on the device has iso_v vertices and iso_t triangles; its two
+    // scalars and the per-label volumes.  iso_have falls with every writer of the density
+    size_t iso_v = 0, iso_t = 0;
     double iso_area = 0., iso_volume = 0.;
     std::vector<double> iso_vbl;
-    // xb_regions_label (host_regions.h): the component of every voxel and the components' seeds on the device (rg_m components,
-    // rg_members voxels in them, rg_seed_cap seeds allocated), whether they are the NCI region's and the stencil they were made with; the last
-    // xb_regions_shares triplets.  rg_have falls with every writer of the density
-    int *rg_map = nullptr, *rg_seed = nullptr;
-    size_t rg_m = 0, rg_members = 0, rg_seed_cap = 0;
+    // xb_regions_label (host_regions.h): rg_m components with rg_members voxels in them, whether they are the NCI region's and the
+    // stencil they were made with; the last xb_regions_shares triplets.  rg_have falls with every writer of the density
+    size_t rg_m = 0, rg_members = 0;
     bool rg_sh_have = false, rg_nci = false, rg_timed = false;
     double rg_ms[4] = {0., 0., 0., 0.};   // XB_DOMAINS_TIMES: tile, link, flatten, numbering of the last labelling
     StCoeffs rg_K{};
@@ -305,6 +276,17 @@ struct DevBuf {
     DevBuf(const DevBuf &) = delete;
     DevBuf &operator=(const DevBuf &) = delete;
 };
+
+// the memory behind the analyses' blocks (ctx_buffers.h): the context's stream to wait for, hipMalloc, hipFree
+struct HipMem {
+    hipStream_t stream;
+    int wait() { HIPCHK(hipStreamSynchronize(stream)); return XB_OK; }
+    int alloc(void **p, size_t bytes) { HIPCHK(hipMalloc(p, bytes)); return XB_OK; }
+    void free(void *p) { hipFree(p); }
+};
+template <int K> static int reserve(xb_ctx *c, const BufWant (&want)[K]) { return buf_reserve(*c, HipMem{c->stream}, want); }
+static int reserve(xb_ctx *c, int b, size_t bytes) { return reserve(c, {{b, bytes, 0}}); }
+static void release(xb_ctx *c, int first, int last) { buf_release(*c, HipMem{c->stream}, first, last); }
 
 // the 14-distance form of the grid for the tiled field kernels; false when dist_mat is not symmetric
 static bool sym_grid(const Grid &g, GridS &s) {
@@ -392,6 +374,7 @@ const char *xb_last_error(void) { return g_err.c_str(); }
 #include "host_hirshfeld.h"
 #include "host_isosurface.h"
 #include "host_regions.h"
+#include "host_analyses.h"
 
 int xb_set_option(xb_ctx *c, int key, int value) {
     if (!c) return fail(XB_E_ARG, "null ctx");
@@ -452,17 +435,7 @@ int xb_memory_stats(xb_ctx *c, int64_t *bytes_total, int64_t *bytes_table, int64
     const long long N = c->N;
     const long long table = c->grad_cap * (long long)sizeof(GradRec);
     const long long scratch = c->list_cap * 4 + (long long)c->stage_bytes + c->ec_buf_cap * 4 + (c->ec_pend ? 8 * N + 16 : 0) +
-                              (c->w_cap ? 25 * c->w_cap + (c->w_S ? 8 * c->w_cap : 0) : 0) /* the weight method's buffers */ +
-                              (long long)c->m_cap * 8 /* xb_moment_sum's buffer */ +
-                              (long long)c->aj_bytes /* xb_adjacency's pair table */ +
-                              (long long)c->mg_cap * MG_BYTES /* xb_merge_basins' per-label buffer */ +
-                              (long long)c->vo_cap * 8 /* xb_voronoi_assign's buffer */ +
-                              (long long)c->cp_cap * 8 + (c->cp_lut ? XB_CRITICAL_LUT_SIZE : 0) /* xb_critical_points' list and table */ +
-                              (long long)c->st_cap * 8 /* xb_laplacian_sum's buffer */ +
-                              (long long)c->nci_cap * 8 /* xb_nci_sum's and xb_nci_hist's buffer */ +
-                              (long long)c->hs_cap * 8 /* xb_hirshfeld_setup's buffer */ +
-                              (long long)c->iso_bytes /* xb_isosurface's mesh */ +
-                              (long long)regions_bytes(c) /* xb_regions_label's map and seeds */;
+                              (long long)buf_counted_bytes(*c) /* what the analyses keep: the blocks of ctx_buffers.h */;
     const long long fixed = 8 * N /* rho */ + 4 * N /* labels */ + (N + 16) /* known */ + 4 * N /* first */ + N /* st */ +
                             2LL * c->max_cap * 4 + (long long)c->ovf_cap * 4 + c->blab_alloc * 13 + (long long)c->walk_cap * 3 * 80 +
                             (1 << 22) /* boxbuf */;

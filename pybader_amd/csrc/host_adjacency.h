@@ -1,16 +1,13 @@
 // host_adjacency.h -- host side, part 10: which labels share a surface (k_adjacency.h).  xb_adjacency reads the resident density and
 // labels of the whole grid and writes neither.
 //
-// One buffer of the context (grown on demand, kept while the grid's shape stays, counted by xb_memory_stats, freed by
-// xb_adjacency_release), in 64-bit words:
+// One block of the context (BLK_AJ, ctx_buffers.h; xb_adjacency_release frees it), in 64-bit words:
 //   dense route  the n (n - 1) / 2 entries of AJ_HEAD + n_dirs words
 //   hash route   the slots' keys, then the slots' entries
 // The occupied entries are compacted on the device in any order into a temporary array of n_pairs rows and sorted by key HERE:
 // n_pairs is small next to the grid in every intended use, and a host sort of rows that are downloaded anyway adds no launch.
 
-static void adjacency_free(xb_ctx *c) {
-    hipFree(c->aj_buf);
-    c->aj_buf = nullptr; c->aj_bytes = 0;
+static void adjacency_forget(xb_ctx *c) {
     c->aj_have = false; c->aj_dirs = 0;
     std::vector<int32_t>().swap(c->aj_a); std::vector<int32_t>().swap(c->aj_b);
     std::vector<int64_t>().swap(c->aj_facets); std::vector<int64_t>().swap(c->aj_sfacet);
@@ -78,16 +75,13 @@ static int adjacency_dirs(const char *who, const int32_t *dirs, int n_dirs, AjDi
 }
 
 int xb_adjacency(xb_ctx *c, const int32_t *dirs, int n_dirs, int64_t n, int64_t *n_pairs) {
-    if (!c || !c->has_grid) return fail(XB_E_STATE, "xb_adjacency: call xb_set_grid first");
+    ANALYSIS_NEED_GRID("xb_adjacency");
     if (!dirs || !n_pairs) return fail(XB_E_ARG, "xb_adjacency: null argument");
     if (n < 1) return fail(XB_E_ARG, "xb_adjacency: %lld labels", (long long)n);
     if (n > XB_INT_MAX) return fail(XB_E_LIMIT, "xb_adjacency: %lld labels exceed %d", (long long)n, XB_INT_MAX);
     AjDirs D;
     if (int rc = adjacency_dirs("xb_adjacency", dirs, n_dirs, D)) return rc;
-    if (c->g.x1 - c->g.x0 != c->g.nx)
-        return fail(XB_E_STATE, "xb_adjacency: the context holds a slab [%d, %d) of %d planes; the adjacency needs the whole grid", c->g.x0, c->g.x1, c->g.nx);
-    if (!c->have_rho) return fail(XB_E_STATE, "xb_adjacency: no density on this grid yet");
-    if (!c->have_labels) return fail(XB_E_STATE, "xb_adjacency: no labels on this grid yet");
+    if (int rc = analysis_ready(c, "xb_adjacency", "the adjacency needs", NEED_WHOLE | NEED_RHO | NEED_LABELS)) return rc;
     HIPCHK(hipSetDevice(c->device));
     if (int rc = settle_labels(c)) return rc;
     const int stride = AJ_HEAD + n_dirs;
@@ -116,20 +110,15 @@ int xb_adjacency(xb_ctx *c, const int32_t *dirs, int n_dirs, int64_t n, int64_t 
     c->aj_a.clear(); c->aj_b.clear(); c->aj_facets.clear(); c->aj_sfacet.clear(); c->aj_saddle.clear();
     std::vector<unsigned long long> rows;
     if (n_slots) {
-        if (c->aj_bytes < words * sizeof(unsigned long long)) {
-            HIPCHK(hipStreamSynchronize(c->stream));
-            hipFree(c->aj_buf);
-            c->aj_buf = nullptr; c->aj_bytes = 0;
-            HIPCHK(hipMalloc(&c->aj_buf, words * sizeof(unsigned long long)));
-            c->aj_bytes = words * sizeof(unsigned long long);
-        }
+        if (int rc = reserve(c, BLK_AJ, words * sizeof(unsigned long long))) return rc;
+        unsigned long long *const aj_buf = c->ptr<unsigned long long>(BLK_AJ);
         int rc;
         if (dense) {
-            const AjDense R{c->aj_buf, stride, (int)n};
+            const AjDense R{aj_buf, stride, (int)n};
             rc = adjacency_run(c, R, D, (int)n, n_slots, (size_t)n * (size_t)n, rows);
         } else {
-            HIPCHK(hipMemsetAsync(c->aj_buf, 0xff, n_slots * sizeof(unsigned long long), c->stream));   // every key AJ_EMPTY
-            const AjHash R{c->aj_buf, c->aj_buf + n_slots, (unsigned long long)(n_slots - 1), stride};
+            HIPCHK(hipMemsetAsync(aj_buf, 0xff, n_slots * sizeof(unsigned long long), c->stream));   // every key AJ_EMPTY
+            const AjHash R{aj_buf, aj_buf + n_slots, (unsigned long long)(n_slots - 1), stride};
             rc = adjacency_run(c, R, D, (int)n, n_slots, n_slots, rows);
         }
         if (rc) return rc;
@@ -167,13 +156,5 @@ int xb_adjacency_fetch(xb_ctx *c, int32_t *a, int32_t *b, int64_t *facets, doubl
         std::memcpy(saddle, c->aj_saddle.data(), np * sizeof(double));
         std::memcpy(saddle_facet, c->aj_sfacet.data(), np * sizeof(int64_t));
     }
-    return XB_OK;
-}
-
-int xb_adjacency_release(xb_ctx *c) {
-    if (!c) return fail(XB_E_ARG, "xb_adjacency_release: null ctx");
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    adjacency_free(c);
     return XB_OK;
 }

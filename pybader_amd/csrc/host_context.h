@@ -31,29 +31,9 @@ int xb_create(int device, xb_ctx **out) {
     return XB_OK;
 }
 
-static void weight_free(xb_ctx *c);
-static void moments_free(xb_ctx *c);
-static void adjacency_free(xb_ctx *c);
-static void merge_free(xb_ctx *c);
-static void voronoi_free(xb_ctx *c);
-static void critical_free(xb_ctx *c);
-static void stencil_free(xb_ctx *c);
-static void nci_free(xb_ctx *c);
-static void hirshfeld_free(xb_ctx *c);
-static void isosurface_free(xb_ctx *c);
-static void regions_free(xb_ctx *c);
+static void analyses_forget(xb_ctx *c, bool shape_only);   // (host_analyses.h)
 static void free_grid(xb_ctx *c) {
-    weight_free(c);
-    moments_free(c);
-    adjacency_free(c);
-    merge_free(c);
-    voronoi_free(c);
-    critical_free(c);
-    stencil_free(c);
-    nci_free(c);
-    hirshfeld_free(c);
-    isosurface_free(c);
-    regions_free(c);
+    analyses_forget(c, false);
     c->have_rho = c->have_labels = false;
     hipFree(c->rho); hipFree(c->grad); hipFree(c->labels); hipFree(c->known); hipFree(c->first); hipFree(c->list);
     hipFree(c->st); hipFree(c->stage); hipFree(c->ec_pend); c->ec_pend = nullptr; hipFree(c->ec_share); c->ec_share = nullptr; hipFree(c->ec_pflag); c->ec_pflag = nullptr; hipFree(c->max_list); hipFree(c->max_aux); hipFree(c->ovf_list);
@@ -189,7 +169,7 @@ int xb_set_grid(xb_ctx *c, const int64_t shape[3], const double dist_mat[27], co
     }
     c->zero_outside[0] = -1;
     Grid &g = c->g;
-    if (g.nx != (int)shape[0] || g.ny != (int)shape[1] || g.nz != (int)shape[2]) { drop_table_and_maxima(*c); c->have_rho = c->have_labels = false; adjacency_free(c); merge_free(c); critical_free(c); isosurface_free(c); regions_free(c); c->hs_have = false; }
+    if (g.nx != (int)shape[0] || g.ny != (int)shape[1] || g.nz != (int)shape[2]) { drop_table_and_maxima(*c); c->have_rho = c->have_labels = false; analyses_forget(c, true); }
     if (dist_mat && !T_grad) return fail(XB_E_ARG, "xb_set_grid: dist_mat without T_grad");
     g.nx = (int)shape[0]; g.ny = (int)shape[1]; g.nz = (int)shape[2];
     g.nyz = g.ny * g.nz;
@@ -266,6 +246,21 @@ static int settle_labels(xb_ctx *c) {
 #define NEED_GRID_THIN(name) \
     NEED_GRID_RAW_THIN(name); \
     if (int rc_ = settle_labels(c)) return rc_
+// What an analysis asks of the context before it runs, refused in this order: a grid; with NEED_WHOLE the whole of it, not a slab
+// (`noun`: "the merge needs", "the weights need"); with NEED_RHO a density; with NEED_LABELS labels.  A call whose own argument
+// checks come between the grid and the rest asks twice: ANALYSIS_NEED_GRID first, the rest after its arguments.
+enum { NEED_WHOLE = 1, NEED_RHO = 2, NEED_LABELS = 4 };
+static int analysis_ready(xb_ctx *c, const char *who, const char *noun, int needs) {
+    if (!c || !c->has_grid) return fail(XB_E_STATE, "%s: call xb_set_grid first", who);
+    const Grid &g = c->g;
+    if ((needs & NEED_WHOLE) && g.x1 - g.x0 != g.nx)
+        return fail(XB_E_STATE, "%s: the context holds a slab [%d, %d) of %d planes; %s the whole grid", who, g.x0, g.x1, g.nx, noun);
+    if ((needs & NEED_RHO) && !c->have_rho) return fail(XB_E_STATE, "%s: no density on this grid yet", who);
+    if ((needs & NEED_LABELS) && !c->have_labels) return fail(XB_E_STATE, "%s: no labels on this grid yet", who);
+    return XB_OK;
+}
+#define ANALYSIS_NEED_GRID(name) \
+    if (int rc_ = analysis_ready(c, name, "", 0)) return rc_
 
 // Large host <-> device transfers of PAGEABLE host memory (every numpy array at the boundary): the runtime stages them
 // through its own pinned buffer with one copying thread (7 GB/s measured for a 128 MB density).  Here: two pinned

@@ -1,17 +1,16 @@
 // host_critical.h -- host side, part 13: the critical points of the density and the bond graph (k_critical.h).  Both calls read the
 // resident density (xb_critical_bonds the resident labels too) of the whole grid and write neither.
 //
-// Two device buffers of the context (kept while the grid's shape stays, counted by xb_memory_stats, freed by xb_critical_release):
-//   cp_lut    the 16 384 bytes of xb_critical_lut, uploaded on the first call that uses the table
-//   cp_list   the records of the last xb_critical_points call, in the order the workgroups claimed their slots.  It starts at
+// Two blocks of the context (ctx_buffers.h; xb_critical_release frees them):
+//   BLK_CP_LUT    the 16 384 bytes of xb_critical_lut, uploaded on the first call that uses the table
+//   BLK_CP_LIST   the records of the last xb_critical_points call, in the order the workgroups claimed their slots.  It starts at
 //             N / 64 + 4096 records; a call that finds more learns the exact number from its own counter, grows the list to it and
 //             runs the pass once more: the list is sized from a count and never cut short.
 // The records are sorted HERE (lin is their high word), as host_adjacency.h sorts its pairs; xb_critical_bonds reduces the bond
 // rows per pair here as well: a count, a maximum of keys and a minimum of indices.
 
-static void critical_free(xb_ctx *c) {
-    hipFree(c->cp_list); hipFree(c->cp_lut);
-    c->cp_list = nullptr; c->cp_lut = nullptr; c->cp_cap = 0; c->cp_n = 0;
+static void critical_forget(xb_ctx *c) {
+    c->cp_n = 0;
     c->cp_have = false; c->cb_have = false; c->cp_bond_voxels = 0;
     std::vector<unsigned long long>().swap(c->cp_rec);
     std::vector<int32_t>().swap(c->cb_a); std::vector<int32_t>().swap(c->cb_b);
@@ -38,45 +37,38 @@ int xb_critical_lut(uint8_t *out) {
 }
 
 int xb_critical_points(xb_ctx *c, double vac_tol, int flags, int64_t counts[6], int64_t *n_list) {
-    if (!c || !c->has_grid) return fail(XB_E_STATE, "xb_critical_points: call xb_set_grid first");
+    ANALYSIS_NEED_GRID("xb_critical_points");
     if (!counts || !n_list) return fail(XB_E_ARG, "xb_critical_points: null argument");
     if (flags & ~XB_CRITICAL_FLOOD) return fail(XB_E_ARG, "xb_critical_points: unknown flag bits 0x%x", flags & ~XB_CRITICAL_FLOOD);
+    if (int rc = analysis_ready(c, "xb_critical_points", "the critical points need", NEED_WHOLE | NEED_RHO)) return rc;
     const Grid &g = c->g;
-    if (g.x1 - g.x0 != g.nx)
-        return fail(XB_E_STATE, "xb_critical_points: the context holds a slab [%d, %d) of %d planes; the critical points need the whole grid", g.x0, g.x1, g.nx);
-    if (!c->have_rho) return fail(XB_E_STATE, "xb_critical_points: no density on this grid yet");
     HIPCHK(hipSetDevice(c->device));
     c->cp_have = false; c->cb_have = false;
     const bool flood = (flags & XB_CRITICAL_FLOOD) != 0;
-    if (!flood && !c->cp_lut) {
-        HIPCHK(hipMalloc(&c->cp_lut, XB_CRITICAL_LUT_SIZE));
-        HIPCHK(hipMemcpyAsync(c->cp_lut, critical_table(), XB_CRITICAL_LUT_SIZE, hipMemcpyHostToDevice, c->stream));
+    if (!flood && !c->bytes(BLK_CP_LUT)) {
+        if (int rc = reserve(c, BLK_CP_LUT, XB_CRITICAL_LUT_SIZE)) return rc;
+        HIPCHK(hipMemcpyAsync(c->ptr<void>(BLK_CP_LUT), critical_table(), XB_CRITICAL_LUT_SIZE, hipMemcpyHostToDevice, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));   // (the table is static, but pageable: the copy is staged before this returns anyway)
     }
     const long long tiles = (long long)((g.nx + CP_TX - 1) / CP_TX) * ((g.ny + CP_TY - 1) / CP_TY) * ((g.nz + CP_TZ - 1) / CP_TZ);   // (at most N)
-    unsigned long long cnt[7] = {0, 0, 0, 0, 0, 0, 0};
+    unsigned long long cnt[7] = {0, 0, 0, 0, 0, 0, 0}, cp_cap = 0;
     for (int pass = 0; pass < 2; pass++) {
         const size_t want = pass == 0 ? (size_t)(c->N / 64 + 4096) : (size_t)cnt[6];
-        if (c->cp_cap < want) {
-            HIPCHK(hipStreamSynchronize(c->stream));
-            hipFree(c->cp_list);
-            c->cp_list = nullptr; c->cp_cap = 0;
-            HIPCHK(hipMalloc(&c->cp_list, want * sizeof(unsigned long long)));
-            c->cp_cap = want;
-        }
+        if (int rc = reserve(c, BLK_CP_LIST, want * sizeof(unsigned long long))) return rc;
+        cp_cap = c->bytes(BLK_CP_LIST) / sizeof(unsigned long long);
         HIPCHK(hipMemsetAsync(c->counters64, 0, sizeof cnt, c->stream));
-        k_critical<<<(unsigned)tiles, TPB, 0, c->stream>>>(g.nx, g.ny, g.nz, c->rho, flood ? nullptr : c->cp_lut, vac_tol == vac_tol ? 1 : 0,
-                                                          vac_tol, c->cp_list, (unsigned long long)c->cp_cap, c->counters64);
+        k_critical<<<(unsigned)tiles, TPB, 0, c->stream>>>(g.nx, g.ny, g.nz, c->rho, flood ? nullptr : c->ptr<unsigned char>(BLK_CP_LUT), vac_tol == vac_tol ? 1 : 0,
+                                                          vac_tol, c->ptr<unsigned long long>(BLK_CP_LIST), cp_cap, c->counters64);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(cnt, c->counters64, sizeof cnt, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
-        if (cnt[6] <= c->cp_cap) break;
-        if (pass == 1) return fail(XB_E_STATE, "xb_critical_points: %llu records after %llu were counted", cnt[6], (unsigned long long)c->cp_cap);
+        if (cnt[6] <= cp_cap) break;
+        if (pass == 1) return fail(XB_E_STATE, "xb_critical_points: %llu records after %llu were counted", cnt[6], cp_cap);
     }
     c->cp_n = (size_t)cnt[6];
     c->cp_rec.resize(c->cp_n);
     if (c->cp_n) {
-        if (int rc = staged_d2h(c, c->cp_rec.data(), c->cp_list, c->cp_n * sizeof(unsigned long long))) return rc;
+        if (int rc = staged_d2h(c, c->cp_rec.data(), c->ptr<unsigned long long>(BLK_CP_LIST), c->cp_n * sizeof(unsigned long long))) return rc;
         std::sort(c->cp_rec.begin(), c->cp_rec.end());
     }
     for (int k = 0; k < XB_CRITICAL_COUNTS; k++) counts[k] = (int64_t)cnt[k];
@@ -102,14 +94,11 @@ int xb_critical_fetch(xb_ctx *c, int64_t *lin, uint16_t *lower_mask, uint8_t *ri
 }
 
 int xb_critical_bonds(xb_ctx *c, int64_t n, int64_t *n_pairs, int64_t *same_basin) {
-    if (!c || !c->has_grid) return fail(XB_E_STATE, "xb_critical_bonds: call xb_set_grid first");
+    ANALYSIS_NEED_GRID("xb_critical_bonds");
     if (!n_pairs || !same_basin) return fail(XB_E_ARG, "xb_critical_bonds: null argument");
     if (n < 1) return fail(XB_E_ARG, "xb_critical_bonds: %lld labels", (long long)n);
+    if (int rc = analysis_ready(c, "xb_critical_bonds", "the bond graph needs", NEED_WHOLE | NEED_RHO | NEED_LABELS)) return rc;
     const Grid &g = c->g;
-    if (g.x1 - g.x0 != g.nx)
-        return fail(XB_E_STATE, "xb_critical_bonds: the context holds a slab [%d, %d) of %d planes; the bond graph needs the whole grid", g.x0, g.x1, g.nx);
-    if (!c->have_rho) return fail(XB_E_STATE, "xb_critical_bonds: no density on this grid yet");
-    if (!c->have_labels) return fail(XB_E_STATE, "xb_critical_bonds: no labels on this grid yet");
     if (!c->cp_have) return fail(XB_E_STATE, "xb_critical_bonds: no critical points of the resident density (call xb_critical_points first)");
     HIPCHK(hipSetDevice(c->device));
     if (int rc = settle_labels(c)) return rc;
@@ -122,7 +111,7 @@ int xb_critical_bonds(xb_ctx *c, int64_t n, int64_t *n_pairs, int64_t *same_basi
         unsigned long long *count = c->counters64 + 8, got = 0;
         HIPCHK(out.alloc(nb * CP_BOND_ROW));
         HIPCHK(hipMemsetAsync(count, 0, sizeof(unsigned long long), c->stream));
-        k_critical_bonds<<<nblocks((long long)c->cp_n), TPB, 0, c->stream>>>(g.nx, g.ny, g.nz, c->rho, c->labels, c->cp_list, (unsigned long long)c->cp_n,
+        k_critical_bonds<<<nblocks((long long)c->cp_n), TPB, 0, c->stream>>>(g.nx, g.ny, g.nz, c->rho, c->labels, c->ptr<unsigned long long>(BLK_CP_LIST), (unsigned long long)c->cp_n,
                                                                          out.p, (unsigned long long)nb, count);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(&got, count, sizeof got, hipMemcpyDeviceToHost, c->stream));
@@ -189,13 +178,5 @@ int xb_critical_bonds_fetch(xb_ctx *c, int32_t *a, int32_t *b, int64_t *saddles,
         std::memcpy(rho_b, c->cb_rho.data(), np * sizeof(double));
         std::memcpy(voxel, c->cb_voxel.data(), np * sizeof(int64_t));
     }
-    return XB_OK;
-}
-
-int xb_critical_release(xb_ctx *c) {
-    if (!c) return fail(XB_E_ARG, "xb_critical_release: null ctx");
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    critical_free(c);
     return XB_OK;
 }

@@ -2,7 +2,7 @@
 // (k_hirshfeld.h).  xb_hirshfeld_setup puts everything that belongs to the grid's shape, the cell, the atoms and the pro-atom
 // tables on the device; xb_hirshfeld_sum and xb_hirshfeld_field read the resident density and write nothing resident.
 //
-// One buffer of the context (grown on demand, counted by xb_memory_stats), in doubles:
+// One block of the context (BLK_HS, ctx_buffers.h; xb_hirshfeld_release frees it), in doubles:
 //   [0, 16)      the lattice (9 used)
 //   then         the position table of k_ms_tables, 3 * (nx + ny + nz)
 //   then         per species r_cut, rc2, inv_h2 (3 S)
@@ -14,10 +14,7 @@
 
 #define HS_HEAD 16
 
-static void hirshfeld_free(xb_ctx *c) {
-    hipFree(c->hs_buf);
-    c->hs_buf = nullptr; c->hs_cap = 0; c->hs_have = false;
-}
+static void hirshfeld_forget(xb_ctx *c) { c->hs_have = false; }
 
 // the inverse of the lattice by cofactors, in the order section 18 writes them (A = the lattice itself); false: det is 0 or not finite
 static bool hs_inverse(const double *lat, double M[3][3]) {
@@ -98,10 +95,8 @@ int xb_hirshfeld_images(const double lattice[9], const double *atoms_cart, const
 int xb_hirshfeld_setup(xb_ctx *c, const double lattice[9], const double *atoms_cart, const int32_t *species, int64_t n,
                        const double *tables, const double *r_cut, int64_t n_species, int64_t knots) {
     if (!c) return fail(XB_E_ARG, "xb_hirshfeld_setup: null ctx");
-    if (!c->has_grid) return fail(XB_E_STATE, "xb_hirshfeld_setup: call xb_set_grid first");
+    if (int rc = analysis_ready(c, "xb_hirshfeld_setup", "the weights need", NEED_WHOLE)) return rc;
     const Grid &g = c->g;
-    if (g.x1 - g.x0 != g.nx)
-        return fail(XB_E_STATE, "xb_hirshfeld_setup: the context holds a slab [%d, %d) of %d planes; the weights need the whole grid", g.x0, g.x1, g.nx);
     if (!tables) return fail(XB_E_ARG, "xb_hirshfeld_setup: null argument");
     if (knots < 1) return fail(XB_E_ARG, "xb_hirshfeld_setup: %lld knots", (long long)knots);
     std::vector<int> lo, hi;
@@ -122,12 +117,7 @@ int xb_hirshfeld_setup(xb_ctx *c, const double lattice[9], const double *atoms_c
     size_t o_tab = HS_HEAD, o_sp = o_tab + 3 * len, o_pairs = o_sp + 3 * (size_t)S;
     o_pairs += o_pairs & 1;
     const size_t o_img = o_pairs + 2 * (size_t)S * K, o_acc = o_img + 4 * (size_t)count, want = o_acc + 2 * (size_t)n + 3;
-    if (c->hs_cap < want) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        hirshfeld_free(c);
-        HIPCHK(hipMalloc(&c->hs_buf, want * sizeof(double)));
-        c->hs_cap = want;
-    }
+    if (int rc = reserve(c, BLK_HS, want * sizeof(double))) return rc;
     // the host image of everything but the position table and the results
     std::vector<double> host(o_acc, 0.);
     for (int k = 0; k < 9; k++) host[k] = lattice[k];
@@ -150,7 +140,7 @@ int xb_hirshfeld_setup(xb_ctx *c, const double lattice[9], const double *atoms_c
                         im->q[j] = atoms_cart[3 * a + j] + ((lattice[j] * (double)x + lattice[3 + j] * (double)y) + lattice[6 + j] * (double)z);
                     im->a = (int)a; im->s = species[a];
                 }
-    double *buf = c->hs_buf;
+    double *buf = c->ptr<double>(BLK_HS);
     HIPCHK(hipMemcpyAsync(buf, host.data(), HS_HEAD * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(buf + o_sp, host.data() + o_sp, (o_acc - o_sp) * sizeof(double), hipMemcpyHostToDevice, c->stream));
     k_ms_tables<<<nblocks(3 * (long long)len), TPB, 0, c->stream>>>(g.nx, g.ny, g.nz, buf, buf + o_tab);
@@ -170,21 +160,11 @@ int xb_hirshfeld_setup(xb_ctx *c, const double lattice[9], const double *atoms_c
     return XB_OK;
 }
 
-int xb_hirshfeld_release(xb_ctx *c) {
-    if (!c) return fail(XB_E_ARG, "xb_hirshfeld_release: null ctx");
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    hirshfeld_free(c);
-    return XB_OK;
-}
-
 // what the two calls check alike: a grid, the whole of it, a setup made on its shape
 static int hirshfeld_ready(xb_ctx *c, const char *who) {
     if (!c) return fail(XB_E_ARG, "%s: null ctx", who);
-    if (!c->has_grid) return fail(XB_E_STATE, "%s: call xb_set_grid first", who);
+    if (int rc = analysis_ready(c, who, "the weights need", NEED_WHOLE)) return rc;
     const Grid &g = c->g;
-    if (g.x1 - g.x0 != g.nx)
-        return fail(XB_E_STATE, "%s: the context holds a slab [%d, %d) of %d planes; the weights need the whole grid", who, g.x0, g.x1, g.nx);
     if (!c->hs_have || c->hs_geom.nx != g.nx || c->hs_geom.ny != g.ny || c->hs_geom.nz != g.nz)
         return fail(XB_E_STATE, "%s: no xb_hirshfeld_setup for this grid's shape", who);
     return XB_OK;
@@ -200,11 +180,11 @@ int xb_hirshfeld_sum(xb_ctx *c, double voxel_volume, int flags, double *charge, 
     if (int rc = hirshfeld_ready(c, "xb_hirshfeld_sum")) return rc;
     if (!charge || !volume || !rest) return fail(XB_E_ARG, "xb_hirshfeld_sum: null argument");
     if (flags & ~XB_HIRSHFELD_FULL_SEARCH) return fail(XB_E_ARG, "xb_hirshfeld_sum: unknown flag bits 0x%x", flags & ~XB_HIRSHFELD_FULL_SEARCH);
-    if (!c->have_rho) return fail(XB_E_STATE, "xb_hirshfeld_sum: no density on this grid yet");
+    if (int rc = analysis_ready(c, "xb_hirshfeld_sum", "", NEED_RHO)) return rc;
     HIPCHK(hipSetDevice(c->device));
     const HsGeom &G = c->hs_geom;
     const size_t n = (size_t)c->hs_n;
-    double *acc = c->hs_buf + c->hs_acc;
+    double *acc = c->ptr<double>(BLK_HS) + c->hs_acc;
     unsigned long long *restn = reinterpret_cast<unsigned long long *>(acc + 2 * n + 1);
     unsigned int *dst = reinterpret_cast<unsigned int *>(acc + 2 * n + 2);
     const long long tiles = hirshfeld_tiles(G);
@@ -243,11 +223,10 @@ int xb_hirshfeld_field(xb_ctx *c, int mode, int flags, double *out_host, void *o
     HIPCHK(hipSetDevice(c->device));
     double *dst = (double *)out_dev;
     if (out_dev) {
-        if ((uintptr_t)out_dev % sizeof(double)) return fail(XB_E_ARG, "xb_hirshfeld_field: %p is not aligned to its 8-byte elements", out_dev);
         uintptr_t lo, hi;
-        if (int rc = io_check_flat(c, "xb_hirshfeld_field", out_dev, sizeof(double), &lo, &hi)) return rc;
+        if (int rc = io_check_dense(c, "xb_hirshfeld_field", out_dev, sizeof(double), &lo, &hi)) return rc;
         if (io_overlaps(lo, hi, c->rho, (size_t)c->N * 8)) return fail(XB_E_ARG, "xb_hirshfeld_field: the destination overlaps the resident density");
-        if (io_overlaps(lo, hi, c->hs_buf, c->hs_cap * 8)) return fail(XB_E_ARG, "xb_hirshfeld_field: the destination overlaps the setup");
+        if (io_overlaps(lo, hi, c->ptr<void>(BLK_HS), c->bytes(BLK_HS))) return fail(XB_E_ARG, "xb_hirshfeld_field: the destination overlaps the setup");
     } else {
         if (c->stage_bytes < (size_t)c->N * sizeof(double)) return fail(XB_E_STATE, "xb_hirshfeld_field: the scratch buffer holds no whole grid");
         stage_clobbered(*c);
@@ -255,7 +234,7 @@ int xb_hirshfeld_field(xb_ctx *c, int mode, int flags, double *out_host, void *o
     }
     const HsGeom &G = c->hs_geom;
     const int forced = (flags & XB_HIRSHFELD_FULL_SEARCH) != 0;
-    unsigned int *st = reinterpret_cast<unsigned int *>(c->hs_buf + c->hs_acc + 2 * (size_t)c->hs_n + 2);
+    unsigned int *st = reinterpret_cast<unsigned int *>(c->ptr<double>(BLK_HS) + c->hs_acc + 2 * (size_t)c->hs_n + 2);
     if (mode == XB_HIRSHFELD_PROMOLECULE) k_hirshfeld<HS_PRO><<<(unsigned)hirshfeld_tiles(G), 256, 0, c->stream>>>(G, c->rho, forced, 0, nullptr, nullptr, dst, st);
     else k_hirshfeld<HS_DEF><<<(unsigned)hirshfeld_tiles(G), 256, 0, c->stream>>>(G, c->rho, forced, 0, nullptr, nullptr, dst, st);
     HIPCHK(hipGetLastError());

@@ -56,6 +56,11 @@ static int io_check_flat(xb_ctx *c, const char *who, const void *p, size_t isz, 
     const int64_t shape[3] = {(int64_t)c->N, 1, 1}, stride[3] = {1, 0, 0};
     return io_check(c, who, p, isz, shape, stride, lo, hi);
 }
+// ... that must also be aligned to its elements: the check of every dense device array a caller hands in or asks for
+static int io_check_dense(xb_ctx *c, const char *who, const void *p, size_t isz, uintptr_t *lo, uintptr_t *hi) {
+    if ((uintptr_t)p % isz) return fail(XB_E_ARG, "%s: %p is not aligned to its %zu-byte elements", who, p, isz);
+    return io_check_flat(c, who, p, isz, lo, hi);
+}
 
 static int io_event(xb_ctx *c) {
     if (!c->io_ev) HIPCHK(hipEventCreateWithFlags(&c->io_ev, hipEventDisableTiming));
@@ -149,10 +154,9 @@ int xb_import_labels(xb_ctx *c, const void *dev_ptr, int dtype, void *stream) {
     if (!c || !c->has_grid) return fail(XB_E_ARG, "xb_import_labels: call xb_set_grid first");
     const size_t sz = dtype_size(dtype);
     if (!sz) return fail(XB_E_ARG, "xb_import_labels: bad dtype code %d", dtype);
-    if ((uintptr_t)dev_ptr % sz) return fail(XB_E_ARG, "xb_import_labels: %p is not aligned to its %zu-byte elements", dev_ptr, sz);
     HIPCHK(hipSetDevice(c->device));
     uintptr_t lo, hi;
-    if (int rc = io_check_flat(c, "xb_import_labels", dev_ptr, sz, &lo, &hi)) return rc;
+    if (int rc = io_check_dense(c, "xb_import_labels", dev_ptr, sz, &lo, &hi)) return rc;
     if (io_overlaps(lo, hi, c->labels, (size_t)c->N * 4)) return fail(XB_E_ARG, "xb_import_labels: the source overlaps the resident labels");
     labels_overwritten(*c, sz >= 4 ? 4 : (int)sz, true);   // from here on as xb_upload_labels
     const hipStream_t s = (hipStream_t)stream;
@@ -177,10 +181,9 @@ int xb_export_labels(xb_ctx *c, void *dev_ptr, int dtype, void *stream) {
     if (!c || !c->has_grid) return fail(XB_E_ARG, "xb_export_labels: call xb_set_grid first");
     const size_t sz = dtype_size(dtype);
     if (!sz) return fail(XB_E_ARG, "xb_export_labels: bad dtype code %d", dtype);
-    if ((uintptr_t)dev_ptr % sz) return fail(XB_E_ARG, "xb_export_labels: %p is not aligned to its %zu-byte elements", dev_ptr, sz);
     HIPCHK(hipSetDevice(c->device));
     uintptr_t lo, hi;
-    if (int rc = io_check_flat(c, "xb_export_labels", dev_ptr, sz, &lo, &hi)) return rc;
+    if (int rc = io_check_dense(c, "xb_export_labels", dev_ptr, sz, &lo, &hi)) return rc;
     if (io_overlaps(lo, hi, c->labels, (size_t)c->N * 4)) return fail(XB_E_ARG, "xb_export_labels: the destination overlaps the resident labels");
     NEED_GRID_THIN("xb_export_labels");
     const hipStream_t s = (hipStream_t)stream;

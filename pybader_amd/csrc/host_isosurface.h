@@ -4,20 +4,15 @@
 // Scratch: the per-voxel words (4 N bytes), the runs' bases (16 bytes per ISO_BLOCK voxels) and the chunks' bases live in `stage`
 // (N doubles on a whole grid: need_scratch), which is scratch between calls; the per-label sums and the workgroups' sums
 // (4 ISO_SLOTS words) in temporary buffers.
-// Kept (counted by xb_memory_stats, freed by xb_isosurface_release, discarded by every writer of the density): the mesh of the
-// last call -- iso_vert [3 V] doubles, iso_col [V] doubles with a colour field, iso_tri [3 T] and iso_cell [T] 64-bit integers,
-// iso_wrap [T] 16-bit integers; every array at least one element long.
+// Kept (the blocks BLK_ISO_* of ctx_buffers.h, freed by xb_isosurface_release, discarded by every writer of the density): the mesh
+// of the last call -- vertices [3 V] doubles, colours [V] doubles with a colour field, triangles [3 T] and cells [T] 64-bit integers,
+// wraps [T] 16-bit integers; every array at least one element long.
 
-static void isosurface_free(xb_ctx *c) {
-    hipFree(c->iso_vert); hipFree(c->iso_col); hipFree(c->iso_tri); hipFree(c->iso_wrap); hipFree(c->iso_cell);
-    c->iso_vert = nullptr; c->iso_col = nullptr; c->iso_tri = nullptr; c->iso_wrap = nullptr; c->iso_cell = nullptr;
-    c->iso_v = 0; c->iso_t = 0; c->iso_bytes = 0; c->iso_have = false;
+static void isosurface_forget(xb_ctx *c) {
+    c->iso_v = 0; c->iso_t = 0; c->iso_have = false;
     std::vector<double>().swap(c->iso_vbl);
 }
-static size_t isosurface_bytes(size_t V, size_t T, bool colour) {
-    const size_t v = std::max<size_t>(V, 1), t = std::max<size_t>(T, 1);
-    return v * 24 + (colour ? v * 8 : 0) + t * (24 + 8 + 2);
-}
+static void isosurface_drop(xb_ctx *c) { isosurface_forget(c); release(c, BLK_ISO_VERT, BLK_ISO_WRAP); }   // the result and its mesh
 
 int xb_isosurface_table(uint8_t *out) {
     if (!out) return fail(XB_E_ARG, "xb_isosurface_table: null argument");
@@ -27,7 +22,7 @@ int xb_isosurface_table(uint8_t *out) {
 
 int xb_isosurface(xb_ctx *c, const void *field_dev, const void *colour_dev, const double lattice[9], double level, int64_t n_labels,
                   int flags, int64_t counts[2]) {
-    STENCIL_NEED_GRID("xb_isosurface");
+    ANALYSIS_NEED_GRID("xb_isosurface");
     if (!lattice || !counts) return fail(XB_E_ARG, "xb_isosurface: null argument");
     if (flags & ~XB_ISO_GATHER) return fail(XB_E_ARG, "xb_isosurface: unknown flag bits 0x%x", flags & ~XB_ISO_GATHER);
     if (!std::isfinite(level)) return fail(XB_E_ARG, "xb_isosurface: the level (%g) must be finite", level);
@@ -46,15 +41,14 @@ int xb_isosurface(xb_ctx *c, const void *field_dev, const void *colour_dev, cons
     const void *const in[2] = {field_dev, colour_dev};
     for (int k = 0; k < 2; k++) {
         if (!in[k]) continue;
-        if ((uintptr_t)in[k] % sizeof(double)) return fail(XB_E_ARG, "xb_isosurface: %p is not aligned to its 8-byte elements", in[k]);
-        if (int rc = io_check_flat(c, "xb_isosurface", in[k], sizeof(double), &lo[k], &hi[k])) return rc;
+        if (int rc = io_check_dense(c, "xb_isosurface", in[k], sizeof(double), &lo[k], &hi[k])) return rc;
         if (io_overlaps(lo[k], hi[k], c->stage, c->stage_bytes)) return fail(XB_E_ARG, "xb_isosurface: a field overlaps the context's scratch");
     }
     if (field_dev && colour_dev && lo[0] < hi[1] && lo[1] < hi[0] && field_dev != colour_dev)
         return fail(XB_E_ARG, "xb_isosurface: the field and the colour overlap without being the same array");
     if (int rc = settle_labels(c)) return rc;
     HIPCHK(hipStreamSynchronize(c->stream));
-    isosurface_free(c);
+    isosurface_drop(c);
     stage_clobbered(*c);
     const double *f = field_dev ? (const double *)field_dev : c->rho;
     const double *gcol = (const double *)colour_dev;
@@ -78,16 +72,11 @@ int xb_isosurface(xb_ctx *c, const void *field_dev, const void *colour_dev, cons
     const size_t V = (size_t)want[0], T = (size_t)want[1];
     if (want[0] > 7ull * (unsigned long long)c->N || want[1] > 12ull * (unsigned long long)c->N)
         return fail(XB_E_STATE, "xb_isosurface: the count pass reports %llu vertices and %llu triangles on %lld voxels", want[0], want[1], c->N);
-    hipError_t bad = hipMalloc(&c->iso_vert, std::max<size_t>(V, 1) * 3 * sizeof(double));
-    if (bad == hipSuccess && gcol) bad = hipMalloc(&c->iso_col, std::max<size_t>(V, 1) * sizeof(double));
-    if (bad == hipSuccess) bad = hipMalloc(&c->iso_tri, std::max<size_t>(T, 1) * 3 * sizeof(long long));
-    if (bad == hipSuccess) bad = hipMalloc(&c->iso_wrap, std::max<size_t>(T, 1) * sizeof(unsigned short));
-    if (bad == hipSuccess) bad = hipMalloc(&c->iso_cell, std::max<size_t>(T, 1) * sizeof(long long));
-    if (bad != hipSuccess) {   // (nothing half allocated stays behind uncounted)
-        isosurface_free(c);
-        HIPCHK(bad);
-    }
-    c->iso_bytes = isosurface_bytes(V, T, gcol != nullptr);
+    const size_t v1 = std::max<size_t>(V, 1), t1 = std::max<size_t>(T, 1);
+    const BufWant mesh[] = {{BLK_ISO_VERT, v1 * 3 * sizeof(double), 0}, {BLK_ISO_COL, gcol ? v1 * sizeof(double) : 0, 0},
+                            {BLK_ISO_TRI, t1 * 3 * sizeof(long long), 0}, {BLK_ISO_CELL, t1 * sizeof(long long), 0},
+                            {BLK_ISO_WRAP, t1 * sizeof(unsigned short), 0}};
+    if (int rc = reserve(c, mesh)) return rc;   // (all five or none)
     const int n = (int)n_labels;
     DevBuf<double> sums;
     HIPCHK(sums.alloc(3 * (size_t)n));
@@ -102,7 +91,7 @@ int xb_isosurface(xb_ctx *c, const void *field_dev, const void *colour_dev, cons
     const double dims[3] = {(double)g.nx, (double)g.ny, (double)g.nz};
     for (int i = 0; i < 3; i++)
         for (int j = 0; j < 3; j++) G.A[3 * i + j] = lattice[3 * i + j] / dims[i];
-    const IsoOut O{c->iso_vert, c->iso_col, c->iso_tri, c->iso_wrap, c->iso_cell, (unsigned long long)V, (unsigned long long)T, gcol};
+    const IsoOut O{c->ptr<double>(BLK_ISO_VERT), c->ptr<double>(BLK_ISO_COL), c->ptr<long long>(BLK_ISO_TRI), c->ptr<unsigned short>(BLK_ISO_WRAP), c->ptr<long long>(BLK_ISO_CELL), (unsigned long long)V, (unsigned long long)T, gcol};
     const bool bins = n >= 1 && n <= ST_BINS;
     if (gather) {
         if (bins) k_iso_emit_gather<true><<<nblocks(c->N), TPB, 0, c->stream>>>(g.nx, g.ny, g.nz, f, level, G, word, tot, O, c->labels, n, vol, mag, cnt, acc);
@@ -125,7 +114,7 @@ int xb_isosurface(xb_ctx *c, const void *field_dev, const void *colour_dev, cons
         got[2] += per_slot[4 * k + 2]; got[3] += per_slot[4 * k + 3];
     }
     if (got[2] != want[0] || got[3] != want[1]) {
-        isosurface_free(c);
+        isosurface_drop(c);
         return fail(XB_E_STATE, "xb_isosurface: %llu vertices and %llu triangles written, %llu and %llu were counted", got[2], got[3], want[0], want[1]);
     }
     // |det A| / 6, the determinant in the order of xb_stencil_coeffs
@@ -145,7 +134,7 @@ int xb_isosurface_fetch(xb_ctx *c, int on_device, void *vertices, void *colour, 
                         int64_t cap_triangles, double scalars[2], double *volume_by_label, int64_t cap_labels) {
     if (!c || !c->iso_have) return fail(XB_E_STATE, "xb_isosurface_fetch: no result (call xb_isosurface first)");
     if (!vertices || !triangles || !wrap || !cell || !scalars) return fail(XB_E_ARG, "xb_isosurface_fetch: null argument");
-    if (colour && !c->iso_col) return fail(XB_E_ARG, "xb_isosurface_fetch: the surface was made without a colour field");
+    if (colour && !c->bytes(BLK_ISO_COL)) return fail(XB_E_ARG, "xb_isosurface_fetch: the surface was made without a colour field");
     const size_t V = c->iso_v, T = c->iso_t, nl = c->iso_vbl.size();
     if (cap_vertices < (int64_t)V || cap_triangles < (int64_t)T)
         return fail(XB_E_ARG, "xb_isosurface_fetch: capacity (%lld, %lld) below %lld vertices and %lld triangles", (long long)cap_vertices,
@@ -154,7 +143,7 @@ int xb_isosurface_fetch(xb_ctx *c, int on_device, void *vertices, void *colour, 
         return fail(XB_E_ARG, "xb_isosurface_fetch: room for %lld labels, %lld were summed", (long long)(volume_by_label ? cap_labels : 0), (long long)nl);
     HIPCHK(hipSetDevice(c->device));
     void *const dst[5] = {vertices, colour, triangles, wrap, cell};
-    const void *const src[5] = {c->iso_vert, c->iso_col, c->iso_tri, c->iso_wrap, c->iso_cell};
+    const void *const src[5] = {c->blk[BLK_ISO_VERT].p, c->blk[BLK_ISO_COL].p, c->blk[BLK_ISO_TRI].p, c->blk[BLK_ISO_WRAP].p, c->blk[BLK_ISO_CELL].p};
     const size_t bytes[5] = {V * 24, V * 8, T * 24, T * 2, T * 8}, elem[5] = {8, 8, 8, 2, 8};
     if (on_device) {
         uintptr_t lo[5], hi[5];
@@ -175,17 +164,9 @@ int xb_isosurface_fetch(xb_ctx *c, int on_device, void *vertices, void *colour, 
     return XB_OK;
 }
 
-int xb_isosurface_release(xb_ctx *c) {
-    if (!c) return fail(XB_E_ARG, "xb_isosurface_release: null ctx");
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    isosurface_free(c);
-    return XB_OK;
-}
-
 int xb_isosurface_nci_mask(xb_ctx *c, void *s_dev, double rho_cut) {
-    STENCIL_NEED_GRID("xb_isosurface_nci_mask");
-    if (!c->have_rho) return fail(XB_E_STATE, "xb_isosurface_nci_mask: no density on this grid yet");
+    ANALYSIS_NEED_GRID("xb_isosurface_nci_mask");
+    if (int rc = analysis_ready(c, "xb_isosurface_nci_mask", "", NEED_RHO)) return rc;
     if (c->g.x1 - c->g.x0 != c->g.nx) return fail(XB_E_STATE, "xb_isosurface_nci_mask: the context holds a slab");
     if (!(rho_cut == rho_cut)) return fail(XB_E_ARG, "xb_isosurface_nci_mask: rho_cut is NaN");
     if (!s_dev || (uintptr_t)s_dev % sizeof(double)) return fail(XB_E_ARG, "xb_isosurface_nci_mask: %p is null or not aligned to its 8-byte elements", s_dev);

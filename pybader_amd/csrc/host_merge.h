@@ -1,15 +1,12 @@
 // host_merge.h -- host side, part 11: merge Bader volumes below a persistence threshold (k_merge.h).  xb_merge_basins reads the
 // resident density and labels of the whole grid and writes neither.
 //
-// One buffer of the context (grown on demand, kept while the grid's shape stays, counted by xb_memory_stats, freed by
-// xb_merge_release), MG_BYTES = 44 bytes per label:
+// One block of the context (BLK_MG, ctx_buffers.h; xb_merge_release frees it), MG_BYTES = 44 bytes per label:
 //   ent 16   best 8   merge_persistence 8   target 4   parent 4   merge_round 4
 // One host wait per round, for the number of merges: it ends the loop and sizes the pointer doubling.
 #define MG_BYTES 44
 
-static void merge_free(xb_ctx *c) {
-    hipFree(c->mg_buf);
-    c->mg_buf = nullptr; c->mg_cap = 0;
+static void merge_forget(xb_ctx *c) {
     c->mg_have = false;
     std::vector<int32_t>().swap(c->mg_root); std::vector<int32_t>().swap(c->mg_round);
     std::vector<double>().swap(c->mg_pers);
@@ -17,7 +14,7 @@ static void merge_free(xb_ctx *c) {
 
 int xb_merge_basins(xb_ctx *c, const int32_t *dirs, int n_dirs, int64_t n, const int64_t *max_idx, double tol, int64_t max_rounds,
                     int64_t *rounds, int64_t *n_survivors, int *converged) {
-    if (!c || !c->has_grid) return fail(XB_E_STATE, "xb_merge_basins: call xb_set_grid first");
+    ANALYSIS_NEED_GRID("xb_merge_basins");
     if (!dirs || !max_idx || !rounds || !n_survivors || !converged) return fail(XB_E_ARG, "xb_merge_basins: null argument");
     if (n < 1) return fail(XB_E_ARG, "xb_merge_basins: %lld labels", (long long)n);
     if (n > XB_INT_MAX) return fail(XB_E_LIMIT, "xb_merge_basins: %lld labels exceed %d", (long long)n, XB_INT_MAX);
@@ -25,10 +22,7 @@ int xb_merge_basins(xb_ctx *c, const int32_t *dirs, int n_dirs, int64_t n, const
     if (int rc = adjacency_dirs("xb_merge_basins", dirs, n_dirs, D)) return rc;
     if (max_rounds < 1) return fail(XB_E_ARG, "xb_merge_basins: %lld rounds", (long long)max_rounds);
     if (!(tol >= 0.)) return fail(XB_E_ARG, "xb_merge_basins: the threshold %g is negative or not a number", tol);
-    if (c->g.x1 - c->g.x0 != c->g.nx)
-        return fail(XB_E_STATE, "xb_merge_basins: the context holds a slab [%d, %d) of %d planes; the merge needs the whole grid", c->g.x0, c->g.x1, c->g.nx);
-    if (!c->have_rho) return fail(XB_E_STATE, "xb_merge_basins: no density on this grid yet");
-    if (!c->have_labels) return fail(XB_E_STATE, "xb_merge_basins: no labels on this grid yet");
+    if (int rc = analysis_ready(c, "xb_merge_basins", "the merge needs", NEED_WHOLE | NEED_RHO | NEED_LABELS)) return rc;
     std::vector<int> idx((size_t)n);
     for (int64_t m = 0; m < n; m++) {
         if (max_idx[m] < 0 || max_idx[m] >= c->N)
@@ -38,16 +32,10 @@ int xb_merge_basins(xb_ctx *c, const int32_t *dirs, int n_dirs, int64_t n, const
     HIPCHK(hipSetDevice(c->device));
     if (int rc = settle_labels(c)) return rc;
     c->mg_have = false;
-    if (c->mg_cap < n) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        hipFree(c->mg_buf);
-        c->mg_buf = nullptr; c->mg_cap = 0;
-        HIPCHK(hipMalloc(&c->mg_buf, (size_t)n * MG_BYTES));
-        c->mg_cap = n;
-    }
+    if (int rc = reserve(c, BLK_MG, (size_t)n * MG_BYTES)) return rc;
     // carved by the capacity, widest first: every array stays aligned to its element
-    const size_t cap = (size_t)c->mg_cap;
-    MgEnt *ent = reinterpret_cast<MgEnt *>(c->mg_buf);
+    const size_t cap = c->bytes(BLK_MG) / MG_BYTES;
+    MgEnt *ent = c->ptr<MgEnt>(BLK_MG);
     unsigned long long *best = reinterpret_cast<unsigned long long *>(ent + cap);
     double *mpers = reinterpret_cast<double *>(best + cap);
     int *target = reinterpret_cast<int *>(mpers + cap);
@@ -114,13 +102,5 @@ int xb_merge_fetch(xb_ctx *c, int32_t *root, int32_t *merge_round, double *merge
     std::memcpy(root, c->mg_root.data(), n * sizeof(int32_t));
     std::memcpy(merge_round, c->mg_round.data(), n * sizeof(int32_t));
     std::memcpy(merge_persistence, c->mg_pers.data(), n * sizeof(double));
-    return XB_OK;
-}
-
-int xb_merge_release(xb_ctx *c) {
-    if (!c) return fail(XB_E_ARG, "xb_merge_release: null ctx");
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    merge_free(c);
     return XB_OK;
 }

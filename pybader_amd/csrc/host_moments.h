@@ -1,7 +1,7 @@
 // host_moments.h -- host side, part 9: moments of the density per label about a centre (k_moments.h).  xb_moment_sum reads the
 // resident density and labels over the owned planes and writes neither.
 //
-// One buffer of the context (grown on demand, kept while the grid stays, counted by xb_memory_stats), in doubles:
+// One block of the context (BLK_M, ctx_buffers.h), in doubles:
 //   [0, 96)      the 27 image vectors (81 used), computed here exactly as the definition writes them
 //   [96, 112)    the lattice (9 used)
 //   then         the position table of k_ms_tables, 3 * (nx + ny + nz)
@@ -9,19 +9,13 @@
 
 #define MS_HEAD 112
 
-static void moments_free(xb_ctx *c) {
-    hipFree(c->m_buf);
-    c->m_buf = nullptr; c->m_cap = 0;
-}
-
 int xb_moment_sum(xb_ctx *c, const double lattice[9], const double *centres_cart, int64_t n, double voxel_volume, double *moments,
                   double *volume) {
-    if (!c || !c->has_grid) return fail(XB_E_STATE, "xb_moment_sum: call xb_set_grid first");
+    ANALYSIS_NEED_GRID("xb_moment_sum");
     if (!lattice || !centres_cart || !moments || !volume) return fail(XB_E_ARG, "xb_moment_sum: null argument");
     if (n < 1) return fail(XB_E_ARG, "xb_moment_sum: %lld labels", (long long)n);
     if (n > XB_INT_MAX / MS_TERMS) return fail(XB_E_LIMIT, "xb_moment_sum: %lld labels exceed %d", (long long)n, XB_INT_MAX / MS_TERMS);
-    if (!c->have_rho) return fail(XB_E_STATE, "xb_moment_sum: no density on this grid yet");
-    if (!c->have_labels) return fail(XB_E_STATE, "xb_moment_sum: no labels on this grid yet");
+    if (int rc = analysis_ready(c, "xb_moment_sum", "", NEED_RHO | NEED_LABELS)) return rc;
     HIPCHK(hipSetDevice(c->device));
     if (int rc = settle_labels(c)) return rc;
     const Grid &g = c->g;
@@ -29,12 +23,7 @@ int xb_moment_sum(xb_ctx *c, const double lattice[9], const double *centres_cart
     const size_t len = (size_t)g.nx + g.ny + g.nz;
     const size_t o_tab = MS_HEAD, o_cen = o_tab + 3 * len, o_sum = o_cen + 3 * (size_t)n, o_cnt = o_sum + MS_TERMS * (size_t)n;
     const size_t want = o_cnt + (size_t)n;
-    if (c->m_cap < want) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        moments_free(c);
-        HIPCHK(hipMalloc(&c->m_buf, want * sizeof(double)));
-        c->m_cap = want;
-    }
+    if (int rc = reserve(c, BLK_M, want * sizeof(double))) return rc;
     double head[MS_HEAD] = {0.};
     MsImages img;
     for (int x = -1; x < 2; x++)
@@ -46,7 +35,7 @@ int xb_moment_sum(xb_ctx *c, const double lattice[9], const double *centres_cart
                     head[3 * i + j] = img.pbc[i][j];
                 }
     for (int k = 0; k < 9; k++) head[96 + k] = lattice[k];
-    double *buf = c->m_buf;
+    double *buf = c->ptr<double>(BLK_M);
     unsigned long long *dcn = reinterpret_cast<unsigned long long *>(buf + o_cnt);
     HIPCHK(hipMemcpyAsync(buf, head, sizeof head, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(buf + o_cen, centres_cart, 3 * (size_t)n * sizeof(double), hipMemcpyHostToDevice, c->stream));

@@ -1,25 +1,12 @@
 // host_nci.h -- host side, part 16: the NCI index (k_nci.h).  The three calls read the resident density (xb_nci_sum the resident
 // labels too) of the whole grid and write neither.
 //
-// One device buffer of the context (grown on demand, kept while the grid stays, counted by xb_memory_stats), in 8-byte words:
-//   nci_buf   xb_nci_sum: sum of rho [3 n], sum of rho^2 [3 n], counts [3 n] (64-bit integers)
+// One block of the context (ctx_buffers.h), in 8-byte words:
+//   BLK_NCI   xb_nci_sum: sum of rho [3 n], sum of rho^2 [3 n], counts [3 n] (64-bit integers)
 //             xb_nci_hist: the thresholds T(e_j) [n_s + 1], the edges of x [n_x + 1], the counts [n_s n_x] (64-bit integers)
 // xb_nci_field with host outputs writes s into `stage` (N doubles on a whole grid: need_scratch) and x into a temporary buffer of
 // N doubles, and copies from there.
 
-static void nci_free(xb_ctx *c) {
-    hipFree(c->nci_buf);
-    c->nci_buf = nullptr; c->nci_cap = 0;
-}
-static int nci_reserve(xb_ctx *c, size_t want) {
-    if (c->nci_cap < want) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        nci_free(c);
-        HIPCHK(hipMalloc(&c->nci_buf, want * sizeof(double)));
-        c->nci_cap = want;
-    }
-    return XB_OK;
-}
 // T(e) of the definition: a = C e, a2 = a a, T = (a2 a2) a2
 static inline double nci_threshold(double e) {
     const double a = XB_NCI_C * e, a2 = a * a;
@@ -27,7 +14,7 @@ static inline double nci_threshold(double e) {
 }
 
 int xb_nci_field(xb_ctx *c, const double lattice[9], int flags, double *s_host, double *x_host, void *s_dev, void *x_dev) {
-    STENCIL_NEED_GRID("xb_nci_field");
+    ANALYSIS_NEED_GRID("xb_nci_field");
     if (!lattice) return fail(XB_E_ARG, "xb_nci_field: null argument");
     const bool host = s_host && x_host && !s_dev && !x_dev, dev = s_dev && x_dev && !s_host && !x_host;
     if (!host && !dev) return fail(XB_E_ARG, "xb_nci_field: either both host outputs or both device outputs are wanted");
@@ -43,8 +30,7 @@ int xb_nci_field(xb_ctx *c, const double lattice[9], int flags, double *s_host, 
         uintptr_t lo[2], hi[2];
         void *const out[2] = {s_dev, x_dev};
         for (int k = 0; k < 2; k++) {
-            if ((uintptr_t)out[k] % sizeof(double)) return fail(XB_E_ARG, "xb_nci_field: %p is not aligned to its 8-byte elements", out[k]);
-            if (int rc = io_check_flat(c, "xb_nci_field", out[k], sizeof(double), &lo[k], &hi[k])) return rc;
+            if (int rc = io_check_dense(c, "xb_nci_field", out[k], sizeof(double), &lo[k], &hi[k])) return rc;
             if (io_overlaps(lo[k], hi[k], c->rho, bytes)) return fail(XB_E_ARG, "xb_nci_field: a destination overlaps the resident density");
         }
         if (lo[0] < hi[1] && lo[1] < hi[0]) return fail(XB_E_ARG, "xb_nci_field: the two destinations overlap");
@@ -68,7 +54,7 @@ int xb_nci_field(xb_ctx *c, const double lattice[9], int flags, double *s_host, 
 
 int xb_nci_sum(xb_ctx *c, const double lattice[9], int64_t n, double voxel_volume, double s_cut, double rho_cut, double rho_split,
                int flags, int64_t *count, double *charge, double *charge2) {
-    STENCIL_NEED_GRID("xb_nci_sum");
+    ANALYSIS_NEED_GRID("xb_nci_sum");
     if (!lattice || !count || !charge || !charge2) return fail(XB_E_ARG, "xb_nci_sum: null argument");
     if (flags & ~XB_STENCIL_GATHER) return fail(XB_E_ARG, "xb_nci_sum: unknown flag bits 0x%x", flags & ~XB_STENCIL_GATHER);
     if (n < 1) return fail(XB_E_ARG, "xb_nci_sum: %lld labels", (long long)n);
@@ -81,8 +67,8 @@ int xb_nci_sum(xb_ctx *c, const double lattice[9], int64_t n, double voxel_volum
     if (int rc = settle_labels(c)) return rc;
     const Grid &g = c->g;
     const size_t keys = 3 * (size_t)n, want = 3 * keys;
-    if (int rc = nci_reserve(c, want)) return rc;
-    double *ds = c->nci_buf, *dq = ds + keys;
+    if (int rc = reserve(c, BLK_NCI, want * sizeof(double))) return rc;
+    double *ds = c->ptr<double>(BLK_NCI), *dq = ds + keys;
     unsigned long long *dc = reinterpret_cast<unsigned long long *>(dq + keys);
     HIPCHK(hipMemsetAsync(ds, 0, want * sizeof(double), c->stream));
     const NciCuts C{nci_threshold(s_cut), rho_cut, rho_split};
@@ -119,7 +105,7 @@ static int nci_edges_ok(const char *what, const double *e, int64_t n, bool posit
 
 int xb_nci_hist(xb_ctx *c, const double lattice[9], const double *s_edges, int64_t n_s, const double *x_edges, int64_t n_x, int flags,
                 int64_t *counts) {
-    STENCIL_NEED_GRID("xb_nci_hist");
+    ANALYSIS_NEED_GRID("xb_nci_hist");
     if (!lattice || !s_edges || !x_edges || !counts) return fail(XB_E_ARG, "xb_nci_hist: null argument");
     if (flags & ~XB_STENCIL_GATHER) return fail(XB_E_ARG, "xb_nci_hist: unknown flag bits 0x%x", flags & ~XB_STENCIL_GATHER);
     if (n_s < 1 || n_x < 1) return fail(XB_E_ARG, "xb_nci_hist: %lld x %lld bins", (long long)n_s, (long long)n_x);
@@ -132,11 +118,11 @@ int xb_nci_hist(xb_ctx *c, const double lattice[9], const double *s_edges, int64
     HIPCHK(hipSetDevice(c->device));
     const Grid &g = c->g;
     const size_t cells = (size_t)(n_s * n_x), n_t = (size_t)n_s + 1, n_e = (size_t)n_x + 1;
-    if (int rc = nci_reserve(c, n_t + n_e + cells)) return rc;
+    if (int rc = reserve(c, BLK_NCI, (n_t + n_e + cells) * sizeof(double))) return rc;
     std::vector<double> tab(n_t + n_e);
     for (size_t j = 0; j < n_t; j++) tab[j] = nci_threshold(s_edges[j]);
     for (size_t j = 0; j < n_e; j++) tab[n_t + j] = x_edges[j];
-    double *dt = c->nci_buf, *de = dt + n_t;
+    double *dt = c->ptr<double>(BLK_NCI), *de = dt + n_t;
     unsigned long long *dc = reinterpret_cast<unsigned long long *>(de + n_e);
     HIPCHK(hipMemcpyAsync(dt, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemsetAsync(dc, 0, cells * sizeof(unsigned long long), c->stream));

@@ -4,33 +4,18 @@
 // Scratch: the roots' numbers (4 N bytes), the runs' counts (16 bytes per RG_BLOCK voxels) and the chunks' sums live in `stage`
 // (N doubles on a whole grid: need_scratch), which is scratch between calls; the sums per component, the share table and the key
 // list in temporary buffers.  With XB_DOMAINS_TIMES five events bracket the four stages (xb_regions_times).
-// Kept (counted by xb_memory_stats, freed by xb_regions_release; the result is discarded by every writer of the density): rg_map,
-// the component of every voxel (4 N bytes), and rg_seed, the smallest index of every component (4 bytes each, at least one).
+// Kept (blocks of ctx_buffers.h, freed by xb_regions_release; the result is discarded by every writer of the density): BLK_RG_MAP,
+// the component of every voxel (4 N bytes), and BLK_RG_SEED, the smallest index of every component (4 bytes each, at least one).
 
-static void regions_free(xb_ctx *c) {
-    hipFree(c->rg_map); hipFree(c->rg_seed);
-    c->rg_map = nullptr; c->rg_seed = nullptr; c->rg_seed_cap = 0;
+static void regions_forget(xb_ctx *c) {
     c->rg_m = 0; c->rg_members = 0; c->rg_have = false; c->rg_sh_have = false;
     std::vector<int32_t>().swap(c->rg_sh_comp); std::vector<int32_t>().swap(c->rg_sh_lab);
     std::vector<int64_t>().swap(c->rg_sh_cnt);
 }
 
-// what xb_memory_stats counts: the map while it is allocated, and the seeds
-static size_t regions_bytes(const xb_ctx *c) { return (c->rg_map ? (size_t)c->N * sizeof(int) : 0) + c->rg_seed_cap * sizeof(int); }
-// the seeds' buffer for n entries (0: none)
-static int regions_seeds(xb_ctx *c, size_t n) {
-    hipFree(c->rg_seed);
-    c->rg_seed = nullptr; c->rg_seed_cap = 0;
-    if (n) {
-        HIPCHK(hipMalloc(&c->rg_seed, n * sizeof(int)));
-        c->rg_seed_cap = n;
-    }
-    return XB_OK;
-}
-
 int xb_regions_label(xb_ctx *c, int mode, const void *field_dev, double level, const double lattice[9], double s_cut, double rho_cut,
                      int flags, int64_t *m_out) {
-    STENCIL_NEED_GRID("xb_regions_label");
+    ANALYSIS_NEED_GRID("xb_regions_label");
     if (!m_out) return fail(XB_E_ARG, "xb_regions_label: null argument");
     if (mode != XB_DOMAINS_ABOVE && mode != XB_DOMAINS_BELOW && mode != XB_DOMAINS_NCI) return fail(XB_E_ARG, "xb_regions_label: unknown mode %d", mode);
     const int known = XB_DOMAINS_GLOBAL | XB_DOMAINS_GATHER | XB_DOMAINS_TIMES;
@@ -48,10 +33,7 @@ int xb_regions_label(xb_ctx *c, int mode, const void *field_dev, double level, c
     } else {
         if (level != level) return fail(XB_E_ARG, "xb_regions_label: the level is NaN");
         if (flags & XB_DOMAINS_GATHER) return fail(XB_E_ARG, "xb_regions_label: XB_DOMAINS_GATHER belongs to the NCI region's predicate");
-        const Grid &g0 = c->g;
-        if (g0.x1 - g0.x0 != g0.nx)
-            return fail(XB_E_STATE, "xb_regions_label: the context holds a slab [%d, %d) of %d planes; the components need the whole grid", g0.x0, g0.x1, g0.nx);
-        if (!c->have_rho) return fail(XB_E_STATE, "xb_regions_label: no density on this grid yet");
+        if (int rc = analysis_ready(c, "xb_regions_label", "the components need", NEED_WHOLE | NEED_RHO)) return rc;
     }
     if (c->N > XB_INT_MAX) return fail(XB_E_LIMIT, "xb_regions_label: %lld voxels exceed %d", c->N, XB_INT_MAX);
     HIPCHK(hipSetDevice(c->device));
@@ -61,14 +43,14 @@ int xb_regions_label(xb_ctx *c, int mode, const void *field_dev, double level, c
     if (c->stage_bytes < off_grand + 16) return fail(XB_E_STATE, "xb_regions_label: the scratch buffer holds no whole grid");
     if (field_dev) {
         uintptr_t lo, hi;
-        if ((uintptr_t)field_dev % sizeof(double)) return fail(XB_E_ARG, "xb_regions_label: %p is not aligned to its 8-byte elements", field_dev);
-        if (int rc = io_check_flat(c, "xb_regions_label", field_dev, sizeof(double), &lo, &hi)) return rc;
+        if (int rc = io_check_dense(c, "xb_regions_label", field_dev, sizeof(double), &lo, &hi)) return rc;
         if (io_overlaps(lo, hi, c->stage, c->stage_bytes)) return fail(XB_E_ARG, "xb_regions_label: the field overlaps the context's scratch");
     }
     HIPCHK(hipStreamSynchronize(c->stream));
     c->rg_have = false; c->rg_sh_have = false;
     stage_clobbered(*c);
-    if (!c->rg_map) HIPCHK(hipMalloc(&c->rg_map, (size_t)N * sizeof(int)));
+    if (int rc = reserve(c, BLK_RG_MAP, (size_t)N * sizeof(int))) return rc;
+    int *const rg_map = c->ptr<int>(BLK_RG_MAP);
     const double *f = field_dev ? (const double *)field_dev : c->rho;
     int *num = reinterpret_cast<int *>(c->stage);
     unsigned long long *tot = reinterpret_cast<unsigned long long *>((char *)c->stage + off_tot);
@@ -86,19 +68,19 @@ int xb_regions_label(xb_ctx *c, int mode, const void *field_dev, double level, c
         for (int k = 0; k < 5; k++) HIPCHK(hipEventCreate(&ev[k]));
         HIPCHK(hipEventRecord(ev[0], c->stream));
     }
-#define RG_TILE_LAUNCH(SRC, LOCAL) k_rg_tile<SRC, LOCAL><<<tiles, TPB, 0, c->stream>>>(g.nx, g.ny, g.nz, f, level, below, K, C, c->rg_map)
+#define RG_TILE_LAUNCH(SRC, LOCAL) k_rg_tile<SRC, LOCAL><<<tiles, TPB, 0, c->stream>>>(g.nx, g.ny, g.nz, f, level, below, K, C, rg_map)
     if (!nci) { if (global) RG_TILE_LAUNCH(RG_SRC_FIELD, false); else RG_TILE_LAUNCH(RG_SRC_FIELD, true); }
     else if (gather) { if (global) RG_TILE_LAUNCH(RG_SRC_NCI_GATHER, false); else RG_TILE_LAUNCH(RG_SRC_NCI_GATHER, true); }
     else { if (global) RG_TILE_LAUNCH(RG_SRC_NCI_TILE, false); else RG_TILE_LAUNCH(RG_SRC_NCI_TILE, true); }
 #undef RG_TILE_LAUNCH
     HIPCHK(hipGetLastError());
     if (timed) HIPCHK(hipEventRecord(ev[1], c->stream));
-    if (global) k_rg_link<true><<<nblocks(N), TPB, 0, c->stream>>>(g.nx, g.ny, g.nz, c->rg_map);
-    else k_rg_link<false><<<nblocks(N), TPB, 0, c->stream>>>(g.nx, g.ny, g.nz, c->rg_map);
+    if (global) k_rg_link<true><<<nblocks(N), TPB, 0, c->stream>>>(g.nx, g.ny, g.nz, rg_map);
+    else k_rg_link<false><<<nblocks(N), TPB, 0, c->stream>>>(g.nx, g.ny, g.nz, rg_map);
     if (timed) HIPCHK(hipEventRecord(ev[2], c->stream));
-    k_rg_flatten<<<nblocks(N), TPB, 0, c->stream>>>(N, c->rg_map);
+    k_rg_flatten<<<nblocks(N), TPB, 0, c->stream>>>(N, rg_map);
     if (timed) HIPCHK(hipEventRecord(ev[3], c->stream));
-    k_rg_count<<<(unsigned)nb, TPB, 0, c->stream>>>(N, c->rg_map, tot);
+    k_rg_count<<<(unsigned)nb, TPB, 0, c->stream>>>(N, rg_map, tot);
     k_iso_scan_sums<<<(unsigned)np, TPB, 0, c->stream>>>(tot, nb, part);
     k_iso_scan_top<<<1, XB_WAVE, 0, c->stream>>>(part, np, grand);
     k_iso_scan_apply<<<(unsigned)np, TPB, 0, c->stream>>>(tot, nb, part);
@@ -109,9 +91,10 @@ int xb_regions_label(xb_ctx *c, int mode, const void *field_dev, double level, c
     if (want[0] > want[1] || want[1] > (unsigned long long)N)
         return fail(XB_E_STATE, "xb_regions_label: the count pass reports %llu roots and %llu members on %lld voxels", want[0], want[1], N);
     const size_t m = (size_t)want[0];
-    if (int rc = regions_seeds(c, std::max<size_t>(m, 1))) return rc;
-    k_rg_emit<<<(unsigned)nb, TPB, 0, c->stream>>>(N, c->rg_map, tot, c->rg_seed, num);
-    k_rg_number<<<nblocks(N), TPB, 0, c->stream>>>(N, c->rg_map, num);
+    release(c, BLK_RG_SEED, BLK_RG_SEED);   // (exactly the last labelling's seeds are kept and counted)
+    if (int rc = reserve(c, BLK_RG_SEED, std::max<size_t>(m, 1) * sizeof(int))) return rc;
+    k_rg_emit<<<(unsigned)nb, TPB, 0, c->stream>>>(N, rg_map, tot, c->ptr<int>(BLK_RG_SEED), num);
+    k_rg_number<<<nblocks(N), TPB, 0, c->stream>>>(N, rg_map, num);
     HIPCHK(hipGetLastError());
     if (timed) HIPCHK(hipEventRecord(ev[4], c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -149,9 +132,9 @@ int xb_regions_sums(xb_ctx *c, double voxel_volume, double rho_split, int64_t *s
     double *ds = buf.p, *dq = ds + keys;
     unsigned long long *dc = reinterpret_cast<unsigned long long *>(dq + keys), *dk = dc + keys, *dl = dk + m;
     HIPCHK(hipMemsetAsync(buf.p, 0, words * sizeof(double), c->stream));
-    if (classes) k_rg_sums<true><<<nblocks((c->N + RG_STEPS - 1) / RG_STEPS), TPB, 0, c->stream>>>(g.nx, g.ny, g.nz, c->rho, c->rg_map, c->rg_K, rho_split, ds, dq, dc, dk);
-    else k_rg_sums<false><<<nblocks((c->N + RG_STEPS - 1) / RG_STEPS), TPB, 0, c->stream>>>(g.nx, g.ny, g.nz, c->rho, c->rg_map, c->rg_K, rho_split, ds, dq, dc, dk);
-    k_rg_top<<<nblocks(c->N), TPB, 0, c->stream>>>(c->N, c->rho, c->rg_map, dk, dl);
+    if (classes) k_rg_sums<true><<<nblocks((c->N + RG_STEPS - 1) / RG_STEPS), TPB, 0, c->stream>>>(g.nx, g.ny, g.nz, c->rho, c->ptr<int>(BLK_RG_MAP), c->rg_K, rho_split, ds, dq, dc, dk);
+    else k_rg_sums<false><<<nblocks((c->N + RG_STEPS - 1) / RG_STEPS), TPB, 0, c->stream>>>(g.nx, g.ny, g.nz, c->rho, c->ptr<int>(BLK_RG_MAP), c->rg_K, rho_split, ds, dq, dc, dk);
+    k_rg_top<<<nblocks(c->N), TPB, 0, c->stream>>>(c->N, c->rho, c->ptr<int>(BLK_RG_MAP), dk, dl);
     HIPCHK(hipGetLastError());
     std::vector<double> hs(keys), hq(keys);
     std::vector<unsigned long long> hc(keys), hl(m);
@@ -160,7 +143,7 @@ int xb_regions_sums(xb_ctx *c, double voxel_volume, double rho_split, int64_t *s
     HIPCHK(hipMemcpyAsync(hq.data(), dq, keys * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipMemcpyAsync(hc.data(), dc, keys * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipMemcpyAsync(hl.data(), dl, m * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(hseed.data(), c->rg_seed, m * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(hseed.data(), c->ptr<int>(BLK_RG_SEED), m * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     for (size_t i = 0; i < m; i++) {
         seed[i] = hseed[i];
@@ -207,8 +190,8 @@ int xb_regions_shares(xb_ctx *c, int64_t n, int flags, int64_t *n_triplets) {
         HIPCHK(hipMemsetAsync(tab.p, 0, cells * sizeof(unsigned long long), c->stream));
         HIPCHK(hipMemsetAsync(used, 0, sizeof(unsigned long long), c->stream));
         const unsigned grid = nblocks((c->N + RG_STEPS - 1) / RG_STEPS);
-        if (cells <= RG_SHARE_LDS) k_rg_share_dense<true><<<grid, TPB, 0, c->stream>>>(c->N, c->rg_map, c->labels, (int)n, (int)cells, tab.p);
-        else k_rg_share_dense<false><<<grid, TPB, 0, c->stream>>>(c->N, c->rg_map, c->labels, (int)n, (int)cells, tab.p);
+        if (cells <= RG_SHARE_LDS) k_rg_share_dense<true><<<grid, TPB, 0, c->stream>>>(c->N, c->ptr<int>(BLK_RG_MAP), c->labels, (int)n, (int)cells, tab.p);
+        else k_rg_share_dense<false><<<grid, TPB, 0, c->stream>>>(c->N, c->ptr<int>(BLK_RG_MAP), c->labels, (int)n, (int)cells, tab.p);
         k_rg_share_compact<<<nblocks((long long)cells), TPB, 0, c->stream>>>((long long)cells, tab.p, pairs.p, (unsigned long long)cap, used);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(&got, used, sizeof got, hipMemcpyDeviceToHost, c->stream));
@@ -231,7 +214,7 @@ int xb_regions_shares(xb_ctx *c, int64_t n, int flags, int64_t *n_triplets) {
         HIPCHK(keys.alloc(cap));
         unsigned long long *used = c->counters64 + 8, got = 0;
         HIPCHK(hipMemsetAsync(used, 0, sizeof(unsigned long long), c->stream));
-        k_rg_share_list<<<nblocks(c->N), TPB, 0, c->stream>>>(c->N, c->rg_map, c->labels, (int)n, keys.p, (unsigned long long)cap, used);
+        k_rg_share_list<<<nblocks(c->N), TPB, 0, c->stream>>>(c->N, c->ptr<int>(BLK_RG_MAP), c->labels, (int)n, keys.p, (unsigned long long)cap, used);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(&got, used, sizeof got, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
@@ -274,22 +257,13 @@ int xb_regions_fetch_map(xb_ctx *c, int on_device, void *map) {
     const size_t bytes = (size_t)c->N * sizeof(int32_t);
     if (on_device) {
         uintptr_t lo, hi;
-        if ((uintptr_t)map % sizeof(int32_t)) return fail(XB_E_ARG, "xb_regions_fetch_map: %p is not aligned to its 4-byte elements", map);
-        if (int rc = io_check_flat(c, "xb_regions_fetch_map", map, sizeof(int32_t), &lo, &hi)) return rc;
-        if (io_overlaps(lo, hi, c->rg_map, bytes)) return fail(XB_E_ARG, "xb_regions_fetch_map: the destination overlaps the kept map");
-        HIPCHK(hipMemcpyAsync(map, c->rg_map, bytes, hipMemcpyDeviceToDevice, c->stream));
+        if (int rc = io_check_dense(c, "xb_regions_fetch_map", map, sizeof(int32_t), &lo, &hi)) return rc;
+        if (io_overlaps(lo, hi, c->ptr<int>(BLK_RG_MAP), bytes)) return fail(XB_E_ARG, "xb_regions_fetch_map: the destination overlaps the kept map");
+        HIPCHK(hipMemcpyAsync(map, c->ptr<int>(BLK_RG_MAP), bytes, hipMemcpyDeviceToDevice, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
         return XB_OK;
     }
-    return staged_d2h(c, map, c->rg_map, bytes);   // (waits)
-}
-
-int xb_regions_release(xb_ctx *c) {
-    if (!c) return fail(XB_E_ARG, "xb_regions_release: null ctx");
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    regions_free(c);
-    return XB_OK;
+    return staged_d2h(c, map, c->ptr<int>(BLK_RG_MAP), bytes);   // (waits)
 }
 
 int xb_regions_times(xb_ctx *c, double ms[4]) {

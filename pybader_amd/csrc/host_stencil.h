@@ -1,16 +1,12 @@
 // host_stencil.h -- host side, part 14: the Laplacian and the Hessian of the density (k_stencil.h).  The three calls read the
 // resident density (xb_laplacian_sum the resident labels too) of the whole grid and write neither.
 //
-// One device buffer of the context (grown on demand, kept while the grid stays, counted by xb_memory_stats), in 8-byte words:
-//   st_buf   xb_laplacian_sum's results: sum[n], the sum of magnitudes [n], the counts [n] (64-bit integers)
+// One block of the context (ctx_buffers.h), in 8-byte words:
+//   BLK_ST   xb_laplacian_sum's results: sum[n], the sum of magnitudes [n], the counts [n] (64-bit integers)
 // xb_laplacian_field with a host output writes into `stage` (N doubles on a whole grid: need_scratch) and copies from there;
 // xb_stencil_points keeps nothing (two temporary buffers of m and 10 m words).
 
 static_assert(sizeof(StCoeffs) == XB_STENCIL_COEFFS * sizeof(double), "StCoeffs is the array of xb_stencil_coeffs");
-static void stencil_free(xb_ctx *c) {
-    hipFree(c->st_buf);
-    c->st_buf = nullptr; c->st_cap = 0;
-}
 
 // the coefficients of the definition (include/bader_hip.h), every operation in the order written there
 int xb_stencil_coeffs(const double lattice[9], int64_t nx, int64_t ny, int64_t nz, double out[XB_STENCIL_COEFFS]) {
@@ -49,22 +45,16 @@ int xb_stencil_coeffs(const double lattice[9], int64_t nx, int64_t ny, int64_t n
 
 // what the three calls check alike once they have a grid and sound arguments of their own: the whole grid, a density (and
 // labels), the lattice
-#define STENCIL_NEED_GRID(name) \
-    if (!c || !c->has_grid) return fail(XB_E_STATE, name ": call xb_set_grid first")
 static int stencil_ready(xb_ctx *c, const char *who, const double *lattice, bool labels, StCoeffs *K) {
-    const Grid &g = c->g;
-    if (g.x1 - g.x0 != g.nx)
-        return fail(XB_E_STATE, "%s: the context holds a slab [%d, %d) of %d planes; the stencil needs the whole grid", who, g.x0, g.x1, g.nx);
-    if (!c->have_rho) return fail(XB_E_STATE, "%s: no density on this grid yet", who);
-    if (labels && !c->have_labels) return fail(XB_E_STATE, "%s: no labels on this grid yet", who);
-    return xb_stencil_coeffs(lattice, g.nx, g.ny, g.nz, reinterpret_cast<double *>(K));
+    if (int rc = analysis_ready(c, who, "the stencil needs", NEED_WHOLE | NEED_RHO | (labels ? NEED_LABELS : 0))) return rc;
+    return xb_stencil_coeffs(lattice, c->g.nx, c->g.ny, c->g.nz, reinterpret_cast<double *>(K));
 }
 static unsigned stencil_tiles(const Grid &g) {   // (at most N)
     return (unsigned)((long long)((g.nx + ST_TX - 1) / ST_TX) * ((g.ny + ST_TY - 1) / ST_TY) * ((g.nz + ST_TZ - 1) / ST_TZ));
 }
 
 int xb_laplacian_field(xb_ctx *c, const double lattice[9], int flags, double *out_host, void *out_dev) {
-    STENCIL_NEED_GRID("xb_laplacian_field");
+    ANALYSIS_NEED_GRID("xb_laplacian_field");
     if (!lattice) return fail(XB_E_ARG, "xb_laplacian_field: null argument");
     if ((out_host != nullptr) == (out_dev != nullptr)) return fail(XB_E_ARG, "xb_laplacian_field: exactly one of out_host and out_dev is wanted");
     if (flags & ~XB_STENCIL_GATHER) return fail(XB_E_ARG, "xb_laplacian_field: unknown flag bits 0x%x", flags & ~XB_STENCIL_GATHER);
@@ -74,9 +64,8 @@ int xb_laplacian_field(xb_ctx *c, const double lattice[9], int flags, double *ou
     const Grid &g = c->g;
     double *dst = (double *)out_dev;
     if (out_dev) {
-        if ((uintptr_t)out_dev % sizeof(double)) return fail(XB_E_ARG, "xb_laplacian_field: %p is not aligned to its 8-byte elements", out_dev);
         uintptr_t lo, hi;
-        if (int rc = io_check_flat(c, "xb_laplacian_field", out_dev, sizeof(double), &lo, &hi)) return rc;
+        if (int rc = io_check_dense(c, "xb_laplacian_field", out_dev, sizeof(double), &lo, &hi)) return rc;
         if (io_overlaps(lo, hi, c->rho, (size_t)c->N * 8)) return fail(XB_E_ARG, "xb_laplacian_field: the destination overlaps the resident density");
     } else {
         if (c->stage_bytes < (size_t)c->N * sizeof(double)) return fail(XB_E_STATE, "xb_laplacian_field: the scratch buffer holds no whole grid");
@@ -93,7 +82,7 @@ int xb_laplacian_field(xb_ctx *c, const double lattice[9], int flags, double *ou
 
 int xb_laplacian_sum(xb_ctx *c, const double lattice[9], int64_t n, double voxel_volume, int flags, double *sum, double *abs_sum,
                      double *volume) {
-    STENCIL_NEED_GRID("xb_laplacian_sum");
+    ANALYSIS_NEED_GRID("xb_laplacian_sum");
     if (!lattice || !sum || !abs_sum || !volume) return fail(XB_E_ARG, "xb_laplacian_sum: null argument");
     if (flags & ~XB_STENCIL_GATHER) return fail(XB_E_ARG, "xb_laplacian_sum: unknown flag bits 0x%x", flags & ~XB_STENCIL_GATHER);
     if (n < 1) return fail(XB_E_ARG, "xb_laplacian_sum: %lld labels", (long long)n);
@@ -104,13 +93,8 @@ int xb_laplacian_sum(xb_ctx *c, const double lattice[9], int64_t n, double voxel
     if (int rc = settle_labels(c)) return rc;
     const Grid &g = c->g;
     const size_t want = 3 * (size_t)n;
-    if (c->st_cap < want) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        stencil_free(c);
-        HIPCHK(hipMalloc(&c->st_buf, want * sizeof(double)));
-        c->st_cap = want;
-    }
-    double *ds = c->st_buf, *dm = ds + n;
+    if (int rc = reserve(c, BLK_ST, want * sizeof(double))) return rc;
+    double *ds = c->ptr<double>(BLK_ST), *dm = ds + n;
     unsigned long long *dc = reinterpret_cast<unsigned long long *>(dm + n);
     HIPCHK(hipMemsetAsync(ds, 0, want * sizeof(double), c->stream));
     const bool bins = n <= ST_BINS;
@@ -136,7 +120,7 @@ int xb_laplacian_sum(xb_ctx *c, const double lattice[9], int64_t n, double voxel
 }
 
 int xb_stencil_points(xb_ctx *c, const double lattice[9], const int64_t *lin, int64_t m, double *out) {
-    STENCIL_NEED_GRID("xb_stencil_points");
+    ANALYSIS_NEED_GRID("xb_stencil_points");
     if (m < 0) return fail(XB_E_ARG, "xb_stencil_points: %lld voxels", (long long)m);
     if (!lattice || (m > 0 && (!lin || !out))) return fail(XB_E_ARG, "xb_stencil_points: null argument");
     StCoeffs K;

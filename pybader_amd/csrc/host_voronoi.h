@@ -1,7 +1,7 @@
 // host_voronoi.h -- host side, part 12: the Voronoi partition (k_voronoi.h).  xb_voronoi_assign writes the resident labels -- a
 // label writer like xb_upload_labels, with everything that call invalidates -- and reads the resident density only for the vacuum.
 //
-// One buffer of the context (grown on demand, kept while the grid stays, counted by xb_memory_stats), in doubles, laid out as
+// One block of the context (BLK_VO, ctx_buffers.h), in doubles, laid out as
 // xb_moment_sum's:
 //   [0, 96)      the 27 image vectors (81 used), computed here exactly as the definition writes them
 //   [96, 112)    the lattice (9 used)
@@ -10,14 +10,9 @@
 
 #define VO_HEAD 112
 
-static void voronoi_free(xb_ctx *c) {
-    hipFree(c->vo_buf);
-    c->vo_buf = nullptr; c->vo_cap = 0;
-}
-
 int xb_voronoi_assign(xb_ctx *c, const double lattice[9], const double *atoms_cart, int64_t n, double vac_tol, int flags,
                       int64_t stats[3]) {
-    if (!c || !c->has_grid) return fail(XB_E_STATE, "xb_voronoi_assign: call xb_set_grid first");
+    ANALYSIS_NEED_GRID("xb_voronoi_assign");
     if (!lattice || !atoms_cart) return fail(XB_E_ARG, "xb_voronoi_assign: null argument");
     if (n < 1) return fail(XB_E_ARG, "xb_voronoi_assign: %lld atoms", (long long)n);
     if (flags & ~XB_VORONOI_FULL_SEARCH) return fail(XB_E_ARG, "xb_voronoi_assign: unknown flag bits 0x%x", flags & ~XB_VORONOI_FULL_SEARCH);
@@ -26,20 +21,14 @@ int xb_voronoi_assign(xb_ctx *c, const double lattice[9], const double *atoms_ca
         if (!std::isfinite(lattice[k])) return fail(XB_E_ARG, "xb_voronoi_assign: the lattice is not finite");
     for (int64_t k = 0; k < 3 * n; k++)
         if (!std::isfinite(atoms_cart[k])) return fail(XB_E_ARG, "xb_voronoi_assign: atom %lld is not finite", (long long)(k / 3));
+    if (int rc = analysis_ready(c, "xb_voronoi_assign", "the partition needs", NEED_WHOLE)) return rc;
     const Grid &g = c->g;
-    if (g.x1 - g.x0 != g.nx)
-        return fail(XB_E_STATE, "xb_voronoi_assign: the context holds a slab [%d, %d) of %d planes; the partition needs the whole grid", g.x0, g.x1, g.nx);
     const bool use_vac = vac_tol == vac_tol;
     if (use_vac && !c->have_rho) return fail(XB_E_STATE, "xb_voronoi_assign: a vacuum tolerance, and no density on this grid yet");
     HIPCHK(hipSetDevice(c->device));
     const size_t len = (size_t)g.nx + g.ny + g.nz;
     const size_t o_tab = VO_HEAD, o_at = o_tab + 3 * len, o_st = o_at + 3 * (size_t)n, want = o_st + 1;
-    if (c->vo_cap < want) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        voronoi_free(c);
-        HIPCHK(hipMalloc(&c->vo_buf, want * sizeof(double)));
-        c->vo_cap = want;
-    }
+    if (int rc = reserve(c, BLK_VO, want * sizeof(double))) return rc;
     // every label of the grid is overwritten (vac_by_tol falls: the other labels are atoms, not the zeros an assignment expects next to its vacuum marks)
     labels_overwritten(*c, label_wire_for(n), use_vac);
     double head[VO_HEAD] = {0.};
@@ -52,7 +41,7 @@ int xb_voronoi_assign(xb_ctx *c, const double lattice[9], const double *atoms_ca
     G.len = 0.;
     for (int k = 0; k < 3; k++) G.len += std::sqrt((lattice[3 * k] * lattice[3 * k] + lattice[3 * k + 1] * lattice[3 * k + 1]) + lattice[3 * k + 2] * lattice[3 * k + 2]);
     for (int k = 0; k < 9; k++) G.lat[k] = head[96 + k] = lattice[k];
-    double *buf = c->vo_buf;
+    double *buf = c->ptr<double>(BLK_VO);
     unsigned int *dst = reinterpret_cast<unsigned int *>(buf + o_st);
     G.tab = buf + o_tab; G.pbc = buf; G.atoms = buf + o_at;
     G.nx = g.nx; G.ny = g.ny; G.nz = g.nz; G.n = (int)n;
