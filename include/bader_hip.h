@@ -735,6 +735,54 @@ int xb_hirshfeld_setup(xb_ctx *c, const double lattice[9], const double *atoms_c
 int xb_hirshfeld_release(xb_ctx *c);
 int xb_hirshfeld_sum(xb_ctx *c, double voxel_volume, int flags, double *charge, double *volume, double rest[2], int64_t stats[3]);
 int xb_hirshfeld_field(xb_ctx *c, int mode, int flags, double *out_host, void *out_dev);
+/* ---- Iterative stockholder atoms (ISA; Lillestolen & Wheatley 2008): Hirshfeld weights WITHOUT pro-atoms.  Each atom's table is the
+ * spherical average of that atom's own share of the density, iterated to self-consistency; the charge HORTON and Chargemol print
+ * beside the plain Hirshfeld one -- no counterpart in the reference ----
+ * Everything not restated here is the Hirshfeld section's, bit for bit: voxel and image positions, d2, the canonical image list and
+ * its margins, u = d2*inv_h2[a], k = min((int)u, K - 1), t = u - k, the running sums in list order, no contraction.
+ *   tables    one per atom: species[a] = a, S = n; atom a has r_cut[a] > 0 and K >= 1 shells, the same K for all.  Shell k is
+ *             k <= u < k + 1; because of the clamp the last shell also takes u up to the cutoff.
+ *   weights   PIECEWISE CONSTANT: the term of an image of atom a at a voxel is A[a][k] when d2 < rc2[a], and 0 otherwise.  In the
+ *             Hirshfeld section's table form this is the pair (A[a][k], +0.0), and f + t*0.0 == f: xb_hirshfeld_sum and
+ *             xb_hirshfeld_field evaluate it with unchanged code and the same bits.
+ *   counts    count[a][k] = the number of (voxel, image of a) pairs with d2 < rc2[a] that fall in shell k, int64.  Geometry only,
+ *             computed once per setup; pairs at voxels with P == 0 count too.
+ *   start     A0[a][k] = 1.0 for all shells, or the caller's [n][K] finite non-negative doubles.
+ *   iteration for every voxel with P > 0 and every pair with term > 0:  c = rho*(term/P),  q = llrint(ldexp(c, e))  (to nearest,
+ *             ties to even: numpy's rint),  bin[a][k] += q  in int64.  Integer addition is associative: the bins do not depend on
+ *             the order of the atomics.  Then  A'[a][k] = bin > 0 ? ldexp((double)bin / (double)count, -e) : 0.0  -- a non-positive
+ *             shell average (negative densities) clamps to zero.  The new tables replace the old, the bins are cleared, and
+ *             qsum[a] = sum_k bin[a][k] (int64, wrapping) is kept per iteration: the atom's fixed-point charge, qsum * 2^-e *
+ *             voxel_volume, for the convergence history.
+ *   exponent  e = 61 - ceil_log2(rho_bound) - ceil_log2(cmax + 1), cmax = max count, formed with frexp and integers only; the
+ *             caller's rho_bound >= max |rho|, finite, > 0.  |q| <= rho_bound*2^e (term <= P: a running sum of non-negative terms
+ *             is monotone), so no bin can reach 2^62.  A voxel whose |rho| is not <= rho_bound adds nothing and is counted; any such
+ *             voxel makes xb_isa_iterate fail with XB_E_ARG after the launch, and the tables stay as before the call.
+ *   results   xb_hirshfeld_sum on the converged tables gives charge, volume and rest; xb_hirshfeld_field the sum of the atoms
+ *             sum_a w_a and rho - sum_a w_a, the non-spherical residual: ISA's own quality figure.
+ * On a uniform grid with piecewise-constant shells this is exactly an ML-EM iteration.
+ * xb_isa_setup: builds the Hirshfeld setup of the context with these tables (it REPLACES an xb_hirshfeld_setup and the reverse; the
+ *             stale-state rules are that call's), runs the counting pass and fixes e.  out_info = {e, cmax, the total number of
+ *             pairs, the number of shells with count 0}.  initial: NULL or [n][K].
+ * xb_isa_iterate: `iters` iterations (1 .. XB_ISA_ITERS_MAX) of the resident density queued back to back, ONE host wait; row i of
+ *             qsum_out[iters][n] is iteration i's qsum.  flags: XB_HIRSHFELD_FULL_SEARCH (every tile runs over the whole list) and
+ *             XB_ISA_DIRECT (one global atomic per pair instead of the waves' LDS windows): second implementations, the same bits.
+ *             stats: NULL or {candidate tiles, full-search tiles, the longest list, voxels beyond rho_bound}.
+ * xb_isa_tables: the current tables A_out[n][K] and the counts count_out[n][K]; either may be NULL, not both.
+ * xb_isa_load: tables[n][K], finite and non-negative, replace the current tables of the setup (the counts and e stay): a caller
+ *             goes back to tables it read earlier without a new setup.
+ * xb_isa_rho_bound: max |rho| of the resident density (a NaN gives a NaN), for the rho_bound of a density that lives on the device.
+ * XB_E_STATE: as the Hirshfeld calls, and xb_isa_iterate / xb_isa_tables / xb_isa_load on a setup that is xb_hirshfeld_setup's;  XB_E_ARG: as
+ * xb_hirshfeld_setup, shells < 1, rho_bound not finite or <= 0, an initial value that is negative or not finite, iters < 1, unknown
+ * flag bits, a density beyond rho_bound;  XB_E_LIMIT: as xb_hirshfeld_setup, n * shells above 2^26, iters above XB_ISA_ITERS_MAX.
+ * Every argument error is found on the host before any launch. */
+enum { XB_ISA_DIRECT = 2, XB_ISA_ITERS_MAX = 64 };
+int xb_isa_setup(xb_ctx *c, const double lattice[9], const double *atoms_cart, int64_t n, const double *r_cut, int64_t shells,
+                 const double *initial, double rho_bound, int64_t out_info[4]);
+int xb_isa_iterate(xb_ctx *c, int64_t iters, int flags, int64_t *qsum_out, int64_t stats[4]);
+int xb_isa_tables(xb_ctx *c, double *A_out, int64_t *count_out);
+int xb_isa_load(xb_ctx *c, const double *tables);
+int xb_isa_rho_bound(xb_ctx *c, double *out);
 /* utils.volume_assign (utils.py:404-421): labels[v] = swap[labels[v]] for labels >= 0 */
 int xb_volume_assign(xb_ctx *c, const int64_t *swap, int64_t n_swap);
 /* utils.atom_assign (utils.py:185-232): nearest atom of every maximum over the 27 periodic images (one

@@ -77,6 +77,10 @@ XB_DOMAINS_SHARE_CELLS = 1 << 24
 XB_HIRSHFELD_FULL_SEARCH = 1
 XB_HIRSHFELD_CAND_MAX = 256
 XB_HIRSHFELD_PROMOLECULE, XB_HIRSHFELD_DEFORMATION = 0, 1
+# xb_isa_iterate: the bit of `flags` (beside XB_HIRSHFELD_FULL_SEARCH) that sends every pair out with a global atomic of its own,
+# and the most iterations one call queues
+XB_ISA_DIRECT = 2
+XB_ISA_ITERS_MAX = 64
 
 # every symbol include/bader_hip.h declares: (restype, argtypes)
 _vp, _i64, _dbl, _int = C.c_void_p, C.c_int64, C.c_double, C.c_int
@@ -181,6 +185,11 @@ SYMBOLS = {
     'xb_hirshfeld_release': (_int, [_vp]),
     'xb_hirshfeld_sum': (_int, [_vp, _dbl, _int, _pdbl, _pdbl, _pdbl, _pi64]),
     'xb_hirshfeld_field': (_int, [_vp, _int, _int, _vp, _vp]),
+    'xb_isa_setup': (_int, [_vp, _pdbl, _pdbl, _i64, _pdbl, _i64, _pdbl, _dbl, _pi64]),
+    'xb_isa_iterate': (_int, [_vp, _i64, _int, _pi64, _pi64]),
+    'xb_isa_tables': (_int, [_vp, _pdbl, _pi64]),
+    'xb_isa_load': (_int, [_vp, _pdbl]),
+    'xb_isa_rho_bound': (_int, [_vp, _pdbl]),
     'xb_volume_assign': (_int, [_vp, _vp, _i64]),
     'xb_atom_assign': (_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp]),
     'xb_surface_distance': (_int, [_vp, _vp, _vp, _i64, _vp, _pi64]),
@@ -1181,6 +1190,59 @@ class Context:
         out = np.empty(self.shape or (0,), np.float64)
         check(self.lib.xb_hirshfeld_field(self.h, int(mode), flags, _ptr(out), None))
         return out
+
+    def isa_setup(self, lattice, atoms_cart, r_cut, shells, rho_bound, initial=None):
+        """the cell, the atoms and the starting tables of the iterative stockholder atoms go to the device and the shells are
+        counted (xb_isa_setup; `r_cut` f64[n], `shells` = K, `initial` None or f64[n, K], `rho_bound` >= max |rho|).  It IS the
+        context's Hirshfeld setup: hirshfeld_sum / hirshfeld_field / hirshfeld_release serve it, hirshfeld_setup replaces it.
+        -> {'e', 'cmax', 'pairs', 'empty_shells'}"""
+        lat, at = _f64(lattice).reshape(9), _f64(atoms_cart).reshape(-1, 3)
+        rc = _f64(r_cut).reshape(-1)
+        self.hirshfeld_key = None   # (whatever hirshfeld._setup remembered is no longer what the library holds)
+        if rc.shape[0] != at.shape[0]:
+            raise ValueError(f'isa_setup: r_cut {rc.shape} for atoms {at.shape}')
+        ini = None
+        if initial is not None:
+            ini = _f64(initial)
+            if ini.shape != (at.shape[0], int(shells)):
+                raise ValueError(f'isa_setup: initial tables {ini.shape}, ({at.shape[0]}, {int(shells)}) is wanted')
+        info = (C.c_int64 * 4)()
+        check(self.lib.xb_isa_setup(self.h, lat.ctypes.data_as(_pdbl), at.ctypes.data_as(_pdbl), at.shape[0], rc.ctypes.data_as(_pdbl),
+                                    int(shells), None if ini is None else ini.ctypes.data_as(_pdbl), float(rho_bound), info))
+        self._hirshfeld_atoms = at.shape[0]
+        self._isa_shells = int(shells)
+        return dict(zip(('e', 'cmax', 'pairs', 'empty_shells'), (int(v) for v in info)))
+
+    def isa_iterate(self, iters=1, direct=False, full_search=False):
+        """`iters` iterations of the setup's tables on the resident density, one host wait (xb_isa_iterate) ->
+        (qsum i64[iters, n]: every iteration's fixed-point charges, {'candidate_tiles', 'full_tiles', 'max_candidates', 'beyond_bound'})"""
+        n = int(getattr(self, '_hirshfeld_atoms', 0))
+        qsum = np.zeros((max(int(iters), 1), max(n, 1)), np.int64)
+        st = (C.c_int64 * 4)()
+        flags = (XB_ISA_DIRECT if direct else 0) | (XB_HIRSHFELD_FULL_SEARCH if full_search else 0)
+        check(self.lib.xb_isa_iterate(self.h, int(iters), flags, qsum.ctypes.data_as(_pi64), st))
+        return qsum[:, :n], dict(zip(('candidate_tiles', 'full_tiles', 'max_candidates', 'beyond_bound'), (int(v) for v in st)))
+
+    def isa_tables(self):
+        """the current tables and the shell counts of the ISA setup (xb_isa_tables) -> (A f64[n, K], count i64[n, K])"""
+        n, K = int(getattr(self, '_hirshfeld_atoms', 0)), int(getattr(self, '_isa_shells', 0))
+        A, count = np.zeros((max(n, 1), max(K, 1))), np.zeros((max(n, 1), max(K, 1)), np.int64)
+        check(self.lib.xb_isa_tables(self.h, A.ctypes.data_as(_pdbl), count.ctypes.data_as(_pi64)))
+        return A[:n, :K], count[:n, :K]
+
+    def isa_load(self, tables):
+        """f64[n, K] replace the current tables of the ISA setup; the counts and the exponent stay (xb_isa_load)"""
+        n, K = int(getattr(self, '_hirshfeld_atoms', 0)), int(getattr(self, '_isa_shells', 0))
+        tab = _f64(tables)
+        if tab.shape != (n, K):
+            raise ValueError(f'isa_load: tables {tab.shape}, ({n}, {K}) is wanted')
+        check(self.lib.xb_isa_load(self.h, tab.ctypes.data_as(_pdbl)))
+
+    def density_absmax(self):
+        """max |rho| of the resident density (xb_isa_rho_bound)"""
+        out = C.c_double()
+        check(self.lib.xb_isa_rho_bound(self.h, C.byref(out)))
+        return float(out.value)
 
     def volume_assign(self, swap):
         self.drop_label_token()

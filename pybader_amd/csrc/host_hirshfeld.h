@@ -9,12 +9,13 @@
 //   then         per species K pairs (f[k], f[k+1] - f[k]) (2 S K; starts at an even word: 16-byte loads)
 //   then         the image list, 4 words per image (q[3], then atom and species as two ints)
 //   then         the results: charge[n], volume[n], the rest's density sum, its voxel count (64-bit), the two statistics words
+//   then         only in an ISA setup (host_isa.h), from the next even word: the second table area, counts, bins, qsum rows, a counter
 // The setup is valid for the shape it was made on (hs_geom records it): xb_set_grid drops it when the shape changes, free_grid with the
 // buffer.  Nothing else the context holds enters it -- not the density, not the labels, not dist_mat.
 
 #define HS_HEAD 16
 
-static void hirshfeld_forget(xb_ctx *c) { c->hs_have = false; }
+static void hirshfeld_forget(xb_ctx *c) { c->hs_have = false; c->hs_isa = false; }
 
 // the inverse of the lattice by cofactors, in the order section 18 writes them (A = the lattice itself); false: det is 0 or not finite
 static bool hs_inverse(const double *lat, double M[3][3]) {
@@ -92,11 +93,14 @@ int xb_hirshfeld_images(const double lattice[9], const double *atoms_cart, const
     return XB_OK;
 }
 
+static int hs_build(xb_ctx *c, const double lattice[9], const double *atoms_cart, const int32_t *species, int64_t n, const double *r_cut,
+                    int64_t S, int64_t K, const std::vector<int> &lo, const std::vector<int> &hi, int64_t count, size_t extra,
+                    size_t *o_extra, const std::vector<double> &pairs);
+
 int xb_hirshfeld_setup(xb_ctx *c, const double lattice[9], const double *atoms_cart, const int32_t *species, int64_t n,
                        const double *tables, const double *r_cut, int64_t n_species, int64_t knots) {
     if (!c) return fail(XB_E_ARG, "xb_hirshfeld_setup: null ctx");
     if (int rc = analysis_ready(c, "xb_hirshfeld_setup", "the weights need", NEED_WHOLE)) return rc;
-    const Grid &g = c->g;
     if (!tables) return fail(XB_E_ARG, "xb_hirshfeld_setup: null argument");
     if (knots < 1) return fail(XB_E_ARG, "xb_hirshfeld_setup: %lld knots", (long long)knots);
     std::vector<int> lo, hi;
@@ -110,13 +114,36 @@ int xb_hirshfeld_setup(xb_ctx *c, const double lattice[9], const double *atoms_c
             if (!std::isfinite(f[k]) || f[k] < 0.) return fail(XB_E_ARG, "xb_hirshfeld_setup: table %lld holds %g at knot %lld", (long long)s, f[k], (long long)k);
         if (f[K] != 0.) return fail(XB_E_ARG, "xb_hirshfeld_setup: table %lld ends with %g, not with 0", (long long)s, f[K]);
     }
+    std::vector<double> pairs(2 * (size_t)S * K);
+    for (int64_t s = 0; s < S; s++) {
+        const double *f = tables + s * (K + 1);
+        for (int64_t k = 0; k < K; k++) {
+            pairs[2 * (s * K + k)] = f[k];
+            pairs[2 * (s * K + k) + 1] = f[k + 1] - f[k];
+        }
+    }
+    return hs_build(c, lattice, atoms_cart, species, n, r_cut, S, K, lo, hi, count, 0, nullptr, pairs);
+}
+
+// the checked arguments become the setup: the block is sized (`extra` more doubles behind the results, from the even word
+// *o_extra on: xb_isa_setup's), filled and its geometry recorded.  pairs: per species the K table pairs
+static int hs_build(xb_ctx *c, const double lattice[9], const double *atoms_cart, const int32_t *species, int64_t n, const double *r_cut,
+                    int64_t S, int64_t K, const std::vector<int> &lo, const std::vector<int> &hi, int64_t count, size_t extra,
+                    size_t *o_extra, const std::vector<double> &pairs) {
+    const Grid &g = c->g;
     HIPCHK(hipSetDevice(c->device));
-    c->hs_have = false;   // (whatever fails from here on leaves no setup behind)
+    hirshfeld_forget(c);   // (whatever fails from here on leaves no setup behind)
     HIPCHK(hipDeviceGetAttribute(&c->hs_cus, hipDeviceAttributeMultiprocessorCount, c->device));
     const size_t len = (size_t)g.nx + g.ny + g.nz;
     size_t o_tab = HS_HEAD, o_sp = o_tab + 3 * len, o_pairs = o_sp + 3 * (size_t)S;
     o_pairs += o_pairs & 1;
-    const size_t o_img = o_pairs + 2 * (size_t)S * K, o_acc = o_img + 4 * (size_t)count, want = o_acc + 2 * (size_t)n + 3;
+    const size_t o_img = o_pairs + 2 * (size_t)S * K, o_acc = o_img + 4 * (size_t)count;
+    size_t want = o_acc + 2 * (size_t)n + 3;
+    if (extra) {
+        want += want & 1;
+        *o_extra = want;
+        want += extra;
+    }
     if (int rc = reserve(c, BLK_HS, want * sizeof(double))) return rc;
     // the host image of everything but the position table and the results
     std::vector<double> host(o_acc, 0.);
@@ -124,12 +151,8 @@ int xb_hirshfeld_setup(xb_ctx *c, const double lattice[9], const double *atoms_c
     for (int64_t s = 0; s < S; s++) {
         const double rc2 = r_cut[s] * r_cut[s];
         host[o_sp + 3 * s] = r_cut[s]; host[o_sp + 3 * s + 1] = rc2; host[o_sp + 3 * s + 2] = (double)K / rc2;
-        const double *f = tables + s * (K + 1);
-        for (int64_t k = 0; k < K; k++) {
-            host[o_pairs + 2 * (s * K + k)] = f[k];
-            host[o_pairs + 2 * (s * K + k) + 1] = f[k + 1] - f[k];
-        }
     }
+    std::copy(pairs.begin(), pairs.end(), host.begin() + o_pairs);
     static_assert(sizeof(HsImage) == 4 * sizeof(double), "an image is four words of the buffer");
     HsImage *im = reinterpret_cast<HsImage *>(host.data() + o_img);
     for (int64_t a = 0; a < n; a++)

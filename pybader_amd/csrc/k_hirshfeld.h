@@ -104,106 +104,84 @@ __device__ __forceinline__ bool hs_close_run(const HsVox &V, double pa_, double 
     return true;
 }
 
-// acc (HS_SUM): charge[n], then volume[n], then the rest's density sum; restn: its voxel count.  out (HS_PRO, HS_DEF): N doubles.
-// stats: [0] tiles answered by the full search, [1] the largest candidate count (both untouched when `forced`)
-template <int MODE>
-__global__ __launch_bounds__(256, MODE == HS_SUM ? HS_SUM_WAVES : 8) void k_hirshfeld(HsGeom G, const double *__restrict__ rho, int forced, int n_atoms,
-                                                   double *__restrict__ acc, unsigned long long *__restrict__ restn,
-                                                   double *__restrict__ out, unsigned int *stats) {
-    __shared__ HsCand s_cand[XB_HIRSHFELD_CAND_MAX];
-    __shared__ double s_binc[MODE == HS_SUM ? XB_HIRSHFELD_CAND_MAX : 1], s_binv[MODE == HS_SUM ? XB_HIRSHFELD_CAND_MAX : 1];
-    __shared__ int s_bina[MODE == HS_SUM ? XB_HIRSHFELD_CAND_MAX : 1];
-    __shared__ double s_rest;
-    __shared__ unsigned int s_restn;
-    __shared__ unsigned int s_wcnt[2][4];
+// phase 1 of one tile (every thread of the workgroup calls it: its barriers are uniform): the survivors of the image list, compacted
+// in list order into s_cand; -> how many survive (more than the cap: the list holds the first XB_HIRSHFELD_CAND_MAX and is not used)
+__device__ __forceinline__ unsigned int hs_candidates(const HsGeom &G, int x0, int y0, int z0, HsCand *s_cand, unsigned int (*s_wcnt)[4],
+                                                      unsigned int *stats) {
     const int tid = threadIdx.x, lane = tid % XB_WAVE, wave = tid / XB_WAVE;
-    if (MODE == HS_SUM) {
-        s_binc[tid] = 0.; s_binv[tid] = 0.;
-        if (tid == 0) { s_rest = 0.; s_restn = 0u; }
-    }
-    static_assert(XB_HIRSHFELD_CAND_MAX == 256, "a bin per thread");
-    // few atoms: a bin per ATOM, kept over all the tiles of this workgroup and flushed once; more: a bin per slot of the tile's list
-    const bool by_atom = n_atoms <= XB_HIRSHFELD_CAND_MAX;
-    const int ntiles = G.ntx * G.nty * G.ntz;
-    for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-    int t = tile;
-    const int tz = t % G.ntz; t /= G.ntz;
-    const int ty = t % G.nty;
-    const int tx = t / G.nty;
-    const int x0 = tx * HS_TILE, y0 = ty * HS_TILE, z0 = tz * HS_TILE;
     unsigned int cnt = 0;
-    if (!forced) {
-        // the clipped extent of the tile, in steps; its centre and circumradius (k_voronoi's expressions)
-        const double ex = (double)(min(HS_TILE, G.nx - x0) - 1), ey = (double)(min(HS_TILE, G.ny - y0) - 1),
-                     ez = (double)(min(HS_TILE, G.nz - z0) - 1);
-        const double fx = (double)x0 + 0.5 * ex, fy = (double)y0 + 0.5 * ey, fz = (double)z0 + 0.5 * ez;
-        double c[3], diag2 = 0.;
-        double u[3][3];
+    // the clipped extent of the tile, in steps; its centre and circumradius (k_voronoi's expressions)
+    const double ex = (double)(min(HS_TILE, G.nx - x0) - 1), ey = (double)(min(HS_TILE, G.ny - y0) - 1),
+                 ez = (double)(min(HS_TILE, G.nz - z0) - 1);
+    const double fx = (double)x0 + 0.5 * ex, fy = (double)y0 + 0.5 * ey, fz = (double)z0 + 0.5 * ez;
+    double c[3], diag2 = 0.;
+    double u[3][3];
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+        c[j] = G.lat[j] * fx / (double)G.nx;
+        c[j] += G.lat[3 + j] * fy / (double)G.ny;
+        c[j] += G.lat[6 + j] * fz / (double)G.nz;
+        u[0][j] = G.lat[j] * ex / (double)G.nx;
+        u[1][j] = G.lat[3 + j] * ey / (double)G.ny;
+        u[2][j] = G.lat[6 + j] * ez / (double)G.nz;
+    }
+#pragma unroll
+    for (int s = 0; s < 4; s++) {
+        const double s1 = (s & 1) ? -1. : 1., s2 = (s & 2) ? -1. : 1.;
+        double d2 = 0.;
 #pragma unroll
         for (int j = 0; j < 3; j++) {
-            c[j] = G.lat[j] * fx / (double)G.nx;
-            c[j] += G.lat[3 + j] * fy / (double)G.ny;
-            c[j] += G.lat[6 + j] * fz / (double)G.nz;
-            u[0][j] = G.lat[j] * ex / (double)G.nx;
-            u[1][j] = G.lat[3 + j] * ey / (double)G.ny;
-            u[2][j] = G.lat[6 + j] * ez / (double)G.nz;
+            const double d = (u[0][j] + s1 * u[1][j]) + s2 * u[2][j];
+            d2 += d * d;
         }
-#pragma unroll
-        for (int s = 0; s < 4; s++) {
-            const double s1 = (s & 1) ? -1. : 1., s2 = (s & 2) ? -1. : 1.;
-            double d2 = 0.;
-#pragma unroll
-            for (int j = 0; j < 3; j++) {
-                const double d = (u[0][j] + s1 * u[1][j]) + s2 * u[2][j];
-                d2 += d * d;
-            }
-            diag2 = fmax(diag2, d2);
-        }
-        const double R = 0.5 * sqrt(diag2);
-        // keep and compact in the list's order (every thread runs every round: the barrier is uniform; n_img + 256 fits 32 bits)
-        int flip = 0;
-        for (unsigned int base = 0; base < G.n_img; base += 256u, flip ^= 1) {
-            const unsigned int idx = base + tid;
-            bool keep = false;
-            HsImage im = {};
-            double rc2 = 0., ih2 = 0.;
-            if (idx < G.n_img) {
-                im = G.img[idx];
-                const double *sp = G.sp + 3 * (size_t)im.s;
-                double lim = sp[0] + R;
-                lim += 0x1p-40 * (lim + G.len);
-                double lim2 = lim * lim;
-                lim2 += 0x1p-40 * lim2;
-                rc2 = sp[1]; ih2 = sp[2];
-                const double e0 = c[0] - im.q[0], e1 = c[1] - im.q[1], e2 = c[2] - im.q[2];
-                keep = (e0 * e0 + e1 * e1) + e2 * e2 <= lim2;
-            }
-            const unsigned long long mask = __ballot(keep);
-            if (lane == 0) s_wcnt[flip][wave] = (unsigned int)__popcll(mask);
-            __syncthreads();
-            const unsigned int w0 = s_wcnt[flip][0], w1 = s_wcnt[flip][1], w2 = s_wcnt[flip][2], w3 = s_wcnt[flip][3];
-            const unsigned int before = wave == 0 ? 0u : (wave == 1 ? w0 : (wave == 2 ? w0 + w1 : w0 + w1 + w2));
-            const unsigned int slot = cnt + before + (unsigned int)__popcll(mask & ((1ull << lane) - 1ull));
-            if (keep && slot < (unsigned int)XB_HIRSHFELD_CAND_MAX) {
-                HsCand &d = s_cand[slot];
-                d.q[0] = im.q[0]; d.q[1] = im.q[1]; d.q[2] = im.q[2];
-                d.rc2 = rc2; d.ih2 = ih2; d.a = im.a; d.s = im.s;
-            }
-            cnt += (w0 + w1) + (w2 + w3);
-        }
-        if (tid == 0) {
-            if (cnt > *(volatile unsigned int *)&stats[1]) atomicMax(&stats[1], cnt);
-            if (cnt > (unsigned int)XB_HIRSHFELD_CAND_MAX) atomicAdd(&stats[0], 1u);
-        }
+        diag2 = fmax(diag2, d2);
     }
-    __syncthreads();   // the candidates and the cleared bins
-    const bool full = forced || cnt > (unsigned int)XB_HIRSHFELD_CAND_MAX;
-    // phase 2: this thread's two voxels (indices clamped into the grid; a voxel outside it is neither stored nor summed)
+    const double R = 0.5 * sqrt(diag2);
+    // keep and compact in the list's order (every thread runs every round: the barrier is uniform; n_img + 256 fits 32 bits)
+    int flip = 0;
+    for (unsigned int base = 0; base < G.n_img; base += 256u, flip ^= 1) {
+        const unsigned int idx = base + tid;
+        bool keep = false;
+        HsImage im = {};
+        double rc2 = 0., ih2 = 0.;
+        if (idx < G.n_img) {
+            im = G.img[idx];
+            const double *sp = G.sp + 3 * (size_t)im.s;
+            double lim = sp[0] + R;
+            lim += 0x1p-40 * (lim + G.len);
+            double lim2 = lim * lim;
+            lim2 += 0x1p-40 * lim2;
+            rc2 = sp[1]; ih2 = sp[2];
+            const double e0 = c[0] - im.q[0], e1 = c[1] - im.q[1], e2 = c[2] - im.q[2];
+            keep = (e0 * e0 + e1 * e1) + e2 * e2 <= lim2;
+        }
+        const unsigned long long mask = __ballot(keep);
+        if (lane == 0) s_wcnt[flip][wave] = (unsigned int)__popcll(mask);
+        __syncthreads();
+        const unsigned int w0 = s_wcnt[flip][0], w1 = s_wcnt[flip][1], w2 = s_wcnt[flip][2], w3 = s_wcnt[flip][3];
+        const unsigned int before = wave == 0 ? 0u : (wave == 1 ? w0 : (wave == 2 ? w0 + w1 : w0 + w1 + w2));
+        const unsigned int slot = cnt + before + (unsigned int)__popcll(mask & ((1ull << lane) - 1ull));
+        if (keep && slot < (unsigned int)XB_HIRSHFELD_CAND_MAX) {
+            HsCand &d = s_cand[slot];
+            d.q[0] = im.q[0]; d.q[1] = im.q[1]; d.q[2] = im.q[2];
+            d.rc2 = rc2; d.ih2 = ih2; d.a = im.a; d.s = im.s;
+        }
+        cnt += (w0 + w1) + (w2 + w3);
+    }
+    if (tid == 0) {
+        if (cnt > *(volatile unsigned int *)&stats[1]) atomicMax(&stats[1], cnt);
+        if (cnt > (unsigned int)XB_HIRSHFELD_CAND_MAX) atomicAdd(&stats[0], 1u);
+    }
+    return cnt;
+}
+
+// phase 2 begins: the positions of this thread's two voxels of the tile at (x0, y0, z0), whether the grid holds them, their indices
+__device__ __forceinline__ void hs_voxels(const HsGeom &G, int x0, int y0, int z0, HsVox &V, size_t &va, size_t &vb) {
+    const int lane = threadIdx.x % XB_WAVE, wave = threadIdx.x / XB_WAVE;
     const int len = G.nx + G.ny + G.nz;
     const int py = y0 + lane / HS_TILE, pz = z0 + lane % HS_TILE;
     const int pxa = x0 + wave, pxb = x0 + wave + 4;
     const int cy = min(py, G.ny - 1), cz = min(pz, G.nz - 1), cxa = min(pxa, G.nx - 1), cxb = min(pxb, G.nx - 1);
-    HsVox V;
 #pragma unroll
     for (int j = 0; j < 3; j++) {
         const double *tj = G.tab + (size_t)j * len;
@@ -217,8 +195,11 @@ __global__ __launch_bounds__(256, MODE == HS_SUM ? HS_SUM_WAVES : 8) void k_hirs
     V.oka = py < G.ny && pz < G.nz && pxa < G.nx;
     V.okb = py < G.ny && pz < G.nz && pxb < G.nx;
     const size_t row = (size_t)cy * G.nz + cz, plane = (size_t)G.ny * G.nz;
-    const size_t va = (size_t)cxa * plane + row, vb = (size_t)cxb * plane + row;
-    // pass 1: P
+    va = (size_t)cxa * plane + row; vb = (size_t)cxb * plane + row;
+}
+
+// pass 1: P of the two voxels, over the tile's candidates in order or (full) over the whole list
+__device__ __forceinline__ void hs_total(const HsGeom &G, HsVox &V, const HsCand *s_cand, unsigned int cnt, bool full) {
     V.Pa = 0.; V.Pb = 0.;
     if (!full) {
 #pragma unroll 2
@@ -239,6 +220,43 @@ __global__ __launch_bounds__(256, MODE == HS_SUM ? HS_SUM_WAVES : 8) void k_hirs
             V.Pb += hs_term(V.pb, im.q[0], im.q[1], im.q[2], rc2, ih2, pr, G.K);
         }
     }
+}
+
+// acc (HS_SUM): charge[n], then volume[n], then the rest's density sum; restn: its voxel count.  out (HS_PRO, HS_DEF): N doubles.
+// stats: [0] tiles answered by the full search, [1] the largest candidate count (both untouched when `forced`)
+template <int MODE>
+__global__ __launch_bounds__(256, MODE == HS_SUM ? HS_SUM_WAVES : 8) void k_hirshfeld(HsGeom G, const double *__restrict__ rho, int forced, int n_atoms,
+                                                   double *__restrict__ acc, unsigned long long *__restrict__ restn,
+                                                   double *__restrict__ out, unsigned int *stats) {
+    __shared__ HsCand s_cand[XB_HIRSHFELD_CAND_MAX];
+    __shared__ double s_binc[MODE == HS_SUM ? XB_HIRSHFELD_CAND_MAX : 1], s_binv[MODE == HS_SUM ? XB_HIRSHFELD_CAND_MAX : 1];
+    __shared__ int s_bina[MODE == HS_SUM ? XB_HIRSHFELD_CAND_MAX : 1];
+    __shared__ double s_rest;
+    __shared__ unsigned int s_restn;
+    __shared__ unsigned int s_wcnt[2][4];
+    const int tid = threadIdx.x, lane = tid % XB_WAVE;
+    if (MODE == HS_SUM) {
+        s_binc[tid] = 0.; s_binv[tid] = 0.;
+        if (tid == 0) { s_rest = 0.; s_restn = 0u; }
+    }
+    static_assert(XB_HIRSHFELD_CAND_MAX == 256, "a bin per thread");
+    // few atoms: a bin per ATOM, kept over all the tiles of this workgroup and flushed once; more: a bin per slot of the tile's list
+    const bool by_atom = n_atoms <= XB_HIRSHFELD_CAND_MAX;
+    const int ntiles = G.ntx * G.nty * G.ntz;
+    for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    int t = tile;
+    const int tz = t % G.ntz; t /= G.ntz;
+    const int ty = t % G.nty;
+    const int tx = t / G.nty;
+    const int x0 = tx * HS_TILE, y0 = ty * HS_TILE, z0 = tz * HS_TILE;
+    const unsigned int cnt = forced ? 0u : hs_candidates(G, x0, y0, z0, s_cand, s_wcnt, stats);
+    __syncthreads();   // the candidates and the cleared bins
+    const bool full = forced || cnt > (unsigned int)XB_HIRSHFELD_CAND_MAX;
+    // phase 2: this thread's two voxels (indices clamped into the grid; a voxel outside it is neither stored nor summed)
+    HsVox V;
+    size_t va, vb;
+    hs_voxels(G, x0, y0, z0, V, va, vb);
+    hs_total(G, V, s_cand, cnt, full);   // pass 1: P
     if (MODE != HS_SUM) {
         if (V.oka) out[va] = MODE == HS_PRO ? V.Pa : rho[va] - V.Pa;
         if (V.okb) out[vb] = MODE == HS_PRO ? V.Pb : rho[vb] - V.Pb;
