@@ -4,6 +4,9 @@ comparison of a result with it, for tests that run the calls one after another o
 Every expectation comes from what the feature's own test file imports (the oracle, or that file's numpy restatement) and every
 comparison is the one that file makes: `==` (or equal bits) where it compares so, its rounding bound with its arguments elsewhere.
 Nothing is restated a second time and no tolerance is new.  Expectations are memoised on (kind, grid, the inputs the kind reads).
+The Hirshfeld, ISA, NCI, isosurface and regions kinds stand on tests/test_hirshfeld_cpu.py, test_isa_cpu.py, test_nci_cpu.py,
+test_isosurface_cpu.py and test_regions_cpu.py, which also hold the comparisons their GPU files make (check_s, check_sums,
+first_difference, sums_difference, ...): those files import tests/test_gpu_history.py, so the helpers cannot live there.
 
     GRIDS, density(grid, name), labels(grid, name), n_of(grid, name)   the inputs
     KINDS                                                               call kind -> (reads the density, reads the map)
@@ -17,14 +20,20 @@ import random
 import numpy as np
 
 import oracle
+import test_hirshfeld_cpu as THS
+import test_isa_cpu as TISA
+import test_isosurface_cpu as TISO
+import test_nci_cpu as TN
+import test_regions_cpu as TR
 from oracle_context import OracleContext
-from pybader_amd import synth
+from pybader_amd import isa, synth
 from pybader_amd.adjacency import active_directions
 from pybader_amd.interface import distance_matrix, gradient_transform
 from pybader_amd.weight import voronoi_weights
 from rough_common import own_map, rank_labels
 from test_adjacency_cpu import reference_adjacency
 from test_critical_cpu import noise_labels, reference_bonds, reference_points
+from test_gpu_isa import restated_sums as isa_sums
 from test_gpu_sums import bound as sum_bound_any_order
 from test_gpu_sums import grouped as sum_grouped
 from test_gpu_sums import swapped
@@ -55,6 +64,12 @@ SWAP = np.array([2, 0, 3, 1], np.int64)                 # volume_assign: labels 
 MASK_LABEL = 1
 N_POINTS = 24
 REFINE_MODE = ('changed', -1)
+SPECIES = np.arange(3, dtype=np.int32)                  # Hirshfeld: a pro-atom per atom
+PRO_R_CUT, PRO_KNOTS = 2.5, 256
+ISA = dict(r_cut=2.5, shells=8, tol=0.0, max_iter=5, check_every=2)        # three library calls: 2 + 2 + 1 iterations
+NCI_CUTS, NCI_EDGES = TN.HISTORY_CUTS, TN.HISTORY_EDGES
+ISO_QUANTILE = 0.7
+FIELD_LEVEL = 0.0                                       # the *_of_field kinds: the zero envelope of the other density's Laplacian
 
 
 def shape_of(grid):
@@ -214,9 +229,18 @@ KINDS = {
     'critical': (True, False), 'critical_flood': (True, False), 'critical_vacuum': (True, False), 'critical_flood_vacuum': (True, False),
     'bond_graph': (True, True),
     'laplacian': (True, False), 'laplacian_gather': (True, False), 'basin_laplacian': (True, True), 'point_properties': (True, False),
+    'hirshfeld_charges': (True, False), 'hirshfeld_charges_full': (True, False), 'promolecule': (False, False), 'deformation': (True, False),
+    'isa_charges': (True, False), 'isa_charges_direct': (True, False), 'isa_residual': (True, False),
+    'nci_fields': (True, False), 'nci_fields_gather': (True, False), 'nci_regions': (True, True), 'nci_histogram': (True, False),
+    'nci_domains': (True, True),
+    'isosurface': (True, True), 'isosurface_gather': (True, True), 'isosurface_of_field': (True, True),
+    'regions': (True, True), 'regions_below': (True, True), 'regions_global': (True, True), 'regions_of_field': (True, True),
 }
 # surface_distance takes the density and its result does not depend on it (the edge voxels are the map's).
-# voronoi_assign without a tolerance reads no density: its second input is the atom set, which goes with the density's name
+# voronoi_assign without a tolerance reads no density: its second input is the atom set, which goes with the density's name;
+# so do the atoms and pro-atoms of the Hirshfeld kinds and the atoms of the ISA kinds (promolecule reads nothing else).
+# The *_of_field kinds take the Laplacian of other(density name) as a host field beside the density: the mesh and the members
+# come from that field, the volumes' shares from the map, top and the sums from the density, which must stay the resident one
 LABEL_WRITERS = ('voronoi', 'voronoi_full', 'voronoi_vacuum', 'voronoi_full_vacuum', 'volume_assign')
 
 
@@ -238,9 +262,9 @@ def maxima_for(grid, mname):
 def _key(kind, grid, dname, mname):
     reads_d, reads_m = KINDS[kind]
     mname = map_for(kind, mname)
-    if kind in ('voronoi', 'voronoi_full'):
+    if kind in ('voronoi', 'voronoi_full', 'promolecule'):
         dname = 'B' if dname.startswith('B') else 'A'
-    return kind, grid, dname if reads_d else None, mname if reads_m else None
+    return kind, grid, dname if reads_d or kind == 'promolecule' else None, mname if reads_m else None
 
 
 def expect(kind, grid, dname, mname):
@@ -252,6 +276,70 @@ def _laplacian(grid, dname):
     lap = restated_laplacian(density(grid, dname), LAT)
     lap.flags.writeable = False
     return lap
+
+
+def atoms_of(dname):
+    return 'B' if dname.startswith('B') else 'A'
+
+
+@functools.lru_cache(maxsize=None)
+def proatoms(which):
+    return THS.synth_proatoms({'A': ATOMS_A, 'B': ATOMS_B}[which], PRO_R_CUT, PRO_KNOTS)
+
+
+@functools.lru_cache(maxsize=None)
+def _promolecule(grid, which):
+    """(P, p) of test_hirshfeld_cpu.restate for the atoms and pro-atoms `which` on a grid"""
+    P, p = THS.restate(GRIDS[grid], LAT, SITES[which], SPECIES, proatoms(which))
+    P.flags.writeable = False
+    p.flags.writeable = False
+    return P, p
+
+
+@functools.lru_cache(maxsize=None)
+def _isa(grid, dname):
+    """the ISA run of a density restated by tests/test_isa_cpu.py: geometry, exponent, the qsum rows and the tables after each of
+    the iterations -> (g, e, rows, tables after the last, max |rho|)"""
+    rho = density(grid, dname)
+    g = _isa_geometry(grid, atoms_of(dname))
+    bound = float(np.max(np.abs(rho)))
+    e = TISA.exponent(bound, g.count.max())
+    rows, tabs = TISA.run(g, rho.reshape(-1), e, ISA['max_iter'])
+    tabs[-1].flags.writeable = False
+    return g, e, rows, tabs[-1], bound
+
+
+@functools.lru_cache(maxsize=None)
+def _isa_geometry(grid, which):
+    return TISA.geometry(GRIDS[grid], LAT, SITES[which], ISA['r_cut'], ISA['shells'])
+
+
+def isa_result(grid, dname):
+    """an IsaResult with the restated tables (no GPU run made it): what isa_residual is handed"""
+    _, _, _, tables, bound = _isa(grid, dname)
+    return isa.IsaResult(tables=tables, r_cut=np.full(3, ISA['r_cut']), shells=ISA['shells'], rho_bound=bound)
+
+
+@functools.lru_cache(maxsize=None)
+def _nci(grid, dname):
+    return TN.restated(density(grid, dname), LAT)
+
+
+def iso_level(grid, dname):
+    return float(np.quantile(density(grid, dname), ISO_QUANTILE))
+
+
+def field_of(grid, dname):
+    """the second field of the *_of_field kinds: the Laplacian of the other density of the grid, a host array"""
+    return _laplacian(grid, other(dname))
+
+
+def _components(mask, rho, lab, n):
+    """the expectation of the regions kinds and of nci_domains from test_regions_cpu's restatement"""
+    reg, seeds = TR.components(mask)
+    count, top, terms = TR.per_component(reg, seeds.size, rho)
+    return {'reg': reg, 'seeds': seeds, 'count': count, 'top': top, 's1': TR.sums(terms)[0], 's2': TR.sums([t * t for t in terms])[0],
+            'shares': TR.shares(reg, lab, n), 'rho': rho}
 
 
 @functools.lru_cache(maxsize=None)
@@ -316,6 +404,42 @@ def _expect(kind, grid, dname, mname):
     if kind == 'point_properties':
         lin = point_list(grid)
         return restated_points(rho, LAT, lin), _laplacian(grid, dname).reshape(-1)[lin]
+    if kind.startswith('hirshfeld_charges'):
+        return THS.restated_sums(rho, *_promolecule(grid, atoms_of(dname)))
+    if kind == 'promolecule':
+        return (_promolecule(grid, dname)[0].reshape(shape),)
+    if kind == 'deformation':
+        return ((rho.reshape(-1) - _promolecule(grid, atoms_of(dname))[0]).reshape(shape),)
+    if kind.startswith('isa_charges'):
+        g, e, rows, tables, _ = _isa(grid, dname)
+        return e, rows, tables, isa_sums(g, rho, tables)
+    if kind == 'isa_residual':
+        g, _, _, tables, _ = _isa(grid, dname)
+        return ((rho.reshape(-1) - TISA.total(g, tables)).reshape(shape),)
+    if kind.startswith('nci_fields'):
+        return (_nci(grid, dname),)
+    if kind == 'nci_regions':
+        return TN.sum_reference(_nci(grid, dname), lab, n, NCI_CUTS)
+    if kind == 'nci_histogram':
+        return (TN.histogram(_nci(grid, dname), *NCI_EDGES),)
+    if kind == 'nci_domains':
+        v = _nci(grid, dname)
+        mask = TN.region(v, *NCI_CUTS[:2])
+        out = _components(mask, rho, lab, n)
+        cls = np.where(mask, TN.classes(v, NCI_CUTS[2]), -1)
+        out['class_count'] = np.stack([np.bincount(out['reg'][cls == k], minlength=out['seeds'].size) for k in range(3)], axis=1).astype(np.int64)
+        out['kind'] = cls.reshape(-1)[out['top']].astype(np.int8)
+        return out
+    if kind in ('isosurface', 'isosurface_gather'):
+        return TISO.restate(rho, iso_level(grid, dname), LAT, TISO.colour_field(shape), lab, n)
+    if kind == 'isosurface_of_field':
+        return TISO.restate(field_of(grid, dname), FIELD_LEVEL, LAT, TISO.colour_field(shape), lab, n)
+    if kind in ('regions', 'regions_global'):
+        return _components(rho >= TR.sum_level(rho), rho, lab, n)
+    if kind == 'regions_below':
+        return _components(rho < TR.sum_level(rho), rho, lab, n)
+    if kind == 'regions_of_field':
+        return _components(field_of(grid, dname) >= FIELD_LEVEL, rho, lab, n)
     raise KeyError(kind)
 
 
@@ -417,6 +541,51 @@ def _compare(kind, got, want, grid, dname, mname):
         return msg
     if kind == 'point_properties':                                # test_gpu_laplacian: equal bits
         return _first('the ten values', got[0], want[0], True) or _first('laplacian', got[1], want[1], True)
+    if kind.startswith('hirshfeld_charges'):                      # test_gpu_hirshfeld.check_sums
+        s = want
+        return (_within('charge', got[0], s['charge'] * VV, THS.sum_bound(s['count'], s['charge_mag'], VV))
+                or _within('volume', got[1], s['volume'] * VV, THS.sum_bound(s['count'], s['volume_mag'], VV))
+                or _within('the rest\'s charge', got[2][:1], [s['rest'][0] * VV], THS.sum_bound(s['rest'][1], s['rest_mag'], VV))
+                or _first('the rest\'s volume', got[2][1:], [s['rest'][1] * VV]))
+    if kind in ('promolecule', 'deformation', 'isa_residual'):    # test_gpu_hirshfeld / test_gpu_isa.same_bits
+        return _first('field', got[0], want[0], bits=True)
+    if kind.startswith('isa_charges'):                            # test_gpu_isa.test_isa_then_hirshfeld_then_isa, check_sums
+        e, rows, tables, s = want
+        history, got_tables, charge, volume, rest = got
+        return (_first('history', history, rows.astype(np.float64) * (2.0 ** -e * VV)) or _first('tables', got_tables, tables, bits=True)
+                or _within('charge', charge, s['charge'] * VV, THS.sum_bound(s['count'], s['charge_mag'], VV))
+                or _within('volume', volume, s['volume'] * VV, THS.sum_bound(s['count'], s['volume_mag'], VV))
+                or _within('the rest\'s charge', rest[:1], [s['rest'][0] * VV], THS.sum_bound(s['rest'][1], s['rest_mag'], VV))
+                or _first('the rest\'s volume', rest[1:], [s['rest'][1] * VV]))
+    if kind.startswith('nci_fields'):                             # test_gpu_nci: x in equal bits, s within S_REL
+        if np.shape(got[0]) != GRIDS[grid] or np.shape(got[1]) != GRIDS[grid]:
+            return f'fields of shape {np.shape(got[0])}, {np.shape(got[1])}'
+        return TN.fields_difference(np.asarray(got[0]), np.asarray(got[1]), want[0], 'fields')
+    if kind == 'nci_regions':
+        cnt = want[0][1]
+        if any(np.shape(a) != (cnt.size // 3, 3) for a in got):
+            return f'sums of shape {np.shape(got[0])}, expected {(cnt.size // 3, 3)}'
+        return TN.regions_difference(*got, want, 'regions')
+    if kind == 'nci_histogram':
+        return TN.histogram_difference(np.asarray(got[0]), want[0], 'histogram')
+    if kind == 'nci_domains' or kind.startswith('regions'):       # test_gpu_regions.regions_call
+        m, reg, seed, count, top, s1, s2, shares = got[:8]
+        least = 2 if kind in ('nci_domains', 'regions', 'regions_global') else 1      # (below the level and on the field: one piece)
+        if m != want['seeds'].size or want['seeds'].size < least or not np.array_equal(reg, want['reg']):
+            return 'the map differs'
+        try:
+            TR.check_sums(kind, (seed, count, top, s1, s2), want['reg'], want['seeds'], want['rho'], VV)
+        except AssertionError as e:
+            return str(e)
+        if not all(np.array_equal(g, w) for g, w in zip(shares, want['shares'])) or want['shares'][2].sum() < 50:
+            return 'the shares differ'
+        if kind == 'nci_domains':                                 # test_gpu_regions.check_domains: the classes' counts, the kinds
+            return _first('count per class', got[8], want['class_count']) or _first('kind', got[9], want['kind'])
+        return None
+    if kind.startswith('isosurface'):                             # test_gpu_isosurface: first_difference, then sums_difference
+        if np.shape(got[7]) != want.volume_by_label.shape:
+            return f'volume_by_label of shape {np.shape(got[7])}, expected {want.volume_by_label.shape}'
+        return TISO.first_difference(got, want, 'mesh') or TISO.sums_difference(got, want, 'mesh')
     raise KeyError(kind)
 
 
@@ -447,15 +616,32 @@ def as_result(kind, want, grid):
         return w['root'], w['merge_round'], w['merge_persistence'], w['rounds'], w['converged'], wmap
     if kind == 'basin_laplacian':
         return want[0] * VV, want[2] * VV, want[1].astype(np.float64) * VV
+    if kind.startswith('hirshfeld_charges'):
+        return want['charge'] * VV, want['volume'] * VV, np.array([want['rest'][0] * VV, want['rest'][1] * VV]), None
+    if kind.startswith('isa_charges'):
+        e, rows, tables, s = want
+        return (rows.astype(np.float64) * (2.0 ** -e * VV), tables, s['charge'] * VV, s['volume'] * VV,
+                np.array([s['rest'][0] * VV, s['rest'][1] * VV]))
+    if kind.startswith('nci_fields'):
+        return want[0]['s'], want[0]['x']
+    if kind == 'nci_regions':
+        (s1, cnt, _), (s2, _, _) = want
+        return cnt.reshape(-1, 3), (s1 * VV).reshape(-1, 3), (s2 * VV).reshape(-1, 3)
+    if kind == 'nci_domains' or kind.startswith('regions'):
+        return ((want['seeds'].size, want['reg'], want['seeds'], want['count'], want['top'], want['s1'] * VV, want['s2'] * VV, want['shares'])
+                + ((want['class_count'], want['kind']) if kind == 'nci_domains' else ()))
+    if kind.startswith('isosurface'):
+        return want.vertices, want.colour, want.triangles, want.wrap, want.cells, want.area, want.volume, want.volume_by_label
     return want
 
 
 # ---- the seeded walks ------------------------------------------------------------------------------------------------------------
 EVENTS = ('shape', 'resident', 'mutate', 'fail')
-FAILURES = ('density of another shape', 'label map of another shape', 'n < 1', 'non-float device dtype')
+FAILURES = ('density of another shape', 'label map of another shape', 'n < 1', 'non-float device dtype',
+            'isa_iterate on a Hirshfeld setup', 'regions_shares without a labelling')
 
 
-def walk(seed, steps=80):
+def walk(seed, steps=140):
     """-> a list of steps, each a dict with 'op':
 
         call      kind, grid, dname, mname: one checked call
@@ -470,10 +656,15 @@ def walk(seed, steps=80):
     kinds = list(KINDS)
     grid, inside, out = 'G1', None, []
     # the kinds whose result shows an edit of a corner block on every input (tests/test_history_cpu.py asserts it for the steps
-    # drawn): the block lies in the tails, where the sparse results -- surfaces, saddles, bond points -- need not pass
+    # drawn): the block lies in the tails, where the sparse results -- surfaces, saddles, bond points -- need not pass.
+    # volume_mask shows a density edit only where the map carries MASK_LABEL in the block (the noise map does not);
+    # isosurface_of_field takes its mesh from the other density's Laplacian and its shares from the map: the density is only kept.
+    # The 0.7 / 0.8 level sets of the density lie at the atoms: a relabelled block in the tails moves no share of theirs on most
+    # inputs (below the level, on the field and in the NCI region the block is inside: those kinds stay)
     reads_d = [k for k in kinds if KINDS[k][0] and k not in ('voronoi', 'voronoi_full', 'adjacency', 'merge', 'critical_vacuum',
-                                                             'critical_flood_vacuum')]
-    reads_m = [k for k in kinds if KINDS[k][1] and k not in ('surface_distance', 'merge', 'bond_graph')]
+                                                             'critical_flood_vacuum', 'volume_mask', 'isosurface_of_field')]
+    reads_m = [k for k in kinds if KINDS[k][1] and k not in ('surface_distance', 'merge', 'bond_graph', 'isosurface', 'isosurface_gather',
+                                                             'regions', 'regions_global')]
     queue = []
     while len(out) < steps:
         r = rng.random()

@@ -6,11 +6,19 @@ buffers kept while the grid's shape stays, the shared scratch -- so here the cal
 order, with and without utils.resident(), over host arrays and device tensors, across grid changes, in-place edits and refused
 calls, and every result is compared with the expectation of tests/history_common.py (the feature's own restatement and bound).
 
-test_every_call_after_every_other   every ordered pair (X, Y) of call kinds on G1, in five settings; one test id per X
-test_seeded_walks                   three seeded walks of about 80 steps over the three grids
-test_a_label_only_call_on_another_grid_inside_resident   the regression case of the defect these tests found
+The kinds (history_common.KINDS): the calls of the reference's pipeline, the weight method, moments, adjacency, merge, Voronoi,
+critical points and bond graph, the Laplacian -- and the five newest analyses: Hirshfeld (hirshfeld_charges, _full, promolecule,
+deformation), ISA (isa_charges, _direct, isa_residual), NCI (nci_fields, _gather, nci_regions, nci_histogram, nci_domains),
+isosurfaces (isosurface, _gather, isosurface_of_field) and connected regions (regions, _below, _global, regions_of_field).  They
+bring the flags "the result is the resident density's" of the mesh and the labelling, the Hirshfeld setup that ISA replaces and
+hirshfeld._setup caches by key, and the calls whose field "becomes the resident density" unless `density=` names it.
 
-Wall time on an MI355X, the whole suite in one process: MEASURED below."""
+test_every_call_after_every_other   every ordered pair (X, Y) of call kinds on G1, in five settings; one test id per X
+test_seeded_walks                   three seeded walks of about 140 steps over the three grids
+test_a_label_only_call_on_another_grid_inside_resident   the regression case of the defect these tests found
+test_a_hirshfeld_setup_replaced_by_isa_and_dropped_with_the_shape_inside_resident   the key of the cached setup across both events
+
+Wall time on an MI355X: MEASURED below."""
 import numpy as np
 import pytest
 try:
@@ -19,13 +27,20 @@ except Exception:  # pragma: no cover
     torch = None
 
 import history_common as H
-from pybader_amd import _lib, adjacency, critical, device, laplacian, merge, multipole, thread_handlers, utils, voronoi, weight
+from pybader_amd import (_lib, adjacency, critical, device, hirshfeld, isa, isosurface, laplacian, merge, multipole, nci, regions,
+                         thread_handlers, utils, voronoi, weight)
+from test_isosurface_cpu import colour_field
 from test_merge_cpu import maxima_of
+from test_regions_cpu import sum_level
 
 pytestmark = pytest.mark.gpu
-MEASURED = ('test_every_call_after_every_other: 0.20 s to 0.62 s per id (weight_other, weight_own 0.6 s; vacuum_assign, the first id, '
-            '0.47 s with the shared restatements); test_seeded_walks: 0.30 s to 0.34 s per seed; the two named cases below 0.05 s.  '
-            'The slowest test of the features\' own files in the same run: test_gpu_adjacency.py::test_adjacency[shape1], 2.15 s.')
+MEASURED = ('this file alone in one process, 47 kinds, about 700 calls per id: test_every_call_after_every_other 0.31 s to 1.49 s per id '
+            '(vacuum_assign, the first id, 1.49 s with the shared restatements; isosurface_of_field 1.18 s, weight_other 0.99 s, weight_own '
+            '0.97 s, isosurface 0.95 s, isosurface_gather 0.86 s, regions_of_field 0.79 s, regions_below 0.75 s, nci_domains 0.74 s; the '
+            'ISA ids 0.32 s to 0.46 s, the Hirshfeld and NCI field ids 0.31 s to 0.33 s); test_seeded_walks 0.89 s, 0.65 s, 0.56 s for '
+            'the seeds 11, 23, 47; the three named cases 0.01 s or less each; 53 tests in 26.2 s (a second run: within 0.2 s per id).  '
+            'The slowest test of the five newer features\' own files in a run of theirs: '
+            'test_gpu_hirshfeld.py::test_sums_are_under_the_bound_through_both_routes[line_more], 1.46 s.')
 
 
 def have_torch():
@@ -148,6 +163,42 @@ class Runner:
             p = laplacian.point_properties(rho, H.LAT, H.point_list(grid))
             ten = np.column_stack([p.rho, p.gradient] + [p.hessian[:, i, j] for i, j in ((0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2))])
             return np.ascontiguousarray(ten), p.laplacian
+        if kind in ('hirshfeld_charges', 'hirshfeld_charges_full', 'promolecule', 'deformation'):
+            atoms = (H.LAT, H.sites_of(dname), H.SPECIES, H.proatoms(H.atoms_of(dname)))
+            if kind.startswith('hirshfeld_charges'):
+                return hirshfeld.hirshfeld_charges(rho, *atoms, H.VV, full_search=kind.endswith('full'))
+            return (host((hirshfeld.promolecule if kind == 'promolecule' else hirshfeld.deformation_density)(rho, *atoms)),)
+        if kind.startswith('isa_charges'):
+            r = isa.isa_charges(rho, H.LAT, H.sites_of(dname), H.VV, direct=kind.endswith('direct'), **H.ISA)
+            return r.history, r.tables, r.charge, r.volume, r.rest
+        if kind == 'isa_residual':
+            return (host(isa.isa_residual(rho, H.LAT, H.sites_of(dname), H.isa_result(grid, dname))),)
+        if kind.startswith('nci_fields'):
+            s, x = nci.nci_fields(rho, H.LAT, gather=kind.endswith('gather'))
+            return host(s), host(x)
+        if kind == 'nci_regions':
+            r = nci.nci_regions(rho, lab, H.LAT, n, H.VV, *H.NCI_CUTS)
+            return r.count, r.charge, r.charge2
+        if kind == 'nci_histogram':
+            return (nci.nci_histogram(rho, H.LAT, *H.NCI_EDGES),)
+        if kind == 'nci_domains':
+            d = nci.nci_domains(rho, H.LAT, lab, n, H.VV, *H.NCI_CUTS)
+            return d.m, host(d.labels), d.seed, d.size, d.top, d.total, d.total2, d.shares, d.count, d.kind
+        if kind.startswith('isosurface'):
+            if kind == 'isosurface_of_field':       # (the field stays a host array in every setting: the scratch upload is the route)
+                m = isosurface.isosurface(H.field_of(grid, dname), H.LAT, H.FIELD_LEVEL, colour=colour_field(shape), volumes=lab, n=n,
+                                          density=rho)
+            else:
+                m = isosurface.isosurface(rho, H.LAT, H.iso_level(grid, dname), colour=colour_field(shape), volumes=lab, n=n,
+                                          gather=kind.endswith('gather'))
+            return m.vertices, m.colour, m.triangles, m.wrap, m.cells, m.area, m.volume, m.volume_by_label
+        if kind.startswith('regions'):
+            if kind == 'regions_of_field':
+                r = regions.connected_regions(H.field_of(grid, dname), H.FIELD_LEVEL, density=rho, voxel_volume=H.VV, volumes=lab, n=n)
+            else:
+                r = regions.connected_regions(rho, sum_level(H.density(grid, dname)), below=kind.endswith('below'), voxel_volume=H.VV,
+                                              volumes=lab, n=n, global_route=kind.endswith('global'))
+            return r.m, host(r.labels), r.seed, r.count, r.top, r.charge, r.charge2, r.shares
         raise KeyError(kind)
 
     def checked(self, kind, grid, dname, mname, **kw):
@@ -200,7 +251,12 @@ def pairs_of(x, run, setting, first, second, pinned=None):
 def test_every_call_after_every_other(x):
     """settings: 1 both calls on (A, bader), outside resident();  2 the same inside resident(A);  3 X on (B, atoms) and Y on
     (A, bader) inside resident(A): B is uploaded over the pinned array and Y must see A again;  4 both on a float32 device tensor
-    of A and an int32 device tensor of the map (expectations from A32.astype(float64));  4r the same inside resident(tensor)"""
+    of A and an int32 device tensor of the map (expectations from A32.astype(float64));  4r the same inside resident(tensor).
+
+    X and Y run over every kind of history_common.KINDS, the Hirshfeld, ISA, NCI, isosurface and regions kinds included: a new
+    analysis after another new one, a Hirshfeld or ISA call next to calls that move the tokens, setting 3 for the calls whose
+    field becomes the resident density, and device tensors for all of them.  The *_of_field kinds hand their field over as a host
+    array in settings 4 and 4r too: it goes through the scratch upload beside the imported tensor."""
     run = Runner()
     bad = pairs_of(x, run, '1 plain', ('A', 'bader'), ('A', 'bader'))
     bad += pairs_of(x, run, '2 resident(A)', ('A', 'bader'), ('A', 'bader'), pinned=H.density('G1', 'A'))
@@ -237,11 +293,22 @@ def refused(ctx, how, grid, run):
             with pytest.raises(_lib.BaderHipError) as e:
                 call()
             assert e.value.code in (_lib.XB_E_ARG, _lib.XB_E_STATE)
-    else:
+    elif how == 'non-float device dtype':
         ints = device.DeviceArray(ctx, H.GRIDS[grid], np.int32)
         with pytest.raises(_lib.BaderHipError) as e:
             critical.critical_points(ints)
         assert e.value.code == _lib.XB_E_ARG
+    elif how == 'isa_iterate on a Hirshfeld setup':
+        hirshfeld.promolecule(rho, H.LAT, H.SITES['A'], H.SPECIES, H.proatoms('A'))      # (a Hirshfeld setup is no ISA setup)
+        with pytest.raises(_lib.BaderHipError) as e:
+            ctx.isa_iterate(1)
+        assert e.value.code == _lib.XB_E_STATE
+    elif how == 'regions_shares without a labelling':
+        with pytest.raises(_lib.BaderHipError) as e:                # (connected_regions and nci_domains release theirs on return)
+            ctx.regions_shares(H.n_of(grid, 'atoms'))
+        assert e.value.code == _lib.XB_E_STATE
+    else:
+        raise KeyError(how)
 
 
 def release_all(ctx):
@@ -249,6 +316,9 @@ def release_all(ctx):
     ctx.merge_release()
     ctx.critical_release()
     ctx.weight_release()
+    ctx.isosurface_release()
+    ctx.regions_release()
+    ctx.hirshfeld_release()
 
 
 @pytest.mark.parametrize('seed', H.SEEDS)
@@ -258,8 +328,8 @@ def test_seeded_walks(seed):
 
     Memory: a change to a grid of another voxel count frees everything the context holds for the grid, so right after set_grid
     memory_stats() must equal what it was after the first set_grid of that shape -- at every return to a shape, and at the end
-    after the four release calls and a last return.  (Between those points the table, the edge buffers and the per-label sum
-    buffers grow with use and have no release call of their own: the four releases can only be shown not to raise the figure.)"""
+    after the seven release calls and a last return.  (Between those points the table, the edge buffers and the per-label sum
+    buffers grow with use and have no release call of their own: the releases can only be shown not to raise the figure.)"""
     ctx = _lib.default_context()
     run = Runner()
     steps = H.walk(seed)
@@ -347,6 +417,19 @@ def test_a_label_only_call_on_another_grid_inside_resident():
                 assert run.checked(between, 'G2', 'A', 'atoms') is None
                 msg = run.checked(kind, 'G1', 'A', 'bader')
                 assert msg is None, f'{kind}, {between} on G2, {kind}: {msg}'
+
+
+def test_a_hirshfeld_setup_replaced_by_isa_and_dropped_with_the_shape_inside_resident():
+    """inside resident(A of G1): hirshfeld_charges, isa_charges (which IS the context's Hirshfeld setup and replaces it),
+    hirshfeld_charges again (hirshfeld._setup must not take the ISA tables for its own: Context.isa_setup clears the key it
+    remembers), the promolecule on G2 (the change of shape drops the setup and the key), then hirshfeld_charges on G1 once more: the
+    setup is made again on a grid that holds no density until the call uploads the pinned one."""
+    run = Runner()
+    with utils.resident(H.density('G1', 'A')):
+        for kind, grid in (('hirshfeld_charges', 'G1'), ('isa_charges', 'G1'), ('hirshfeld_charges', 'G1'), ('promolecule', 'G2'),
+                           ('hirshfeld_charges', 'G1')):
+            msg = run.checked(kind, grid, 'A', 'atoms')
+            assert msg is None, msg
 
 
 # ---- the label token at the level of the Context -----------------------------------------------------------------------------------

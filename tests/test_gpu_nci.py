@@ -31,13 +31,13 @@ from pybader_amd import _lib, device, nci, thread_handlers, utils
 from test_gpu_history import Runner
 from test_laplacian_cpu import grouped, restated_values, sum_bound
 from test_multipole_cpu import VV, label_map
-from test_nci_cpu import (LABELS_LDS, LATS, SUM_CUTS, classes, density, histogram, keys, region, restated, sum_inputs,
+from test_nci_cpu import (HISTORY_CUTS, HISTORY_EDGES, LABELS_LDS, LATS, S_REL, SUM_CUTS, check_s, check_sums, classes, density,
+                          fields_difference, histogram, histogram_difference, keys, region, regions_difference, restated, sum_inputs,
                           sum_reference, thresholds, values)
 from test_nci_cpu import test_the_bound_notices_a_voxel_in_the_wrong_class  # noqa: F401 -- runs here too
 
 pytestmark = pytest.mark.gpu
 FIELD_SHAPES = [(13, 17, 19), (20, 9, 33), (1, 2, 5), (2, 1, 40), (16, 16, 64)]
-S_REL = 16 * 2.0 ** -52
 LDS_BINS = _lib.XB_NCI_HIST_LDS_BINS
 
 
@@ -60,18 +60,6 @@ def same_bits(got, want, what):
     assert got.dtype == np.float64 and got.shape == want.shape, what
     diff = np.ascontiguousarray(got).view(np.uint64) != np.ascontiguousarray(want).view(np.uint64)
     assert not diff.any(), f'{what}: {int(diff.sum())} of {diff.size} values differ from the restatement, first at {np.argwhere(diff)[0].tolist()}'
-
-
-def check_s(got, v, what):
-    """+inf exactly where the restatement has it, within the bound elsewhere (the measured maximum printed first)"""
-    want = v['s']
-    assert got.dtype == np.float64 and got.shape == want.shape, what
-    assert np.array_equal(np.isposinf(got), ~v['pos']), f'{what}: s is +inf exactly where rho <= 0'
-    fin = v['pos']
-    err = np.abs(got[fin] - want[fin])
-    rel = float(np.max(err / np.where(want[fin] > 0, want[fin], 1.0), initial=0.0))
-    print(f'{what}: s off by at most {rel / 2.0 ** -52:.2f} * 2^-52 relative (bound 16)')
-    assert np.all(err <= S_REL * want[fin]), f'{what}: s off by {rel / 2.0 ** -52:.2f} * 2^-52 relative'
 
 
 # ---- the fields -------------------------------------------------------------------------------------------------------------------
@@ -138,22 +126,6 @@ def test_fields_of_device_tensors_and_a_host_array_through_the_python_layer():
 
 
 # ---- the region's sums ------------------------------------------------------------------------------------------------------------
-def check_sums(got, v, lab, n, what, cuts=SUM_CUTS):
-    """counts ==; the bound for the sums of rho and of rho^2 of every key (each figure printed before it is asserted)"""
-    (s1, cnt, mag1), (s2, cnt2, mag2) = sum_reference(v, lab, n, cuts)
-    count, charge, charge2 = got
-    assert count.shape == charge.shape == charge2.shape == (n, 3) and count.dtype == np.int64
-    assert np.array_equal(count.reshape(-1), cnt) and np.array_equal(cnt, cnt2), f'{what}: counts'
-    for name, g, w, mag in (('sum of rho', charge, s1, mag1), ('sum of rho^2', charge2, s2, mag2)):
-        lim = sum_bound(cnt, mag)
-        err = np.abs(g.reshape(-1) - w * VV)
-        k = int(np.argmax(err - lim))
-        print(f'{what}: {name}, worst key {k} ({cnt[k]} voxels): off by {err[k]:.3e}, bound {lim[k]:.3e}')
-        assert np.all(err <= lim), f'{what}: {name} of key {k} ({cnt[k]} voxels) off by {err[k]:.3e}, bound {lim[k]:.3e}'
-        assert not g.reshape(-1)[cnt == 0].any(), f'{what}: something landed on a key nobody carries'
-    return cnt
-
-
 def test_sums_on_every_input_through_both_routes(ctx):
     assert LABELS_LDS == 85
     resident = None
@@ -401,10 +373,6 @@ def test_error_codes():
 
 
 # ---- call history -------------------------------------------------------------------------------------------------------------------
-HISTORY_CUTS = (1.0, 1.0, 0.03)
-HISTORY_EDGES = (np.array([0.1, 0.3, 0.5, 1.0, 2.0]), np.array([-0.5, -0.03, 0.0, 0.03, 0.5]))
-
-
 @functools.lru_cache(maxsize=None)
 def history_values(grid):
     return restated(H.density(grid, 'A'), H.LAT)
@@ -416,25 +384,12 @@ def nci_call(kind, grid):
     rho, lab, n, v = H.density(grid, 'A'), H.labels(grid, 'atoms'), H.n_of(grid, 'atoms'), history_values(grid)
     if kind == 'fields':
         s, x = nci.nci_fields(rho, H.LAT)
-        if not np.array_equal(x.view(np.uint64), v['x'].view(np.uint64)):
-            return f'nci_fields on {grid}: x differs'
-        ok = v['pos']
-        if not np.array_equal(np.isposinf(s), ~ok) or not np.all(np.abs(s[ok] - v['s'][ok]) <= S_REL * v['s'][ok]):
-            return f'nci_fields on {grid}: s differs'
-        return None
+        return fields_difference(s, x, v, f'nci_fields on {grid}')
     if kind == 'regions':
         r = nci.nci_regions(rho, lab, H.LAT, n, VV, *HISTORY_CUTS)
-        (s1, cnt, mag1), (s2, _, mag2) = sum_reference(v, lab, n, HISTORY_CUTS)
-        if not np.array_equal(r.count.reshape(-1), cnt) or cnt.sum() < 100:
-            return f'nci_regions on {grid}: counts differ'
-        if not np.all(np.abs(r.charge.reshape(-1) - s1 * VV) <= sum_bound(cnt, mag1)):
-            return f'nci_regions on {grid}: the sums of rho differ'
-        if not np.all(np.abs(r.charge2.reshape(-1) - s2 * VV) <= sum_bound(cnt, mag2)):
-            return f'nci_regions on {grid}: the sums of rho^2 differ'
-        return None
+        return regions_difference(r.count, r.charge, r.charge2, sum_reference(v, lab, n, HISTORY_CUTS), f'nci_regions on {grid}')
     got = nci.nci_histogram(rho, H.LAT, *HISTORY_EDGES)
-    want = histogram(v, *HISTORY_EDGES)
-    return None if np.array_equal(got, want) and want.sum() > 100 else f'nci_histogram on {grid}: {int((got != want).sum())} bins differ'
+    return histogram_difference(got, histogram(v, *HISTORY_EDGES), f'nci_histogram on {grid}')
 
 
 @pytest.mark.parametrize('other', ['basin_laplacian', 'critical', 'voronoi'])

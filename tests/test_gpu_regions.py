@@ -19,6 +19,7 @@ import test_regions_cpu as R
 from pybader_amd import _lib, critical, device, nci, regions, thread_handlers, utils
 from test_gpu_history import Runner
 from test_multipole_cpu import VV, bound, label_map
+from test_regions_cpu import check_sums
 from test_regions_cpu import test_the_bound_notices_a_voxel_in_the_wrong_component  # noqa: F401 -- runs here too
 
 pytestmark = pytest.mark.gpu
@@ -45,25 +46,6 @@ def upload(ctx, rho):
     if ctx.shape != rho.shape:
         ctx.set_grid(rho.shape, np.zeros(27), np.zeros(9))
     ctx.upload_density(rho)
-
-
-def check_sums(what, got, reg, seeds, rho, vv=VV):
-    """seed, count, top with ==; the sums of rho and rho^2 under the bound (the worst figure printed before it is asserted)"""
-    seed, count, top, s1, s2 = got[:5]
-    m = seeds.size
-    want_count, want_top, terms = R.per_component(reg, m, rho)
-    assert seed.dtype == count.dtype == top.dtype == np.int64 and s1.dtype == s2.dtype == np.float64
-    assert np.array_equal(seed, seeds), f'{what}: seeds'
-    assert np.array_equal(count, want_count), f'{what}: counts'
-    assert np.array_equal(top, want_top), f'{what}: tops'
-    for name, g, tt in (('sum of rho', s1, terms), ('sum of rho^2', s2, [t * t for t in terms])):
-        w, mag = R.sums(tt)
-        lim = bound(want_count, mag[:, None], vv)[:, 0] if m else np.zeros(0)
-        err = np.abs(g - w * vv)
-        if m:
-            k = int(np.argmax(err - lim))
-            print(f'{what}: {name}, worst component {k} ({want_count[k]} voxels): off by {err[k]:.3e}, bound {lim[k]:.3e}')
-        assert np.all(err <= lim), f'{what}: {name}'
 
 
 def both_routes(ctx, what, mode, reg, seeds, rho, level=0.5, **kw):

@@ -1,6 +1,7 @@
 """The check of the check for tests/test_gpu_history.py (no GPU): the inputs of tests/history_common.py tell a stale upload from a
-fresh one for every call kind, the seeded walks reach every kind and every event, no generated step is left out, and the
-oracle-built maps are converged."""
+fresh one for every call kind -- the Hirshfeld, ISA, NCI, isosurface and regions kinds included --, the seeded walks reach every
+kind and every event, no generated step is left out, the oracle-built maps are converged, and the newer analyses' expectations
+are no empty sets on any grid (voxels no pro-atom reaches, no empty ISA shell, two components, two NCI domains, meshes, shares)."""
 import collections
 
 import numpy as np
@@ -24,10 +25,25 @@ def test_every_kind_tells_the_two_inputs_apart(grid):
             assert msg is not None and msg.startswith(f'{kind} on {grid} density A map bader: '), (kind, other, msg)
 
 
+def test_the_newer_kinds_accept_their_own_expectation_on_every_input_a_walk_can_draw():
+    """the comparisons of the regions, domains and NCI kinds also ask that the expectation is no empty set (2 components, 50
+    shared voxels, 100 counted ones): that holds on every grid, density and map, so a walk's step cannot fail on its input"""
+    new = list(H.KINDS)[list(H.KINDS).index('hirshfeld_charges'):]
+    for grid in H.GRIDS:
+        for kind in new:
+            for d in H.densities(grid):
+                for m in H.maps(grid):
+                    assert H.check(kind, H.as_result(kind, H.expect(kind, grid, d, m), grid), (grid, d, m)) is None
+
+
 def test_the_float32_density_is_told_from_the_float64_one():
     """setting 4 of the pair matrix computes its expectations from A32.astype(float64): they differ from A's wherever the kind
     returns a float, so a device import that is not the tensor's content cannot pass"""
-    for kind in ('charge_sum', 'volume_mask', 'weight_own', 'moment_sum', 'laplacian', 'basin_laplacian', 'point_properties'):
+    # every new kind that returns a float: all but promolecule, which reads no density, and nci_histogram, which returns counts
+    new = [k for k in H.KINDS if k.startswith(('hirshfeld_charges', 'deformation', 'isa_', 'nci_', 'isosurface', 'regions'))
+           and k != 'nci_histogram']
+    assert len(new) == 17
+    for kind in ['charge_sum', 'volume_mask', 'weight_own', 'moment_sum', 'laplacian', 'basin_laplacian', 'point_properties'] + new:
         got = H.as_result(kind, H.expect(kind, 'G1', 'A32', 'bader'), 'G1')
         assert H.check(kind, got, ('G1', 'A', 'bader')) is not None, kind
 
@@ -37,7 +53,7 @@ def test_the_walks_reach_every_kind_and_every_event_and_leave_no_step_out():
     for seed in H.SEEDS:
         steps = H.walk(seed)
         assert steps == H.walk(seed), 'the walk is a function of its seed'
-        assert 75 <= len(steps) <= 90, len(steps)
+        assert 135 <= len(steps) <= 150, len(steps)
         grid, inside = 'G1', False
         for s in steps:
             total += 1
@@ -88,6 +104,10 @@ def test_the_edits_of_the_walks_show_in_the_expectation():
             assert H.check(kind, after, (grid, d, m)) is not None, s
             seen += 1
     assert seen >= 3
+    # ... and of the kinds added with the five newest analyses, at least 12 can be drawn for such a step
+    new = list(H.KINDS)[list(H.KINDS).index('hirshfeld_charges'):]
+    assert len(new) == 19 and sum(H.check(k, H.as_result(k, H.expect(k, 'G1', 'A+', 'bader'), 'G1'), ('G1', 'A', 'bader')) is not None
+                                  for k in new if H.KINDS[k][0] and k != 'isosurface_of_field') >= 12
 
 
 def test_the_oracle_built_maps_are_converged():
@@ -118,3 +138,18 @@ def test_the_inputs_are_what_the_issue_asks_for():
     # the merge has something to merge on the noisy density, and does not merge everything
     want, _ = H.expect('merge', 'G1', 'N', 'baderN')
     assert 1 < want['n_survivors'] < H.n_of('G1', 'baderN') and want['converged']
+    # the five newest analyses have something to say on every grid and both densities
+    for grid in H.GRIDS:
+        for d in ('A', 'B'):
+            s = H.expect('hirshfeld_charges', grid, d, 'atoms')
+            assert s['rest'][1] > 0 and (s['count'] >= 100).all(), 'voxels no pro-atom reaches, and every atom weighs voxels'
+            g = H._isa(grid, d)[0]
+            assert (g.count > 0).all(), 'no ISA shell is empty'
+            assert H.expect('regions', grid, d, 'atoms')['seeds'].size >= 2 and H.expect('regions_below', grid, d, 'atoms')['seeds'].size >= 1
+            assert H.expect('nci_domains', grid, d, 'atoms')['seeds'].size >= 2
+            for kind in ('isosurface', 'isosurface_of_field'):
+                mesh = H.expect(kind, grid, d, 'atoms')
+                assert mesh.vertices.shape[0] > 100 and mesh.triangles.shape[0] > 100, (kind, grid, d)
+            for kind in ('regions', 'regions_below', 'regions_of_field', 'nci_domains'):
+                assert H.expect(kind, grid, d, 'atoms')['shares'][2].sum() >= 50, (kind, grid, d)
+            assert H.expect('nci_regions', grid, d, 'atoms')[0][1].sum() >= 100 and H.expect('nci_histogram', grid, d, 'atoms')[0].sum() > 100

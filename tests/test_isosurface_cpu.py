@@ -20,7 +20,7 @@ import pytest
 
 from pybader_amd import _lib, build, isosurface, synth
 from test_critical_cpu import FULL, case, reference_points
-from test_laplacian_cpu import geometry
+from test_laplacian_cpu import geometry, sum_bound
 from test_multipole_cpu import U
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -198,6 +198,44 @@ def restate(f, level, lattice, g=None, labels=None, n=0):
 
 def as_mesh(r, lattice):
     return isosurface.Mesh(r.shape, r.level, lattice, r.vertices, r.colour, r.triangles, r.wrap, r.cells, r.area, r.volume, r.volume_by_label)
+
+
+# ---- the comparisons of tests/test_gpu_isosurface.py (here, so that tests/history_common.py can make them too) ---------------------
+def first_difference(got, want, what):
+    """None, or where the mesh `got` (the tuple of Context.isosurface) first differs from the restatement `want`"""
+    vert, col, tri, wrap, cell = got[:5]
+    if (vert.shape[0], tri.shape[0]) != (want.vertices.shape[0], want.triangles.shape[0]):
+        return f'{what}: {vert.shape[0]} vertices and {tri.shape[0]} triangles, restated {want.vertices.shape[0]} and {want.triangles.shape[0]}'
+    for name, a, b in (('triangles', tri, want.triangles), ('wrap', wrap, want.wrap), ('cells', cell, want.cells)):
+        if not np.array_equal(a, b):
+            return f'{what}: {name} differ at {int(np.flatnonzero((a != b).reshape(a.shape[0], -1).any(axis=1))[0])}'
+    for name, a, b in (('vertices', vert, want.vertices), ('colour', col, want.colour)):
+        if b is None:
+            continue
+        if not np.array_equal(a.view(np.uint64), b.view(np.uint64)):
+            bad = np.flatnonzero((a != b).reshape(a.shape[0], -1).any(axis=1))
+            return f'{what}: {name} differ in {bad.shape[0]} rows, first {int(bad[0])}: {a[bad[0]]!r} against {b[bad[0]]!r}'
+    return None
+
+
+def sums_difference(got, want, what):
+    """None, or which of area, volume and volume_by_label lies outside the bound of the sums around math.fsum of the terms"""
+    area, volume, vbl = got[5:]
+    one = np.ones(1, np.int64)
+    mag_a = np.array([math.fsum(want.area_terms)])
+    if not abs(area - want.area) <= sum_bound(one * want.area_terms.shape[0], mag_a, 1.0)[0]:
+        return f'{what}: area {area!r} against {want.area!r}'
+    frac = want.frac.reshape(-1)
+    terms = frac[frac != 0.0]
+    mag_v = np.array([math.fsum(np.abs(terms))])
+    if not abs(volume - want.volume) <= sum_bound(one * terms.shape[0], mag_v, float(want.tet))[0]:
+        return f'{what}: volume {volume!r} against {want.volume!r}'
+    if want.n:
+        lim = sum_bound(want.share_count, want.share_sum, float(want.tet))
+        off = np.abs(vbl - want.volume_by_label) > lim
+        if vbl.shape != want.volume_by_label.shape or off.any():
+            return f'{what}: volume_by_label differs for {int(off.sum())} labels, first {int(np.flatnonzero(off)[0])}'
+    return None
 
 
 def alternating_sum(rho, level):

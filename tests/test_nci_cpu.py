@@ -208,6 +208,69 @@ def sum_reference(v, lab, n, cuts=SUM_CUTS):
     return grouped(v['rho'], k, 3 * n), grouped(v['r2'], k, 3 * n)
 
 
+# ---- the comparisons of tests/test_gpu_nci.py (here, so that tests/history_common.py can make them too) ------------------------
+S_REL = 16 * 2.0 ** -52
+
+
+def check_s(got, v, what):
+    """+inf exactly where the restatement has it, within the bound elsewhere (the measured maximum printed first)"""
+    want = v['s']
+    assert got.dtype == np.float64 and got.shape == want.shape, what
+    assert np.array_equal(np.isposinf(got), ~v['pos']), f'{what}: s is +inf exactly where rho <= 0'
+    fin = v['pos']
+    err = np.abs(got[fin] - want[fin])
+    rel = float(np.max(err / np.where(want[fin] > 0, want[fin], 1.0), initial=0.0))
+    print(f'{what}: s off by at most {rel / 2.0 ** -52:.2f} * 2^-52 relative (bound 16)')
+    assert np.all(err <= S_REL * want[fin]), f'{what}: s off by {rel / 2.0 ** -52:.2f} * 2^-52 relative'
+
+
+def check_sums(got, v, lab, n, what, cuts=SUM_CUTS):
+    """counts ==; the bound for the sums of rho and of rho^2 of every key (each figure printed before it is asserted)"""
+    (s1, cnt, mag1), (s2, cnt2, mag2) = sum_reference(v, lab, n, cuts)
+    count, charge, charge2 = got
+    assert count.shape == charge.shape == charge2.shape == (n, 3) and count.dtype == np.int64
+    assert np.array_equal(count.reshape(-1), cnt) and np.array_equal(cnt, cnt2), f'{what}: counts'
+    for name, g, w, mag in (('sum of rho', charge, s1, mag1), ('sum of rho^2', charge2, s2, mag2)):
+        lim = sum_bound(cnt, mag)
+        err = np.abs(g.reshape(-1) - w * VV)
+        k = int(np.argmax(err - lim))
+        print(f'{what}: {name}, worst key {k} ({cnt[k]} voxels): off by {err[k]:.3e}, bound {lim[k]:.3e}')
+        assert np.all(err <= lim), f'{what}: {name} of key {k} ({cnt[k]} voxels) off by {err[k]:.3e}, bound {lim[k]:.3e}'
+        assert not g.reshape(-1)[cnt == 0].any(), f'{what}: something landed on a key nobody carries'
+    return cnt
+
+
+# the thresholds and edges of the call-history tests: the region and the bins hold voxels on every grid of history_common
+HISTORY_CUTS = (1.0, 1.0, 0.03)
+HISTORY_EDGES = (np.array([0.1, 0.3, 0.5, 1.0, 2.0]), np.array([-0.5, -0.03, 0.0, 0.03, 0.5]))
+
+
+def fields_difference(s, x, v, what):
+    """None, or which of the two fields of nci_fields differs from the restated values `v`"""
+    if not np.array_equal(x.view(np.uint64), v['x'].view(np.uint64)):
+        return f'{what}: x differs'
+    ok = v['pos']
+    if not np.array_equal(np.isposinf(s), ~ok) or not np.all(np.abs(s[ok] - v['s'][ok]) <= S_REL * v['s'][ok]):
+        return f'{what}: s differs'
+    return None
+
+
+def regions_difference(count, charge, charge2, reference, what):
+    """None, or what of nci_regions differs from `reference` = sum_reference(v, lab, n, cuts)"""
+    (s1, cnt, mag1), (s2, _, mag2) = reference
+    if not np.array_equal(count.reshape(-1), cnt) or cnt.sum() < 100:
+        return f'{what}: counts differ'
+    if not np.all(np.abs(charge.reshape(-1) - s1 * VV) <= sum_bound(cnt, mag1)):
+        return f'{what}: the sums of rho differ'
+    if not np.all(np.abs(charge2.reshape(-1) - s2 * VV) <= sum_bound(cnt, mag2)):
+        return f'{what}: the sums of rho^2 differ'
+    return None
+
+
+def histogram_difference(got, want, what):
+    return None if np.array_equal(got, want) and want.sum() > 100 else f'{what}: {int((got != want).sum())} bins differ'
+
+
 # ---- 1. sigma against eigvalsh ---------------------------------------------------------------------------------------------------
 def full(H):
     xx, xy, xz, yy, yz, zz = (np.asarray(a, dtype=np.float64) for a in H)

@@ -100,6 +100,26 @@ def atoms_of(m, triplets):
     return out
 
 
+# the comparison of tests/test_gpu_regions.py (here, so that tests/history_common.py can make it too)
+def check_sums(what, got, reg, seeds, rho, vv=VV):
+    """seed, count, top with ==; the sums of rho and rho^2 under the bound (the worst figure printed before it is asserted)"""
+    seed, count, top, s1, s2 = got[:5]
+    m = seeds.size
+    want_count, want_top, terms = per_component(reg, m, rho)
+    assert seed.dtype == count.dtype == top.dtype == np.int64 and s1.dtype == s2.dtype == np.float64
+    assert np.array_equal(seed, seeds), f'{what}: seeds'
+    assert np.array_equal(count, want_count), f'{what}: counts'
+    assert np.array_equal(top, want_top), f'{what}: tops'
+    for name, g, tt in (('sum of rho', s1, terms), ('sum of rho^2', s2, [t * t for t in terms])):
+        w, mag = sums(tt)
+        lim = bound(want_count, mag[:, None], vv)[:, 0] if m else np.zeros(0)
+        err = np.abs(g - w * vv)
+        if m:
+            k = int(np.argmax(err - lim))
+            print(f'{what}: {name}, worst component {k} ({want_count[k]} voxels): off by {err[k]:.3e}, bound {lim[k]:.3e}')
+        assert np.all(err <= lim), f'{what}: {name}'
+
+
 # ---- 2. the masks both files use ---------------------------------------------------------------------------------------------------
 def voxels(shape, *points):
     m = np.zeros(shape, bool)
