@@ -65,7 +65,19 @@ int xb_download_density(xb_ctx *c, double *rho_host);
  * whitespace separated decimal numbers in Fortran order (x fastest); they are converted exactly as numpy's
  * string -> float64 does (correctly rounded), divided by `divisor` (the cell volume) and stored as the
  * resident density rho[x][y][z].  The text is uploaded as it is and parsed on the device; tokens outside the
- * exact fast path go through strtod on the host (n_host of them).  SURVEY.md 8(f) rank 4. */
+ * exact fast path are converted on the host (n_host of them, however many: a file written with 17 digits leaves
+ * every one), in the C locale whatever LC_NUMERIC is.  Tokens after the grid's last number are ignored.
+ * SURVEY.md 8(f) rank 4.
+ * What converts: the tokens numpy's string -> float64 takes -- decimals with or without point and e / E exponent,
+ * inf, infinity, nan in any letter case, each with an optional sign (a nan's sign and payload are not pinned) --
+ * with two deliberate divergences: '_' between digits ("1_0") and non-ASCII digits, which numpy takes, are
+ * refused; no writer emits them.  What numpy refuses is refused: hex floats, nan(...), a Fortran D exponent, ...
+ * Errors of the two parse calls: XB_E_STATE no grid; XB_E_ARG an empty text, a bad divisor, nval or pick, an axis
+ * below 3 voxels, a token among those used that does not convert; XB_E_SHORT fewer numbers than the grid needs;
+ * XB_E_LIMIT a text of 2^43 bytes or more than 2^31 - 1 numbers; XB_E_HIP the runtime (out of memory, ...).
+ * The resident density after a refused call: unchanged after every refusal but two -- after XB_E_ARG for a token
+ * that does not convert, and after XB_E_HIP, it is unspecified (the values the device converted are already stored,
+ * or added with `accumulate`; the host's are not): parse again in store mode, or upload, before using it. */
 int xb_parse_density_text(xb_ctx *c, const char *text, int64_t nbytes, double divisor, int64_t *n_tokens,
                           int64_t *n_host);
 /* The density block of a cube file (io/cube.py:93-123): `text` holds nx*ny*nz*nval (or more) whitespace separated

@@ -16,6 +16,10 @@
  * Every function cites the reference file:line it follows.  Arrays are C-order [x][y][z].
  * Labels ("volumes") are int32 here; known flags int8; indices int64.
  */
+#ifndef _GNU_SOURCE
+#define _GNU_SOURCE /* newlocale, strtod_l (orc_parse_density_text) under -std=c11 */
+#endif
+#include <locale.h>
 #include <math.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -540,25 +544,62 @@ void orc_synth_density(const int64_t shape[3], const double *lattice, const doub
     }
 }
 
+/* q spells w (lower case) in any letter case, and ends there */
+static int orc_word(const char *q, const char *w) {
+    for (; *w; q++, w++)
+        if ((*q | 0x20) != *w) return 0;
+    return *q == 0;
+}
+/* numpy's string -> float64 on one ASCII token: strtod alone takes more than numpy does (hex floats,
+ * nan(n-char-seq)), so the token is first held to numpy's grammar
+ *   [+-] ( digits [. [digits]] | . digits ) [ (e|E) [+-] digits ]  |  [+-] inf | infinity | nan   (any letter case)
+ * ('_' between digits and non-ASCII digits, which numpy takes, are refused as the library refuses them); the
+ * value is strtod_l's in the C locale (correctly rounded, whatever LC_NUMERIC is).  0 when the token is refused. */
+static int orc_number(const char *s, double *out) {
+    static locale_t c_locale = (locale_t)0;
+    const char *p = s;
+    if (*p == '+' || *p == '-') p++;
+    if (!(orc_word(p, "inf") || orc_word(p, "infinity") || orc_word(p, "nan"))) {
+        int digits = 0;
+        for (; *p >= '0' && *p <= '9'; p++) digits++;
+        if (*p == '.')
+            for (p++; *p >= '0' && *p <= '9'; p++) digits++;
+        if (!digits) return 0;
+        if (*p == 'e' || *p == 'E') {
+            p++;
+            if (*p == '+' || *p == '-') p++;
+            if (!(*p >= '0' && *p <= '9')) return 0;
+            while (*p >= '0' && *p <= '9') p++;
+        }
+        if (*p) return 0;
+    }
+    if (!c_locale) c_locale = newlocale(LC_ALL_MASK, "C", (locale_t)0);
+    char *stop;
+    *out = c_locale ? strtod_l(s, &stop, c_locale) : strtod(s, &stop);
+    return stop != s && !*stop;
+}
+
 /* The density block of a CHGCAR (io/vasp.py:90-104, 147-149): whitespace separated decimal numbers in
- * Fortran order (x fastest), each converted by strtod (correctly rounded, as numpy's string -> float64),
+ * Fortran order (x fastest), each converted as numpy's string -> float64 converts it (orc_number),
  * stored as out[x][y][z] = value / divisor.  Returns the number of tokens converted (stops after nx*ny*nz),
  * or -1 - k when token k is malformed. */
 int64_t orc_parse_density_text(const char *text, int64_t nbytes, const int64_t shape[3], double divisor, double *out) {
     const int64_t nx = shape[0], ny = shape[1], nz = shape[2], N = nx * ny * nz;
     int64_t pos = 0, k = 0;
-    char buf[128];
+    char small[128];
     while (k < N) {
         while (pos < nbytes && (text[pos] == ' ' || (text[pos] >= 9 && text[pos] <= 13))) pos++;
         if (pos >= nbytes) break;
         int64_t end = pos;
         while (end < nbytes && !(text[end] == ' ' || (text[end] >= 9 && text[end] <= 13))) end++;
-        if (end - pos >= (int64_t)sizeof buf) return -1 - k;
+        char *buf = end - pos < (int64_t)sizeof small ? small : malloc((size_t)(end - pos) + 1); /* (a long run of zeros) */
+        if (!buf) return -1 - k;
         memcpy(buf, text + pos, (size_t)(end - pos));
         buf[end - pos] = 0;
-        char *stop;
-        const double v = strtod(buf, &stop);
-        if (stop == buf || *stop) return -1 - k;
+        double v;
+        const int ok = orc_number(buf, &v);
+        if (buf != small) free(buf);
+        if (!ok) return -1 - k;
         const int64_t x = k % nx, r = k / nx;
         out[(x * ny + r % ny) * nz + r / ny] = v / divisor;
         k++;

@@ -14,6 +14,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <locale.h>   // newlocale, strtod_l: the text reader's host conversions do not depend on LC_NUMERIC
 #include <mutex>
 #include <string>
 #include <thread>

@@ -376,9 +376,44 @@ static int device_scan(xb_ctx *c, int *data, int n, int *scratch) {
     }
     return XB_OK;
 }
+// The host's conversion of one token the device left: numpy's string -> float64 on ASCII text.  strtod alone takes
+// more than numpy does (hex floats, nan(n-char-seq)), so the token is first held to numpy's grammar
+//   [+-] ( digits [. [digits]] | . digits ) [ (e|E) [+-] digits ]  |  [+-] inf | infinity | nan   (any letter case)
+// and refused otherwise; '_' between digits and non-ASCII digits, which numpy takes, are refused too (bader_hip.h).
+// The value is strtod_l's in the C locale: correctly rounded, and the caller's LC_NUMERIC does not matter.
+static bool host_number(const char *s, double *out) {
+    static const locale_t c_locale = newlocale(LC_ALL_MASK, "C", (locale_t)0);
+    const char *p = s;
+    if (*p == '+' || *p == '-') p++;
+    auto word = [](const char *q, const char *w) {   // q spells w (lower case) in any letter case, and ends there
+        for (; *w; q++, w++)
+            if ((*q | 0x20) != *w) return false;
+        return *q == 0;
+    };
+    if (!(word(p, "inf") || word(p, "infinity") || word(p, "nan"))) {
+        int digits = 0;
+        for (; *p >= '0' && *p <= '9'; p++) digits++;
+        if (*p == '.')
+            for (p++; *p >= '0' && *p <= '9'; p++) digits++;
+        if (!digits) return false;
+        if (*p == 'e' || *p == 'E') {
+            p++;
+            if (*p == '+' || *p == '-') p++;
+            if (!(*p >= '0' && *p <= '9')) return false;
+            while (*p >= '0' && *p <= '9') p++;
+        }
+        if (*p) return false;
+    }
+    char *stop = nullptr;
+    *out = c_locale ? strtod_l(s, &stop, c_locale) : std::strtod(s, &stop);
+    return stop != s && *stop == 0;
+}
 // Upload `text`, count its tokens, scan the counts, convert the tokens `map` uses into c->rho (k_text_parse); the
-// tokens outside the device's exact fast path go through strtod here and are stored by k_text_patch.  The token
-// offsets of the scan are int: a text that could hold more than XB_INT_MAX numbers has its count checked in 64 bits.
+// tokens outside the device's exact fast path are converted here (host_number) and stored by k_text_patch.  Their
+// list starts at TXT_TODO_FIRST entries; a text that leaves more (every token of a file written with 17 digits) has
+// them listed again by a pass that stores nothing, into a list of exactly their number.  The token offsets of the
+// scan are int: a text that could hold more than XB_INT_MAX numbers has its count checked in 64 bits.
+enum { TXT_TODO_FIRST = 1 << 20 };
 extern "C++" {  // (this file sits in bader_hip.hip's extern "C" block)
 template <class Map>
 static int parse_text(xb_ctx *c, const char *who, const char *text, int64_t nbytes, const Map &map, int64_t *n_tokens,
@@ -389,7 +424,7 @@ static int parse_text(xb_ctx *c, const char *who, const char *text, int64_t nbyt
     static const double P10[23] = {1e0, 1e1, 1e2, 1e3, 1e4, 1e5, 1e6, 1e7, 1e8, 1e9, 1e10, 1e11,
                                    1e12, 1e13, 1e14, 1e15, 1e16, 1e17, 1e18, 1e19, 1e20, 1e21, 1e22};
     const int nblk = (int)((nbytes + TPB * TXT_BYTES - 1) / (TPB * TXT_BYTES));
-    const int todo_cap = 1 << 20;
+    int todo_cap = TXT_TODO_FIRST;
     unsigned char *dtext = nullptr;
     int *counts = nullptr;
     double *dp10 = nullptr;
@@ -423,13 +458,26 @@ static int parse_text(xb_ctx *c, const char *who, const char *text, int64_t nbyt
     if (e == hipSuccess && rc == XB_OK && tokens < map.count())
         rc = fail(XB_E_SHORT, "%s: %lld numbers in the text, the grid needs %lld", who, tokens, map.count());
     if (e == hipSuccess && rc == XB_OK) {
-        k_text_parse<<<nblk, TPB, 0, c->stream>>>(dtext, nbytes, counts, dp10, map, c->rho, dtodo, c->counters + CT_TEXT_TODO, todo_cap);
+        k_text_parse<<<nblk, TPB, 0, c->stream>>>(dtext, nbytes, counts, dp10, map, c->rho, dtodo, c->counters + CT_TEXT_TODO, todo_cap, 0);
         e = hipGetLastError();
         if (e == hipSuccess) rc = read_counter(c, CT_TEXT_TODO, &n_todo);
     }
-    if (e == hipSuccess && rc == XB_OK && n_todo > todo_cap)
-        rc = fail(XB_E_LIMIT, "%s: %d tokens need the host parser (cap %d)", who, n_todo, todo_cap);
-    if (e == hipSuccess && rc == XB_OK && n_todo) {  // the rare tokens outside the exact fast path: strtod on the host
+    if (e == hipSuccess && rc == XB_OK && n_todo > todo_cap) {  // the list overflowed: list again, storing nothing (the
+        const int listed = n_todo;                              // first pass stored, or added, every value it converted)
+        hipFree(dtodo);
+        dtodo = nullptr;
+        todo_cap = listed;
+        e = hipMalloc(&dtodo, (size_t)todo_cap * 2 * sizeof(long long));
+        if (e == hipSuccess) e = hipMemsetAsync(c->counters + CT_TEXT_TODO, 0, sizeof(int), c->stream);
+        if (e == hipSuccess) {
+            k_text_parse<<<nblk, TPB, 0, c->stream>>>(dtext, nbytes, counts, dp10, map, c->rho, dtodo, c->counters + CT_TEXT_TODO, todo_cap, 1);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) rc = read_counter(c, CT_TEXT_TODO, &n_todo);
+        if (e == hipSuccess && rc == XB_OK && n_todo != listed)
+            rc = fail(XB_E_HIP, "%s: %d tokens left to the host, then %d", who, listed, n_todo);
+    }
+    if (e == hipSuccess && rc == XB_OK && n_todo) {  // the tokens outside the exact fast path: host_number
         std::vector<long long> todo(2 * (size_t)n_todo), at(n_todo);
         std::vector<double> val(n_todo);
         e = hipMemcpyAsync(todo.data(), dtodo, todo.size() * sizeof(long long), hipMemcpyDeviceToHost, c->stream);
@@ -439,9 +487,7 @@ static int parse_text(xb_ctx *c, const char *who, const char *text, int64_t nbyt
             long long end = off;
             while (end < nbytes && !(text[end] == ' ' || (text[end] >= 9 && text[end] <= 13))) end++;
             const std::string tok(text + off, text + end);
-            char *stop = nullptr;
-            val[k] = std::strtod(tok.c_str(), &stop);
-            if (stop == tok.c_str() || *stop != 0) rc = fail(XB_E_ARG, "%s: could not convert '%s' to a number", who, tok.c_str());
+            if (!host_number(tok.c_str(), &val[k])) rc = fail(XB_E_ARG, "%s: could not convert '%.60s' to a number", who, tok.c_str());
             map.voxel(idx, at[k]);                                    // (only used tokens are listed)
         }
         if (e == hipSuccess && rc == XB_OK) {

@@ -16,7 +16,10 @@
 // m * 10^e or m / 10^-e with both operands exact doubles, i.e. ONE correctly rounded IEEE operation
 // (Clinger's fast path) -- every number a VASP / pybader writer produces (<= 17 digits would not fit, 11-12
 // do).  Anything else (longer mantissas, huge exponents, nan/inf, malformed tokens) is listed and converted
-// by strtod on the host, so the result equals numpy's for every input the reference accepts.
+// on the host (host_number in host_context.h: numpy's grammar, strtod's value), so the result equals numpy's for
+// every input the reference accepts ('_' between digits and non-ASCII digits apart: refused here, see bader_hip.h),
+// and what numpy refuses is refused.  The 18-digit bound keeps m inside
+// 64 bits (20 digits can wrap); every 17- to 19-digit mantissa is at least 2^53 and goes to the host by that test.
 // ---------------------------------------------------------------------------------------------
 #define TXT_BYTES 16  // bytes per thread
 __device__ __forceinline__ bool txt_blank(unsigned char ch) { return ch == ' ' || (ch >= 9 && ch <= 13); }
@@ -150,12 +153,14 @@ struct TxtCube {  // cube (io/cube.py:93-123): C order, nval values per voxel, t
 };
 
 // block_off: exclusive scan of the block counts.  Token i of the text goes where `map` says; tokens from
-// map.count() on are ignored.  todo: (byte offset, token index) of the used tokens left to the host.
+// map.count() on are ignored.  todo: (byte offset, token index) of the used tokens left to the host; *n_todo counts
+// them all, also those beyond todo_cap.  list_only: store nothing -- the second pass after a list that overflowed
+// (a store in accumulate mode must happen once).
 template <class Map>
 __global__ __launch_bounds__(TPB) void k_text_parse(const unsigned char *__restrict__ t, long long n,
                                                     const int *__restrict__ block_off, const double *__restrict__ p10,
                                                     Map map, double *__restrict__ rho, long long *todo, int *n_todo,
-                                                    int todo_cap) {
+                                                    int todo_cap, int list_only) {
     const long long base = ((long long)blockIdx.x * TPB + threadIdx.x) * TXT_BYTES;
     const unsigned int starts = base < n ? txt_starts(t, base, n) : 0u;
     int total;
@@ -167,8 +172,9 @@ __global__ __launch_bounds__(TPB) void k_text_parse(const unsigned char *__restr
         if (!map.voxel(idx, vox)) continue;
         const long long at = base + (__ffs(m) - 1);
         double v;
-        if (txt_parse(t + at, t + n, p10, v)) map.store(rho, vox, v);
-        else {
+        if (txt_parse(t + at, t + n, p10, v)) {
+            if (!list_only) map.store(rho, vox, v);
+        } else {
             const int k = atomicAdd(n_todo, 1);
             if (k < todo_cap) { todo[2 * k] = at; todo[2 * k + 1] = idx; }
         }
