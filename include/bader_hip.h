@@ -168,7 +168,11 @@ int xb_vacuum_assign(xb_ctx *c, double vac_tol, double voxel_volume, double *vac
  * discovers maxima).  neargrid computes every voxel's own dr=0 trajectory -- the order-independent
  * map the reference's refinement converges to.
  * n_maxima: number of basins.  With several slabs the numbering is completed by
- * xb_assign_finish after the per-rank maxima tables were merged. */
+ * xb_assign_finish after the per-rank maxima tables were merged.
+ * XB_E_LIMIT: more maxima than the maxima table holds, min(N, 2^22) = 4 194 304 entries ("<count> maxima exceed the table
+ * capacity <capacity>"; exactly 2^22 maxima still fit).  The labels and xb_get_maxima's list are undefined after this refusal;
+ * nothing else is lost: the density stays resident, and the caller may upload another density or assign again (either method)
+ * on the same context -- it returns what a fresh context returns and holds the device memory a fresh one holds (xb_memory_stats). */
 int xb_assign(xb_ctx *c, int method, int64_t *n_maxima);
 /* bader_max of thread_handlers.py:75: voxel indices int64[n][3] in label order */
 int xb_get_maxima(xb_ctx *c, int64_t *maxima_out, int64_t capacity);
@@ -243,7 +247,8 @@ int xb_refine(xb_ctx *c, int mode, int64_t iters, int64_t *log, int64_t log_capa
 /* Bader.bader_calc + Bader.refine_volumes back to back, as Bader.__call__ issues them (interface.py:406-416, 471-490), in ONE call:
  * the refinement's first iteration is queued behind the assignment and one host wait serves both.  Results, maxima (xb_get_maxima)
  * and log equal xb_assign followed by xb_refine; combinations other than the one-GPU neargrid path without vacuum, and assignments
- * that do not end the usual way (tie voxels, walkers for the exact slow path), run as those two calls. */
+ * that do not end the usual way (tie voxels, walkers for the exact slow path, more than 2048 maxima), run as those two calls.
+ * XB_E_LIMIT: more than min(N, 2^22) maxima, as xb_assign states it, with the same leave to upload or assign again afterwards. */
 int xb_assign_refine(xb_ctx *c, int method, int mode, int64_t iters, int64_t *n_maxima, int64_t *log, int64_t log_capacity, int64_t *n_iters);
 
 /* utils.charge_sum (utils.py:235-252) via Bader.sum_volumes (interface.py:492-525) */
