@@ -378,7 +378,7 @@ int xb_weight_release(xb_ctx *c);
  *             not read at all (a context without one is accepted).
  * One workgroup per 8 x 8 x 8 tile of voxels.  It keeps the images whose distance from the tile's centre is at most d_min + 2 R +
  * slack (d_min the smallest such distance, R the tile's circumradius: no other image can be nearest, or tied for it, at any voxel of
- * the tile; csrc/k_voronoi.h derives the slack), compacts them into LDS and lets every voxel search those.  A tile that keeps more
+ * the tile; csrc/k_cell.h derives the slack), compacts them into LDS and lets every voxel search those.  A tile that keeps more
  * than XB_VORONOI_CAND_MAX images searches all 27 n from global memory; XB_VORONOI_FULL_SEARCH in `flags` makes every tile do so:
  * the second implementation, for tests and benchmarks -- both give the same labels.
  *   stats     NULL, or {tiles answered from a candidate list, tiles answered by the full search, the largest number of images a
@@ -734,7 +734,7 @@ int xb_regions_release(xb_ctx *c);
  *             of the context's device that overlaps neither the resident density nor the setup) -- exactly one of the two is
  *             non-null.  The promolecule reads no density: a context without one is accepted.
  * One workgroup per 8 x 8 x 8 tile of voxels.  It keeps the images within r_cut[s] + R + slack of the tile's centre (R the tile's
- * circumradius; csrc/k_hirshfeld.h derives the slack), compacts them IN LIST ORDER into LDS and lets every voxel run over those.  A
+ * circumradius; csrc/k_cell.h derives the slack), compacts them IN LIST ORDER into LDS and lets every voxel run over those.  A
  * tile that keeps more than XB_HIRSHFELD_CAND_MAX images runs over the whole list from global memory; XB_HIRSHFELD_FULL_SEARCH in
  * `flags` makes every tile do so: the second implementation, for tests and benchmarks -- both give the same bits.
  * XB_E_STATE: no grid, no setup for this grid's shape, no density where it is read, a context that holds a slab;

@@ -39,10 +39,7 @@ static int hs_ranges(const char *who, const double *lattice, const double *atoms
     if (n < 1) return fail(XB_E_ARG, "%s: %lld atoms", who, (long long)n);
     if (S < 1) return fail(XB_E_ARG, "%s: %lld species", who, (long long)S);
     if (n > XB_INT_MAX) return fail(XB_E_LIMIT, "%s: %lld atoms exceed %d", who, (long long)n, XB_INT_MAX);
-    for (int k = 0; k < 9; k++)
-        if (!std::isfinite(lattice[k])) return fail(XB_E_ARG, "%s: the lattice is not finite", who);
-    for (int64_t k = 0; k < 3 * n; k++)
-        if (!std::isfinite(atoms[k])) return fail(XB_E_ARG, "%s: atom %lld is not finite", who, (long long)(k / 3));
+    if (int rc = cell_check(who, lattice, atoms, n)) return rc;
     for (int64_t a = 0; a < n; a++)
         if (species[a] < 0 || species[a] >= S) return fail(XB_E_ARG, "%s: atom %lld has species %d, outside [0, %lld)", who, (long long)a, species[a], (long long)S);
     for (int64_t s = 0; s < S; s++)
@@ -159,25 +156,20 @@ static int hs_build(xb_ctx *c, const double lattice[9], const double *atoms_cart
         for (int x = lo[3 * a]; x <= hi[3 * a]; x++)
             for (int y = lo[3 * a + 1]; y <= hi[3 * a + 1]; y++)
                 for (int z = lo[3 * a + 2]; z <= hi[3 * a + 2]; z++, im++) {
-                    for (int j = 0; j < 3; j++)
-                        im->q[j] = atoms_cart[3 * a + j] + ((lattice[j] * (double)x + lattice[3 + j] * (double)y) + lattice[6 + j] * (double)z);
+                    for (int j = 0; j < 3; j++) im->q[j] = atoms_cart[3 * a + j] + cell_shift(lattice, x, y, z, j);
                     im->a = (int)a; im->s = species[a];
                 }
     double *buf = c->ptr<double>(BLK_HS);
     HIPCHK(hipMemcpyAsync(buf, host.data(), HS_HEAD * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(buf + o_sp, host.data() + o_sp, (o_acc - o_sp) * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    k_ms_tables<<<nblocks(3 * (long long)len), TPB, 0, c->stream>>>(g.nx, g.ny, g.nz, buf, buf + o_tab);
+    cell_tables(c, buf, buf + o_tab);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(c->stream));   // (`host` goes)
     HsGeom &G = c->hs_geom;
-    G.tab = buf + o_tab; G.img = reinterpret_cast<const HsImage *>(buf + o_img); G.sp = buf + o_sp;
+    cell_geom(G, g, lattice, HS_TILE, buf + o_tab);
+    G.img = reinterpret_cast<const HsImage *>(buf + o_img); G.sp = buf + o_sp;
     G.pairs = reinterpret_cast<const double2 *>(buf + o_pairs);
-    G.len = 0.;
-    for (int k = 0; k < 3; k++) G.len += std::sqrt((lattice[3 * k] * lattice[3 * k] + lattice[3 * k + 1] * lattice[3 * k + 1]) + lattice[3 * k + 2] * lattice[3 * k + 2]);
-    for (int k = 0; k < 9; k++) G.lat[k] = lattice[k];
     G.n_img = (unsigned int)count; G.K = (int)K;
-    G.nx = g.nx; G.ny = g.ny; G.nz = g.nz;
-    G.ntx = (g.nx + HS_TILE - 1) / HS_TILE; G.nty = (g.ny + HS_TILE - 1) / HS_TILE; G.ntz = (g.nz + HS_TILE - 1) / HS_TILE;
     c->hs_n = n; c->hs_acc = o_acc;
     c->hs_have = true;
     return XB_OK;
@@ -228,12 +220,7 @@ int xb_hirshfeld_sum(xb_ctx *c, double voxel_volume, int flags, double *charge, 
     memcpy(st, &res[2 * n + 2], sizeof st);
     rest[0] = res[2 * n] * voxel_volume;
     rest[1] = (double)cn * voxel_volume;
-    if (stats) {
-        const long long full = forced ? tiles : (long long)st[0];
-        stats[0] = tiles - full;
-        stats[1] = full;
-        stats[2] = st[1];
-    }
+    tile_route_stats(stats, tiles, forced, st);
     return XB_OK;
 }
 

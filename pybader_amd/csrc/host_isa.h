@@ -123,10 +123,9 @@ int xb_isa_iterate(xb_ctx *c, int64_t iters, int flags, int64_t *qsum_out, int64
     HIPCHK(hipStreamSynchronize(c->stream));   // the one wait of the call
     c->hs_have = true;
     const long long tiles = hirshfeld_tiles(c->hs_geom);
-    if (stats) {
-        const long long full = forced ? tiles : (long long)(st[0] / (unsigned long long)iters);   // (every iteration counted them)
-        stats[0] = tiles - full; stats[1] = full; stats[2] = st[1]; stats[3] = (long long)(res.back() / (unsigned long long)iters);
-    }
+    st[0] = (unsigned int)(st[0] / (unsigned long long)iters);   // (every iteration counted the overflowing tiles)
+    tile_route_stats(stats, tiles, forced, st);
+    if (stats) stats[3] = (long long)(res.back() / (unsigned long long)iters);
     // with a voxel beyond the bound every update wrote the old tables again: both areas hold what the call found
     if (res.back())
         return fail(XB_E_ARG, "xb_isa_iterate: %llu voxels of the density lie beyond rho_bound = %g", res.back() / (unsigned long long)iters, c->isa_bound);

@@ -10,12 +10,9 @@
 // Image i of species s is kept iff  d_c(i) <= r_cut[s] + R + slack:  |d(v, i) - d_c(i)| <= R for a voxel v of the tile, so a
 // dropped image lies at or beyond r_cut from every voxel of the tile and its term is the exact zero of the definition.
 //
-// SLACK.  As k_voronoi.h derives it (u = 2^-53, L = |a| + |b| + |c|): positions carry at most 4 u L per component, so
-// max_v D(pc(v), c) <= R_exact + 14 u L and the computed R >= R_exact (1 - 8 u); a computed d2 carries (1 + u)^5 on D^2, its root
-// 3 u D; rc2 = r_cut * r_cut carries one u, its root half of one.  A voxel with computed d2(v, i) < rc2 therefore has
-// D(c, i) <= (r_cut + R) (1 + 8 u) + 28 u L, and squaring the threshold adds a few u more: all below 64 u (r_cut + R + L).  The
-// kernel adds 2^-40 (r_cut + R + L) before squaring and 2^-40 of the square after, more than a hundred times the need.  Here the
-// slack only has to be conservative: an image kept without need adds +0 to every voxel -- time, not bits.
+// SLACK (k_cell.h derives it, with lim = r_cut + R).  rc2 = r_cut * r_cut carries one u, its root half of one: a voxel with
+// computed d2(v, i) < rc2 has  D(c, i) <= (r_cut + R) (1 + 8 u) + 28 u L.  Here the slack only has to be conservative: an image
+// kept without need adds +0 to every voxel -- time, not bits.
 //
 // THE ORDER MATTERS (unlike k_voronoi's): P and p_a are running sums in the canonical order of the image list.  The survivors
 // are compacted deterministically, a round of 256 images at a time: a ballot per wave, the four wave counts through LDS (two sets
@@ -56,29 +53,33 @@ enum { HS_SUM = 0, HS_PRO = 1, HS_DEF = 2 };
 struct HsCand { double q[3]; double rc2, ih2; int a, s; };   // 48 B
 struct HsImage { double q[3]; int a, s; };                   // 32 B, the list of the setup
 
-struct HsGeom {
-    const double *tab;        // the position table of k_ms_tables
+struct HsGeom : CellGeom {
     const HsImage *img;       // the canonical image list
     const double *sp;         // per species: r_cut, rc2, inv_h2
     const double2 *pairs;     // per species K pairs (f[k], f[k+1] - f[k])
-    double lat[9];
-    double len;               // L = |a| + |b| + |c|
     unsigned int n_img;
     int K;
-    int nx, ny, nz;
-    int ntx, nty, ntz;
 };
 
+// the term of one image at one voxel, and its shell (-1: d2 >= rc2); pr = nullptr (k_isa's counting pass): the shell alone
 __device__ __forceinline__ double hs_term(const double pc[3], double q0, double q1, double q2, double rc2, double ih2,
-                                          const double2 *__restrict__ pr, int K) {
-    const double e0 = pc[0] - q0, e1 = pc[1] - q1, e2 = pc[2] - q2;
-    const double d2 = (e0 * e0 + e1 * e1) + e2 * e2;
+                                          const double2 *__restrict__ pr, int K, int &shell) {
+    const double d2 = cell_d2(pc, q0, q1, q2);
+    shell = -1;
     if (d2 >= rc2) return 0.;
     const double u = d2 * ih2;
     const int k = min((int)u, K - 1);
+    shell = k;
+    if (!pr) return 0.;
     const double t = u - (double)k;
     const double2 f = pr[k];
     return f.x + t * f.y;
+}
+__device__ __forceinline__ double hs_term(const double pc[3], double q0, double q1, double q2, double rc2, double ih2,
+                                          const double2 *__restrict__ pr, int K) {
+    int shell;
+    __builtin_assume(pr != nullptr);   // (the Hirshfeld kernels always have a table: no test of it per term)
+    return hs_term(pc, q0, q1, q2, rc2, ih2, pr, K, shell);
 }
 __device__ __forceinline__ double hs_wave_sum(double v) {
 #pragma unroll
@@ -86,11 +87,9 @@ __device__ __forceinline__ double hs_wave_sum(double v) {
     return v;
 }
 
-// the two voxels of a thread in phase 2
-struct HsVox {
-    double pa[3], pb[3];
+// the two voxels of a thread in phase 2 (cell_two_voxels), their P and their density
+struct HsVox : CellVox {
     double Pa, Pb, ra, rb;
-    bool oka, okb;
 };
 
 // one atom's run is over: w_a and term_a of the two voxels, over the wave; lane 0 gets the sums (false: the wave holds none)
@@ -110,33 +109,8 @@ __device__ __forceinline__ unsigned int hs_candidates(const HsGeom &G, int x0, i
                                                       unsigned int *stats) {
     const int tid = threadIdx.x, lane = tid % XB_WAVE, wave = tid / XB_WAVE;
     unsigned int cnt = 0;
-    // the clipped extent of the tile, in steps; its centre and circumradius (k_voronoi's expressions)
-    const double ex = (double)(min(HS_TILE, G.nx - x0) - 1), ey = (double)(min(HS_TILE, G.ny - y0) - 1),
-                 ez = (double)(min(HS_TILE, G.nz - z0) - 1);
-    const double fx = (double)x0 + 0.5 * ex, fy = (double)y0 + 0.5 * ey, fz = (double)z0 + 0.5 * ez;
-    double c[3], diag2 = 0.;
-    double u[3][3];
-#pragma unroll
-    for (int j = 0; j < 3; j++) {
-        c[j] = G.lat[j] * fx / (double)G.nx;
-        c[j] += G.lat[3 + j] * fy / (double)G.ny;
-        c[j] += G.lat[6 + j] * fz / (double)G.nz;
-        u[0][j] = G.lat[j] * ex / (double)G.nx;
-        u[1][j] = G.lat[3 + j] * ey / (double)G.ny;
-        u[2][j] = G.lat[6 + j] * ez / (double)G.nz;
-    }
-#pragma unroll
-    for (int s = 0; s < 4; s++) {
-        const double s1 = (s & 1) ? -1. : 1., s2 = (s & 2) ? -1. : 1.;
-        double d2 = 0.;
-#pragma unroll
-        for (int j = 0; j < 3; j++) {
-            const double d = (u[0][j] + s1 * u[1][j]) + s2 * u[2][j];
-            d2 += d * d;
-        }
-        diag2 = fmax(diag2, d2);
-    }
-    const double R = 0.5 * sqrt(diag2);
+    double c[3];
+    const double R = 0.5 * sqrt(cell_tile_ball<HS_TILE>(G, x0, y0, z0, c));
     // keep and compact in the list's order (every thread runs every round: the barrier is uniform; n_img + 256 fits 32 bits)
     int flip = 0;
     for (unsigned int base = 0; base < G.n_img; base += 256u, flip ^= 1) {
@@ -147,13 +121,8 @@ __device__ __forceinline__ unsigned int hs_candidates(const HsGeom &G, int x0, i
         if (idx < G.n_img) {
             im = G.img[idx];
             const double *sp = G.sp + 3 * (size_t)im.s;
-            double lim = sp[0] + R;
-            lim += 0x1p-40 * (lim + G.len);
-            double lim2 = lim * lim;
-            lim2 += 0x1p-40 * lim2;
             rc2 = sp[1]; ih2 = sp[2];
-            const double e0 = c[0] - im.q[0], e1 = c[1] - im.q[1], e2 = c[2] - im.q[2];
-            keep = (e0 * e0 + e1 * e1) + e2 * e2 <= lim2;
+            keep = cell_d2(c, im.q[0], im.q[1], im.q[2]) <= cell_slack2(sp[0] + R, G.len);
         }
         const unsigned long long mask = __ballot(keep);
         if (lane == 0) s_wcnt[flip][wave] = (unsigned int)__popcll(mask);
@@ -173,29 +142,6 @@ __device__ __forceinline__ unsigned int hs_candidates(const HsGeom &G, int x0, i
         if (cnt > (unsigned int)XB_HIRSHFELD_CAND_MAX) atomicAdd(&stats[0], 1u);
     }
     return cnt;
-}
-
-// phase 2 begins: the positions of this thread's two voxels of the tile at (x0, y0, z0), whether the grid holds them, their indices
-__device__ __forceinline__ void hs_voxels(const HsGeom &G, int x0, int y0, int z0, HsVox &V, size_t &va, size_t &vb) {
-    const int lane = threadIdx.x % XB_WAVE, wave = threadIdx.x / XB_WAVE;
-    const int len = G.nx + G.ny + G.nz;
-    const int py = y0 + lane / HS_TILE, pz = z0 + lane % HS_TILE;
-    const int pxa = x0 + wave, pxb = x0 + wave + 4;
-    const int cy = min(py, G.ny - 1), cz = min(pz, G.nz - 1), cxa = min(pxa, G.nx - 1), cxb = min(pxb, G.nx - 1);
-#pragma unroll
-    for (int j = 0; j < 3; j++) {
-        const double *tj = G.tab + (size_t)j * len;
-        V.pa[j] = tj[cxa];
-        V.pa[j] += tj[G.nx + cy];
-        V.pa[j] += tj[G.nx + G.ny + cz];
-        V.pb[j] = tj[cxb];
-        V.pb[j] += tj[G.nx + cy];
-        V.pb[j] += tj[G.nx + G.ny + cz];
-    }
-    V.oka = py < G.ny && pz < G.nz && pxa < G.nx;
-    V.okb = py < G.ny && pz < G.nz && pxb < G.nx;
-    const size_t row = (size_t)cy * G.nz + cz, plane = (size_t)G.ny * G.nz;
-    va = (size_t)cxa * plane + row; vb = (size_t)cxb * plane + row;
 }
 
 // pass 1: P of the two voxels, over the tile's candidates in order or (full) over the whole list
@@ -244,94 +190,85 @@ __global__ __launch_bounds__(256, MODE == HS_SUM ? HS_SUM_WAVES : 8) void k_hirs
     const bool by_atom = n_atoms <= XB_HIRSHFELD_CAND_MAX;
     const int ntiles = G.ntx * G.nty * G.ntz;
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-    int t = tile;
-    const int tz = t % G.ntz; t /= G.ntz;
-    const int ty = t % G.nty;
-    const int tx = t / G.nty;
-    const int x0 = tx * HS_TILE, y0 = ty * HS_TILE, z0 = tz * HS_TILE;
-    const unsigned int cnt = forced ? 0u : hs_candidates(G, x0, y0, z0, s_cand, s_wcnt, stats);
-    __syncthreads();   // the candidates and the cleared bins
-    const bool full = forced || cnt > (unsigned int)XB_HIRSHFELD_CAND_MAX;
-    // phase 2: this thread's two voxels (indices clamped into the grid; a voxel outside it is neither stored nor summed)
-    HsVox V;
-    size_t va, vb;
-    hs_voxels(G, x0, y0, z0, V, va, vb);
-    hs_total(G, V, s_cand, cnt, full);   // pass 1: P
-    if (MODE != HS_SUM) {
-        if (V.oka) out[va] = MODE == HS_PRO ? V.Pa : rho[va] - V.Pa;
-        if (V.okb) out[vb] = MODE == HS_PRO ? V.Pb : rho[vb] - V.Pb;
-    }
-    int nslots = 0;
-    if (MODE == HS_SUM) {
-    V.ra = V.oka ? rho[va] : 0.;
-    V.rb = V.okb ? rho[vb] : 0.;
-    // the rest: voxels no pro-atom reaches
-    {
-        const bool za = V.oka && !(V.Pa > 0.), zb = V.okb && !(V.Pb > 0.);
-        if (__ballot(za || zb)) {
-            const double s = hs_wave_sum((za ? V.ra : 0.) + (zb ? V.rb : 0.));
-            const unsigned int m = (unsigned int)__popcll(__ballot(za)) + (unsigned int)__popcll(__ballot(zb));
-            if (lane == 0) { atomicAdd(&s_rest, s); atomicAdd(&s_restn, m); }
+        int x0, y0, z0;
+        cell_tile_origin<HS_TILE>(G, tile, x0, y0, z0);
+        const unsigned int cnt = forced ? 0u : hs_candidates(G, x0, y0, z0, s_cand, s_wcnt, stats);
+        __syncthreads();   // the candidates and the cleared bins
+        const bool full = forced || cnt > (unsigned int)XB_HIRSHFELD_CAND_MAX;
+        // phase 2: this thread's two voxels (indices clamped into the grid; a voxel outside it is neither stored nor summed)
+        HsVox V;
+        cell_two_voxels<HS_TILE>(G, x0, y0, z0, V);
+        hs_total(G, V, s_cand, cnt, full);   // pass 1: P
+        if (MODE != HS_SUM) {
+            if (V.oka) out[V.va] = MODE == HS_PRO ? V.Pa : rho[V.va] - V.Pa;
+            if (V.okb) out[V.vb] = MODE == HS_PRO ? V.Pb : rho[V.vb] - V.Pb;
         }
-    }
-    // pass 2: p_a over each run of one atom
-    double tc = 0., tv = 0.;
-    if (!full) {
-        int cur = -1;
-        double pa_ = 0., pb_ = 0.;
-        for (unsigned int k = 0; k < cnt; k++) {
-            const HsCand &d = s_cand[k];
-            const int a = d.a;
-            if (a != cur) {
-                if (cur >= 0 && hs_close_run(V, pa_, pb_, tc, tv) && lane == 0) {
-                    const int bin = by_atom ? cur : nslots - 1;
-                    atomicAdd(&s_binc[bin], tc); atomicAdd(&s_binv[bin], tv);
+        int nslots = 0;
+        if (MODE == HS_SUM) {
+            V.ra = V.oka ? rho[V.va] : 0.;
+            V.rb = V.okb ? rho[V.vb] : 0.;
+            // the rest: voxels no pro-atom reaches
+            {
+                const bool za = V.oka && !(V.Pa > 0.), zb = V.okb && !(V.Pb > 0.);
+                if (__ballot(za || zb)) {
+                    const double s = hs_wave_sum((za ? V.ra : 0.) + (zb ? V.rb : 0.));
+                    const unsigned int m = (unsigned int)__popcll(__ballot(za)) + (unsigned int)__popcll(__ballot(zb));
+                    if (lane == 0) { atomicAdd(&s_rest, s); atomicAdd(&s_restn, m); }
                 }
-                if (tid == 0 && !by_atom) s_bina[nslots] = a;
-                nslots++;
-                cur = a; pa_ = 0.; pb_ = 0.;
             }
-            const double q0 = d.q[0], q1 = d.q[1], q2 = d.q[2], rc2 = d.rc2, ih2 = d.ih2;
-            const double2 *pr = G.pairs + (size_t)d.s * G.K;
-            pa_ += hs_term(V.pa, q0, q1, q2, rc2, ih2, pr, G.K);
-            pb_ += hs_term(V.pb, q0, q1, q2, rc2, ih2, pr, G.K);
-        }
-        if (cur >= 0 && hs_close_run(V, pa_, pb_, tc, tv) && lane == 0) {
-            const int bin = by_atom ? cur : nslots - 1;
-            atomicAdd(&s_binc[bin], tc); atomicAdd(&s_binv[bin], tv);
-        }
-    } else {
-        int cur = -1;
-        double pa_ = 0., pb_ = 0.;
-        for (unsigned int k = 0; k <= G.n_img; k++) {   // (one step past the list closes the last run)
-            const bool end = k == G.n_img;
-            const HsImage im = G.img[end ? 0u : k];
-            if (end || im.a != cur) {
-                if (cur >= 0 && hs_close_run(V, pa_, pb_, tc, tv) && lane == 0) {
-                    if (by_atom) { atomicAdd(&s_binc[cur], tc); atomicAdd(&s_binv[cur], tv); }
-                    else { atomicAdd(&acc[cur], tc); atomicAdd(&acc[n_atoms + cur], tv); }
+            // pass 2: p_a over each run of one atom.  A run of atom `cur` is over (every lane calls it): close the run, and lane 0 adds
+            // the wave's sums into the atom's bin -- s_binc, s_binv[bin] in LDS, or its result in global memory
+            int cur = -1;
+            double pa_ = 0., pb_ = 0.;
+            auto add_run = [&](bool lds, int bin) {
+                double tc, tv;
+                if (cur < 0 || !hs_close_run(V, pa_, pb_, tc, tv) || lane != 0) return;
+                if (lds) { atomicAdd(&s_binc[bin], tc); atomicAdd(&s_binv[bin], tv); }
+                else { atomicAdd(&acc[cur], tc); atomicAdd(&acc[n_atoms + cur], tv); }
+            };
+            if (!full) {
+                for (unsigned int k = 0; k < cnt; k++) {
+                    const HsCand &d = s_cand[k];
+                    const int a = d.a;
+                    if (a != cur) {
+                        add_run(true, by_atom ? cur : nslots - 1);
+                        if (tid == 0 && !by_atom) s_bina[nslots] = a;
+                        nslots++;
+                        cur = a; pa_ = 0.; pb_ = 0.;
+                    }
+                    const double q0 = d.q[0], q1 = d.q[1], q2 = d.q[2], rc2 = d.rc2, ih2 = d.ih2;
+                    const double2 *pr = G.pairs + (size_t)d.s * G.K;
+                    pa_ += hs_term(V.pa, q0, q1, q2, rc2, ih2, pr, G.K);
+                    pb_ += hs_term(V.pb, q0, q1, q2, rc2, ih2, pr, G.K);
                 }
-                if (end) break;
-                cur = im.a; pa_ = 0.; pb_ = 0.;
+                add_run(true, by_atom ? cur : nslots - 1);
+            } else {
+                for (unsigned int k = 0; k <= G.n_img; k++) {   // (one step past the list closes the last run)
+                    const bool end = k == G.n_img;
+                    const HsImage im = G.img[end ? 0u : k];
+                    if (end || im.a != cur) {
+                        add_run(by_atom, cur);
+                        if (end) break;
+                        cur = im.a; pa_ = 0.; pb_ = 0.;
+                    }
+                    const double *sp = G.sp + 3 * (size_t)im.s;
+                    const double rc2 = sp[1], ih2 = sp[2];
+                    const double2 *pr = G.pairs + (size_t)im.s * G.K;
+                    pa_ += hs_term(V.pa, im.q[0], im.q[1], im.q[2], rc2, ih2, pr, G.K);
+                    pb_ += hs_term(V.pb, im.q[0], im.q[1], im.q[2], rc2, ih2, pr, G.K);
+                }
+                nslots = 0;   // (no slot bins on this route)
             }
-            const double *sp = G.sp + 3 * (size_t)im.s;
-            const double rc2 = sp[1], ih2 = sp[2];
-            const double2 *pr = G.pairs + (size_t)im.s * G.K;
-            pa_ += hs_term(V.pa, im.q[0], im.q[1], im.q[2], rc2, ih2, pr, G.K);
-            pb_ += hs_term(V.pb, im.q[0], im.q[1], im.q[2], rc2, ih2, pr, G.K);
         }
-        nslots = 0;   // (no slot bins on this route)
-    }
-    }
-    __syncthreads();   // every wave is done with the candidates; the tile's bins are complete
-    if (MODE == HS_SUM && !by_atom && tid < nslots) {   // (nslots <= cnt <= 256: a bin per thread)
-        if (s_binc[tid] != 0. || s_binv[tid] != 0.) {
-            const int a = s_bina[tid];
-            atomicAdd(&acc[a], s_binc[tid]);
-            atomicAdd(&acc[n_atoms + a], s_binv[tid]);
+        __syncthreads();   // every wave is done with the candidates; the tile's bins are complete
+        if (MODE == HS_SUM && !by_atom && tid < nslots) {   // (nslots <= cnt <= 256: a bin per thread)
+            if (s_binc[tid] != 0. || s_binv[tid] != 0.) {
+                const int a = s_bina[tid];
+                atomicAdd(&acc[a], s_binc[tid]);
+                atomicAdd(&acc[n_atoms + a], s_binv[tid]);
+            }
+            s_binc[tid] = 0.; s_binv[tid] = 0.;   // (the next tile's first atomic lies behind its own barrier)
         }
-        s_binc[tid] = 0.; s_binv[tid] = 0.;   // (the next tile's first atomic lies behind its own barrier)
-    }
     }
     if (MODE != HS_SUM) return;
     if (by_atom && tid < n_atoms && (s_binc[tid] != 0. || s_binv[tid] != 0.)) {

@@ -3,10 +3,10 @@
 // DESIGN.md section 23).  Included by bader_hip.hip after k_hirshfeld.h, whose phases it calls.
 #pragma once
 
-// k_isa runs k_hirshfeld's tile: phase 1 (hs_candidates), the two voxels of a thread (hs_voxels), pass 1 (hs_total, with the
+// k_isa runs k_hirshfeld's tile: phase 1 (hs_candidates), the two voxels of a thread (cell_two_voxels), pass 1 (hs_total, with the
 // table pairs (A[a][k], +0.0): the same code, the same bits as the field kernels form).  Pass 2 is new: every (voxel, image) pair
-// with a term gets its shell k and its integer share q, and q goes into bin[a][k].  The bins are 64-bit INTEGERS, so the order of the
-// atomics is free and every bin is bit-defined; a negative q is added as its two's complement.
+// with a term gets its shell k (hs_term forms it with the term) and its integer share q, and q goes into bin[a][k].  The bins are
+// 64-bit INTEGERS, so the order of the atomics is free and every bin is bit-defined; a negative q is added as its two's complement.
 //   ISA_COUNT  q = 1 for every pair with d2 < rc2 (no density, no P): count[a][k], once per setup
 //   ISA_SHELL  q = llrint(ldexp(rho * (term / P), e)) for P > 0 and term > 0
 //
@@ -32,21 +32,6 @@ struct IsaArgs {
     int direct;                 // route (a) for every tile
 };
 
-// hs_term's expressions, and the shell as well (-1: d2 >= rc2)
-__device__ __forceinline__ double isa_term(const double pc[3], double q0, double q1, double q2, double rc2, double ih2,
-                                           const double2 *__restrict__ pr, int K, int &shell) {
-    const double e0 = pc[0] - q0, e1 = pc[1] - q1, e2 = pc[2] - q2;
-    const double d2 = (e0 * e0 + e1 * e1) + e2 * e2;
-    shell = -1;
-    if (d2 >= rc2) return 0.;
-    const double u = d2 * ih2;
-    const int k = min((int)u, K - 1);
-    shell = k;
-    if (!pr) return 0.;
-    const double t = u - (double)k;
-    const double2 f = pr[k];
-    return f.x + t * f.y;
-}
 // the integer share of one pair (0: none)
 template <int MODE>
 __device__ __forceinline__ long long isa_share(bool ok, int shell, double term, double P, double rho, int e) {
@@ -71,22 +56,18 @@ __global__ __launch_bounds__(256) void k_isa(HsGeom G, const double *__restrict_
     for (int j = lane; j < ISA_WIN; j += XB_WAVE) s_win[wave][j] = 0ull;
     const int ntiles = G.ntx * G.nty * G.ntz;
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        int t = tile;
-        const int tz = t % G.ntz; t /= G.ntz;
-        const int ty = t % G.nty;
-        const int tx = t / G.nty;
-        const int x0 = tx * HS_TILE, y0 = ty * HS_TILE, z0 = tz * HS_TILE;
+        int x0, y0, z0;
+        cell_tile_origin<HS_TILE>(G, tile, x0, y0, z0);
         const unsigned int cnt = forced ? 0u : hs_candidates(G, x0, y0, z0, s_cand, s_wcnt, stats);
         __syncthreads();   // the candidates
         const bool full = forced || cnt > (unsigned int)XB_HIRSHFELD_CAND_MAX;
         HsVox V;
-        size_t va, vb;
-        hs_voxels(G, x0, y0, z0, V, va, vb);
+        cell_two_voxels<HS_TILE>(G, x0, y0, z0, V);
         V.Pa = 0.; V.Pb = 0.; V.ra = 0.; V.rb = 0.;
         if (MODE == ISA_SHELL) {
             hs_total(G, V, s_cand, cnt, full);
-            V.ra = V.oka ? rho[va] : 0.;
-            V.rb = V.okb ? rho[vb] : 0.;
+            V.ra = V.oka ? rho[V.va] : 0.;
+            V.rb = V.okb ? rho[V.vb] : 0.;
             // a density beyond the bound could overflow a bin: such a voxel adds nothing and makes the call fail
             const bool xa = !(fabs(V.ra) <= A.rho_bound), xb = !(fabs(V.rb) <= A.rho_bound);
             if (xa) V.oka = false;
@@ -99,8 +80,8 @@ __global__ __launch_bounds__(256) void k_isa(HsGeom G, const double *__restrict_
                 const HsCand &d = s_cand[i];
                 const double2 *pr = MODE == ISA_SHELL ? G.pairs + (size_t)d.s * G.K : nullptr;
                 int ka, kb;
-                const double ta = isa_term(V.pa, d.q[0], d.q[1], d.q[2], d.rc2, d.ih2, pr, G.K, ka);
-                const double tb = isa_term(V.pb, d.q[0], d.q[1], d.q[2], d.rc2, d.ih2, pr, G.K, kb);
+                const double ta = hs_term(V.pa, d.q[0], d.q[1], d.q[2], d.rc2, d.ih2, pr, G.K, ka);
+                const double tb = hs_term(V.pb, d.q[0], d.q[1], d.q[2], d.rc2, d.ih2, pr, G.K, kb);
                 const long long qa = isa_share<MODE>(V.oka, ka, ta, V.Pa, V.ra, A.e), qb = isa_share<MODE>(V.okb, kb, tb, V.Pb, V.rb, A.e);
                 if (!__ballot(qa != 0 || qb != 0)) continue;   // (wave-uniform)
                 int kmin = min(qa != 0 ? ka : G.K, qb != 0 ? kb : G.K);
@@ -141,8 +122,8 @@ __global__ __launch_bounds__(256) void k_isa(HsGeom G, const double *__restrict_
                 }
                 const double2 *pr = MODE == ISA_SHELL ? G.pairs + (size_t)s * G.K : nullptr;
                 int ka, kb;
-                const double ta = isa_term(V.pa, q0, q1, q2, rc2, ih2, pr, G.K, ka);
-                const double tb = isa_term(V.pb, q0, q1, q2, rc2, ih2, pr, G.K, kb);
+                const double ta = hs_term(V.pa, q0, q1, q2, rc2, ih2, pr, G.K, ka);
+                const double tb = hs_term(V.pb, q0, q1, q2, rc2, ih2, pr, G.K, kb);
                 const long long qa = isa_share<MODE>(V.oka, ka, ta, V.Pa, V.ra, A.e), qb = isa_share<MODE>(V.okb, kb, tb, V.Pb, V.rb, A.e);
                 unsigned long long *row = A.bins + (size_t)a * G.K;
                 if (qa != 0) atomicAdd(&row[ka], (unsigned long long)qa);

@@ -25,8 +25,7 @@
 // host as (lat[j] * x + lat[3 + j] * y) + lat[6 + j] * z (IEEE, no contraction) and passed by value (scalar loads)
 struct MsImages { double pbc[27][3]; };
 
-// tab: the three terms of the voxel position per axis index, pos[j][p] = lat[3 * axis + j] * p / n_axis, laid out
-// tab[j * (nx + ny + nz) + offset(axis) + p]; pbc_dev: MsImages again, for the one lookup by a per-lane index
+// tab: the position table of k_ms_tables (k_cell.h); pbc_dev: MsImages again, for the one lookup by a per-lane index
 struct MsGeom {
     const double *tab;
     const double *pbc_dev;
@@ -34,39 +33,20 @@ struct MsGeom {
     int nx, ny, nz, nyz;
 };
 
-__global__ __launch_bounds__(TPB) void k_ms_tables(int nx, int ny, int nz, const double *__restrict__ lat, double *__restrict__ tab) {
-    const int len = nx + ny + nz, t = blockIdx.x * TPB + threadIdx.x;
-    if (t >= 3 * len) return;
-    const int j = t / len, q = t - j * len;
-    const int axis = q < nx ? 0 : (q < nx + ny ? 1 : 2);
-    const int p = axis == 0 ? q : (axis == 1 ? q - nx : q - nx - ny);
-    const int n = axis == 0 ? nx : (axis == 1 ? ny : nz);
-    tab[t] = lat[3 * axis + j] * (double)p / (double)n;
-}
-
 // the ten terms of voxel v with label a (0 <= a < n) and density w
 __device__ __forceinline__ void ms_terms(const MsGeom &G, const MsImages &I, int v, int a, double w, double t[MS_TERMS]) {
     const int p0 = v / G.nyz;
     const int r = v - p0 * G.nyz;
     const int p1 = r / G.nz, p2 = r - p1 * G.nz;
-    const int len = G.nx + G.ny + G.nz;
     double pc[3], ce[3];
+    cell_pos(G.tab, G.nx, G.ny, G.nz, p0, p1, p2, pc);
 #pragma unroll
-    for (int j = 0; j < 3; j++) {
-        const double *tj = G.tab + (size_t)j * len;
-        pc[j] = tj[p0];
-        pc[j] += tj[G.nx + p1];
-        pc[j] += tj[G.nx + G.ny + p2];
-        ce[j] = G.centres[3 * (size_t)a + j];
-    }
+    for (int j = 0; j < 3; j++) ce[j] = G.centres[3 * (size_t)a + j];
     double best = 1.7976931348623157e308;
     int which = 0;
 #pragma unroll
     for (int i = 0; i < 27; i++) {
-        const double e0 = pc[0] - (ce[0] + I.pbc[i][0]);
-        const double e1 = pc[1] - (ce[1] + I.pbc[i][1]);
-        const double e2 = pc[2] - (ce[2] + I.pbc[i][2]);
-        const double d2 = (e0 * e0 + e1 * e1) + e2 * e2;
+        const double d2 = cell_d2(pc, ce[0] + I.pbc[i][0], ce[1] + I.pbc[i][1], ce[2] + I.pbc[i][2]);
         if (d2 < best) { best = d2; which = i; }
     }
     double d[3];

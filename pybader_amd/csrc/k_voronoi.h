@@ -15,20 +15,12 @@
 // a dropped image is farther from every voxel of the tile than the image of d_min is.  Everything is compared squared; the one
 // square root is d_min's.
 //
-// SLACK.  Read the computed float64 triples -- pc(v) of a voxel, c, q(i) = atom + pbc of an image -- as exact points and write D for
-// exact distances between them, u = 2^-53.  Let L = |a| + |b| + |c| of the cell.
-//   (a) pc(v) and c are sums of three terms lat * p / n, each rounded twice, added with two roundings: every component lies within
-//       4 u L of the exact position, so  max_v D(pc(v), c) <= R_exact + 14 u L,  and the computed R >= R_exact (1 - 8 u).
-//   (b) the computed d2 = (e0 e0 + e1 e1) + e2 e2 with e = pc - q carries at most (1 + u)^5 on D^2: its root lies within 3 u D of D.
-//       The computed d_c^2 likewise; d_min's computed root adds one u.
-//   (c) w wins, or ties in computed d2, at voxel v; m is the image of d_min.  computed d2(v, w) <= computed d2(v, m) gives
-//       D(v, w) (1 - 3 u) <= D(v, m) (1 + 3 u), and with the triangle inequality and (a)
-//       D(c, w) <= D(c, m) + 2 R + (7 u + ...) (D(c, m) + 2 R) + 28 u L.
-//   (d) squaring the threshold and the sums that form it add a few u more.
-// All of it is below 64 u (d_min + 2 R + L).  The kernel adds 2^-40 (d_min + 2 R + L) = 8192 u (...) before squaring and 2^-40 of
-// the square after: more than a hundred times the need, and about 1e-12 of the radius, so it keeps no candidate a sharp bound would
-// drop unless the image is tied to that precision.  A computed tie satisfies (c) like a win: an image tied with the winner is kept,
-// so the lexicographic minimum of (d2, atom) over the candidates is the one over all images.
+// SLACK (k_cell.h derives it, with lim = d_min + 2 R).  Here it decides labels, so ties matter.  w wins, or ties in computed d2, at
+// voxel v; m is the image of d_min.  computed d2(v, w) <= computed d2(v, m) gives  D(v, w) (1 - 3 u) <= D(v, m) (1 + 3 u),  hence
+// D(c, w) <= D(c, m) + 2 R + (7 u + ...) (D(c, m) + 2 R) + 28 u L;  d_min's computed root adds one u.  The slack is about 1e-12 of
+// the radius, so it keeps no candidate a sharp bound would drop unless the image is tied to that precision.  A computed tie
+// satisfies the comparison like a win: an image tied with the winner is kept, so the lexicographic minimum of (d2, atom) over the
+// candidates is the one over all images.
 //
 // The survivors go to LDS as q and the atom's index, compacted per wave by ballot and prefix count (their order is free: a
 // lexicographic minimum does not depend on it).  XB_VORONOI_CAND_MAX = 512 candidates of 32 B are 16 KiB, with the image vectors and
@@ -43,23 +35,15 @@
 
 struct VoCand { double q[3]; int a; int pad; };   // 32 B: two 16-byte LDS reads
 
-struct VoGeom {
-    const double *tab;      // the position table of k_ms_tables
+struct VoGeom : CellGeom {
     const double *pbc;      // 27 image vectors, [i][j]
     const double *atoms;    // n * 3, Cartesian
-    double lat[9];
-    double len;             // L = |a| + |b| + |c|
-    int nx, ny, nz, n;
-    int ntx, nty, ntz;      // tiles per axis
+    int n;
 };
 
 // the lexicographic minimum of (d2, a), in any order of the calls
 __device__ __forceinline__ void vo_take(double d2, int a, double &best, int &who) {
     if (d2 < best || (d2 == best && a < who)) { best = d2; who = a; }
-}
-__device__ __forceinline__ double vo_d2(const double pc[3], double q0, double q1, double q2) {
-    const double e0 = pc[0] - q0, e1 = pc[1] - q1, e2 = pc[2] - q2;
-    return (e0 * e0 + e1 * e1) + e2 * e2;
 }
 
 // stats: [0] tiles answered by the full search, [1] the largest candidate count (both untouched when `forced`)
@@ -70,60 +54,29 @@ __global__ __launch_bounds__(256) void k_voronoi(VoGeom G, const double *__restr
     __shared__ double s_red[4];
     __shared__ int s_cnt;
     const int tid = threadIdx.x, lane = tid % XB_WAVE, wave = tid / XB_WAVE;
-    int t = blockIdx.x;
-    const int tz = t % G.ntz; t /= G.ntz;
-    const int ty = t % G.nty;
-    const int tx = t / G.nty;
-    const int x0 = tx * VO_TILE, y0 = ty * VO_TILE, z0 = tz * VO_TILE;
+    int x0, y0, z0;
+    cell_tile_origin<VO_TILE>(G, blockIdx.x, x0, y0, z0);
     if (tid < 81) s_pbc[tid] = G.pbc[tid];
     if (tid == 0) s_cnt = 0;
     __syncthreads();
     const unsigned int total = 27u * (unsigned int)G.n;   // (n <= INT_MAX / 27, checked on the host: total + 256 fits 32 bits)
     int cnt = 0;
     if (!forced) {
-        // the clipped extent of the tile, in steps; its centre and circumradius
-        const double ex = (double)(min(VO_TILE, G.nx - x0) - 1), ey = (double)(min(VO_TILE, G.ny - y0) - 1),
-                     ez = (double)(min(VO_TILE, G.nz - z0) - 1);
-        const double fx = (double)x0 + 0.5 * ex, fy = (double)y0 + 0.5 * ey, fz = (double)z0 + 0.5 * ez;
-        double c[3], diag2 = 0.;
-        double u[3][3];
-#pragma unroll
-        for (int j = 0; j < 3; j++) {
-            c[j] = G.lat[j] * fx / (double)G.nx;
-            c[j] += G.lat[3 + j] * fy / (double)G.ny;
-            c[j] += G.lat[6 + j] * fz / (double)G.nz;
-            u[0][j] = G.lat[j] * ex / (double)G.nx;
-            u[1][j] = G.lat[3 + j] * ey / (double)G.ny;
-            u[2][j] = G.lat[6 + j] * ez / (double)G.nz;
-        }
-#pragma unroll
-        for (int s = 0; s < 4; s++) {
-            const double s1 = (s & 1) ? -1. : 1., s2 = (s & 2) ? -1. : 1.;
-            double d2 = 0.;
-#pragma unroll
-            for (int j = 0; j < 3; j++) {
-                const double d = (u[0][j] + s1 * u[1][j]) + s2 * u[2][j];
-                d2 += d * d;
-            }
-            diag2 = fmax(diag2, d2);
-        }
-        const double two_r = sqrt(diag2);
+        double c[3];
+        const double two_r = sqrt(cell_tile_ball<VO_TILE>(G, x0, y0, z0, c));
         // pass 1: d_min
         double m2 = __builtin_huge_val();
         for (unsigned int idx = tid; idx < total; idx += 256u) {
             const int a = (int)(idx / 27u), i = (int)(idx - 27u * (unsigned int)a);
             const double *at = G.atoms + 3 * (size_t)a;
-            m2 = fmin(m2, vo_d2(c, at[0] + s_pbc[3 * i], at[1] + s_pbc[3 * i + 1], at[2] + s_pbc[3 * i + 2]));
+            m2 = fmin(m2, cell_d2(c, at[0] + s_pbc[3 * i], at[1] + s_pbc[3 * i + 1], at[2] + s_pbc[3 * i + 2]));
         }
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) m2 = fmin(m2, __shfl_xor(m2, o));
         if (lane == 0) s_red[wave] = m2;
         __syncthreads();
         m2 = fmin(fmin(s_red[0], s_red[1]), fmin(s_red[2], s_red[3]));
-        double lim = sqrt(m2) + two_r;
-        lim += 0x1p-40 * (lim + G.len);
-        double lim2 = lim * lim;
-        lim2 += 0x1p-40 * lim2;
+        const double lim2 = cell_slack2(sqrt(m2) + two_r, G.len);
         // pass 2: keep and compact (every lane of a wave runs the same number of rounds)
         for (unsigned int base = 0; base < total; base += 256u) {
             const unsigned int idx = base + tid;
@@ -135,7 +88,7 @@ __global__ __launch_bounds__(256) void k_voronoi(VoGeom G, const double *__restr
                 const int i = (int)(idx - 27u * (unsigned int)a);
                 const double *at = G.atoms + 3 * (size_t)a;
                 q0 = at[0] + s_pbc[3 * i]; q1 = at[1] + s_pbc[3 * i + 1]; q2 = at[2] + s_pbc[3 * i + 2];
-                keep = vo_d2(c, q0, q1, q2) <= lim2;
+                keep = cell_d2(c, q0, q1, q2) <= lim2;
             }
             const unsigned long long mask = __ballot(keep);
             if (mask) {
@@ -158,21 +111,8 @@ __global__ __launch_bounds__(256) void k_voronoi(VoGeom G, const double *__restr
     }
     const bool full = forced || cnt > XB_VORONOI_CAND_MAX;
     // phase 2: this thread's two voxels (indices clamped into the grid; a voxel outside it is not stored)
-    const int len = G.nx + G.ny + G.nz;
-    const int py = y0 + lane / VO_TILE, pz = z0 + lane % VO_TILE;
-    const int pxa = x0 + wave, pxb = x0 + wave + 4;
-    const int cy = min(py, G.ny - 1), cz = min(pz, G.nz - 1), cxa = min(pxa, G.nx - 1), cxb = min(pxb, G.nx - 1);
-    double pa[3], pb[3];
-#pragma unroll
-    for (int j = 0; j < 3; j++) {
-        const double *tj = G.tab + (size_t)j * len;
-        pa[j] = tj[cxa];
-        pa[j] += tj[G.nx + cy];
-        pa[j] += tj[G.nx + G.ny + cz];
-        pb[j] = tj[cxb];
-        pb[j] += tj[G.nx + cy];
-        pb[j] += tj[G.nx + G.ny + cz];
-    }
+    CellVox V;
+    cell_two_voxels<VO_TILE>(G, x0, y0, z0, V);
     double besta = __builtin_huge_val(), bestb = __builtin_huge_val();
     int whoa = XB_INT_MAX, whob = XB_INT_MAX;
     if (!full) {
@@ -180,8 +120,8 @@ __global__ __launch_bounds__(256) void k_voronoi(VoGeom G, const double *__restr
         for (int k = 0; k < cnt; k++) {
             const double q0 = s_cand[k].q[0], q1 = s_cand[k].q[1], q2 = s_cand[k].q[2];
             const int a = s_cand[k].a;
-            vo_take(vo_d2(pa, q0, q1, q2), a, besta, whoa);
-            vo_take(vo_d2(pb, q0, q1, q2), a, bestb, whob);
+            vo_take(cell_d2(V.pa, q0, q1, q2), a, besta, whoa);
+            vo_take(cell_d2(V.pb, q0, q1, q2), a, bestb, whob);
         }
     } else {
         for (int a = 0; a < G.n; a++) {
@@ -190,22 +130,17 @@ __global__ __launch_bounds__(256) void k_voronoi(VoGeom G, const double *__restr
 #pragma unroll 1
             for (int i = 0; i < 27; i++) {
                 const double q0 = a0 + s_pbc[3 * i], q1 = a1 + s_pbc[3 * i + 1], q2 = a2 + s_pbc[3 * i + 2];
-                vo_take(vo_d2(pa, q0, q1, q2), a, besta, whoa);
-                vo_take(vo_d2(pb, q0, q1, q2), a, bestb, whob);
+                vo_take(cell_d2(V.pa, q0, q1, q2), a, besta, whoa);
+                vo_take(cell_d2(V.pb, q0, q1, q2), a, bestb, whob);
             }
         }
     }
-    if (py < G.ny && pz < G.nz) {
-        const size_t row = (size_t)py * G.nz + pz, plane = (size_t)G.ny * G.nz;
-        if (pxa < G.nx) {
-            const size_t v = (size_t)pxa * plane + row;
-            if (use_vac && rho[v] <= tol) whoa = -1;
-            labels[v] = whoa;
-        }
-        if (pxb < G.nx) {
-            const size_t v = (size_t)pxb * plane + row;
-            if (use_vac && rho[v] <= tol) whob = -1;
-            labels[v] = whob;
-        }
+    if (V.oka) {
+        if (use_vac && rho[V.va] <= tol) whoa = -1;
+        labels[V.va] = whoa;
+    }
+    if (V.okb) {
+        if (use_vac && rho[V.vb] <= tol) whob = -1;
+        labels[V.vb] = whob;
     }
 }
