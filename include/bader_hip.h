@@ -981,6 +981,10 @@ enum {
 /* ... and one more: the edge sweep of the listed tiles voxel by voxel (k_edge_flag_listed) with the dilation in a kernel of its
  * own, instead of by row bit masks with the dilation fused in (k_edge_sweep_bits).  CROSS_CHECK_VOXEL_SWEEP in pybader_amd._lib. */
 #define XB_CHECK_VOXEL_SWEEP 256
+/* ... and one more: the generic retrace kernel (k_refine_trace) where the lean retrace of one GPU (k_refine_trace_lean: a whole-grid
+ * table of whole bricks with valid neighbour bits, the labels of the last neargrid assignment, no vacuum, at most 2^27 voxels) would
+ * run.  CROSS_CHECK_GENERIC_RETRACE in pybader_amd._lib. */
+#define XB_CHECK_GENERIC_RETRACE 512
 /* value of XB_OPT_DEBUG (bits 1, 2 and 8 are not in use) */
 enum {
     XB_DBG_EC_PASSES = 4,         /* print the passes of edge_check and what the middle tier leaves for the exact slow kernel */
@@ -988,6 +992,10 @@ enum {
     XB_DBG_STAGE_WAIT = 32,       /* wait after every stage of an assignment and say so */
     XB_DBG_SHORT_TIERS = 64       /* the exact slow path with tiers of 3 / 5 / 8 path voxels, so that a test reaches its last tier */
 };
+/* One more bit of the same value, a macro like XB_CHECK_BRICK_LOOKUP (tests/test_abi_cpu.py pins the enumerators above): the voxels
+ * the first retrace of every edge list puts on its overflow list are kept on the host for xb_retrace_overflow
+ * (DEBUG_KEEP_RETRACE_OVERFLOW in pybader_amd._lib). */
+#define XB_DBG_KEEP_RETRACE_OVERFLOW 128
 /* Switches.  A USER of the library sets none of them: every default is the measured best, and no switch but
  * XB_OPT_WEIGHT_NO_LABELS changes a result.  A key that is not an XB_OPT_* value, or a value outside the range its key states, is
  * XB_E_ARG.  (Round 4 removed keys 0, 2, 9-12, 15, 21; round 6 removed 7, 8, 16, 22 -- routes and launch shapes nobody set -- and
@@ -1018,6 +1026,15 @@ int xb_deferred_stats(xb_ctx *c, int64_t *refine_total);
  * at least 16 x 16 x 80 voxels, no table whose brick bytes flag every brick as a possible maximum's, fewer maxima in the last assignment than one per 8 bricks), and by the per-voxel kernels
  * (everything else, and everything under XB_CHECK_VOXEL_SWEEP) */
 int xb_sweep_stats(xb_ctx *c, int64_t *bit_sweeps, int64_t *voxel_sweeps);
+/* first retraces of an edge list launched since the context was created: by the lean kernel of one GPU (k_refine_trace_lean: a
+ * whole-grid table of whole bricks with valid neighbour bits, the labels of the last neargrid assignment on a grid of at least
+ * 16 voxels per axis, no vacuum, at most 2^27 voxels) and by the generic kernel (everything else, and everything under
+ * XB_CHECK_GENERIC_RETRACE) */
+int xb_retrace_stats(xb_ctx *c, int64_t *lean_launches, int64_t *generic_launches);
+/* with XB_DBG_KEEP_RETRACE_OVERFLOW set: the start voxels those retraces have put on their overflow lists since the last call that
+ * took them, in list order, launch after launch.  *n is set to their number; they are copied and forgotten when `capacity`
+ * (ints) holds them all */
+int xb_retrace_overflow(xb_ctx *c, int32_t *out, int64_t capacity, int64_t *n);
 /* after xb_edge_find, while its edge list is valid (nothing has rewritten `known` since): the list as the sweep left it -- voxel
  * indices, tile by tile in the order the tiles' workgroups arrived, by row and z inside a tile -- and how many tiles the sweep
  * listed (-1: this edge_find swept without a tile list).  `capacity` in ints; *edges is set even where the list does not fit. */

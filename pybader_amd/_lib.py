@@ -26,8 +26,10 @@ XB_OPT_CROSS_CHECK = 2
  XB_CHECK_NO_EC_SHARE, XB_CHECK_IO_GATHER) = (1, 2, 4, 8, 16, 32, 64)
 CROSS_CHECK_BRICK_LOOKUP = 128   # the header's macro XB_CHECK_BRICK_LOOKUP, one more bit of XB_OPT_CROSS_CHECK (its enumerators are pinned)
 CROSS_CHECK_VOXEL_SWEEP = 256    # XB_CHECK_VOXEL_SWEEP, likewise: the per-voxel edge sweep + the dilation kernel instead of row bit masks
+CROSS_CHECK_GENERIC_RETRACE = 512   # XB_CHECK_GENERIC_RETRACE, likewise: the generic retrace kernel where the lean one would run
 XB_OPT_DEBUG = 3
 XB_DBG_EC_PASSES, XB_DBG_SLAB_STATS, XB_DBG_STAGE_WAIT, XB_DBG_SHORT_TIERS = 4, 16, 32, 64
+DEBUG_KEEP_RETRACE_OVERFLOW = 128   # the header's macro XB_DBG_KEEP_RETRACE_OVERFLOW, one more bit of XB_OPT_DEBUG (its enumerators are pinned)
 XB_OPT_EC_GROUPS = 4
 XB_OPT_EC_QCAP = 5
 XB_OPT_DROP_TABLE = 6
@@ -221,6 +223,8 @@ SYMBOLS = {
     'xb_deferred_stats': (_int, [_vp, _pi64]),
     'xb_sweep_stats': (_int, [_vp, _pi64, _pi64]),
     'xb_edge_list': (_int, [_vp, _vp, _i64, _pi64, _pi64]),
+    'xb_retrace_stats': (_int, [_vp, _pi64, _pi64]),
+    'xb_retrace_overflow': (_int, [_vp, _vp, _i64, _pi64]),
     'xb_growth_stats': (_int, [_vp, _pi64, _pi64]),
     'xb_comm_unique_id': (_int, [_vp]),
     'xb_comm_init': (_int, [_vp, _int, _int, _vp]),
@@ -1488,6 +1492,21 @@ class Context:
         a, b = C.c_int64(), C.c_int64()
         check(self.lib.xb_sweep_stats(self.h, C.byref(a), C.byref(b)))
         return a.value, b.value
+
+    def retrace_stats(self):
+        """(first retraces of an edge list launched as the lean kernel, as the generic kernel) since the context was made"""
+        a, b = C.c_int64(), C.c_int64()
+        check(self.lib.xb_retrace_stats(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def retrace_overflow(self):
+        """the voxels the retraces put on their overflow lists since the last call (DEBUG_KEEP_RETRACE_OVERFLOW set), taken"""
+        n = C.c_int64()
+        check(self.lib.xb_retrace_overflow(self.h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, np.int32)
+        if n.value:
+            check(self.lib.xb_retrace_overflow(self.h, _ptr(out), out.size, C.byref(n)))
+        return out
 
     def edge_list(self):
         """(the edge list the last edge_find() left, in the sweep's order; tiles the sweep listed, -1 without a tile list)"""

@@ -112,6 +112,7 @@ struct xb_ctx : CtxState, CtxBuffers {   // (ctx_state.h: the flags of the cache
         int ec_share = 1;          // k_ec_chase: a long queue sheds its surplus into other workgroups' mailboxes (0: every workgroup keeps what it wakes; A/B, XB_CHECK_NO_EC_SHARE)
         int nb_bits = 1;           // lean walker / lean retrace: "no records there" from the neighbour bits of the record in hand (0: the brick label / brick byte per step; tests compare, XB_CHECK_BRICK_LOOKUP)
         int bit_sweep = 1;         // edge sweep of the listed tiles: row bit masks with the dilation fused in (k_edge_sweep_bits); 0: k_edge_flag_listed + k_edge_dilate_tiles (tests compare, XB_CHECK_VOXEL_SWEEP)
+        int lean_retrace = 1;      // refinement on one GPU: k_refine_trace_lean where its case holds (host_stages.h, lean_retrace_ok); 0: the generic k_refine_trace there too (tests compare, XB_CHECK_GENERIC_RETRACE)
         int io_tiled = 1;          // xb_import_density: permuted layouts through the LDS tile (0: the plain strided gather; tests and the benchmark compare)
         int dbg = 0;               // XB_OPT_DEBUG: XB_DBG_* bits
         int ec_groups = 256;       // XB_OPT_EC_GROUPS: workgroups of k_ec_chase (at most one per CU)
@@ -149,6 +150,8 @@ struct xb_ctx : CtxState, CtxBuffers {   // (ctx_state.h: the flags of the cache
     long long stat_deferred = 0;   // retraces redone by the from-rho kernel (sparse table)
     long long stat_bit_sweeps = 0, stat_voxel_sweeps = 0;   // edge sweeps launched by row bit masks / by the per-voxel kernels
     long long stat_ovf_assign = 0, stat_ovf_refine = 0;   // trajectories handed to the exact slow kernel
+    long long stat_lean_retraces = 0, stat_generic_retraces = 0;   // first retraces of an edge list launched as k_refine_trace_lean / as the generic kernel (launch_edge_retrace)
+    std::vector<int> dbg_retrace_ovf;   // XB_DBG_KEEP_RETRACE_OVERFLOW: the voxels those retraces put on the overflow list, until xb_retrace_overflow takes them
     int *bres_last = nullptr;   // the fused neargrid assignment's per-brick trace results (inside `list`), or null
     int *blab = nullptr;        // brick labels of the trapping regions (inside `list`), or null
     int nbk[3] = {0, 0, 0};
@@ -393,7 +396,7 @@ int xb_set_option(xb_ctx *c, int key, int value) {
     switch (key) {
     case XB_OPT_REGIONS: c->opt.boxes = (value & XB_REGIONS_BOXES) != 0; c->opt.bricks = (value & XB_REGIONS_BRICKS) != 0; break;
     case XB_OPT_CROSS_CHECK:
-        if (!(ok = value >= 0 && value < 2 * XB_CHECK_VOXEL_SWEEP)) break;
+        if (!(ok = value >= 0 && value < 2 * XB_CHECK_GENERIC_RETRACE)) break;
         c->opt.mirror = !(value & XB_CHECK_NO_MIRROR);
         c->opt.lean = !(value & XB_CHECK_GENERIC_WALKER);
         c->opt.mask_diag = !(value & XB_CHECK_FULL_TGRAD);
@@ -403,6 +406,7 @@ int xb_set_option(xb_ctx *c, int key, int value) {
         c->opt.io_tiled = !(value & XB_CHECK_IO_GATHER);
         c->opt.nb_bits = !(value & XB_CHECK_BRICK_LOOKUP);
         c->opt.bit_sweep = !(value & XB_CHECK_VOXEL_SWEEP);
+        c->opt.lean_retrace = !(value & XB_CHECK_GENERIC_RETRACE);
         break;
     case XB_OPT_DEBUG: c->opt.dbg = value; break;
     case XB_OPT_EC_GROUPS: if ((ok = value >= 1 && value <= 4096)) c->opt.ec_groups = value; break;
@@ -432,6 +436,21 @@ int xb_sweep_stats(xb_ctx *c, int64_t *bit_sweeps, int64_t *voxel_sweeps) {
     if (!c) return fail(XB_E_ARG, "null ctx");
     if (bit_sweeps) *bit_sweeps = c->stat_bit_sweeps;
     if (voxel_sweeps) *voxel_sweeps = c->stat_voxel_sweeps;
+    return XB_OK;
+}
+int xb_retrace_stats(xb_ctx *c, int64_t *lean_launches, int64_t *generic_launches) {
+    if (!c) return fail(XB_E_ARG, "null ctx");
+    if (lean_launches) *lean_launches = c->stat_lean_retraces;
+    if (generic_launches) *generic_launches = c->stat_generic_retraces;
+    return XB_OK;
+}
+int xb_retrace_overflow(xb_ctx *c, int32_t *out, int64_t capacity, int64_t *n) {
+    if (!c || !n || capacity < 0 || (capacity > 0 && !out)) return fail(XB_E_ARG, "xb_retrace_overflow: null ctx / count, or a capacity without a buffer");
+    *n = (int64_t)c->dbg_retrace_ovf.size();
+    if (capacity >= *n) {   // (handed over: the next retraces start a new record)
+        std::copy(c->dbg_retrace_ovf.begin(), c->dbg_retrace_ovf.end(), out);
+        c->dbg_retrace_ovf.clear();
+    }
     return XB_OK;
 }
 int xb_slow_path_stats(xb_ctx *c, int64_t *assign_total, int64_t *refine_total) {

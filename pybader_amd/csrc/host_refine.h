@@ -358,9 +358,9 @@ static int refine_trace_impl(xb_ctx *c, int flag, int64_t *changed, int64_t *esc
                 }
             }
             HIPCHK(hipMemsetAsync(c->counters + CT_DEFER, 0, sizeof(int), c->stream));
-            // (NB: `missing` from the neighbour bits of the record in hand -- a whole-grid table that vouches for them)
-            (brec && !slab && nb_bits_ok(c) ? launch_refine_trace<2, false, false, false, true> : launch_refine_trace<2, false>)(c, nblocks(n), TPB, c->list, n, nullptr, c->counters + CT_CHANGED, c->counters + CT_ESCAPED, c->ovf_list,
-                                          c->counters + CT_N_OVF, c->ovf_cap, brec, defer, c->counters + CT_DEFER, regions_ok, slab_regions, WalkerIO{});
+            // (the lean retrace of one GPU where its case holds, else the generic kernel: launch_edge_retrace)
+            launch_edge_retrace(c, nblocks(n), TPB, c->list, n, nullptr, c->counters + CT_CHANGED, c->counters + CT_ESCAPED, c->counters + CT_N_OVF, brec, slab,
+                                defer, c->counters + CT_DEFER, regions_ok, slab_regions);
             if (brec || slab || table_windowed(c))
                 launch_refine_trace<2, true>(c, 512, TPB, defer, 0, c->counters + CT_DEFER, c->counters + CT_CHANGED, c->counters + CT_ESCAPED, c->ovf_list,
                                              c->counters + CT_N_OVF, c->ovf_cap, brec, nullptr, nullptr, 0, slab_regions, wio);
@@ -379,6 +379,7 @@ static int refine_trace_impl(xb_ctx *c, int flag, int64_t *changed, int64_t *esc
         }
         if (novf > c->ovf_cap) return fail(XB_E_LIMIT, "%d retraces need the slow path (cap %d)", novf, c->ovf_cap);
         c->stat_ovf_refine += novf;
+        if (int rc = keep_retrace_overflow(c, novf)) return rc;
         if (novf > 0) {
             if (int rc = run_slow(c, novf, 1)) return rc;
             HIPCHK(hipMemcpyAsync(c->host_ints, c->counters + CT_CHANGED, CT_INTS(CT_CHANGED, CT_ESCAPED) * sizeof(int), hipMemcpyDeviceToHost, c->stream));
@@ -801,10 +802,9 @@ static int refine_iteration_fused(xb_ctx *c, int64_t *edges, int64_t *changed, b
         int *defer = (int *)c->stage;
         WalkerIO wl{};   // (no walkers on one GPU)
         constexpr int XB_RT_BLOCK = 128;   // (threads per workgroup of the retrace kernel: 64 / 128 / 256 measured 0.512 / 0.495 / 0.514 ms on the whole list)
-        // (NB: `missing` from the neighbour bits of the record in hand -- a whole-grid table that vouches for them)
-        (brec && nb_bits_ok(c) ? launch_refine_trace<2, false, false, false, true> : launch_refine_trace<2, false>)(c, (unsigned)((c->N / 16 + XB_RT_BLOCK - 1) / XB_RT_BLOCK), XB_RT_BLOCK, c->list, 0, fs + FS_N_EDGES,
-                                      fs + FS_CHANGED, fs + FS_ESCAPED, c->ovf_list, fs + FS_R_OVF, c->ovf_cap, brec, defer, fs + FS_R_DEFER,
-                                      regions_ok, nullptr, wl);
+        // (the lean retrace where its case holds, else the generic kernel: launch_edge_retrace; no slab on this path)
+        launch_edge_retrace(c, (unsigned)((c->N / 16 + XB_RT_BLOCK - 1) / XB_RT_BLOCK), XB_RT_BLOCK, c->list, 0, fs + FS_N_EDGES, fs + FS_CHANGED,
+                            fs + FS_ESCAPED, fs + FS_R_OVF, brec, false, defer, fs + FS_R_DEFER, regions_ok, nullptr);
         if (c->grad_cover == 1 && !regions_ok)   // the few retraces whose walk goes on through a brick without records (count on the
                                                   // device); with regions_ok a retrace stops on such a brick: nothing is deferred
             launch_refine_trace<2, true>(c, 512, TPB, (int *)c->stage, 0, fs + FS_R_DEFER, fs + FS_CHANGED, fs + FS_ESCAPED, c->ovf_list,
@@ -832,6 +832,7 @@ static int refine_iteration_fused(xb_ctx *c, int64_t *edges, int64_t *changed, b
     if (hr[2]) return fail(XB_E_STATE, "xb_refine: %d traces left the grid", hr[2]);
     if (novf > c->ovf_cap) return fail(XB_E_LIMIT, "%d retraces need the slow path (cap %d)", novf, c->ovf_cap);
     c->stat_ovf_refine += novf;
+    if (int rc = keep_retrace_overflow(c, novf)) return rc;
     if (novf > 0) {
         // Round 5, the MIDDLE TIER of the assignment (host_assign.h) for the retraces: the listed ones once more on the table with an
         // exact path window of XB_MID_K voxels instead of two -- what the running-maximum test could not decide is mostly a dip below a

@@ -198,3 +198,42 @@ static void launch_refine_trace(xb_ctx *c, unsigned grid, int block, const int *
                                                                            escaped, ovf_list, ovf_count, ovf_cap, trace_maxsteps(c->g), c->rho,
                                                                            c->dist_dev, brec, defer_list, defer_count, regions_ok, region_blab, wio);
 }
+
+// The first retrace of an edge list (a two-voxel window, on the table).  One GPU's common case takes k_refine_trace_lean
+// (k_edges.h): the table is the whole grid's (no window, no slab), of whole bricks whose records carry valid neighbour bits (brec
+// and nb_bits_ok), the labels are the last neargrid assignment's without vacuum (regions_ok: nothing is deferred, a retrace ends
+// on the first brick without records), there are no slab regions, index products fit 24 bits and record byte offsets 32.
+// Everything else -- and everything under XB_CHECK_GENERIC_RETRACE -- takes the generic kernel as before: with the neighbour bits
+// where the table vouches for them (not on a slab), with the brick byte per step otherwise.
+static bool lean_retrace_ok(const xb_ctx *c, const unsigned char *brec, bool slab, int regions_ok, const int *region_blab) {
+    const Grid &g = c->g;
+    return c->opt.lean_retrace && brec && !slab && nb_bits_ok(c) && regions_ok && !region_blab && !table_windowed(c) && g.x0 == 0 && g.x1 == g.nx &&
+           g.vlen == g.nx && light(g).use24 && c->N <= (1LL << 27);
+}
+static void launch_edge_retrace(xb_ctx *c, unsigned grid, int block, const int *list, int n_host, const int *n_dev, int *changed, int *escaped,
+                                int *ovf_count, const unsigned char *brec, bool slab, int *defer_list, int *defer_count, int regions_ok,
+                                const int *region_blab) {
+    if (lean_retrace_ok(c, brec, slab, regions_ok, region_blab)) {
+        // (the lean kernel neither defers nor escapes -- regions_ok holds and there is no slab --: `escaped`, `defer_list` and
+        // `defer_count` stay as the caller cleared them, and its from-rho pass finds an empty list)
+        c->stat_lean_retraces++;
+        k_refine_trace_lean<<<grid, block, 0, c->stream>>>(light(c->g), c->grad, c->labels, c->known, list, n_host, n_dev, changed, c->ovf_list, ovf_count,
+                                                           c->ovf_cap, trace_maxsteps(c->g), brec);
+        return;
+    }
+    c->stat_generic_retraces++;
+    // (NB: `missing` from the neighbour bits of the record in hand -- a whole-grid table that vouches for them)
+    (brec && !slab && nb_bits_ok(c) ? launch_refine_trace<2, false, false, false, true> : launch_refine_trace<2, false>)(
+        c, grid, block, list, n_host, n_dev, changed, escaped, c->ovf_list, ovf_count, c->ovf_cap, brec, defer_list, defer_count, regions_ok, region_blab,
+        WalkerIO{});
+}
+// XB_DBG_KEEP_RETRACE_OVERFLOW (tests): what the retraces just waited for put on the overflow list -- ovf_list[0 .. novf) -- is
+// copied to the host before the middle tier and the exact slow kernel work it off; xb_retrace_overflow hands it out.
+static int keep_retrace_overflow(xb_ctx *c, int novf) {
+    if (!(c->opt.dbg & XB_DBG_KEEP_RETRACE_OVERFLOW) || novf <= 0) return XB_OK;
+    const size_t at = c->dbg_retrace_ovf.size();
+    c->dbg_retrace_ovf.resize(at + (size_t)novf);
+    HIPCHK(hipMemcpyAsync(c->dbg_retrace_ovf.data() + at, c->ovf_list, (size_t)novf * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return XB_OK;
+}

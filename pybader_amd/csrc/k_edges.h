@@ -1206,6 +1206,123 @@ __global__ __launch_bounds__(TPB) void k_refine_trace(GridL g, const GradRec *__
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Round 10: the lean retrace of one GPU.  Same walk, same exits in the same order and the same results as
+// k_refine_trace<2, false, false, false, true> -- tests/test_gpu_lean_retrace.py runs both -- for the one case the headline
+// workload is: a whole-grid table of whole bricks whose records carry valid neighbour bits, the labels of the last neargrid
+// assignment without vacuum (regions_ok: a retrace ends on the first brick without records), index products within 24 bits and
+// record byte offsets within 32 (N <= 2^27).  No slabs, no table window, no walkers, no deferral, no from-rho fallback: what the
+// generic template carries as run-time tests is not here at all.  What differs is how a step is issued, after ng_walk_lean
+// (k_trace.h):
+//   * the natural divergent loop: a lane that ends leaves the execution mask, neither a `moving` flag nor a `result` crosses
+//     the back edge, labels[result] is loaded after the loop;
+//   * PathWindow<2> by hand; linear indices by 24-bit multiply-adds, the periodic wrap only in a wave that left [0, n), the
+//     brick-crossing bits from the unwrapped move, as ng_walk_lean forms them (an axis ONE brick wide does not come here: below
+//     16 voxels on an axis the assignment leaves no region labels, regions_ok is 0 and the generic kernel runs);
+//   * the record by scalar base + 32-bit lane offset, the flag byte likewise (lq < 2^31), both in flight together;
+//   * the rare outcomes -- a maximum, a brick without records, an undecidable membership, a known == 2 voxel -- behind ONE
+//     test after the wait, told apart in the generic kernel's order only by the lanes that leave.
+// The record of a step into a brick without records, which nobody ever wrote, is still gathered, as in the generic retrace and unlike
+// the walker: skipping it measured no faster here (0.427 against 0.418 ms at 512^3 in one call, inside the 0.412-0.429 the kept form
+// spans between calls: the gather lands behind an exec branch, and the form without the branch is the simpler one).
+// An edge voxel whose own brick holds no record keeps its label: the one brick byte of the prologue.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(TPB) void k_refine_trace_lean(GridL g, const GradRec *__restrict__ G, int *labels, int8_t *known,
+                                                           const int *__restrict__ list, int n_host, const int *n_dev, int *changed,
+                                                           int *ovf_list, int *ovf_count, int ovf_cap, int maxsteps,
+                                                           const unsigned char *__restrict__ brick_rec) {
+    const int n = n_dev ? *n_dev : n_host;   // the list length may live on the device: the grid strides over it
+    const int nb1 = (g.ny + 7) >> 3, nb2 = (g.nz + 7) >> 3;
+    int n_ch = 0;
+    // (XCD k retraces the k-th contiguous eighth of the list, which is in tile order: xcd_range)
+    const XcdRange xr = xcd_range((n + (int)blockDim.x - 1) / (int)blockDim.x);
+    for (int chunk = xr.begin; chunk < xr.end; chunk += xr.step) {   // uniform per block (any block size up to TPB)
+        const int t = chunk * (int)blockDim.x + threadIdx.x;
+        if (t >= n) continue;
+        const int v = list[t];
+        int px = v / g.nyz;
+        const int r = v - px * g.nyz;
+        int py = r / g.nz;
+        int pz = r - py * g.nz;
+        // the three start loads travel together
+        GradRec rec = fetch_rec_o<true>(G, v);
+        const int vol_num = labels[v];
+        const bool has_rec = (brick_rec[(unsigned)mad24(mad24(px >> 3, nb1, py >> 3), nb2, pz >> 3)] & 1) != 0;
+        int result = v;   // an edge voxel inside a trapping region: it ends there, label unchanged
+        int i0 = v, i1 = -1, steps = 0;
+        double dr0 = 0., dr1 = 0., dr2 = 0.;
+        double k0 = rec.key, k1 = -1.7976931348623157e308, m_old = -1.7976931348623157e308;
+#ifdef XB_DEBUG_COUNT
+        int dbg_it = 0;
+#endif
+        if (has_rec) for (;;) {
+#ifdef XB_DEBUG_COUNT
+            dbg_it++;
+#endif
+            const int bits = key_bits(rec.key);
+            // refinement.py:142-154: dr += r; corr = rha(dr); q = p + int_grad + corr; dr -= corr (a voxel without a gradient step
+            // has code 63 and r = 0: the move below is garbage for it and replaced by the ongrid step)
+            const double t0 = dr0 + rec.r0, t1 = dr1 + rec.r1, t2 = dr2 + rec.r2;
+            const int id0 = rha_cs(t0), id1 = rha_cs(t1), id2 = rha_cs(t2);
+            const int m0 = (bits & 3) + id0 - 1, m1 = ((bits >> 2) & 3) + id1 - 1, m2 = ((bits >> 4) & 3) + id2 - 1;
+            // the axes on which the move leaves the brick of p (before the wrap: -1 and n are other bricks than 0 and n - 1)
+            int cross = (((px ^ (px + m0)) >> 3) != 0) | ((((py ^ (py + m1)) >> 3) != 0) << 1) | ((((pz ^ (pz + m2)) >> 3) != 0) << 2);
+            px += m0; py += m1; pz += m2;
+            dr0 = t0 - (double)id0; dr1 = t1 - (double)id1; dr2 = t2 - (double)id2;
+            if (__builtin_amdgcn_ballot_w64((unsigned)px >= (unsigned)g.nx || (unsigned)py >= (unsigned)g.ny || (unsigned)pz >= (unsigned)g.nz) != 0) {
+                px = wrap3(px, g.nx); py = wrap3(py, g.ny); pz = wrap3(pz, g.nz);
+            }
+            int lq = lin24(g, px, py, pz);
+            const bool og_move = (bits & 63) == XB_STAY_CODE || lq == i0 || lq == i1;   // refinement.py:200: already on this path
+            bool at_max = false;
+            if (__builtin_amdgcn_ballot_w64(og_move) != 0) {   // rare: dr = 0 and one ongrid step from p (refinement.py:201-235, tabulated)
+                if (og_move) {
+                    const int og = (bits >> 6) & 31;
+                    int ox, oy, oz;
+                    og_offsets(og, ox, oy, oz);
+                    at_max = og == XB_OG_SELF;   // a maximum: refinement.py:283-292
+                    dr0 = dr1 = dr2 = 0.;
+                    const int ux = wrap3(px - m0, g.nx), uy = wrap3(py - m1, g.ny), uz = wrap3(pz - m2, g.nz);   // p again
+                    cross = (((ux ^ (ux + ox)) >> 3) != 0) | ((((uy ^ (uy + oy)) >> 3) != 0) << 1) | ((((uz ^ (uz + oz)) >> 3) != 0) << 2);
+                    px = wrap3(ux + ox, g.nx);
+                    py = wrap3(uy + oy, g.ny);
+                    pz = wrap3(uz + oz, g.nz);
+                    lq = lin24(g, px, py, pz);   // (== i0 at a maximum)
+                }
+            }
+            const bool norec = cross != 0 && ((bits >> (XB_NB_SHIFT - 1) >> cross) & 1) != 0;   // (bit nb_index = cross - 1)
+            // both gathers in flight together; a lane at its maximum reloads its own record (harmless)
+            rec = fetch_rec_o<true>(G, lq);
+            const int8_t kq = *(reinterpret_cast<const int8_t *>(known) + (unsigned)lq);
+            steps++;
+            // the generic kernel's order: a maximum ends on p; a brick without records is a trapping region, closed and of one
+            // label, the retrace ends in it whatever comes next; membership undecidable from the window (an ongrid move is
+            // appended without the test) or too many steps: the overflow list; a known == 2 voxel: refinement.py:294-303
+            const bool undecided = (!og_move && rec.key <= m_old) || steps > maxsteps;
+            if (at_max || norec || undecided || kq == 2) {
+                result = at_max ? i0 : norec ? lq : undecided ? -2 : lq;
+                break;
+            }
+            m_old = max_raw(m_old, k1);
+            i1 = i0; k1 = k0;
+            i0 = lq; k0 = rec.key;
+        }
+#ifdef XB_DEBUG_COUNT
+        if (xb_dbg_steps) xb_dbg_steps[v] = (signed char)min(dbg_it + 1, 127);   // (+1: an edge voxel whose retrace ends before its first step still counts)
+#endif
+        if (result >= 0) {
+            const int nv = labels[result];
+            if (nv != vol_num) { labels[v] = nv; known[v] = -2; n_ch++; }  // refinement.py:288-289
+            else known[v] = -1;                                            // refinement.py:291 (+5 +1 -5)
+        } else {
+            const int k = atomicAdd(ovf_count, 1);
+            if (k < ovf_cap) ovf_list[k] = v;
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) n_ch += __shfl_down(n_ch, o);
+    if (threadIdx.x % XB_WAVE == 0 && n_ch) atomicAdd(changed, n_ch);
+}
+
 // the (start voxel, final label) pairs of carried-on walkers, applied by the owner of the start voxel exactly as the
 // retrace itself would have (refinement.py:288-291); a stuck walker stays parked (known == -6)
 __global__ void k_walkers_apply(GridL g, const int *__restrict__ res, int n, int own0, int own1, int *labels, int8_t *known,
