@@ -1031,6 +1031,11 @@ int xb_sweep_stats(xb_ctx *c, int64_t *bit_sweeps, int64_t *voxel_sweeps);
  * 16 voxels per axis, no vacuum, at most 2^27 voxels) and by the generic kernel (everything else, and everything under
  * XB_CHECK_GENERIC_RETRACE) */
 int xb_retrace_stats(xb_ctx *c, int64_t *lean_launches, int64_t *generic_launches);
+/* launches of the persistent group trace since the context was created, by the walker that ran: the lean walker on a packed
+ * position with neighbour bits (one GPU: a whole-grid table of whole bricks that vouches for its neighbour bits), the lean walker
+ * with the brick-label lookup (cut bricks, slabs, XB_CHECK_BRICK_LOOKUP), and the generic walker (index products beyond 24
+ * bits, XB_CHECK_GENERIC_WALKER) */
+int xb_trace_stats(xb_ctx *c, int64_t *nb_lean_launches, int64_t *lookup_lean_launches, int64_t *generic_launches);
 /* with XB_DBG_KEEP_RETRACE_OVERFLOW set: the start voxels those retraces have put on their overflow lists since the last call that
  * took them, in list order, launch after launch.  *n is set to their number; they are copied and forgotten when `capacity`
  * (ints) holds them all */

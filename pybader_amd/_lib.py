@@ -224,6 +224,7 @@ SYMBOLS = {
     'xb_sweep_stats': (_int, [_vp, _pi64, _pi64]),
     'xb_edge_list': (_int, [_vp, _vp, _i64, _pi64, _pi64]),
     'xb_retrace_stats': (_int, [_vp, _pi64, _pi64]),
+    'xb_trace_stats': (_int, [_vp, _pi64, _pi64, _pi64]),
     'xb_retrace_overflow': (_int, [_vp, _vp, _i64, _pi64]),
     'xb_growth_stats': (_int, [_vp, _pi64, _pi64]),
     'xb_comm_unique_id': (_int, [_vp]),
@@ -1498,6 +1499,13 @@ class Context:
         a, b = C.c_int64(), C.c_int64()
         check(self.lib.xb_retrace_stats(self.h, C.byref(a), C.byref(b)))
         return a.value, b.value
+
+    def trace_stats(self):
+        """(group traces launched with the packed neighbour-bits walker, the lean walker with the brick-label lookup, the generic
+        walker) since the context was made"""
+        a, b, g = C.c_int64(), C.c_int64(), C.c_int64()
+        check(self.lib.xb_trace_stats(self.h, C.byref(a), C.byref(b), C.byref(g)))
+        return a.value, b.value, g.value
 
     def retrace_overflow(self):
         """the voxels the retraces put on their overflow lists since the last call (DEBUG_KEEP_RETRACE_OVERFLOW set), taken"""

@@ -223,6 +223,112 @@ static_assert(nb_side(0) == -1 && nb_side(1) == -1 && nb_side(3) == -1 && nb_sid
               "the low side is within reach from positions 0-1 only, the high side from 6-7 only");
 static_assert(key_low(XB_STAY_CODE, 26, 127) == 0x3FEBF && key_low(63, 31, 127) < (1 << 18), "bits 18-20 stay 0");
 }
+
+// The packed position of the lean walker with neighbour bits (k_trace.h, ng_walk_packed).  One 32-bit word of three 10-bit
+// fields, x highest: the walker's offset from the origin of a WINDOW of the grid, 512 voxels per axis, whose origin is a
+// multiple of 8 (pw_win) -- so the low three bits of a field are the position inside the 8-voxel brick.  Bit 9 of a field is
+// its guard: a field that leaves 0..511 sets it (a negative one by its borrow), and a grid narrower than 512 voxels adds
+// 512 - n first (pw_hiw), so that ONE test says "this lane left its window or crossed a face of the grid"; such a lane gets a
+// new window round its wrapped position (rare: pw_rebase, k_trace.h).  Every per-axis question of a step is asked once, on the
+// word:
+//   the move     a packed signed sum m0 * 2^20 + m1 * 2^10 + m2 (pw_delta: the record's three 2-bit codes spread by one 24-bit
+//                multiply, the three corrections by two shift-adds); the path test "back on one of the last two voxels" is made
+//                on moves (this one is 0, or cancels the last one), exact for any axis longer than 4 voxels;
+//   own brick    every bit above the low three of each field equals the own brick's (pw_own);
+//   LDS slot     the three low-3-bit fields gathered to 9 adjacent bits by one 24-bit multiply (pw_slot);
+//   crossings    (low three bits | 8) + move per field is 8..15 exactly when the move stays in the brick: bit 3 clear = crossed;
+//                the three sparse bits gather to nb_index + 1 by one 24-bit multiply (pw_cross).
+// The multipliers are sums of powers of two whose cross terms land on distinct bits, so no product carries into the bits read.
+constexpr unsigned PW_ONES = 1u | (1u << 10) | (1u << 20);
+constexpr unsigned PW_LOW3 = 7u * PW_ONES, PW_EIGHTS = 8u * PW_ONES, PW_GUARD = 512u * PW_ONES;
+constexpr unsigned PW_NO_MOVE = 0x40000000u;   // "no move before this one": cancels no move
+constexpr unsigned PW_NO_BRICK = 0xFFFFFFFFu;  // own brick outside the window: equals no in-window word
+constexpr int PW_SPAN = 512;                   // voxels per axis a window covers
+constexpr __host__ __device__ unsigned pw_pack(int fx, int fy, int fz) { return ((unsigned)fx << 20) + ((unsigned)fy << 10) + (unsigned)fz; }
+constexpr __host__ __device__ int pw_x(unsigned p) { return (int)(p >> 20); }   // (an in-window word: bits 30-31 are 0)
+constexpr __host__ __device__ int pw_y(unsigned p) { return (int)((p >> 10) & 1023u); }
+constexpr __host__ __device__ int pw_z(unsigned p) { return (int)(p & 1023u); }
+// the window origin for a lane at a (inside the grid of n voxels, n a multiple of 8): 256 below a's brick, kept inside the grid
+constexpr __host__ __device__ int pw_win(int a, int n) {
+    const int w = (a & ~7) - PW_SPAN / 2, top = n > PW_SPAN ? n - PW_SPAN : 0;
+    return w < 0 ? 0 : (w > top ? top : w);
+}
+constexpr __host__ __device__ unsigned pw_hiw(int nx, int ny, int nz) {
+    return pw_pack(nx < PW_SPAN ? PW_SPAN - nx : 0, ny < PW_SPAN ? PW_SPAN - ny : 0, nz < PW_SPAN ? PW_SPAN - nz : 0);
+}
+constexpr __host__ __device__ bool pw_left(unsigned p, unsigned hiw) { return ((p | (p + hiw)) & PW_GUARD) != 0; }
+constexpr __host__ __device__ unsigned pw_delta(int bits, int id0, int id1, int id2) {
+    const unsigned code = (unsigned)bits & 63u;   // x at bits 0-1, y at 2-3, z at 4-5, each 0..2 (move + 1)
+    return (((code * 0x100100u) & 0x300C00u) | (code >> 4)) + pw_pack(id0, id1, id2) - PW_ONES;
+}
+constexpr __host__ __device__ int pw_sext10(unsigned d) { return (int)((d + 512u) & 1023u) - 512; }
+constexpr __host__ __device__ int pw_delta_z(unsigned d) { return pw_sext10(d); }
+constexpr __host__ __device__ int pw_delta_y(unsigned d) { return pw_sext10((d - (unsigned)pw_delta_z(d)) >> 10); }
+constexpr __host__ __device__ int pw_delta_x(unsigned d) { return pw_sext10((((d - (unsigned)pw_delta_z(d)) >> 10) - (unsigned)pw_delta_y(d)) >> 10); }
+constexpr __host__ __device__ bool pw_own(unsigned p, unsigned own_high) { return (p & ~PW_LOW3) == own_high; }
+constexpr __host__ __device__ int pw_slot(unsigned p) { return (int)((((p & PW_LOW3) * 0x4081u) >> 14) & 511u); }
+// cx + 2 cy + 4 cz = nb_index + 1 of the move d from p (0: the move stays in p's brick)
+constexpr __host__ __device__ int pw_cross(unsigned p, unsigned d) {
+    const unsigned s = ((p & PW_LOW3) | PW_EIGHTS) + d;
+    return (int)((((~s & PW_EIGHTS) * 0x400801u) >> 23) & 7u);
+}
+namespace pw_check {
+// every local position of a brick (here the row lx, ly) and every move -2..2 per axis against the plain per-axis formulas, for
+// bricks at the low edge, the middle and the high edge of a window (a voxel without a gradient step has code 3 per axis: a
+// move of up to 3 that goes through pw_delta and is replaced by the ongrid step before anything else sees it -- codes_ok)
+constexpr bool row_ok(int lx, int ly) {
+    const int org[3][3] = {{0, 256, 504}, {504, 0, 256}, {8, 496, 0}};
+    for (int lz = 0; lz < 8; lz++)
+        for (int k = 0; k < 3; k++) {
+            const int ox = org[k][0], oy = org[k][1], oz = org[k][2];
+            const unsigned p = pw_pack(ox + lx, oy + ly, oz + lz), high = pw_pack(ox, oy, oz);
+            if (pw_x(p) != ox + lx || pw_y(p) != oy + ly || pw_z(p) != oz + lz) return false;
+            if (!pw_own(p, high) || pw_slot(p) != ((lx << 6) | (ly << 3) | lz) || pw_left(p, 0)) return false;
+            for (int m0 = -2; m0 <= 2; m0++)
+                for (int m1 = -2; m1 <= 2; m1++)
+                    for (int m2 = -2; m2 <= 2; m2++) {
+                        const unsigned d = pw_pack(m0, m1, m2), q = p + d;
+                        if (pw_delta_x(d) != m0 || pw_delta_y(d) != m1 || pw_delta_z(d) != m2) return false;
+                        const int qx = ox + lx + m0, qy = oy + ly + m1, qz = oz + lz + m2;
+                        const bool cx = (lx + m0) < 0 || (lx + m0) > 7, cy = (ly + m1) < 0 || (ly + m1) > 7, cz = (lz + m2) < 0 || (lz + m2) > 7;
+                        if (pw_cross(p, d) != (cx ? 1 : 0) + (cy ? 2 : 0) + (cz ? 4 : 0)) return false;
+                        if ((cx || cy || cz) && pw_cross(p, d) != nb_index(cx, cy, cz) + 1) return false;
+                        const bool out = qx < 0 || qx >= PW_SPAN || qy < 0 || qy >= PW_SPAN || qz < 0 || qz >= PW_SPAN;
+                        if (pw_left(q, 0) != out) return false;
+                        if (!out && (pw_x(q) != qx || pw_y(q) != qy || pw_z(q) != qz || pw_own(q, high) != !(cx || cy || cz))) return false;
+                        if ((d == 0) != (m0 == 0 && m1 == 0 && m2 == 0)) return false;
+                    }
+        }
+    return true;
+}
+constexpr bool codes_ok() {   // the move from a record's codes and the three corrections; moves that cancel; grids below 512 voxels
+    for (int code = 0; code < 64; code++)
+        for (int id = 0; id < 27; id++) {
+            const int id0 = id / 9 - 1, id1 = (id / 3) % 3 - 1, id2 = id % 3 - 1;
+            const int m0 = (code & 3) + id0 - 1, m1 = ((code >> 2) & 3) + id1 - 1, m2 = ((code >> 4) & 3) + id2 - 1;
+            const unsigned d = pw_delta(code | (21 << 6) | (127 << XB_NB_SHIFT), id0, id1, id2);
+            if (d != pw_pack(m0, m1, m2)) return false;
+            if (d + pw_pack(-m0, -m1, -m2) != 0 || d + PW_NO_MOVE == 0) return false;
+            for (int e = 0; e < 27; e++)   // d + e == 0 only for e = -d
+                if ((d + pw_pack(e / 9 - 1, (e / 3) % 3 - 1, e % 3 - 1) == 0) != (m0 == 1 - e / 9 && m1 == 1 - (e / 3) % 3 && m2 == 1 - e % 3)) return false;
+        }
+    for (int n = 8; n <= 1032; n += 8) {   // the window of every brick of an axis holds the brick; the high face answers through pw_hiw
+        const unsigned hiw = pw_hiw(n, 4096, n);
+        for (int o = 0; o < n; o += 8) {
+            const int w = pw_win(o, n);
+            if (w < 0 || (w & 7) || o - w < 0 || o - w + 8 > PW_SPAN || (n >= PW_SPAN && w + PW_SPAN > n) || (n < PW_SPAN && w != 0)) return false;
+        }
+        const int w = pw_win(n - 8, n);
+        for (int a = n - 3; a < n + 3; a++)
+            if (pw_left(pw_pack(a - w, 5, a - w), hiw) != (a >= n)) return false;
+        if (!pw_left(pw_pack(-1, 5, 5), hiw) || !pw_left(pw_pack(5, -2, 5), hiw) || !pw_left(pw_pack(5, 5, -3), hiw)) return false;
+    }
+    return true;
+}
+template <int K> struct rows { static_assert(row_ok(K >> 3, K & 7), "packed position: own test, LDS slot, crossing index, window test"); rows<K - 1> rest; };
+template <> struct rows<-1> {};
+static_assert(sizeof(rows<63>) > 0 && codes_ok(), "packed position: pack / unpack and the move equal the per-axis formulas");
+}
 __device__ __forceinline__ double pack_key(double rho, int code, int og, int nb = 0) {
     return __longlong_as_double((__double_as_longlong(rho) & ~0x1FFFFFLL) | (long long)key_low(code, og, nb));
 }

@@ -130,6 +130,7 @@ static bool launch_persistent_trace(xb_ctx *c, bool lean_ok, bool part, const in
     const int ovf_cap = window ? (int)std::min<size_t>(c->stage_bytes / sizeof(int), 0x7fffffffu) : c->ovf_cap;
     // (the neighbour bits: whole bricks, the whole grid, and a table that vouches for them -- else the brick label per step)
     const bool nb = lean && !window && !part && nb_bits_ok(c);
+    (nb ? c->stat_nb_traces : lean ? c->stat_lookup_traces : c->stat_generic_traces)++;
     auto kernel = !lean ? k_ng_trace_g<2, 0>
                 : nb ? (lean == 4 ? k_ng_trace_g<2, 4, false, false, true> : k_ng_trace_g<2, 3, false, false, true>)
                 : window ? (lean == 4 ? k_ng_trace_g<2, 4, true> : k_ng_trace_g<2, 3, true>)

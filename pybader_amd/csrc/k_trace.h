@@ -284,11 +284,8 @@ __device__ __forceinline__ void ng_walk_wave(const GridL &g, const GradRec *__re
 //     at the back-edge), linear and brick indices by 24-bit multiply-adds (the generic form compiles to the
 //     quarter-rate v_mad_u64_u32), the periodic wrap is one v_min3_u32 of (q, q + n, q - n);
 //   * no window / table-cover tests.
-// NB (round 7; a whole-grid table of whole bricks whose records carry valid neighbour bits, bader_kernels.h): the record in hand
-// says whether the brick the move enters holds records.  It does: the one gather, no brick-label load.  It does not: no gather
-// at all (the slot was never written; those gathers went all the way to HBM) -- the lane leaves the loop and only then loads
-// its brick label, to tell a trapping region from a vacuum brick.  Without NB (cut bricks, slabs, XB_CHECK_BRICK_LOOKUP): the
-// record gather and the brick-label load of every step that leaves the own brick, in flight together.
+// This walker serves cut bricks, slabs and XB_CHECK_BRICK_LOOKUP: the record gather and the brick-label load of every step that
+// leaves the own brick, in flight together.  Where the records carry valid neighbour bits, ng_walk_packed below runs instead.
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ int wrap3(int q, int n) {   // q in [-n, 2n) -> [0, n)
     return (int)min(min((unsigned)q, (unsigned)(q + n)), (unsigned)(q - n));
@@ -320,14 +317,13 @@ __device__ __forceinline__ GradRec fetch_rec_o(const GradRec *__restrict__ G, in
 // (48 KB of LDS: three workgroups per compute unit), **4 x 1 1.135**, 4 x 2 1.56, 2 x 1 1.45 (the last two lose occupancy to LDS).
 constexpr int XB_TRACE_WAVES = 4;
 __shared__ GradRec xb_s_rec[512];   // the records of the brick a workgroup of the group trace walks (16 KB)
-template <bool OFF32, bool CACHE, bool WINDOW = false, bool NB = false>
+template <bool OFF32, bool CACHE, bool WINDOW = false>
 __device__ __forceinline__ int ng_walk_lean(const GridL &g, const GradRec *__restrict__ G, const int *__restrict__ box_max,
                                              const int *__restrict__ blab, int nb1, int nb2, int sx, int sy, int sz,
                                              int *labels, int *first, int *max_list, int *max_count, int max_cap,
                                              int *ovf_list, int *ovf_count, int ovf_cap, int maxsteps, bool has_vacuum) {
     // every start voxel is valid: the walk list holds whole bricks, and the lanes of a brick the grid cuts start from its
     // voxels inside the grid (k_ng_trace_g PART)
-    static_assert(!NB || (CACHE && !WINDOW), "neighbour bits: the whole-grid table of the group trace");
     const int v = lin24(g, sx, sy, sz);
     const int lab0 = has_vacuum ? labels[v] : 0;   // without vacuum `labels` is write-only here
     const int ox8 = sx & ~7, oy8 = sy & ~7, oz8 = sz & ~7;   // origin of the own brick
@@ -341,7 +337,6 @@ __device__ __forceinline__ int ng_walk_lean(const GridL &g, const GradRec *__res
     // 2.6 M with 3, 2.3 K / 1.2 M with 4; the headline pays 1.5 % / 3 % of the trace for a wider one, so 2 it is and the slow path
     // got its tiers instead: host_assign.h run_slow.)
     int i0 = v, i1 = -1;
-    bool norec = false;   // NB: left the loop on arrival in a brick without records
     double k0 = rec.key, k1 = -1.7976931348623157e308, m_old = -1.7976931348623157e308;
 #ifdef XB_DEBUG_COUNT
     int dbg_lane_steps = 0;
@@ -358,8 +353,6 @@ __device__ __forceinline__ int ng_walk_lean(const GridL &g, const GradRec *__res
         const double t0 = dr0 + rec.r0, t1 = dr1 + rec.r1, t2 = dr2 + rec.r2;
         const int id0 = rha_cs(t0), id1 = rha_cs(t1), id2 = rha_cs(t2);
         const int m0 = (bits & 3) + id0 - 1, m1 = ((bits >> 2) & 3) + id1 - 1, m2 = ((bits >> 4) & 3) + id2 - 1;
-        // NB: the axes on which the move leaves the brick of p (before the wrap: -1 and n are other bricks than 0 and n - 1)
-        int cross = NB ? (((px ^ (px + m0)) >> 3) != 0) | ((((py ^ (py + m1)) >> 3) != 0) << 1) | ((((pz ^ (pz + m2)) >> 3) != 0) << 2) : 0;
         px += m0; py += m1; pz += m2;
         dr0 = t0 - (double)id0; dr1 = t1 - (double)id1; dr2 = t2 - (double)id2;
         // the periodic wrap only for the waves that touch the faces of the grid
@@ -377,7 +370,6 @@ __device__ __forceinline__ int ng_walk_lean(const GridL &g, const GradRec *__res
                 at_max = og == XB_OG_SELF;   // break_flag: p is the maximum
                 dr0 = dr1 = dr2 = 0.;
                 const int ux = wrap3(px - m0, g.nx), uy = wrap3(py - m1, g.ny), uz = wrap3(pz - m2, g.nz);   // p again
-                if (NB) cross = (((ux ^ (ux + ox)) >> 3) != 0) | ((((uy ^ (uy + oy)) >> 3) != 0) << 1) | ((((uz ^ (uz + oz)) >> 3) != 0) << 2);
                 px = wrap3(ux + ox, g.nx);
                 py = wrap3(uy + oy, g.ny);
                 pz = wrap3(uz + oz, g.nz);
@@ -388,11 +380,8 @@ __device__ __forceinline__ int ng_walk_lean(const GridL &g, const GradRec *__res
         int bl = 0;
         const bool own = CACHE && (unsigned)((px ^ ox8) | (py ^ oy8) | (pz ^ oz8)) < 8u;
         const bool in_win = !WINDOW || own || plane_in_window(g, px);
-        if (NB) norec = cross != 0 && ((bits >> (XB_NB_SHIFT - 1) >> cross) & 1) != 0;   // (bit nb_index = cross - 1)
         if (own) rec = xb_s_rec[((px & 7) << 6) | ((py & 7) << 3) | (pz & 7)];
-        else if (NB) {
-            if (!norec) rec = fetch_rec_o<OFF32>(G, lq);
-        } else {
+        else {
             rec = fetch_rec_o<OFF32>(G, WINDOW ? (in_win ? rec_slot(g, lq) : 0) : lq);   // (outside the window: any valid slot, the value is not used)
             const unsigned bidx = (unsigned)mad24(mad24(px >> 3, nb1, py >> 3), nb2, pz >> 3);
             bl = *reinterpret_cast<const int *>(reinterpret_cast<const char *>(blab) + (bidx << 2));
@@ -404,7 +393,6 @@ __device__ __forceinline__ int ng_walk_lean(const GridL &g, const GradRec *__res
         // arrived inside a trapping region (q cannot be an old path voxel: the trajectory would have stopped there
         // already); membership undecidable from the window: exact slow kernel (ongrid moves are appended without a
         // membership test, methods.py:513-521)
-        if (NB && norec) break;   // a trapping region or a vacuum brick: which of them is asked after the loop
         const bool arrived = bl > 0 && !at_max;
         const bool undecided = (!og_move && rec.key <= m_old) || steps > maxsteps || (WINDOW && !in_win) || bl == XB_NOREC;   // (a vacuum brick: no records)
         if (arrived) result = box_max[bl - 1];
@@ -415,11 +403,125 @@ __device__ __forceinline__ int ng_walk_lean(const GridL &g, const GradRec *__res
         i1 = i0; k1 = k0;
         i0 = lq; k0 = rec.key;
     }
-    if (NB && norec) {   // (px, py, pz) is the voxel arrived at
-        const unsigned bidx = (unsigned)mad24(mad24(px >> 3, nb1, py >> 3), nb2, pz >> 3);
+#ifdef XB_DEBUG_COUNT
+    if (xb_dbg_steps) xb_dbg_steps[v] = (signed char)min(dbg_lane_steps, 127);   // tools/walk_lengths.py
+#endif
+    // a maximum that is itself vacuum hands its -1 to the start voxel (methods.py:449-452)
+    if (has_vacuum && result >= 0 && result != v && labels[result] == -1) result = -1;
+    labels[v] = result;
+    note_maximum_wave(result >= 0, result, v, first, max_list, max_count, max_cap);
+    if (result == -2) {
+        const int k = atomicAdd(ovf_count, 1);
+        if (k < ovf_cap) ovf_list[k] = v;
+    }
+    return result;
+}
+// ---------------------------------------------------------------------------------------------
+// The lean walker with neighbour bits (round 7; a whole-grid table of whole bricks whose records carry valid neighbour bits,
+// bader_kernels.h): the record in hand says whether the brick the move enters holds records.  It does: the one gather, no
+// brick-label load.  It does not: no gather at all (the slot was never written; those gathers went all the way to HBM) -- the
+// lane leaves the loop and only then loads its brick label, to tell a trapping region from a vacuum brick.
+// Same trajectory, same exits in the same order and the same results as ng_walk_lean<.., CACHE> with the brick-label lookup
+// (XB_CHECK_BRICK_LOOKUP; tests/test_gpu_packed_walker.py runs both).  What differs (round 11) is the position: ONE packed word
+// (bader_kernels.h, pw_*) relative to a window of the grid instead of three coordinates, the path window kept as moves instead
+// of voxel indices, so that the move, the own-brick test, the LDS slot, the crossing index and the face test are one to five
+// instructions each on the word.  A lane keeps the linear index `lb` and the brick index `wb` of its window's origin; the gather
+// address and the brick of arrival are those plus the fields' products.  A lane that leaves its window or crosses a face of
+// the grid (pw_left; rare: a branch most waves skip) takes a new window round its wrapped position -- the walk has no range
+// limit.  The rare blocks are plain divergent branches (a wave none of whose lanes takes one jumps over it) and the loop keeps
+// no flag across its back edge: scalar mask instructions count like vector ones in a wave's instruction stream (HISTORY
+// "Round 11").  (bx8, by8, bz8): the origin of the own brick, the same for the whole wave.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ int pw_lin(const GridL &g, unsigned p, int lb) { return mad24(mad24(pw_x(p), g.ny, pw_y(p)), g.nz, pw_z(p)) + lb; }
+__device__ __forceinline__ void pw_rebase(const GridL &g, int nb1, int nb2, int bx8, int by8, int bz8, unsigned p_old, unsigned d,
+                                          unsigned &p, unsigned &own_high, int &lb, int &wb) {
+    const int wx = (wb / (nb1 * nb2)) << 3, wy = ((wb / nb2) % nb1) << 3, wz = (wb % nb2) << 3;   // the old window's origin
+    const int ax = wrap3(wx + pw_x(p_old) + pw_delta_x(d), g.nx), ay = wrap3(wy + pw_y(p_old) + pw_delta_y(d), g.ny),
+              az = wrap3(wz + pw_z(p_old) + pw_delta_z(d), g.nz);   // the voxel arrived at
+    const int ux = pw_win(ax, g.nx), uy = pw_win(ay, g.ny), uz = pw_win(az, g.nz);
+    p = pw_pack(ax - ux, ay - uy, az - uz);
+    lb = lin24(g, ux, uy, uz);
+    wb = ((ux >> 3) * nb1 + (uy >> 3)) * nb2 + (uz >> 3);
+    const int rx = bx8 - ux, ry = by8 - uy, rz = bz8 - uz;
+    own_high = (unsigned)(rx | ry | rz) < (unsigned)PW_SPAN ? pw_pack(rx, ry, rz) : PW_NO_BRICK;
+}
+template <bool OFF32>
+__device__ __forceinline__ int ng_walk_packed(const GridL &g, const GradRec *__restrict__ G, const int *__restrict__ box_max,
+                                               const int *__restrict__ blab, int nb1, int nb2, int bx8, int by8, int bz8, int sx, int sy, int sz,
+                                               int *labels, int *first, int *max_list, int *max_count, int max_cap,
+                                               int *ovf_list, int *ovf_count, int ovf_cap, int maxsteps, bool has_vacuum) {
+    const int v = lin24(g, sx, sy, sz);
+    const int lab0 = has_vacuum ? labels[v] : 0;   // without vacuum `labels` is write-only here
+    GradRec rec = xb_s_rec[((sx & 7) << 6) | ((sy & 7) << 3) | (sz & 7)];
+    const unsigned hiw = pw_hiw(g.nx, g.ny, g.nz);
+    int lb, wb;
+    unsigned p, own_high;
+    {
+        const int wx = pw_win(bx8, g.nx), wy = pw_win(by8, g.ny), wz = pw_win(bz8, g.nz);
+        p = pw_pack(sx - wx, sy - wy, sz - wz);
+        own_high = pw_pack(bx8 - wx, by8 - wy, bz8 - wz);
+        lb = lin24(g, wx, wy, wz);
+        wb = ((wx >> 3) * nb1 + (wy >> 3)) * nb2 + (wz >> 3);
+    }
+    int steps = 0;
+    double dr0 = 0., dr1 = 0., dr2 = 0.;
+    // PathWindow<2> by hand (see ng_walk_lean): the keys as there; the two voxels as moves -- the current voxel is reached again
+    // by a move of 0, the one before by a move that cancels the last one (d_prev)
+    unsigned d_prev = PW_NO_MOVE;
+    double k0 = rec.key, k1 = -1.7976931348623157e308, m_old = -1.7976931348623157e308;
+    // How a lane left the loop is read afterwards from two registers it leaves behind, not from flags kept across the back edge
+    // (each such flag costs three scalar mask instructions per step): `norec` != 0 -- it arrived in a brick without records --,
+    // else `d` == 0 -- its last step did not move: the ongrid step of a maximum, the only step of length 0 that is ever applied
+    // (a gradient move of 0 is replaced by the ongrid step, whose offsets are 0 for XB_OG_SELF alone) --, else undecided.
+    unsigned d = PW_NO_MOVE;
+    int norec = 0;
+#ifdef XB_DEBUG_COUNT
+    int dbg_lane_steps = 0;
+#endif
+    if (lab0 != -1) for (;;) {
+        const int bits = key_bits(rec.key);
+        const double t0 = dr0 + rec.r0, t1 = dr1 + rec.r1, t2 = dr2 + rec.r2;
+        const int id0 = rha_cs(t0), id1 = rha_cs(t1), id2 = rha_cs(t2);
+        d = pw_delta(bits, id0, id1, id2);
+        dr0 = t0 - (double)id0; dr1 = t1 - (double)id1; dr2 = t2 - (double)id2;
+        // methods.py:411: no gradient step, or already on this path -- one of three words is 0 (one compare)
+        const bool og_move = min(min(((unsigned)bits & 63u) ^ (unsigned)XB_STAY_CODE, d), d + d_prev) == 0u;
+        if (og_move) {   // rare: dr = 0 and one ongrid step from p (methods.py:412-447, tabulated); XB_OG_SELF: p is the maximum
+            int ox, oy, oz;
+            og_offsets((bits >> 6) & 31, ox, oy, oz);
+            dr0 = dr1 = dr2 = 0.;
+            d = pw_pack(ox, oy, oz);
+        }
+        const int cross = pw_cross(p, d);   // the axes on which the move leaves the brick of p (before the wrap: -1 and n are other bricks than 0 and n - 1)
+        const unsigned p_old = p;
+        p += d;
+        // rare: out of the window, or through a face of the grid
+        if (pw_left(p, hiw)) pw_rebase(g, nb1, nb2, bx8, by8, bz8, p_old, d, p, own_high, lb, wb);
+        const bool own = pw_own(p, own_high);
+        norec = (((bits >> XB_NB_SHIFT) << 1) >> cross) & 1;   // (bit nb_index = cross - 1; cross == 0, the brick of p: 0)
+        // a lane at its maximum reloads its own record (harmless)
+        if (own) rec = xb_s_rec[pw_slot(p)];
+        else if (!norec) rec = fetch_rec_o<OFF32>(G, pw_lin(g, p, lb));
+        steps++;
+#ifdef XB_DEBUG_COUNT
+        dbg_lane_steps++;
+#endif
+        // the exits, in this order: a trapping region or a vacuum brick (which of them is asked after the loop); the maximum;
+        // membership undecidable from the window: exact slow kernel (ongrid moves are appended without a membership test,
+        // methods.py:513-521)
+        if (norec != 0 || d == 0u || (!og_move && rec.key <= m_old) || steps > maxsteps) break;
+        m_old = max_raw(m_old, k1);
+        k1 = k0; k0 = rec.key;
+        d_prev = d;
+    }
+    asm volatile("" : "+v"(norec), "+v"(d));   // (read as registers: no lane mask of the loop's compares is kept for this)
+    int result = -1;
+    if (norec != 0) {   // p is the voxel arrived at
+        const unsigned bidx = (unsigned)(mad24(mad24(pw_x(p) >> 3, nb1, pw_y(p) >> 3), nb2, pw_z(p) >> 3) + wb);
         const int bl = *reinterpret_cast<const int *>(reinterpret_cast<const char *>(blab) + (bidx << 2));
         result = bl > 0 ? box_max[bl - 1] : -2;   // (XB_NOREC, a vacuum brick: the exact slow kernel works from rho)
-    }
+    } else if (d == 0u) result = pw_lin(g, p, lb);
+    else if (lab0 != -1) result = -2;
 #ifdef XB_DEBUG_COUNT
     if (xb_dbg_steps) xb_dbg_steps[v] = (signed char)min(dbg_lane_steps, 127);   // tools/walk_lengths.py
 #endif
@@ -620,8 +722,14 @@ __global__ __launch_bounds__(XB_WAVE * XB_TRACE_WAVES, 8) void k_ng_trace_g(Grid
 #ifdef XB_DEBUG_COUNT
                     const long long pr_c = clock64();
 #endif
-                    const int res = ng_walk_lean<LEAN == 4, CACHE, WINDOW, NB>(g, G, box_max, blab, nb1, nb2, sx, sy, sz, labels, first, max_list, &fs[FS_N_MAX],
-                                                                max_cap, ovf_list, &fs[FS_N_OVF], ovf_cap, maxsteps, has_vacuum != 0);
+                    int res;
+                    if constexpr (NB) {
+                        const int wbrick = walk[item >> 3];   // (uniform: the own brick of the whole wave)
+                        res = ng_walk_packed<LEAN == 4>(g, G, box_max, blab, nb1, nb2, (wbrick / (nb1 * nb2)) << 3, ((wbrick / nb2) % nb1) << 3, (wbrick % nb2) << 3,
+                                                        sx, sy, sz, labels, first, max_list, &fs[FS_N_MAX], max_cap, ovf_list, &fs[FS_N_OVF], ovf_cap, maxsteps, has_vacuum != 0);
+                    } else
+                        res = ng_walk_lean<LEAN == 4, CACHE, WINDOW>(g, G, box_max, blab, nb1, nb2, sx, sy, sz, labels, first, max_list, &fs[FS_N_MAX],
+                                                                     max_cap, ovf_list, &fs[FS_N_OVF], ovf_cap, maxsteps, has_vacuum != 0);
 #ifdef XB_DEBUG_COUNT
                     pr_walk += clock64() - pr_c;
 #endif
