@@ -52,10 +52,18 @@ void *xb_stream(xb_ctx *c);                      /* the hipStream_t every kernel
  * SIZE LIMIT (the reference indexes with int64 throughout, methods.py / refinement.py): voxel indices are int32 on the
  * device, so a grid needs nx*ny*nz < 2^31 - 1 voxels (1024^3 = 2^30 fits; 1290^3 is the largest cube) -- more returns
  * XB_E_LIMIT before anything is allocated.  Every entry point works up to that size.
+ * AXIS LIMITS: the tile launches put the tile counts of y and x into gridDim.y and gridDim.z, which the device bounds
+ * (hipDeviceProp_t::maxGridSize, read when the context is created).  nx may be at most 4 * maxGridSize[2] (the 4-plane tiles of the
+ * edge sweep and the relabel), ny at most 8 * maxGridSize[1] (the 8-row tiles of pass A, the edge sweep and the bricks): with
+ * 65 536 for both, 262 144 and 524 288 voxels.  nz has no limit of its own.  A longer axis returns XB_E_LIMIT before anything is
+ * allocated, with the axis and the limit in the message ("axis x of ... voxels exceeds the launch limit of ... voxels on x");
+ * xb_axis_limits reads both limits.
  * An axis of one or two voxels (it meets itself through the wrap) is accepted for the transfers, xb_vacuum_assign and the weight
  * method; the assignment, refinement, table and sum entry points answer XB_E_ARG on such a grid. */
 int xb_set_grid(xb_ctx *c, const int64_t shape[3], const double dist_mat[27], const double T_grad[9],
                 int64_t x0, int64_t x1);
+/* the longest x and y axis xb_set_grid accepts on this context's device (AXIS LIMITS above); host only */
+int xb_axis_limits(xb_ctx *c, int64_t *nx_max, int64_t *ny_max);
 int xb_upload_density(xb_ctx *c, const double *rho_host);           /* H2D, nx*ny*nz float64 */
 /* workload generator, bit-identical to pybader_amd/synth.py (bench + tests; not in the reference) */
 int xb_synth_density(xb_ctx *c, const double lattice[9], const double *atoms5, int64_t n_atoms,
@@ -1034,8 +1042,10 @@ int xb_retrace_stats(xb_ctx *c, int64_t *lean_launches, int64_t *generic_launche
 /* launches of the persistent group trace since the context was created, by the walker that ran: the lean walker on a packed
  * position with neighbour bits (one GPU: a whole-grid table of whole bricks that vouches for its neighbour bits), the lean walker
  * with the brick-label lookup (cut bricks, slabs, XB_CHECK_BRICK_LOOKUP), and the generic walker (index products beyond 24
- * bits, XB_CHECK_GENERIC_WALKER) */
-int xb_trace_stats(xb_ctx *c, int64_t *nb_lean_launches, int64_t *lookup_lean_launches, int64_t *generic_launches);
+ * bits, XB_CHECK_GENERIC_WALKER); and how many of the first two took 64-bit table offsets (a table window of more than 2^27
+ * voxels; up to there a lean walker forms 32-bit byte offsets) */
+int xb_trace_stats(xb_ctx *c, int64_t *nb_lean_launches, int64_t *lookup_lean_launches, int64_t *generic_launches,
+                   int64_t *wide_lean_launches);
 /* with XB_DBG_KEEP_RETRACE_OVERFLOW set: the start voxels those retraces have put on their overflow lists since the last call that
  * took them, in list order, launch after launch.  *n is set to their number; they are copied and forgotten when `capacity`
  * (ints) holds them all */

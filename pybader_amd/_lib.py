@@ -224,7 +224,8 @@ SYMBOLS = {
     'xb_sweep_stats': (_int, [_vp, _pi64, _pi64]),
     'xb_edge_list': (_int, [_vp, _vp, _i64, _pi64, _pi64]),
     'xb_retrace_stats': (_int, [_vp, _pi64, _pi64]),
-    'xb_trace_stats': (_int, [_vp, _pi64, _pi64, _pi64]),
+    'xb_trace_stats': (_int, [_vp, _pi64, _pi64, _pi64, _pi64]),
+    'xb_axis_limits': (_int, [_vp, _pi64, _pi64]),
     'xb_retrace_overflow': (_int, [_vp, _vp, _i64, _pi64]),
     'xb_growth_stats': (_int, [_vp, _pi64, _pi64]),
     'xb_comm_unique_id': (_int, [_vp]),
@@ -1504,8 +1505,21 @@ class Context:
         """(group traces launched with the packed neighbour-bits walker, the lean walker with the brick-label lookup, the generic
         walker) since the context was made"""
         a, b, g = C.c_int64(), C.c_int64(), C.c_int64()
-        check(self.lib.xb_trace_stats(self.h, C.byref(a), C.byref(b), C.byref(g)))
+        check(self.lib.xb_trace_stats(self.h, C.byref(a), C.byref(b), C.byref(g), None))
         return a.value, b.value, g.value
+
+    def trace_offset_stats(self):
+        """(group traces launched with a lean walker that forms 32-bit table offsets, with one that forms 64-bit offsets -- a table
+        of more than 2^27 voxels) since the context was made; together the first two entries of trace_stats()"""
+        a, b, w = C.c_int64(), C.c_int64(), C.c_int64()
+        check(self.lib.xb_trace_stats(self.h, C.byref(a), C.byref(b), None, C.byref(w)))
+        return a.value + b.value - w.value, w.value
+
+    def axis_limits(self):
+        """(the longest x axis, the longest y axis) set_grid accepts on this device: the tile launches' gridDim.z / gridDim.y"""
+        a, b = C.c_int64(), C.c_int64()
+        check(self.lib.xb_axis_limits(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     def retrace_overflow(self):
         """the voxels the retraces put on their overflow lists since the last call (DEBUG_KEEP_RETRACE_OVERFLOW set), taken"""

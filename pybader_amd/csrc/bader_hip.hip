@@ -152,6 +152,8 @@ struct xb_ctx : CtxState, CtxBuffers {   // (ctx_state.h: the flags of the cache
     long long stat_ovf_assign = 0, stat_ovf_refine = 0;   // trajectories handed to the exact slow kernel
     long long stat_lean_retraces = 0, stat_generic_retraces = 0;   // first retraces of an edge list launched as k_refine_trace_lean / as the generic kernel (launch_edge_retrace)
     long long stat_nb_traces = 0, stat_lookup_traces = 0, stat_generic_traces = 0;   // group traces launched with ng_walk_packed / ng_walk_lean / ng_walk_wave (launch_persistent_trace)
+    long long stat_wide_traces = 0;   // ... those of the two lean walkers that took 64-bit table offsets (more than 2^27 window voxels; the others take 32-bit ones)
+    int max_grid[3] = {0, 0, 0};      // hipDeviceProp_t::maxGridSize of the context's device, read once by xb_create (xb_set_grid's per-axis limits)
     std::vector<int> dbg_retrace_ovf;   // XB_DBG_KEEP_RETRACE_OVERFLOW: the voxels those retraces put on the overflow list, until xb_retrace_overflow takes them
     int *bres_last = nullptr;   // the fused neargrid assignment's per-brick trace results (inside `list`), or null
     int *blab = nullptr;        // brick labels of the trapping regions (inside `list`), or null
@@ -445,8 +447,9 @@ int xb_retrace_stats(xb_ctx *c, int64_t *lean_launches, int64_t *generic_launche
     if (generic_launches) *generic_launches = c->stat_generic_retraces;
     return XB_OK;
 }
-int xb_trace_stats(xb_ctx *c, int64_t *nb_lean_launches, int64_t *lookup_lean_launches, int64_t *generic_launches) {
+int xb_trace_stats(xb_ctx *c, int64_t *nb_lean_launches, int64_t *lookup_lean_launches, int64_t *generic_launches, int64_t *wide_lean_launches) {
     if (!c) return fail(XB_E_ARG, "null ctx");
+    if (wide_lean_launches) *wide_lean_launches = c->stat_wide_traces;
     if (nb_lean_launches) *nb_lean_launches = c->stat_nb_traces;
     if (lookup_lean_launches) *lookup_lean_launches = c->stat_lookup_traces;
     if (generic_launches) *generic_launches = c->stat_generic_traces;

@@ -527,14 +527,9 @@ static int assign_neargrid_fused(xb_ctx *c, int64_t *n_maxima) {
     {   // region fill / notes, then the walkers of the uncertain bricks
         ScopedTimer t_assign(c, XB_TIMER_ASSIGN);
         {
-            int bits = 0;
-            while ((1 << bits) < std::max(std::max(nb0, nb1), nb2)) bits++;
-            const unsigned n_codes = 1u << (3 * bits);
             // (with a vacuum tolerance the bricks that lie below it altogether stay off the list: k_brick_walk_list_morton)
             const bool vac = c->has_vacuum && c->vac_by_tol;
-            k_brick_walk_list_morton<<<(n_codes + 16 * TPB - 1) / (16 * TPB), TPB, 0, c->stream>>>(nb0, nb1, nb2, n_codes, c->blab, walk,
-                                                                                                  fs + FS_N_WALK, fs + FS_GROW_RETRY,
-                                                                                                  vac ? bpot : nullptr, c->vac_tol);
+            launch_walk_list(c, nb0, nb1, nb2, walk, vac ? bpot : nullptr, c->vac_tol);
         }
         {   // pass B: records for the bricks of the walk list only
             ScopedTimer t_records(c, XB_TIMER_BRICK_RECORDS);
@@ -735,11 +730,7 @@ static int assign_ongrid_fused(xb_ctx *c, int64_t *n_maxima) {
     c->nbk[0] = nb0; c->nbk[1] = nb1; c->nbk[2] = nb2;
     {
         ScopedTimer t_assign(c, XB_TIMER_ASSIGN);
-        int bits = 0;
-        while ((1 << bits) < std::max(std::max(nb0, nb1), nb2)) bits++;
-        const unsigned n_codes = 1u << (3 * bits);
-        k_brick_walk_list_morton<<<(n_codes + 16 * TPB - 1) / (16 * TPB), TPB, 0, c->stream>>>(nb0, nb1, nb2, n_codes, c->blab, walk,
-                                                                                              fs + FS_N_WALK, fs + FS_GROW_RETRY);
+        launch_walk_list(c, nb0, nb1, nb2, walk, nullptr, 0.);
         k_note_regions<<<1, XB_BOXES_MAX, 0, c->stream>>>(gl, nb1, nb2, fs, box_first, box_max, c->first, c->max_list, fs + FS_N_MAX, c->max_cap);
         c->regions_pending = true;
         k_og_walk_dev<<<16384, XB_WAVE, 0, c->stream>>>(gl, box_max, c->blab, nb1, nb2, walk, fs, c->labels, c->first, c->max_list, c->max_cap,

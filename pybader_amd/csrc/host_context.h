@@ -27,7 +27,32 @@ int xb_create(int device, xb_ctx **out) {
     HIPCHK(hipMalloc(&c->dist_dev, 36 * sizeof(double)));  // dist_mat (27) then T_grad (9): make_rec_rho
     HIPCHK(hipMalloc(&c->boxbuf, (size_t)(1 << 20) * sizeof(int)));
     HIPCHK(hipHostMalloc(&c->host_ints, HI_TOTAL * sizeof(int)));
+    hipDeviceProp_t prop;
+    HIPCHK(hipGetDeviceProperties(&prop, device));
+    for (int k = 0; k < 3; k++) c->max_grid[k] = prop.maxGridSize[k];
     *out = c;
+    return XB_OK;
+}
+
+// The longest x and y axis xb_set_grid accepts: tile counts of y and x become gridDim.y and gridDim.z of the tile launches of
+// the assignment and refinement path, and the device bounds those (maxGridSize[1], [2]; gridDim.x, which takes the tiles of z,
+// reaches 2^31 - 1 and is covered by the voxel limit).  Per axis the smallest tile edge decides:
+//   gridDim.y  ceil(ny / GT_Y)  k_brick_masks, k_og_masks (launch_brick_masks, assign_ongrid*)
+//              ceil(ny / ET_Y)  k_edge_flag_tiled (edge_find, the fused refinement iteration)
+//              ceil(ny / BRK)   k_relabel_regions_brick (launch_relabel: nb1); k_brick_grow_dev takes ceil(nb1 / BG)
+//   gridDim.z  ceil(nx / GT_X)  k_brick_masks, k_og_masks
+//              ceil(nx / ET_X)  k_edge_flag_tiled
+//              ceil(nx / RELABEL_X)  k_relabel_regions_brick (groups of 4 planes); k_brick_grow_dev takes ceil(nb0 / BG)
+// (a slab launches over its own planes only, but every rank may hold the whole axis: the limit is on the grid, not the slab)
+#define RELABEL_X 4
+static long long axis_limit(int axis, const int max_grid[3]) {
+    const int tile = axis == 0 ? std::min(std::min(GT_X, ET_X), RELABEL_X) : std::min(std::min(GT_Y, ET_Y), BRK);
+    return std::min<long long>((long long)tile * max_grid[axis == 0 ? 2 : 1], XB_INT_MAX);
+}
+int xb_axis_limits(xb_ctx *c, int64_t *nx_max, int64_t *ny_max) {
+    if (!c) return fail(XB_E_ARG, "null ctx");
+    if (nx_max) *nx_max = axis_limit(0, c->max_grid);
+    if (ny_max) *ny_max = axis_limit(1, c->max_grid);
     return XB_OK;
 }
 
@@ -148,6 +173,10 @@ int xb_set_grid(xb_ctx *c, const int64_t shape[3], const double dist_mat[27], co
     }
     const long long N = (long long)shape[0] * shape[1] * shape[2];
     if (N >= 2147483647LL) return fail(XB_E_LIMIT, "xb_set_grid: %lld voxels exceed the int32 index range", N);
+    for (int j = 0; j < 2; j++)
+        if (shape[j] > axis_limit(j, c->max_grid))
+            return fail(XB_E_LIMIT, "xb_set_grid: axis %c of %lld voxels exceeds the launch limit of %lld voxels on %c", "xy"[j], (long long)shape[j],
+                        axis_limit(j, c->max_grid), "xy"[j]);
     if (x0 < 0 || x1 > shape[0] || x0 >= x1) return fail(XB_E_ARG, "xb_set_grid: bad slab [%lld,%lld)", (long long)x0, (long long)x1);
     HIPCHK(hipSetDevice(c->device));
     if (N != c->n_alloc) {

@@ -114,6 +114,20 @@ static void launch_window_bricks(xb_ctx *c, int *list, int *count, const int *sk
     if (wn > run1) k_brick_walk_list<<<grid, TPB, 0, c->stream>>>(nbr, 0, (wn - run1) * per_plane, c->blab, list, count, skip);
 }
 
+// One GPU: the bricks of the whole grid outside the regions -> walk[0 .. *FS_N_WALK) in Morton order of their coordinates
+// (k_brick_walk_list_morton; bpot: with a vacuum tolerance the bricks below it stay off the list).  The codes enumerate the cube
+// of 2^bits bricks per axis that holds the grid; beyond XB_MORTON_BITS bits -- an axis of more than 8192 voxels -- they no longer
+// fit the code word (1u << 3 * bits wrapped, and the list held a few bricks of the grid's corner: 64 of 65 536 basins found on
+// 16 x 16 x 524288), and the list is made in linear brick order.
+static void launch_walk_list(xb_ctx *c, int nb0, int nb1, int nb2, int *walk, const int *bpot, double vac_tol) {
+    int bits = 0;
+    while ((1 << bits) < std::max(std::max(nb0, nb1), nb2)) bits++;
+    const bool linear = bits > XB_MORTON_BITS;
+    const unsigned n_codes = linear ? (unsigned)(nb0 * nb1 * nb2) : 1u << (3 * bits);
+    k_brick_walk_list_morton<<<(n_codes + 16 * TPB - 1) / (16 * TPB), TPB, 0, c->stream>>>(nb0, nb1, nb2, n_codes, linear ? 1 : 0, c->blab, walk,
+                                                                                          c->fs + FS_N_WALK, c->fs + FS_GROW_RETRY, bpot, vac_tol);
+}
+
 // The persistent trace of the walk list's bricks (k_ng_trace_g): workgroups of XB_TRACE_WAVES waves, one brick per pull
 // (per-XCD cursors over the list, its length on the device).  lean_ok: the lean walker, the own brick's records in LDS, when
 // the index products fit 24 bits (32-bit table offsets up to 2^27 window voxels); otherwise the generic walker (XB_CHECK_GENERIC_WALKER:
@@ -131,6 +145,7 @@ static bool launch_persistent_trace(xb_ctx *c, bool lean_ok, bool part, const in
     // (the neighbour bits: whole bricks, the whole grid, and a table that vouches for them -- else the brick label per step)
     const bool nb = lean && !window && !part && nb_bits_ok(c);
     (nb ? c->stat_nb_traces : lean ? c->stat_lookup_traces : c->stat_generic_traces)++;
+    if (lean == 3) c->stat_wide_traces++;
     auto kernel = !lean ? k_ng_trace_g<2, 0>
                 : nb ? (lean == 4 ? k_ng_trace_g<2, 4, false, false, true> : k_ng_trace_g<2, 3, false, false, true>)
                 : window ? (lean == 4 ? k_ng_trace_g<2, 4, true> : k_ng_trace_g<2, 3, true>)
@@ -162,7 +177,7 @@ static void launch_relabel(xb_ctx *c, int *fs, int n_maxima, bool regions, const
     int *ubuf = reinterpret_cast<int *>(c->st);
     if (regions) {
         const int v = g.nz % 4 == 0 ? 4 : 1;
-        (v == 4 ? k_relabel_regions_brick<4> : k_relabel_regions_brick<1>)<<<dim3((g.nz / v + 63) / 64, nb1, (g.x1 - g.x0 + 3) / 4), TPB, 0, c->stream>>>(
+        (v == 4 ? k_relabel_regions_brick<4> : k_relabel_regions_brick<1>)<<<dim3((g.nz / v + 63) / 64, nb1, (g.x1 - g.x0 + RELABEL_X - 1) / RELABEL_X), TPB, 0, c->stream>>>(
             gl, c->labels, c->first, c->blab, nb1, nb2, box_max, fs, gate, fs ? -1 : c->n_boxes);
         if (buni == BUNI_MIXED) k_fill<int><<<(nbr + 4 * TPB - 1) / (4 * TPB), TPB, 0, c->stream>>>(ubuf, XB_MIXED, nbr);
         if (buni != BUNI_NONE && bres)

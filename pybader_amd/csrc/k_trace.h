@@ -151,7 +151,11 @@ __device__ __forceinline__ bool brick_is_vacuum(const int *__restrict__ bpot, in
     const double f = (double)__int_as_float(p >= 0 ? p : p ^ 0x7fffffff);
     return f + fmax(fabs(f) * 1e-6, 1.1754943508222875e-38 /* FLT_MIN */) < vac_tol;
 }
-__global__ __launch_bounds__(TPB) void k_brick_walk_list_morton(int nb0, int nb1, int nb2, unsigned n_codes,
+// A Morton code holds XB_MORTON_BITS bits per axis (compact3; 3 * 10 bits of an unsigned code): up to 1024 bricks, 8192 voxels, on
+// every axis.  A grid with a longer axis takes the list in LINEAR brick order instead (linear: the codes are the brick indices,
+// n_codes of them) -- the order only decides which bricks are traced side by side, not what is traced.
+#define XB_MORTON_BITS 10
+__global__ __launch_bounds__(TPB) void k_brick_walk_list_morton(int nb0, int nb1, int nb2, unsigned n_codes, int linear,
                                                                 int *blab, int *walk, int *n_walk, const int *skip,
                                                                 const int *__restrict__ bpot = nullptr, double vac_tol = 0.) {
     if (skip && *skip) return;   // (the region growth asks for a repeat: no list, nothing to trace)
@@ -162,8 +166,8 @@ __global__ __launch_bounds__(TPB) void k_brick_walk_list_morton(int nb0, int nb1
     for (int k = 0; k < 16; k++) {
         const unsigned code = base + k;
         const int b2 = compact3(code), b1 = compact3(code >> 1), b0 = compact3(code >> 2);
-        const bool in = code < n_codes && b0 < nb0 && b1 < nb1 && b2 < nb2;
-        bidx[k] = in ? (b0 * nb1 + b1) * nb2 + b2 : 0;
+        const bool in = code < n_codes && (linear || (b0 < nb0 && b1 < nb1 && b2 < nb2));
+        bidx[k] = in ? (linear ? (int)code : (b0 * nb1 + b1) * nb2 + b2) : 0;
         if (in && blab[bidx[k]] <= 0) {
             if (brick_is_vacuum(bpot, bidx[k], vac_tol)) blab[bidx[k]] = XB_NOREC;
             else hits |= 1u << k;

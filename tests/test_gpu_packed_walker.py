@@ -48,18 +48,11 @@ def long_walk_case():
     """16 x 16 x 640: the density rises along z from its minimum at z = 30 to its crest at z = 630 and falls from there through
     the periodic face back to z = 30; a modulation across y puts two ridges (y = 0 and y = 8) and the surfaces between them
     (y = 4, y = 12) inside every brick, so no brick is certified.  Walkers from z = 31 travel 600 voxels up, through more than
-    one 512-voxel window; walkers from z < 30 travel down through the face at z = 0 into the window at the grid's other end."""
-    shape = (16, 16, 640)
-    z = np.arange(640, dtype=np.float64)
-    up = (z - 30.0) % 640.0                      # 0 at z = 30, 600 at z = 630
-    prof = np.where(up <= 600.0, up / 600.0, (640.0 - up) / 40.0)   # rises over 600 voxels, falls over 40
-    y = np.arange(16, dtype=np.float64)
-    x = np.arange(16, dtype=np.float64)
-    ridge = 1.0 + 0.02 * np.cos(2.0 * np.pi * y / 8.0)[None, :, None] + 0.001 * np.cos(2.0 * np.pi * x / 16.0)[:, None, None]
-    rho = np.ascontiguousarray((1.0 + 40.0 * prof)[None, None, :] * ridge)
-    lat = np.diag([1.6, 1.6, 64.0])
-    vl = np.divide(lat, shape)
-    return rho, distance_matrix(vl), gradient_transform(vl), None
+    one 512-voxel window; walkers from z < 30 travel down through the face at z = 0 into the window at the grid's other end.
+    (tests/elongated_common.py builds it for any long axis and length; tests/test_elongated_cpu.py pins this one to the values
+    stated here, and tests/test_gpu_elongated.py runs the other axes and the lengths around a window.)"""
+    import elongated_common
+    return elongated_common.long_walk(2, 640) + (None,)
 
 
 def quant_case():
