@@ -808,6 +808,63 @@ int xb_isa_iterate(xb_ctx *c, int64_t iters, int flags, int64_t *qsum_out, int64
 int xb_isa_tables(xb_ctx *c, double *A_out, int64_t *count_out);
 int xb_isa_load(xb_ctx *c, const double *tables);
 int xb_isa_rho_bound(xb_ctx *c, double *out);
+/* ---- Minimal-basis iterative stockholder atoms (MBIS; Verstraelen et al., JCTC 2016): iterative Hirshfeld weights whose pro-atoms
+ * are sums of a few Slater shells, rho0_a(r) = sum_i N_ai / (8 pi sigma_ai^3) exp(-r / sigma_ai) -- 2 to 16 numbers of state per
+ * atom instead of ISA's table; the charge HORTON, Psi4, Multiwfn and Chargemol print -- no counterpart in the reference ----
+ * Everything not restated here is the Hirshfeld section's, bit for bit: voxel and image positions, d2, the canonical image list and its
+ * margins (species[a] = a: r_cut and rc2 are per atom), the running sums in list order, IEEE float64 without contraction.  Double
+ * sqrt and / are taken to be correctly rounded on the device.
+ *   table     NO exp ON THE DEVICE.  The caller passes ONE table E[0..KE], E[k] = exp(-k / J) for k < KE (J knots per unit of
+ *             x = r / sigma) and E[KE] = 0.0 exactly; finite, non-negative, J >= 1, 1 <= KE <= 2^26.  The library keeps the pairs
+ *             (f[k], d[k]) = (E[k], E[k+1] - E[k]), the differences formed on the host.
+ *   shells    shells[a] in 1 .. XB_MBIS_SHELLS_MAX; M = max_a shells[a] is the row stride of every [n][M] array (entries beyond an
+ *             atom's own shells are not read; they come back as N = 0, sigma = 1).  Per shell, on the host at setup and load and in
+ *             the update kernel alike:  den = ((EIGHT_PI*sigma)*sigma)*sigma,  c = (N > 0 && isfinite(N/den)) ? N/den : 0,
+ *             is = 1.0/sigma,  EIGHT_PI the double 8.0 * M_PI.
+ *   pair      (voxel, image of atom a) with d2 < rc2[a]:  r = sqrt(d2);  for i = 0 .. shells[a]-1:  u = (r*is_i)*(double)J,
+ *             t_i = 0 when !(u < (double)KE), otherwise k = (int)u, w = u - k, t_i = c_i*(f[k] + w*d[k]).  The image's term is
+ *             T = ((0 + t_0) + t_1) + ...;  P(v) = the left-to-right running sum of T in list order.
+ *   iteration for every voxel with |rho| <= rho_bound and P > 0, and every pair: for each shell with t_i > 0
+ *             s = rho*(t_i/P),  binN[a][i] += llrint(ldexp(s, eN)),  binS[a][i] += llrint(ldexp(r*s, eS));  with T > 0
+ *             binV[a] += llrint(ldexp(T/P, eV)).  A voxel with !(P > 0) gives restq += llrint(ldexp(rho, eR)), restn += 1.  A voxel
+ *             whose |rho| is not <= rho_bound adds nothing and is counted; any such voxel makes xb_mbis_iterate fail with XB_E_ARG
+ *             after the launch, and the parameters stay as before the call.  All bins are int64: the order of the adds is free.
+ *   exponents count[a] = the number of pairs with d2 < rc2[a] (a counting pass at setup), cmax = max count, cl2 = ceil_log2 by frexp
+ *             and integers only:  eN = 61 - cl2(rho_bound) - cl2(cmax + 1),  eS = eN - max(0, cl2(max r_cut)),
+ *             eV = 61 - cl2(cmax + 1),  eR = 61 - cl2(rho_bound) - cl2(N_vox + 1).  t_i <= T <= P (running sums of non-negative
+ *             terms are monotone), so no bin reaches 2^62.
+ *   update    per (a, i):  raw = ldexp((double)binN, -eN);  binN > 0:  N' = raw*voxel_volume,
+ *             s1 = ldexp((double)binS, -eS) / (3.0*raw),  sigma' = (binS > 0 && s1 > 0 && isfinite(s1)) ? s1 : sigma;  otherwise
+ *             N' = 0, sigma' = sigma: a dead shell stays dead.  Kept as a row per iteration: qsum[a] = sum_i binN[a][i] (int64),
+ *             vsum[a] = binV[a], restq, restn.  The bins are cleared and the two parameter areas swapped.
+ *   results   charge[a] = voxel_volume * ldexp((double)qsum[a], -eN) of the last iteration, volume[a] = voxel_volume *
+ *             ldexp((double)vsum[a], -eV), rest = {voxel_volume * ldexp((double)restq, -eR), voxel_volume * restn}: exact, no extra pass.
+ * xb_mbis_setup: builds the geometry of a Hirshfeld setup of the context (it REPLACES an xb_hirshfeld_setup or xb_isa_setup and the
+ *             reverse), runs the counting pass and fixes the exponents.  init_N, init_sigma: [n][M], N finite and >= 0, sigma finite
+ *             and > 0.  out_info = {eN, eS, eV, eR, cmax, the total number of pairs}.
+ * xb_mbis_iterate: `iters` iterations (1 .. XB_MBIS_ITERS_MAX) of the resident density queued back to back, ONE host wait; row i of
+ *             qsum_out[iters][n], vsum_out[iters][n] and rest_out[iters][2] = {restq, restn} is iteration i's.  flags:
+ *             XB_HIRSHFELD_FULL_SEARCH (every tile runs over the whole list), XB_MBIS_DIRECT (one global integer atomic per pair and
+ *             shell instead of the sums in registers, over the wave and in LDS): second implementations, the same bits;
+ *             XB_MBIS_KEEP (iters == 1 only): the pass and its row, the parameters stay -- the spin density summed on converged
+ *             weights.  stats: NULL or {candidate tiles, full-search tiles, the longest list, voxels beyond rho_bound}.
+ * xb_mbis_params: the current N_out[n][M], sigma_out[n][M] and count_out[n]; each may be NULL, not all.
+ * xb_mbis_load: N[n][M] and sigma[n][M], checked as at setup, replace the current parameters (the counts and exponents stay).
+ * xb_mbis_field: sum_a rho0_a (XB_HIRSHFELD_PROMOLECULE) or rho minus it (XB_HIRSHFELD_DEFORMATION) of the current parameters; the
+ *             destination rules are xb_hirshfeld_field's.
+ * XB_E_STATE: as the Hirshfeld calls; xb_hirshfeld_sum, xb_hirshfeld_field and the xb_isa_* calls on an MBIS setup, the xb_mbis_* calls
+ * on a setup of another kind;  XB_E_ARG: as xb_isa_setup, a shell count outside 1 .. 8, sigma not > 0, a population that is negative or
+ * not finite, a bad table, voxel_volume not finite or <= 0, iters < 1, unknown flag bits, XB_MBIS_KEEP with iters != 1, a density
+ * beyond rho_bound;  XB_E_LIMIT: as xb_hirshfeld_setup, KE above 2^26, n above 2^23, iters above XB_MBIS_ITERS_MAX.
+ * Every argument error is found on the host before any launch. */
+enum { XB_MBIS_DIRECT = 2, XB_MBIS_KEEP = 4, XB_MBIS_ITERS_MAX = 64, XB_MBIS_SHELLS_MAX = 8 };
+int xb_mbis_setup(xb_ctx *c, const double lattice[9], const double *atoms_cart, int64_t n, const double *r_cut, const int32_t *shells,
+                  const double *etable, int64_t J, int64_t KE, const double *init_N, const double *init_sigma, double rho_bound,
+                  double voxel_volume, int64_t out_info[6]);
+int xb_mbis_iterate(xb_ctx *c, int64_t iters, int flags, int64_t *qsum_out, int64_t *vsum_out, int64_t *rest_out, int64_t stats[4]);
+int xb_mbis_params(xb_ctx *c, double *N_out, double *sigma_out, int64_t *count_out);
+int xb_mbis_load(xb_ctx *c, const double *N, const double *sigma);
+int xb_mbis_field(xb_ctx *c, int mode, int flags, double *out_host, void *out_dev);
 /* utils.volume_assign (utils.py:404-421): labels[v] = swap[labels[v]] for labels >= 0 */
 int xb_volume_assign(xb_ctx *c, const int64_t *swap, int64_t n_swap);
 /* utils.atom_assign (utils.py:185-232): nearest atom of every maximum over the 27 periodic images (one

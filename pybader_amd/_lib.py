@@ -83,6 +83,12 @@ XB_HIRSHFELD_PROMOLECULE, XB_HIRSHFELD_DEFORMATION = 0, 1
 # and the most iterations one call queues
 XB_ISA_DIRECT = 2
 XB_ISA_ITERS_MAX = 64
+# xb_mbis_iterate: XB_MBIS_DIRECT sends every pair and shell out with a global atomic of its own, XB_MBIS_KEEP (one iteration only)
+# leaves the parameters as they are; at most XB_MBIS_SHELLS_MAX shells per atom
+XB_MBIS_DIRECT = 2
+XB_MBIS_KEEP = 4
+XB_MBIS_ITERS_MAX = 64
+XB_MBIS_SHELLS_MAX = 8
 
 # every symbol include/bader_hip.h declares: (restype, argtypes)
 _vp, _i64, _dbl, _int = C.c_void_p, C.c_int64, C.c_double, C.c_int
@@ -192,6 +198,11 @@ SYMBOLS = {
     'xb_isa_tables': (_int, [_vp, _pdbl, _pi64]),
     'xb_isa_load': (_int, [_vp, _pdbl]),
     'xb_isa_rho_bound': (_int, [_vp, _pdbl]),
+    'xb_mbis_setup': (_int, [_vp, _pdbl, _pdbl, _i64, _pdbl, _vp, _pdbl, _i64, _i64, _pdbl, _pdbl, _dbl, _dbl, _pi64]),
+    'xb_mbis_iterate': (_int, [_vp, _i64, _int, _pi64, _pi64, _pi64, _pi64]),
+    'xb_mbis_params': (_int, [_vp, _pdbl, _pdbl, _pi64]),
+    'xb_mbis_load': (_int, [_vp, _pdbl, _pdbl]),
+    'xb_mbis_field': (_int, [_vp, _int, _int, _vp, _vp]),
     'xb_volume_assign': (_int, [_vp, _vp, _i64]),
     'xb_atom_assign': (_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp]),
     'xb_surface_distance': (_int, [_vp, _vp, _vp, _i64, _vp, _pi64]),
@@ -1243,6 +1254,71 @@ class Context:
         if tab.shape != (n, K):
             raise ValueError(f'isa_load: tables {tab.shape}, ({n}, {K}) is wanted')
         check(self.lib.xb_isa_load(self.h, tab.ctypes.data_as(_pdbl)))
+
+    def mbis_setup(self, lattice, atoms_cart, r_cut, shells, etable, knots_per_unit, init_N, init_sigma, rho_bound, voxel_volume):
+        """the cell, the atoms, the exp table and the starting shells of the minimal-basis iterative stockholder atoms go to the
+        device and the pairs are counted (xb_mbis_setup; `r_cut` f64[n], `shells` int[n] in 1 .. 8, `etable` f64[KE + 1] with
+        E[k] = exp(-k / knots_per_unit) and a last 0, `init_N`, `init_sigma` f64[n, M], M = max shells).  It replaces the context's
+        Hirshfeld or ISA setup and the reverse.  -> {'eN', 'eS', 'eV', 'eR', 'cmax', 'pairs'}"""
+        lat, at = _f64(lattice).reshape(9), _f64(atoms_cart).reshape(-1, 3)
+        rc, tab = _f64(r_cut).reshape(-1), _f64(etable).reshape(-1)
+        sh = np.ascontiguousarray(shells, dtype=np.int32).reshape(-1)
+        self.hirshfeld_key = None   # (whatever hirshfeld._setup remembered is no longer what the library holds)
+        if rc.shape[0] != at.shape[0] or sh.shape[0] != at.shape[0]:
+            raise ValueError(f'mbis_setup: r_cut {rc.shape}, shells {sh.shape} for atoms {at.shape}')
+        M = int(sh.max()) if sh.size else 0
+        N0, s0 = _f64(init_N), _f64(init_sigma)
+        if N0.shape != (at.shape[0], M) or s0.shape != N0.shape:
+            raise ValueError(f'mbis_setup: initial shells {N0.shape}, {s0.shape}, ({at.shape[0]}, {M}) is wanted')
+        info = (C.c_int64 * 6)()
+        check(self.lib.xb_mbis_setup(self.h, lat.ctypes.data_as(_pdbl), at.ctypes.data_as(_pdbl), at.shape[0], rc.ctypes.data_as(_pdbl),
+                                     _ptr(sh), tab.ctypes.data_as(_pdbl), int(knots_per_unit), tab.shape[0] - 1,
+                                     N0.ctypes.data_as(_pdbl), s0.ctypes.data_as(_pdbl), float(rho_bound), float(voxel_volume), info))
+        self._hirshfeld_atoms = at.shape[0]
+        self._mbis_stride = M
+        return dict(zip(('eN', 'eS', 'eV', 'eR', 'cmax', 'pairs'), (int(v) for v in info)))
+
+    def mbis_iterate(self, iters=1, direct=False, full_search=False, keep=False):
+        """`iters` iterations of the setup's shells on the resident density, one host wait (xb_mbis_iterate; `keep`: one pass that
+        leaves the parameters) -> (qsum i64[iters, n], vsum i64[iters, n], rest i64[iters, 2],
+        {'candidate_tiles', 'full_tiles', 'max_candidates', 'beyond_bound'})"""
+        n, k = int(getattr(self, '_hirshfeld_atoms', 0)), max(int(iters), 1)
+        qsum, vsum, rest = np.zeros((k, max(n, 1)), np.int64), np.zeros((k, max(n, 1)), np.int64), np.zeros((k, 2), np.int64)
+        st = (C.c_int64 * 4)()
+        flags = (XB_MBIS_DIRECT if direct else 0) | (XB_HIRSHFELD_FULL_SEARCH if full_search else 0) | (XB_MBIS_KEEP if keep else 0)
+        check(self.lib.xb_mbis_iterate(self.h, int(iters), flags, qsum.ctypes.data_as(_pi64), vsum.ctypes.data_as(_pi64),
+                                       rest.ctypes.data_as(_pi64), st))
+        return qsum[:, :n], vsum[:, :n], rest, dict(zip(('candidate_tiles', 'full_tiles', 'max_candidates', 'beyond_bound'), (int(v) for v in st)))
+
+    def mbis_params(self):
+        """the current shells and the pair counts of the MBIS setup (xb_mbis_params) -> (N f64[n, M], sigma f64[n, M], count i64[n])"""
+        n, M = int(getattr(self, '_hirshfeld_atoms', 0)), int(getattr(self, '_mbis_stride', 0))
+        N, sg, count = np.zeros((max(n, 1), max(M, 1))), np.zeros((max(n, 1), max(M, 1))), np.zeros(max(n, 1), np.int64)
+        check(self.lib.xb_mbis_params(self.h, N.ctypes.data_as(_pdbl), sg.ctypes.data_as(_pdbl), count.ctypes.data_as(_pi64)))
+        return N[:n, :M], sg[:n, :M], count[:n]
+
+    def mbis_load(self, N, sigma):
+        """f64[n, M] populations and widths replace the current shells of the MBIS setup (xb_mbis_load)"""
+        n, M = int(getattr(self, '_hirshfeld_atoms', 0)), int(getattr(self, '_mbis_stride', 0))
+        N, sg = _f64(N), _f64(sigma)
+        if N.shape != (n, M) or sg.shape != (n, M):
+            raise ValueError(f'mbis_load: shells {N.shape}, {sg.shape}, ({n}, {M}) is wanted')
+        check(self.lib.xb_mbis_load(self.h, N.ctypes.data_as(_pdbl), sg.ctypes.data_as(_pdbl)))
+
+    def mbis_field(self, mode, full_search=False, on_device=False, out=None):
+        """the sum of the MBIS pro-atoms (mode XB_HIRSHFELD_PROMOLECULE) or the resident density minus it (XB_HIRSHFELD_DEFORMATION)
+        at every voxel (xb_mbis_field) -> f64 of the grid's shape: a host array, or with `on_device` a device.DeviceArray"""
+        flags = XB_HIRSHFELD_FULL_SEARCH if full_search else 0
+        if on_device or out is not None:
+            from . import device
+            if out is None:
+                out = device.DeviceArray(self, self.shape or (0,), np.float64)
+            d, _ = self._flat('mbis_field', out, {np.dtype(np.float64): 64}, True)
+            check(self.lib.xb_mbis_field(self.h, int(mode), flags, None, C.c_void_p(d.ptr)))
+            return out
+        out = np.empty(self.shape or (0,), np.float64)
+        check(self.lib.xb_mbis_field(self.h, int(mode), flags, _ptr(out), None))
+        return out
 
     def density_absmax(self):
         """max |rho| of the resident density (xb_isa_rho_bound)"""

@@ -1,7 +1,7 @@
 // bader_hip.hip -- libbader_hip.so: HIP kernels + C ABI (include/bader_hip.h) for gfx950.  ONE translation unit:
-//   kernels    k_common.h k_masks.h k_fused.h k_trace.h k_ongrid.h k_edges.h k_sums.h k_text.h k_format.h (fmt_core.h) k_interop.h k_weight.h k_cell.h (the cell and tile geometry of the four atom-centred analyses) k_moments.h k_adjacency.h k_merge.h k_voronoi.h k_critical.h k_stencil.h k_nci.h k_hirshfeld.h k_isa.h k_isosurface.h k_regions.h
+//   kernels    k_common.h k_masks.h k_fused.h k_trace.h k_ongrid.h k_edges.h k_sums.h k_text.h k_format.h (fmt_core.h) k_interop.h k_weight.h k_cell.h (the cell and tile geometry of the four atom-centred analyses) k_moments.h k_adjacency.h k_merge.h k_voronoi.h k_critical.h k_stencil.h k_nci.h k_hirshfeld.h k_isa.h k_mbis.h k_isosurface.h k_regions.h
 //   host side  this file (context struct, options, statistics, timing) + ctx_state.h (the cached-state flags and their invalidation events; plain C++) + ctx_buffers.h (the device blocks the analyses keep, their table and their accounting; plain C++) + host_context.h (life cycle, transfers)
-//              + host_assign.h (the table outside an assignment, the assignments) + host_refine.h + host_sums.h + host_slab_table.h (host-driven slab calls) + host_interop.h (device arrays in and out) + host_weight.h (the weight method) + host_cell.h (the host side of k_cell.h) + host_moments.h (moments per label) + host_adjacency.h (surfaces between labels) + host_merge.h (merging volumes by persistence) + host_voronoi.h (the nearest-atom partition) + host_critical.h (critical points and the bond graph) + host_stencil.h (the Laplacian and the Hessian of the density) + host_nci.h (the NCI index: reduced gradient, sign(lambda2) rho, region sums, histogram) + host_hirshfeld.h (Hirshfeld charges, the promolecular and the deformation density) + host_isa.h (iterative stockholder atoms on the Hirshfeld setup) + host_isosurface.h (isosurfaces by marching tetrahedra) + host_regions.h (connected components of a mask: level-set islands, pockets, NCI domains) + host_analyses.h (what the analyses forget with the grid or its shape, their release calls) + comm.h (RCCL through the ABI)
+//              + host_assign.h (the table outside an assignment, the assignments) + host_refine.h + host_sums.h + host_slab_table.h (host-driven slab calls) + host_interop.h (device arrays in and out) + host_weight.h (the weight method) + host_cell.h (the host side of k_cell.h) + host_moments.h (moments per label) + host_adjacency.h (surfaces between labels) + host_merge.h (merging volumes by persistence) + host_voronoi.h (the nearest-atom partition) + host_critical.h (critical points and the bond graph) + host_stencil.h (the Laplacian and the Hessian of the density) + host_nci.h (the NCI index: reduced gradient, sign(lambda2) rho, region sums, histogram) + host_hirshfeld.h (Hirshfeld charges, the promolecular and the deformation density) + host_isa.h host_mbis.h (iterative stockholder atoms on the Hirshfeld setup) + host_isosurface.h (isosurfaces by marching tetrahedra) + host_regions.h (connected components of a mask: level-set islands, pockets, NCI domains) + host_analyses.h (what the analyses forget with the grid or its shape, their release calls) + comm.h (RCCL through the ABI)
 //              + slab_step.h (the slab step with its control flow on the device)
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -shared (see pybader_amd/build.py).
 #include "bader_kernels.h"
@@ -49,6 +49,7 @@ static inline hipError_t xb_counted_sync(hipStream_t s) { xb_waits++; return (hi
 #include "k_nci.h"
 #include "k_hirshfeld.h"
 #include "k_isa.h"
+#include "k_mbis.h"
 #include "k_isosurface.h"
 #include "k_regions.h"
 
@@ -246,6 +247,15 @@ struct xb_ctx : CtxState, CtxBuffers {   // (ctx_state.h: the flags of the cache
     size_t isa_x = 0, isa_pairs0 = 0;
     int isa_e = 0, isa_cur = 0;
     double isa_bound = 0.;
+    // xb_mbis_setup (host_mbis.h): hs_mbis: the setup is an MBIS one (the Hirshfeld setup's geometry with one cutoff per atom, whose
+    // buffer also holds the table, the parameters and the bins, from the double mbis_x on).  M: the largest shell count, the row
+    // stride of the parameters; MS: the least of 1, 2, 4, 8 that holds it; mbis_e: eN, eS, eV, eR; mbis_cur: the current parameter area
+    bool hs_mbis = false;
+    size_t mbis_x = 0;
+    int mbis_M = 0, mbis_MS = 0, mbis_cur = 0, mbis_e[4] = {0, 0, 0, 0};
+    int64_t mbis_J = 0, mbis_KE = 0;
+    double mbis_bound = 0., mbis_vv = 0.;
+    std::vector<int32_t> mbis_shells;
     // xb_isosurface (host_isosurface.h): the mesh of the last call on the device has iso_v vertices and iso_t triangles; its two
     // scalars and the per-label volumes.  iso_have falls with every writer of the density
     size_t iso_v = 0, iso_t = 0;
@@ -389,6 +399,7 @@ const char *xb_last_error(void) { return g_err.c_str(); }
 #include "host_nci.h"
 #include "host_hirshfeld.h"
 #include "host_isa.h"
+#include "host_mbis.h"
 #include "host_isosurface.h"
 #include "host_regions.h"
 #include "host_analyses.h"

@@ -1,6 +1,6 @@
 // host_cell.h -- host side of the geometry the atom-centred analyses share (k_cell.h): the image vectors, the cell's length, the
 // tiles per axis, the finite checks, the block head with the position table, the statistics of a tile kernel's two routes.
-// Used by host_moments.h, host_voronoi.h, host_hirshfeld.h and host_isa.h.  The first part is plain C++ (<cmath>, <cstdint>) and
+// Used by host_moments.h, host_voronoi.h, host_hirshfeld.h, host_isa.h and host_mbis.h.  The first part is plain C++ (<cmath>, <cstdint>) and
 // compiles alone (tests/test_cell_cpu.py); the second needs the library's translation unit.
 #pragma once
 #include <cmath>

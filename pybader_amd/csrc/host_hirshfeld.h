@@ -10,12 +10,13 @@
 //   then         the image list, 4 words per image (q[3], then atom and species as two ints)
 //   then         the results: charge[n], volume[n], the rest's density sum, its voxel count (64-bit), the two statistics words
 //   then         only in an ISA setup (host_isa.h), from the next even word: the second table area, counts, bins, qsum rows, a counter
+//   or           only in an MBIS setup (host_mbis.h), from the next even word: the exp table, two parameter areas, counts, bins, rows
 // The setup is valid for the shape it was made on (hs_geom records it): xb_set_grid drops it when the shape changes, free_grid with the
 // buffer.  Nothing else the context holds enters it -- not the density, not the labels, not dist_mat.
 
 #define HS_HEAD 16
 
-static void hirshfeld_forget(xb_ctx *c) { c->hs_have = false; c->hs_isa = false; }
+static void hirshfeld_forget(xb_ctx *c) { c->hs_have = false; c->hs_isa = false; c->hs_mbis = false; }
 
 // the inverse of the lattice by cofactors, in the order section 18 writes them (A = the lattice itself); false: det is 0 or not finite
 static bool hs_inverse(const double *lat, double M[3][3]) {
@@ -193,6 +194,7 @@ static unsigned hirshfeld_groups(const xb_ctx *c) {
 
 int xb_hirshfeld_sum(xb_ctx *c, double voxel_volume, int flags, double *charge, double *volume, double rest[2], int64_t stats[3]) {
     if (int rc = hirshfeld_ready(c, "xb_hirshfeld_sum")) return rc;
+    if (c->hs_mbis) return fail(XB_E_STATE, "xb_hirshfeld_sum: the setup of this grid is xb_mbis_setup's: its pro-atoms are no radial tables");
     if (!charge || !volume || !rest) return fail(XB_E_ARG, "xb_hirshfeld_sum: null argument");
     if (flags & ~XB_HIRSHFELD_FULL_SEARCH) return fail(XB_E_ARG, "xb_hirshfeld_sum: unknown flag bits 0x%x", flags & ~XB_HIRSHFELD_FULL_SEARCH);
     if (int rc = analysis_ready(c, "xb_hirshfeld_sum", "", NEED_RHO)) return rc;
@@ -226,6 +228,7 @@ int xb_hirshfeld_sum(xb_ctx *c, double voxel_volume, int flags, double *charge, 
 
 int xb_hirshfeld_field(xb_ctx *c, int mode, int flags, double *out_host, void *out_dev) {
     if (int rc = hirshfeld_ready(c, "xb_hirshfeld_field")) return rc;
+    if (c->hs_mbis) return fail(XB_E_STATE, "xb_hirshfeld_field: the setup of this grid is xb_mbis_setup's: its pro-atoms are no radial tables");
     if (mode != XB_HIRSHFELD_PROMOLECULE && mode != XB_HIRSHFELD_DEFORMATION) return fail(XB_E_ARG, "xb_hirshfeld_field: unknown mode %d", mode);
     if ((out_host != nullptr) == (out_dev != nullptr)) return fail(XB_E_ARG, "xb_hirshfeld_field: exactly one of out_host and out_dev is wanted");
     if (flags & ~XB_HIRSHFELD_FULL_SEARCH) return fail(XB_E_ARG, "xb_hirshfeld_field: unknown flag bits 0x%x", flags & ~XB_HIRSHFELD_FULL_SEARCH);

@@ -85,7 +85,7 @@ int xb_isa_setup(xb_ctx *c, const double lattice[9], const double *atoms_cart, i
 // what the ISA calls check alike: hirshfeld_ready, and that the setup is an ISA one
 static int isa_ready(xb_ctx *c, const char *who) {
     if (int rc = hirshfeld_ready(c, who)) return rc;
-    if (!c->hs_isa) return fail(XB_E_STATE, "%s: the setup of this grid is xb_hirshfeld_setup's, not xb_isa_setup's", who);
+    if (!c->hs_isa) return fail(XB_E_STATE, "%s: the setup of this grid is %s, not xb_isa_setup's", who, c->hs_mbis ? "xb_mbis_setup's" : "xb_hirshfeld_setup's");
     return XB_OK;
 }
 

@@ -1,4 +1,4 @@
-// k_cell.h -- device side of the geometry the atom-centred analyses share (k_moments.h, k_voronoi.h, k_hirshfeld.h, k_isa.h; the
+// k_cell.h -- device side of the geometry the atom-centred analyses share (k_moments.h, k_voronoi.h, k_hirshfeld.h, k_isa.h, k_mbis.h; the
 // host side is host_cell.h): the position of a voxel, the squared distance, the tile of T^3 voxels, its ball and the slack of a
 // bound on it, a thread's two voxels.  Every result of those analyses is bit-defined, so each float64 expression they must agree on
 // is written here ONCE.  Included by bader_hip.hip (one translation unit); everything but k_ms_tables inlines into its caller.

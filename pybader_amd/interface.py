@@ -426,6 +426,39 @@ class Bader:
             ensure_density(ctx, self.spin)
             self.isa_spin, _, _, _ = ctx.hirshfeld_sum(self.voxel_volume)
 
+    mbis_flag = False    # True: _run runs mbis_analysis() before voronoi_partition() (no other step changes)
+    mbis_shells = 1      # the Slater shells per atom: a number or one per atom, 1 .. 8
+    mbis_r_cut = 5.0     # where an atom's weight ends: a number or one per atom
+    mbis_tol = 1e-6      # the convergence threshold on the largest change of an atom's charge between two iterations
+
+    def mbis_analysis(self):
+        """Minimal-basis iterative stockholder (MBIS) charges next to the Bader ones (pybader_amd.mbis): iterative Hirshfeld
+        weights from a few Slater shells per atom -- no counterpart in the reference.  Sets mbis_charge, mbis_volume per atom (on
+        the charge density), mbis_rest (charge and volume of the voxels no atom reaches), mbis_populations, mbis_widths,
+        mbis_iterations and mbis_converged; mbis_spin with spin_bool, from one pass on the spin density that leaves the converged
+        shells as they are (the bound of the integer sums covers both densities).  Atoms are atoms - voxel_offset.  It reads the
+        density alone and rewrites nothing."""
+        from .isa import _context, _rho_bound
+        from .mbis import _results, mbis_charges
+        from .utils import ensure_density
+        atoms = self.atoms - self.voxel_offset
+        bound = None
+        if self.spin_bool:
+            ctx = _context(self.spin)
+            ensure_density(ctx, self.spin)
+            bound = _rho_bound(ctx, self.spin)
+            ensure_density(ctx, self.density)
+            bound = max(bound, _rho_bound(ctx, self.density))
+        r = mbis_charges(self.density, self.lattice, atoms, self.voxel_volume, shells=self.mbis_shells, r_cut=self.mbis_r_cut,
+                         tol=self.mbis_tol, rho_bound=bound)
+        self.mbis_charge, self.mbis_volume, self.mbis_rest = r.charge, r.volume, r.rest
+        self.mbis_populations, self.mbis_widths = r.populations, r.widths
+        self.mbis_iterations, self.mbis_converged = r.iterations, r.converged
+        if self.spin_bool:   # (the setup is still the converged one)
+            ensure_density(ctx, self.spin)
+            q, v, rest, _ = ctx.mbis_iterate(1, keep=True)
+            self.mbis_spin = _results(r.stats, self.voxel_volume, q[0], v[0], rest[0])[0]
+
     voronoi_flag = False   # True: _run ends with voronoi_partition() (no other step changes)
 
     def voronoi_partition(self):
@@ -499,6 +532,8 @@ class Bader:
             self.hirshfeld_analysis()
         if self.isa_flag:   # (as hirshfeld_analysis)
             self.isa_analysis()
+        if self.mbis_flag:   # (as hirshfeld_analysis)
+            self.mbis_analysis()
         if self.voronoi_flag:   # (last: it rewrites the device's label map)
             self.voronoi_partition()
 
