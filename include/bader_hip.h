@@ -865,6 +865,52 @@ int xb_mbis_iterate(xb_ctx *c, int64_t iters, int flags, int64_t *qsum_out, int6
 int xb_mbis_params(xb_ctx *c, double *N_out, double *sigma_out, int64_t *count_out);
 int xb_mbis_load(xb_ctx *c, const double *N, const double *sigma);
 int xb_mbis_field(xb_ctx *c, int mode, int flags, double *out_host, void *out_dev);
+/* ---- Stockholder atomic multipoles and radial moments: charge, dipole, second moments, <r^3> and <r^4> of every atom's share
+ * w_a rho (what Psi4, HORTON and Multiwfn print after the stockholder charge; <r^3> / <r^3>_free is the Hirshfeld volume ratio of
+ * the Tkatchenko-Scheffler correction).  xb_moment_sum needs a label map; a weight several atoms share at a voxel is none -- no
+ * counterpart in the reference ----
+ * One more pass over the (voxel, image) pairs of the setup that is current -- xb_hirshfeld_setup's, xb_isa_setup's or
+ * xb_mbis_setup's -- on the resident density.  Everything not restated here is the Hirshfeld section's, bit for bit: the voxel
+ * position pc, the image q and e[j] = pc[j] - q[j], d2 = (e0*e0 + e1*e1) + e2*e2, the canonical list with P(v) the running sum in
+ * list order, IEEE float64 without contraction; double sqrt and / are taken to be correctly rounded on the device.
+ *   term      T of an image at a voxel is the current setup's own: on a Hirshfeld or ISA setup the Hirshfeld section's term (the
+ *             table uniform in r^2), on an MBIS setup that section's T = ((0 + t_0) + t_1) + ... with r = sqrt(d2) and the current
+ *             parameters.
+ *   pair      a voxel v and an image of atom a with  |rho(v)| <= rho_bound,  P(v) > 0,  d2 < rc2  and  T > 0.
+ *   its terms left to right:  w = T / P,  s = rho * w,  r = sqrt(d2),  t_j = s * e[j],  u = s * d2
+ *   bins      twelve int64 per atom, bins[a][0..11]:
+ *               [0]      += llrint(ldexp(s, E0))
+ *               [1 + j]  += llrint(ldexp(t_j, E1))                for j = 0, 1, 2
+ *               [4 .. 9] += llrint(ldexp(t_j * e[k], E2))         for (j, k) = 00, 01, 02, 11, 12, 22: xb_moment_sum's columns
+ *               [10]     += llrint(ldexp(u * r, E3))
+ *               [11]     += llrint(ldexp(u * d2, E4))
+ *             EACH IMAGE IS ITS OWN COPY OF THE ATOM: the displacement is the one to that image, not a minimum image, so an atom
+ *             whose r_cut exceeds half the cell is summed consistently.  Integer addition is associative: the bins do not depend
+ *             on the order of the atomics.
+ *   exponents with frexp and integers only (cl2 = ceil_log2):  L = max(0, cl2(max r_cut)) over the setup's cutoffs;  count[a] = the
+ *             number of (voxel, image of a) pairs with d2 < rc2, cmax = max_a count[a] -- ISA and MBIS setups hold the counts, a
+ *             plain Hirshfeld setup gets them from one counting pass on its first moments call, kept with the setup;
+ *               E_k = 61 - cl2(rho_bound) - cl2(cmax + 1) - k*L      for k = 0 .. 4
+ *             NO BIN REACHES 2^62:  T <= P (running sums of non-negative terms are monotone), so w <= 1 and |s| <= rho_bound;
+ *             |e_j| <= r < r_cut <= 2^L up to an ulp and d2 < rc2 <= 2^(2L) (1 + 2^-52), so a share of order k is below
+ *             rho_bound 2^(k L) (1 + 2^-50) in magnitude and its integer below 2^(61 - cl2(cmax + 1)) (1 + 2^-50) + 1/2; at most
+ *             cmax < 2^cl2(cmax + 1) of them meet in a bin: below 2^61 (1 + 2^-50) + cmax / 2 < 2^62.
+ *   bound     a voxel whose |rho| is not <= rho_bound adds nothing and is counted; any such voxel makes the call fail with
+ *             XB_E_ARG after the launch, and bins_out is then untouched (MBIS's rule).
+ *   results   exact scalings:  moments[a][c] = voxel_volume * ldexp((double)bins[a][c], -E_order(c)),  order(c) = 0, 1 1 1,
+ *             2 2 2 2 2 2, 3, 4.  Columns 0 .. 9 read exactly as a row of xb_moment_sum (m0; m1 x y z; m2 xx xy xz yy yz zz);
+ *             columns 10 and 11 are the integrals of w_a rho r^3 and w_a rho r^4; <r^2> is the trace of the second moments.
+ * xb_stockholder_moments: bins_out[n][12];  info = {E0, E1, E2, E3, E4, cmax, the total number of pairs with d2 < rc2, the voxels
+ *             beyond rho_bound};  stats: NULL or xb_hirshfeld_sum's.  flags: XB_HIRSHFELD_FULL_SEARCH (every tile runs over the
+ *             whole list) and XB_STOCKMOM_DIRECT (one global integer atomic per pair and bin instead of the sums in registers, over
+ *             the wave and in LDS): second implementations, the same bits.  ONE host wait (a plain Hirshfeld setup's first call
+ *             has one more, for its counts).  It writes nothing resident: not the density, not the tables, not the parameters;
+ *             the bins of a call live in the buffer of xb_moment_sum, grown on demand and counted by xb_memory_stats.
+ * XB_E_STATE: no grid, no setup for this grid's shape, no density, a context that holds a slab;  XB_E_ARG: a null pointer (a null
+ * context included), rho_bound not finite or <= 0, unknown flag bits, a density beyond rho_bound.  Every error but the last is
+ * found before any launch.  No option key, no timer slot: a caller times the call. */
+enum { XB_STOCKMOM_DIRECT = 2 };
+int xb_stockholder_moments(xb_ctx *c, double rho_bound, int flags, int64_t *bins_out /* n*12 */, int64_t info[8], int64_t stats[3]);
 /* utils.volume_assign (utils.py:404-421): labels[v] = swap[labels[v]] for labels >= 0 */
 int xb_volume_assign(xb_ctx *c, const int64_t *swap, int64_t n_swap);
 /* utils.atom_assign (utils.py:185-232): nearest atom of every maximum over the 27 periodic images (one

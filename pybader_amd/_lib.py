@@ -89,6 +89,9 @@ XB_MBIS_DIRECT = 2
 XB_MBIS_KEEP = 4
 XB_MBIS_ITERS_MAX = 64
 XB_MBIS_SHELLS_MAX = 8
+# xb_stockholder_moments: the bit of `flags` (beside XB_HIRSHFELD_FULL_SEARCH) that sends every pair and bin out with a global atomic
+# of its own
+XB_STOCKMOM_DIRECT = 2
 
 # every symbol include/bader_hip.h declares: (restype, argtypes)
 _vp, _i64, _dbl, _int = C.c_void_p, C.c_int64, C.c_double, C.c_int
@@ -203,6 +206,7 @@ SYMBOLS = {
     'xb_mbis_params': (_int, [_vp, _pdbl, _pdbl, _pi64]),
     'xb_mbis_load': (_int, [_vp, _pdbl, _pdbl]),
     'xb_mbis_field': (_int, [_vp, _int, _int, _vp, _vp]),
+    'xb_stockholder_moments': (_int, [_vp, _dbl, _int, _pi64, _pi64, _pi64]),
     'xb_volume_assign': (_int, [_vp, _vp, _i64]),
     'xb_atom_assign': (_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp]),
     'xb_surface_distance': (_int, [_vp, _vp, _vp, _i64, _vp, _pi64]),
@@ -1319,6 +1323,19 @@ class Context:
         out = np.empty(self.shape or (0,), np.float64)
         check(self.lib.xb_mbis_field(self.h, int(mode), flags, _ptr(out), None))
         return out
+
+    def stockholder_moments(self, rho_bound, direct=False, full_search=False):
+        """the twelve integer sums per atom of the current setup -- Hirshfeld, ISA or MBIS -- on the resident density, one host wait
+        (xb_stockholder_moments; `rho_bound` >= max |rho|) -> (bins i64[n, 12], {'E': (E0 .. E4), 'cmax', 'pairs', 'beyond_bound'},
+        {'candidate_tiles', 'full_tiles', 'max_candidates'})"""
+        n = int(getattr(self, '_hirshfeld_atoms', 0))
+        bins = np.zeros((max(n, 1), 12), np.int64)
+        info, st = (C.c_int64 * 8)(), (C.c_int64 * 3)()
+        flags = (XB_STOCKMOM_DIRECT if direct else 0) | (XB_HIRSHFELD_FULL_SEARCH if full_search else 0)
+        check(self.lib.xb_stockholder_moments(self.h, float(rho_bound), flags, bins.ctypes.data_as(_pi64), info, st))
+        v = [int(x) for x in info]
+        return (bins[:n], {'E': tuple(v[:5]), 'cmax': v[5], 'pairs': v[6], 'beyond_bound': v[7]},
+                dict(zip(('candidate_tiles', 'full_tiles', 'max_candidates'), (int(x) for x in st))))
 
     def density_absmax(self):
         """max |rho| of the resident density (xb_isa_rho_bound)"""

@@ -16,6 +16,7 @@
 #include <cstring>
 #include <locale.h>   // newlocale, strtod_l: the text reader's host conversions do not depend on LC_NUMERIC
 #include <mutex>
+#include <numeric>
 #include <string>
 #include <thread>
 #include <vector>
@@ -50,6 +51,7 @@ static inline hipError_t xb_counted_sync(hipStream_t s) { xb_waits++; return (hi
 #include "k_hirshfeld.h"
 #include "k_isa.h"
 #include "k_mbis.h"
+#include "k_stockmom.h"
 #include "k_isosurface.h"
 #include "k_regions.h"
 
@@ -256,6 +258,10 @@ struct xb_ctx : CtxState, CtxBuffers {   // (ctx_state.h: the flags of the cache
     int64_t mbis_J = 0, mbis_KE = 0;
     double mbis_bound = 0., mbis_vv = 0.;
     std::vector<int32_t> mbis_shells;
+    // xb_stockholder_moments (host_stockmom.h): what its exponents need of the current setup: the largest cutoff, the largest and the
+    // total pair count (sm_cmax < 0: not counted yet -- a plain Hirshfeld setup before its first moments call)
+    double sm_rmax = 0.;
+    long long sm_cmax = -1, sm_pairs = 0;
     // xb_isosurface (host_isosurface.h): the mesh of the last call on the device has iso_v vertices and iso_t triangles; its two
     // scalars and the per-label volumes.  iso_have falls with every writer of the density
     size_t iso_v = 0, iso_t = 0;
@@ -400,6 +406,7 @@ const char *xb_last_error(void) { return g_err.c_str(); }
 #include "host_hirshfeld.h"
 #include "host_isa.h"
 #include "host_mbis.h"
+#include "host_stockmom.h"
 #include "host_isosurface.h"
 #include "host_regions.h"
 #include "host_analyses.h"

@@ -16,7 +16,7 @@
 
 #define HS_HEAD 16
 
-static void hirshfeld_forget(xb_ctx *c) { c->hs_have = false; c->hs_isa = false; c->hs_mbis = false; }
+static void hirshfeld_forget(xb_ctx *c) { c->hs_have = false; c->hs_isa = false; c->hs_mbis = false; c->sm_cmax = -1; }
 
 // the inverse of the lattice by cofactors, in the order section 18 writes them (A = the lattice itself); false: det is 0 or not finite
 static bool hs_inverse(const double *lat, double M[3][3]) {
@@ -172,6 +172,7 @@ static int hs_build(xb_ctx *c, const double lattice[9], const double *atoms_cart
     G.pairs = reinterpret_cast<const double2 *>(buf + o_pairs);
     G.n_img = (unsigned int)count; G.K = (int)K;
     c->hs_n = n; c->hs_acc = o_acc;
+    c->sm_rmax = *std::max_element(r_cut, r_cut + S);   // (xb_stockholder_moments' exponents)
     c->hs_have = true;
     return XB_OK;
 }

@@ -76,6 +76,8 @@ int xb_isa_setup(xb_ctx *c, const double lattice[9], const double *atoms_cart, i
     for (long long v : cnt) { cmax = std::max(cmax, v); total += v; empty += v == 0; }
     c->isa_e = 61 - isa_ceil_log2(rho_bound) - isa_ceil_log2((unsigned long long)cmax + 1ull);
     c->isa_bound = rho_bound;
+    c->sm_cmax = 0; c->sm_pairs = total;   // (xb_stockholder_moments' exponents: the pairs per atom)
+    for (int64_t a = 0; a < n; a++) c->sm_cmax = std::max(c->sm_cmax, std::accumulate(cnt.begin() + a * K, cnt.begin() + (a + 1) * K, 0ll));
     c->hs_isa = true;
     c->hs_have = true;
     out_info[0] = c->isa_e; out_info[1] = cmax; out_info[2] = total; out_info[3] = empty;

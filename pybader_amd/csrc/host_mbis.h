@@ -135,6 +135,7 @@ int xb_mbis_setup(xb_ctx *c, const double lattice[9], const double *atoms_cart, 
     c->mbis_e[1] = c->mbis_e[0] - std::max(0, isa_ceil_log2(rmax));
     c->mbis_e[2] = 61 - lc;
     c->mbis_e[3] = 61 - lb - isa_ceil_log2((unsigned long long)c->N + 1ull);
+    c->sm_cmax = cmax; c->sm_pairs = total;   // (xb_stockholder_moments' exponents)
     c->hs_mbis = true;
     c->hs_have = true;
     for (int k = 0; k < 4; k++) out_info[k] = c->mbis_e[k];

@@ -89,6 +89,27 @@ class ProAtoms:
         tab[-1] = 0.0
         return cls(tab[None, :], [float(r_cut)])
 
+    def radial_moment(self, k):
+        """4 pi * the integral of rho0 r^(k + 2) dr from 0 to r_cut, per species -> f64[S]; k = 0 is the population, k = 3 the free
+        atom's <r^3> of the Hirshfeld volume ratio.  The closed form for the table's OWN interpolant, which is piecewise linear in
+        x = r^2: with p = (k + 1) / 2 and r^(k + 2) dr = x^p dx / 2, segment j (x_j .. x_j+1, slope b_j = (f_j+1 - f_j) / h2) gives
+          2 pi * [ f_j * A_j + b_j * (B_j - x_j * A_j) ],   A_j = (x_j+1^(p+1) - x_j^(p+1)) / (p + 1),  B_j = (x_j+1^(p+2) - x_j^(p+2)) / (p + 2)
+        k > -3 (the integrand is integrable at the nucleus)."""
+        p = (float(k) + 1.0) / 2.0
+        if not p + 1.0 > 0.0:
+            raise ValueError(f'ProAtoms.radial_moment: k = {k}; k > -3 is wanted')
+        K = self.knots
+        out = np.zeros(self.n_species)
+        for s in range(self.n_species):
+            h2 = self.r_cut[s] * self.r_cut[s] / np.float64(K)
+            x = np.arange(K + 1, dtype=np.float64) * h2
+            f = self.tables[s]
+            A = np.diff(x ** (p + 1.0)) / (p + 1.0)
+            B = np.diff(x ** (p + 2.0)) / (p + 2.0)
+            b = np.diff(f) / h2
+            out[s] = 2.0 * np.pi * float(np.sum(f[:-1] * A + b * (B - x[:-1] * A)))
+        return out
+
     def joined(self, other):
         """the species of self followed by those of `other` (the same number of knots)"""
         return ProAtoms(np.concatenate([self.tables, other.tables]), np.concatenate([self.r_cut, other.r_cut]))

@@ -380,6 +380,19 @@ class Bader:
         self.isosurface, self.isosurface_area, self.isosurface_volume = m, m.area, m.volume
         self.atoms_isosurface_volume = m.volume_by_label
 
+    # True: each of hirshfeld_analysis(), isa_analysis() and mbis_analysis() that runs also sets <kind>_moments f64[n, 12] (the rows of
+    # stockholder.StockholderMoments), <kind>_dipole, <kind>_quadrupole, <kind>_r3 and <kind>_r4 of its atoms on the charge density,
+    # right after its charges, while its setup is current; Hirshfeld also hirshfeld_volume_ratio (<r^3> / <r^3> of the free atom)
+    stockholder_moments_flag = False
+
+    def _stockholder_moments(self, kind, species=None):
+        from .isa import _context
+        from .stockholder import _moments
+        m = _moments(_context(self.density), self.density, self.voxel_volume, None, False, False, f'{kind}_analysis', species)
+        for what, value in (('moments', m.moments), ('dipole', m.dipole), ('quadrupole', m.quadrupole), ('r3', m.r3), ('r4', m.r4)):
+            setattr(self, f'{kind}_{what}', value)
+        return m
+
     hirshfeld_flag = False    # True: _run runs hirshfeld_analysis() before voronoi_partition() (no other step changes)
     hirshfeld_field = False   # ... and True: it keeps the deformation density as well
     proatoms = None           # a hirshfeld.ProAtoms: the free atoms hirshfeld_analysis() weighs with
@@ -400,6 +413,8 @@ class Bader:
         args = (self.lattice, atoms, self.species, self.proatoms)
         self.hirshfeld_charge, self.hirshfeld_volume, self.hirshfeld_rest, self.hirshfeld_stats = hirshfeld_charges(
             self.density, *args, self.voxel_volume)
+        if self.stockholder_moments_flag:
+            self.hirshfeld_volume_ratio = self._stockholder_moments('hirshfeld', self.species).volume_ratio(self.proatoms.radial_moment(3))
         if self.hirshfeld_field:
             self.hirshfeld_deformation = deformation_density(self.density, *args)
         if self.spin_bool:
@@ -421,6 +436,8 @@ class Bader:
         r = isa_charges(self.density, self.lattice, atoms, self.voxel_volume, r_cut=self.isa_r_cut, shells=self.isa_shells, tol=self.isa_tol)
         self.isa_charge, self.isa_volume, self.isa_rest = r.charge, r.volume, r.rest
         self.isa_iterations, self.isa_converged = r.iterations, r.converged
+        if self.stockholder_moments_flag:
+            self._stockholder_moments('isa')
         if self.spin_bool:   # (the setup is still the converged one)
             ctx = _context(self.spin)
             ensure_density(ctx, self.spin)
@@ -454,6 +471,8 @@ class Bader:
         self.mbis_charge, self.mbis_volume, self.mbis_rest = r.charge, r.volume, r.rest
         self.mbis_populations, self.mbis_widths = r.populations, r.widths
         self.mbis_iterations, self.mbis_converged = r.iterations, r.converged
+        if self.stockholder_moments_flag:
+            self._stockholder_moments('mbis')
         if self.spin_bool:   # (the setup is still the converged one)
             ensure_density(ctx, self.spin)
             q, v, rest, _ = ctx.mbis_iterate(1, keep=True)
