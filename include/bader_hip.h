@@ -557,6 +557,58 @@ int xb_nci_sum(xb_ctx *c, const double lattice[9], int64_t n, double voxel_volum
                int flags, int64_t *count, double *charge, double *charge2);
 int xb_nci_hist(xb_ctx *c, const double lattice[9], const double *s_edges, int64_t n_s, const double *x_edges, int64_t n_x, int flags,
                 int64_t *counts);
+/* ---- DORI, the density overlap regions indicator (de Silva & Corminboeuf, J. Chem. Theory Comput. 10, 3745 (2014); what Multiwfn
+ * prints): covalent and non-covalent overlap of the density in one field gamma on [0, 1], sign(lambda2) rho as its colour, and the
+ * sums over the region gamma >= d_cut per label split into attractive, van der Waals and repulsive parts -- no counterpart in the
+ * reference ----
+ * Both calls read the resident density rho of the whole grid (xb_dori_sum the resident labels too); nothing resident is written.
+ * lattice[9]: the cell, a row per axis.
+ *   voxel     c = rho(p), the gradient g0 g1 g2 and the Hessian xx xy xz yy yz zz are EXACTLY the ten values of xb_stencil_points:
+ *             the coefficients of xb_stencil_coeffs, the operations in the order written in the stencil block above.  Then, every
+ *             line one IEEE float64 operation per operator, parenthesised as written:
+ *               gg  = (g0*g0 + g1*g1) + g2*g2                                     (|grad rho|^2)
+ *               h0  = (xx*g0 + xy*g1) + xz*g2
+ *               h1  = (xy*g0 + yy*g1) + yz*g2
+ *               h2  = (xz*g0 + yz*g1) + zz*g2                                     (H g)
+ *               u_a = c*h_a - gg*g_a            (a = 0, 1, 2)                     (rho H g - |g|^2 g)
+ *               N   = 4.0 * ((u0*u0 + u1*u1) + u2*u2)
+ *               D   = (gg*gg)*gg
+ *               S   = N + D
+ *   gamma     = 0.0     if not (c > rho_min)                           (a NaN, +0, -0, a negative density: 0)
+ *             = N / S   if S > 0 and S is finite
+ *             = 1.0     if S == 0 and some component of the Hessian is not 0   (a critical point of the discrete field)
+ *             = 0.0     otherwise                                      (a flat field, an overflow, a NaN)
+ *             This is theta / (1 + theta) with theta = |grad k^2|^2 / (k^2)^3, k = grad rho / rho: grad k^2 = 2 u / rho^3 and
+ *             (k^2)^3 = D / rho^6, so rho^6 cancels between numerator and denominator and no power of rho is formed.  No sqrt, no
+ *             cbrt, no eigen-solve: gamma is bit-defined.  0 <= gamma <= 1 (S >= N by the monotony of rounding).  Range: N and D
+ *             are of the sixth order in rho; a density scaled by 2^k gives the same bits while no product over- or underflows
+ *             (|k| <= 100 on densities of order 1; not at |k| = 170), and so does a lattice scaled by 2^k.
+ *   colour    x = sigma * c where c > rho_min, +0.0 elsewhere; sigma is the sign of lambda2 of the NCI block above (its I1, I2, I3
+ *             and its Descartes rule).  With rho_min = 0 this is the x of xb_nci_field.
+ *   region    gamma >= d_cut, decided on the value the field holds: field, sums, domains and surface agree by construction.  Its
+ *             classes are those of the NCI block:  0 attractive, x < -rho_split;  1 van der Waals, -rho_split <= x <= rho_split;
+ *             2 repulsive, x > rho_split.  gamma is dimensionless; rho_min and rho_split are in the density's units.
+ *   field     xb_dori_field: gamma of every voxel, N doubles in C order, into g_host (host memory) or g_dev (device memory of the
+ *             context's device) -- exactly one of the two is non-null -- and, if it is asked for, x into x_host or x_dev on the
+ *             same side (null: gamma alone, and sigma is not formed).  A device output overlaps neither the resident density nor
+ *             the other.  The call returns when the result is written.
+ *   sums      xb_dori_sum: over the voxels of the region that carry a label a with 0 <= a < n (labels < 0 and >= n are skipped),
+ *             per key 3*a + class:  count[key] = the voxel count,  charge[key] = the sum of rho times voxel_volume,  charge2[key]
+ *             = the sum of rho*rho times voxel_volume; 3 n entries each.  The terms are bit-defined; the order of the sums is free
+ *             (float atomics, as xb_nci_sum).  n <= 85 labels (3 n <= 256 keys) sum in LDS bins per block, more in global memory.
+ * XB_STENCIL_GATHER in `flags` reads the 19 values from global memory, one thread per voxel, instead of staging 8 x 8 x 32 tiles
+ * with their halo in LDS: the second implementation of both, same bits.
+ * XB_E_STATE: no grid, no density (sums: no labels) on this grid yet, a context that holds a slab, host outputs while the context's
+ * scratch buffer holds no whole grid;  XB_E_ARG: a null pointer, gamma on neither or on both sides, x on the other side, unknown
+ * flag bits, n < 1, rho_min or rho_split not finite or negative, d_cut outside (0, 1], a lattice xb_stencil_coeffs refuses, a
+ * device output that is not N doubles of device memory or overlaps the resident density or the other output;  XB_E_LIMIT: n above
+ * (2^31 - 1) / 3.  No option key, no timer slot: a caller times the calls.  The sums use the device buffer of xb_nci_sum (72 n
+ * bytes, kept while the grid stays and counted by xb_memory_stats); the field for host outputs goes through the context's scratch
+ * and, with x, a temporary buffer of N doubles. */
+int xb_dori_field(xb_ctx *c, const double lattice[9], double rho_min, int flags, double *g_host, double *x_host, void *g_dev,
+                  void *x_dev);
+int xb_dori_sum(xb_ctx *c, const double lattice[9], int64_t n, double voxel_volume, double d_cut, double rho_min, double rho_split,
+                int flags, int64_t *count, double *charge, double *charge2);
 /* ---- isosurfaces: marching tetrahedra on the Freudenthal (Kuhn) triangulation of the periodic voxel lattice (the 0.001 a.u.
  * molecular surface with its area and volume, in total and per atom; the zero envelopes of the Laplacian; the s = 0.5 surface of
  * the NCI index coloured by sign(lambda2) rho) -- no counterpart in the reference ----

@@ -177,6 +177,8 @@ SYMBOLS = {
     'xb_nci_field': (_int, [_vp, _pdbl, _int, _vp, _vp, _vp, _vp]),
     'xb_nci_sum': (_int, [_vp, _pdbl, _i64, _dbl, _dbl, _dbl, _dbl, _int, _pi64, _pdbl, _pdbl]),
     'xb_nci_hist': (_int, [_vp, _pdbl, _pdbl, _i64, _pdbl, _i64, _int, _pi64]),
+    'xb_dori_field': (_int, [_vp, _pdbl, _dbl, _int, _vp, _vp, _vp, _vp]),
+    'xb_dori_sum': (_int, [_vp, _pdbl, _i64, _dbl, _dbl, _dbl, _dbl, _int, _pi64, _pdbl, _pdbl]),
     'xb_isosurface_table': (_int, [_vp]),
     'xb_isosurface': (_int, [_vp, _vp, _vp, _pdbl, _dbl, _i64, _int, _pi64]),
     'xb_isosurface_fetch': (_int, [_vp, _int, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _pdbl, _pdbl, _i64]),
@@ -1050,6 +1052,39 @@ class Context:
         check(self.lib.xb_nci_hist(self.h, lat.ctypes.data_as(_pdbl), se.ctypes.data_as(_pdbl), n_s, xe.ctypes.data_as(_pdbl), n_x,
                                    XB_STENCIL_GATHER if gather else 0, counts.ctypes.data_as(_pi64)))
         return counts
+
+    def dori_field(self, lattice, rho_min, gather=False, on_device=False, colour=True, out=None):
+        """DORI's gamma and, with `colour`, x = sign(lambda2) rho of the resident density at every voxel (xb_dori_field; `lattice`
+        the cell, a row per axis; gamma = 0 and x = 0 where rho is not above `rho_min`; `gather`: the second implementation, as in
+        laplacian_field) -> (gamma, x), f64 of the grid's shape each, x None without `colour`: host arrays, or with `on_device`
+        device.DeviceArrays (`out`: a pair to write into instead of new ones, its second entry None for gamma alone)"""
+        lat = _f64(lattice).reshape(9)
+        flags = XB_STENCIL_GATHER if gather else 0
+        if on_device or out is not None:
+            from . import device
+            if out is None:
+                out = [device.DeviceArray(self, self.shape or (0,), np.float64) for _ in range(2 if colour else 1)] + [None]
+            ptr = [None if o is None else C.c_void_p(self._flat('dori_field', o, {np.dtype(np.float64): 64}, True)[0].ptr) for o in out[:2]]
+            check(self.lib.xb_dori_field(self.h, lat.ctypes.data_as(_pdbl), float(rho_min), flags, None, None, ptr[0], ptr[1]))
+            return out[0], out[1]
+        g = np.empty(self.shape or (0,), np.float64)
+        x = np.empty(self.shape or (0,), np.float64) if colour else None
+        check(self.lib.xb_dori_field(self.h, lat.ctypes.data_as(_pdbl), float(rho_min), flags, _ptr(g), None if x is None else _ptr(x),
+                                     None, None))
+        return g, x
+
+    def dori_sum(self, lattice, n, voxel_volume, d_cut, rho_min, rho_split, gather=False):
+        """the DORI region (gamma >= d_cut; gamma = 0 where rho is not above rho_min) of the resident density summed over the
+        voxels of each resident label 0 .. n - 1 and each class (attractive, van der Waals, repulsive by sign(lambda2) rho against
+        rho_split) (xb_dori_sum) -> (count i64[n, 3], charge f64[n, 3], charge2 f64[n, 3]): the voxel count, the sums of rho and
+        of rho^2, the sums multiplied once by voxel_volume"""
+        lat, n = _f64(lattice).reshape(9), int(n)
+        count = np.zeros((max(n, 0), 3), np.int64)
+        charge, charge2 = np.zeros((max(n, 0), 3), np.float64), np.zeros((max(n, 0), 3), np.float64)
+        check(self.lib.xb_dori_sum(self.h, lat.ctypes.data_as(_pdbl), n, float(voxel_volume), float(d_cut), float(rho_min),
+                                   float(rho_split), XB_STENCIL_GATHER if gather else 0, count.ctypes.data_as(_pi64),
+                                   charge.ctypes.data_as(_pdbl), charge2.ctypes.data_as(_pdbl)))
+        return count, charge, charge2
 
     def _field_ptr(self, what, obj):
         """the device pointer of a C-contiguous float64 device array of the grid's shape, or None for None; the context's stream

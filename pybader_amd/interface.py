@@ -368,6 +368,43 @@ class Bader:
 
     nci_domains_flag = False    # True: nci_analysis() also splits the region into its connected domains (no other step changes)
 
+    dori_flag = False           # True: _run runs dori_analysis() after nci_analysis() (no other step changes)
+    dori_cut = 0.9              # the DORI region: gamma at or above this,
+    dori_rho_min = 1e-3         # ... gamma being 0 where the reference density is not above this (its units; 0.001 e / bohr^3)
+    dori_rho_split = 0.01       # |sign(lambda2) rho| up to which a voxel of the region counts as van der Waals
+    dori_domains_flag = False   # True: _run also splits the DORI region into its connected domains (with or without dori_flag)
+
+    def dori_analysis(self):
+        """The density overlap regions of the reference density per atom (pybader_amd.dori) -- no counterpart in the reference.
+        The region is gamma >= dori_cut (gamma = 0 where the density is not above dori_rho_min); its classes by sign(lambda2) rho
+        against dori_rho_split are attractive, van der Waals and repulsive.  From atoms_volumes: atoms_dori_count [n, 3] (voxels),
+        atoms_dori_volume [n, 3] and atoms_dori_charge [n, 3] (the integral of the reference density: the electrons of the atom
+        that sit in overlap regions).  With critical_flag set as well (critical_analysis() runs before this): critical_dori [P],
+        gamma at every critical point of critical_points, and atoms_bond_dori [B], gamma at every bond voxel
+        atoms_bond_graph.voxel."""
+        from .dori import bond_dori, dori_regions
+        r = dori_regions(self.reference, self.atoms_volumes, self.lattice, self.atoms.shape[0], self.voxel_volume, self.dori_cut,
+                         self.dori_rho_min, self.dori_rho_split)
+        self.atoms_dori_count, self.atoms_dori_volume, self.atoms_dori_charge = r.count, r.volume, r.charge
+        if self.critical_flag:
+            self.critical_dori = bond_dori(self.reference, self.lattice, self.critical_points.lin, self.dori_rho_min)
+            self.atoms_bond_dori = bond_dori(self.reference, self.lattice, self.atoms_bond_graph.voxel, self.dori_rho_min)
+
+    def dori_domain_analysis(self):
+        """The connected domains of the DORI region (dori.dori_domains).  Sets dori_domains (a dori.DoriDomains) and, per domain,
+        dori_domain_count [m] (voxels), dori_domain_volume [m], dori_domain_charge [m] (the integral of the reference density: the
+        electrons in this bond's or contact's overlap region), dori_domain_kind [m] (the class of the domain's top voxel),
+        dori_domain_value [m] (gamma there), dori_domain_atoms [m, 2] (the two atoms of atoms_volumes that hold most of it, -1
+        where fewer) and dori_domain_position [m, 3] (the Cartesian position of the top voxel, voxel_offset added)."""
+        from .critical import positions
+        from .dori import dori_domains
+        d = dori_domains(self.reference, self.lattice, self.atoms_volumes, self.atoms.shape[0], self.voxel_volume, self.dori_cut,
+                         self.dori_rho_min, self.dori_rho_split)
+        self.dori_domains = d
+        self.dori_domain_count, self.dori_domain_volume, self.dori_domain_charge = d.count, d.volume, d.charge
+        self.dori_domain_kind, self.dori_domain_value, self.dori_domain_atoms = d.kind, d.value, d.atoms
+        self.dori_domain_position = positions(d.top, d.shape, self.lattice) + self.voxel_offset
+
     isosurface_level = None   # a value: _run runs isosurface_analysis() after nci_analysis() (None: no step changes)
 
     def isosurface_analysis(self):
@@ -543,6 +580,10 @@ class Bader:
             self.laplacian_analysis()
         if self.nci_flag:   # (after critical_analysis, whose bond voxels it reads when both are set; it reads atoms_volumes)
             self.nci_analysis()
+        if self.dori_flag:   # (as nci_analysis: after critical_analysis, reading atoms_volumes; it rewrites nothing)
+            self.dori_analysis()
+        if self.dori_domains_flag:
+            self.dori_domain_analysis()
         if self.isosurface_level is not None:   # (it reads the reference density and atoms_volumes and rewrites nothing)
             self.isosurface_analysis()
         if self.adjacency_flag:
