@@ -963,6 +963,65 @@ int xb_mbis_field(xb_ctx *c, int mode, int flags, double *out_host, void *out_de
  * found before any launch.  No option key, no timer slot: a caller times the call. */
 enum { XB_STOCKMOM_DIRECT = 2 };
 int xb_stockholder_moments(xb_ctx *c, double rho_bound, int flags, int64_t *bins_out /* n*12 */, int64_t info[8], int64_t stats[3]);
+/* ---- IGM, the independent gradient model (Lefebvre et al., Phys. Chem. Chem. Phys. 19, 17928 (2017); the Hirshfeld-partitioned
+ * IGMH of Lu and Chen, J. Comput. Chem. 43, 539 (2022); what IGMPlot and Multiwfn print): delta-g, the norm the density gradient
+ * would have if the atomic gradients could not cancel minus the norm it has, and delta-g_inter, in which only the cancellation
+ * BETWEEN user-named fragments counts -- no counterpart in the reference ----
+ * xb_igm_field reads the current table setup (xb_hirshfeld_setup's or xb_isa_setup's, not xb_mbis_setup's) and the resident
+ * density of the whole grid; nothing resident is written.  Everything not restated here is the Hirshfeld block's, bit for bit: pc,
+ * q, e[j] = pc[j] - q[j], d2, rc2, ih2, the canonical image list, IEEE float64, no contraction.  Double sqrt and / are taken as
+ * correctly rounded (the reliance of the stockholder moments).
+ *   inputs    fragment[a], one int32 per atom of the setup, in -1 .. F-1 with 1 <= F <= 4 = XB_IGM_FRAGMENTS_MAX;  p_min >= 0;
+ *             a mode, XB_IGM_PRO or XB_IGM_STOCKHOLDER.
+ *   image     Per image i of atom a at voxel v: if d2 >= rc2 the image contributes nothing.  Otherwise, with k, t and the table
+ *             pair (f, df) = (f[k], f[k+1] - f[k]) as in the Hirshfeld term:
+ *               T    = f + t*df
+ *               sl   = df * ih2
+ *               c    = sl + sl
+ *               G[j] = c * e[j]            (j = 0, 1, 2)
+ *             G is the EXACT gradient of the table's own interpolant, which is linear in r^2: its slope is piecewise constant
+ *             (it jumps at the knots; no smoothing is applied), and no square root is taken.
+ *   sums      Running sums in list order:  P and gP[j] over all images;  p_a and gp_a[j] over atom a's images, started from 0.
+ *   reached   A voxel is reached iff P > p_min.  At a voxel that is not reached both fields are +0.0.  The floor keeps 1/P finite:
+ *             near the tables' cutoff P -> 0 while rho does not.
+ *   atom      The atomic gradient ga[j] exists only for an atom with fragment[a] >= 0 and p_a > 0:
+ *               XB_IGM_PRO           ga[j] = gp_a[j]
+ *               XB_IGM_STOCKHOLDER   iP = 1.0 / P
+ *                                    w  = p_a * iP
+ *                                    ga[j] = w * gr[j] + rho * ((gp_a[j] - w * gP[j]) * iP)
+ *             gr is the gradient of the resident density rho at v: values 1..3 of xb_stencil_points.  Atoms with fragment[a] == -1
+ *             enter P and gP only.
+ *   total     Atoms ascending:  g[j] += ga[j];  gI[j] += fabs(ga[j]);  gF[fragment[a]][j] += ga[j].  Then
+ *               gX[j]  = ((|gF[0][j]| + |gF[1][j]|) + ...) over the F fragments
+ *               nrm(v) = sqrt((v0*v0 + v1*v1) + v2*v2)
+ *   fields    dg  = nrm(gI) - nrm(g)          (delta-g)
+ *             dgi = nrm(gX) - nrm(g)          (delta-g_inter)
+ *             Neither is clamped: mathematically 0 <= dgi <= dg, rounding gives values a few 1e-15 below 0.  delta-g_intra =
+ *             dg - dgi is the caller's subtraction.  An image beyond its cutoff and an atom with p_a == 0 add nothing, so no bit
+ *             depends on the image range or on the route a tile takes.
+ * xb_igm_field: dg into dg_host (host memory) or dg_dev (device memory of the context's device) or nowhere (both null), dgi
+ *             likewise; at least one of the four is non-null; N doubles in C order each.  lattice[9] is the setup's (the gradient
+ *             of rho needs it).  flags: XB_HIRSHFELD_FULL_SEARCH (every tile runs over the whole list; the same bits).  stats:
+ *             NULL or xb_hirshfeld_sum's.  The call returns when the results are written.
+ * xb_igm_sum: one pass over the resident density rho, the resident labels and two fields of N doubles in device memory, val and
+ *             x.  Over the voxels with val >= cut (decided on the STORED value, so that field, sums, domains and surface agree)
+ *             that carry a label a with 0 <= a < n, per key 3*a + class (0: x < -rho_split;  2: x > rho_split;  1: otherwise):
+ *             count[key] = the voxel count,  charge[key] = the sum of rho times voxel_volume,  integral[key] = the sum of val
+ *             times voxel_volume; 3 n entries each.  The order of the sums is free (float atomics, as xb_nci_sum).
+ * XB_E_STATE: no grid, no table setup for this grid's shape, an MBIS setup current, no density (sums: no labels), a context that
+ * holds a slab, host outputs while the context's scratch buffer holds no whole grid;  XB_E_ARG: a null context (field), a null
+ * pointer, fragment[a] outside -1 .. n_fragments-1, n_fragments outside 1 .. 4, an unknown mode, unknown flag bits, p_min negative
+ * or not finite, a lattice xb_stencil_coeffs refuses or other than the setup's, a field asked for on both sides or none asked
+ * for, a device array that is not N doubles of device memory, an output that overlaps the resident density, the setup, the
+ * context's buffers or the other output; n < 1, rho_split negative or not finite, cut not above 0 or not finite;  XB_E_LIMIT: n
+ * above (2^31 - 1) / 3.  Every error is found before any launch.  No option key, no timer slot: a caller times the calls.  Both use
+ * the device buffer of xb_nci_sum (8 + 4 n bytes for the field, 72 n for the sums; counted by xb_memory_stats); host outputs go
+ * through the context's scratch and, when both fields go to the host, a temporary buffer of N doubles. */
+enum { XB_IGM_PRO = 0, XB_IGM_STOCKHOLDER = 1, XB_IGM_FRAGMENTS_MAX = 4 };
+int xb_igm_field(xb_ctx *c, const double lattice[9], const int32_t *fragment /* n */, int n_fragments, int mode, double p_min, int flags,
+                 double *dg_host, double *dgi_host, void *dg_dev, void *dgi_dev, int64_t stats[3]);
+int xb_igm_sum(xb_ctx *c, const void *val_dev, const void *x_dev, int64_t n, double voxel_volume, double cut, double rho_split,
+               int64_t *count /* n*3 */, double *charge, double *integral);
 /* utils.volume_assign (utils.py:404-421): labels[v] = swap[labels[v]] for labels >= 0 */
 int xb_volume_assign(xb_ctx *c, const int64_t *swap, int64_t n_swap);
 /* utils.atom_assign (utils.py:185-232): nearest atom of every maximum over the 27 periodic images (one

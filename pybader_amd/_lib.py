@@ -92,6 +92,9 @@ XB_MBIS_SHELLS_MAX = 8
 # xb_stockholder_moments: the bit of `flags` (beside XB_HIRSHFELD_FULL_SEARCH) that sends every pair and bin out with a global atomic
 # of its own
 XB_STOCKMOM_DIRECT = 2
+# xb_igm_field: the modes (the atomic gradients are the free atoms' own, or the stockholder shares of the density's), the most fragments
+XB_IGM_PRO, XB_IGM_STOCKHOLDER = 0, 1
+XB_IGM_FRAGMENTS_MAX = 4
 
 # every symbol include/bader_hip.h declares: (restype, argtypes)
 _vp, _i64, _dbl, _int = C.c_void_p, C.c_int64, C.c_double, C.c_int
@@ -179,6 +182,8 @@ SYMBOLS = {
     'xb_nci_hist': (_int, [_vp, _pdbl, _pdbl, _i64, _pdbl, _i64, _int, _pi64]),
     'xb_dori_field': (_int, [_vp, _pdbl, _dbl, _int, _vp, _vp, _vp, _vp]),
     'xb_dori_sum': (_int, [_vp, _pdbl, _i64, _dbl, _dbl, _dbl, _dbl, _int, _pi64, _pdbl, _pdbl]),
+    'xb_igm_field': (_int, [_vp, _pdbl, _vp, _int, _int, _dbl, _int, _vp, _vp, _vp, _vp, _pi64]),
+    'xb_igm_sum': (_int, [_vp, _vp, _vp, _i64, _dbl, _dbl, _dbl, _pi64, _pdbl, _pdbl]),
     'xb_isosurface_table': (_int, [_vp]),
     'xb_isosurface': (_int, [_vp, _vp, _vp, _pdbl, _dbl, _i64, _int, _pi64]),
     'xb_isosurface_fetch': (_int, [_vp, _int, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _pdbl, _pdbl, _i64]),
@@ -1246,6 +1251,48 @@ class Context:
         out = np.empty(self.shape or (0,), np.float64)
         check(self.lib.xb_hirshfeld_field(self.h, int(mode), flags, _ptr(out), None))
         return out
+
+    def igm_field(self, lattice, fragment, mode=XB_IGM_STOCKHOLDER, p_min=0.0, full_search=False, on_device=False, want=(True, True), out=None,
+                  n_fragments=None):
+        """IGM's delta-g and delta-g_inter of the current table setup (hirshfeld_setup's or isa_setup's) and the resident density at
+        every voxel (xb_igm_field; `lattice` the setup's cell; `fragment` int[n], -1 .. F - 1 with F <= XB_IGM_FRAGMENTS_MAX, F = `n_fragments`,
+        None: max(fragment) + 1 and at least 1; `mode` XB_IGM_PRO or XB_IGM_STOCKHOLDER; both fields are +0 where P is not above
+        `p_min`) -> (dg, dgi, {'candidate_tiles', 'full_tiles', 'max_candidates'}), f64 of the grid's shape each: host arrays, or
+        with `on_device` device.DeviceArrays (`out`: a pair to write into instead of new ones); a field `want` leaves out, or
+        whose entry of `out` is None, is None and is not stored"""
+        lat = _f64(lattice).reshape(9)
+        fr = np.ascontiguousarray(fragment, dtype=np.int32).reshape(-1)
+        n = int(getattr(self, '_hirshfeld_atoms', fr.shape[0]))
+        if fr.shape[0] != n:
+            raise ValueError(f'igm_field: {fr.shape[0]} fragments for the {n} atoms of the setup')
+        nf = max(int(fr.max()) + 1 if fr.size else 1, 1) if n_fragments is None else int(n_fragments)
+        flags = XB_HIRSHFELD_FULL_SEARCH if full_search else 0
+        st = (C.c_int64 * 3)()
+        if on_device or out is not None:
+            from . import device
+            if out is None:
+                out = [device.DeviceArray(self, self.shape or (0,), np.float64) if w else None for w in want]
+            ptr = [None if o is None else C.c_void_p(self._flat('igm_field', o, {np.dtype(np.float64): 64}, True)[0].ptr) for o in out[:2]]
+            check(self.lib.xb_igm_field(self.h, lat.ctypes.data_as(_pdbl), _ptr(fr), nf, int(mode), float(p_min), flags, None, None,
+                                        ptr[0], ptr[1], st))
+        else:
+            out = [np.empty(self.shape or (0,), np.float64) if w else None for w in want]
+            check(self.lib.xb_igm_field(self.h, lat.ctypes.data_as(_pdbl), _ptr(fr), nf, int(mode), float(p_min), flags,
+                                        None if out[0] is None else _ptr(out[0]), None if out[1] is None else _ptr(out[1]), None, None, st))
+        return out[0], out[1], dict(zip(('candidate_tiles', 'full_tiles', 'max_candidates'), (int(v) for v in st)))
+
+    def igm_sum(self, val, x, n, voxel_volume, cut, rho_split):
+        """the region val >= cut of the device field `val` (f64 of the grid's shape; `x` likewise: the class by x against rho_split,
+        as nci_sum's) summed over the voxels of each resident label 0 .. n - 1 and each class (xb_igm_sum) ->
+        (count i64[n, 3], charge f64[n, 3], integral f64[n, 3]): the voxel count, the sums of the resident density and of val, the
+        sums multiplied once by voxel_volume"""
+        n = int(n)
+        count = np.zeros((max(n, 0), 3), np.int64)
+        charge, integral = np.zeros((max(n, 0), 3), np.float64), np.zeros((max(n, 0), 3), np.float64)
+        check(self.lib.xb_igm_sum(self.h, self._field_ptr('igm_sum', val), self._field_ptr('igm_sum', x), n, float(voxel_volume),
+                                  float(cut), float(rho_split), count.ctypes.data_as(_pi64), charge.ctypes.data_as(_pdbl),
+                                  integral.ctypes.data_as(_pdbl)))
+        return count, charge, integral
 
     def isa_setup(self, lattice, atoms_cart, r_cut, shells, rho_bound, initial=None):
         """the cell, the atoms and the starting tables of the iterative stockholder atoms go to the device and the shells are

@@ -1,7 +1,7 @@
 // bader_hip.hip -- libbader_hip.so: HIP kernels + C ABI (include/bader_hip.h) for gfx950.  ONE translation unit:
-//   kernels    k_common.h k_masks.h k_fused.h k_trace.h k_ongrid.h k_edges.h k_sums.h k_text.h k_format.h (fmt_core.h) k_interop.h k_weight.h k_cell.h (the cell and tile geometry of the four atom-centred analyses) k_moments.h k_adjacency.h k_merge.h k_voronoi.h k_critical.h k_stencil.h k_nci.h k_dori.h k_hirshfeld.h k_isa.h k_mbis.h k_isosurface.h k_regions.h
+//   kernels    k_common.h k_masks.h k_fused.h k_trace.h k_ongrid.h k_edges.h k_sums.h k_text.h k_format.h (fmt_core.h) k_interop.h k_weight.h k_cell.h (the cell and tile geometry of the four atom-centred analyses) k_moments.h k_adjacency.h k_merge.h k_voronoi.h k_critical.h k_stencil.h k_nci.h k_dori.h k_hirshfeld.h k_isa.h k_mbis.h k_igm.h k_isosurface.h k_regions.h
 //   host side  this file (context struct, options, statistics, timing) + ctx_state.h (the cached-state flags and their invalidation events; plain C++) + ctx_buffers.h (the device blocks the analyses keep, their table and their accounting; plain C++) + host_context.h (life cycle, transfers)
-//              + host_assign.h (the table outside an assignment, the assignments) + host_refine.h + host_sums.h + host_slab_table.h (host-driven slab calls) + host_interop.h (device arrays in and out) + host_weight.h (the weight method) + host_cell.h (the host side of k_cell.h) + host_moments.h (moments per label) + host_adjacency.h (surfaces between labels) + host_merge.h (merging volumes by persistence) + host_voronoi.h (the nearest-atom partition) + host_critical.h (critical points and the bond graph) + host_stencil.h (the Laplacian and the Hessian of the density) + host_nci.h (the NCI index: reduced gradient, sign(lambda2) rho, region sums, histogram) + host_dori.h (DORI: the density overlap regions indicator, region sums) + host_hirshfeld.h (Hirshfeld charges, the promolecular and the deformation density) + host_isa.h host_mbis.h (iterative stockholder atoms on the Hirshfeld setup) + host_isosurface.h (isosurfaces by marching tetrahedra) + host_regions.h (connected components of a mask: level-set islands, pockets, NCI domains) + host_analyses.h (what the analyses forget with the grid or its shape, their release calls) + comm.h (RCCL through the ABI)
+//              + host_assign.h (the table outside an assignment, the assignments) + host_refine.h + host_sums.h + host_slab_table.h (host-driven slab calls) + host_interop.h (device arrays in and out) + host_weight.h (the weight method) + host_cell.h (the host side of k_cell.h) + host_moments.h (moments per label) + host_adjacency.h (surfaces between labels) + host_merge.h (merging volumes by persistence) + host_voronoi.h (the nearest-atom partition) + host_critical.h (critical points and the bond graph) + host_stencil.h (the Laplacian and the Hessian of the density) + host_nci.h (the NCI index: reduced gradient, sign(lambda2) rho, region sums, histogram) + host_dori.h (DORI: the density overlap regions indicator, region sums) + host_hirshfeld.h (Hirshfeld charges, the promolecular and the deformation density) + host_isa.h host_mbis.h (iterative stockholder atoms on the Hirshfeld setup) + host_igm.h (IGM: the independent gradient model on the table setup, region sums) + host_isosurface.h (isosurfaces by marching tetrahedra) + host_regions.h (connected components of a mask: level-set islands, pockets, NCI domains) + host_analyses.h (what the analyses forget with the grid or its shape, their release calls) + comm.h (RCCL through the ABI)
 //              + slab_step.h (the slab step with its control flow on the device)
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -shared (see pybader_amd/build.py).
 #include "bader_kernels.h"
@@ -52,6 +52,7 @@ static inline hipError_t xb_counted_sync(hipStream_t s) { xb_waits++; return (hi
 #include "k_hirshfeld.h"
 #include "k_isa.h"
 #include "k_mbis.h"
+#include "k_igm.h"
 #include "k_stockmom.h"
 #include "k_isosurface.h"
 #include "k_regions.h"
@@ -408,6 +409,7 @@ const char *xb_last_error(void) { return g_err.c_str(); }
 #include "host_hirshfeld.h"
 #include "host_isa.h"
 #include "host_mbis.h"
+#include "host_igm.h"
 #include "host_stockmom.h"
 #include "host_isosurface.h"
 #include "host_regions.h"

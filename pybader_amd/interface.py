@@ -473,12 +473,64 @@ class Bader:
         r = isa_charges(self.density, self.lattice, atoms, self.voxel_volume, r_cut=self.isa_r_cut, shells=self.isa_shells, tol=self.isa_tol)
         self.isa_charge, self.isa_volume, self.isa_rest = r.charge, r.volume, r.rest
         self.isa_iterations, self.isa_converged = r.iterations, r.converged
+        if self.igm_flag or self.igm_domains_flag:
+            self._igm_isa = r   # (igm_analysis() loads the converged tables again)
         if self.stockholder_moments_flag:
             self._stockholder_moments('isa')
         if self.spin_bool:   # (the setup is still the converged one)
             ctx = _context(self.spin)
             ensure_density(ctx, self.spin)
             self.isa_spin, _, _, _ = ctx.hirshfeld_sum(self.voxel_volume)
+
+    igm_flag = False            # True: _run runs igm_analysis() after hirshfeld_analysis() / isa_analysis() (no other step changes)
+    igm_fragments = None        # int[n]: the fragment 0 .. F - 1 (F <= 4) of every atom, -1 for an atom in none
+    igm_mode = 'stockholder'    # 'stockholder' (IGMH: the gradients of the atoms' shares of the density) or 'pro' (the free atoms' own)
+    igm_cut = 0.01              # the IGM region: delta-g_inter at or above this (igm.DG_CUT: a choice)
+    igm_rho_split = 0.01        # |sign(lambda2) rho| up to which a voxel of the region counts as van der Waals
+    igm_p_min = 1e-6            # both fields are 0 where the promolecular density is not above this (igm.P_MIN: a choice)
+    igm_domains_flag = False    # True: _run also splits the IGM region into its connected domains (with or without igm_flag)
+
+    def _igm_args(self, who):
+        """what the pybader_amd.igm calls take after the density: the setup of whichever of hirshfeld_analysis() (it wins when
+        both ran) and isa_analysis() ran"""
+        if self.igm_fragments is None:
+            raise ValueError(f'{who}: set igm_fragments (int[n_atoms]: the fragment of every atom, -1 for none)')
+        kw = {'mode': self.igm_mode, 'p_min': self.igm_p_min}
+        if getattr(self, 'hirshfeld_charge', None) is not None and self.proatoms is not None and self.species is not None:
+            kw.update(species=self.species, proatoms=self.proatoms)
+        elif getattr(self, '_igm_isa', None) is not None:
+            kw.update(isa=self._igm_isa)
+        else:
+            raise ValueError(f'{who}: IGM takes its atomic densities from the Hirshfeld or the ISA analysis, and neither ran: set '
+                             'hirshfeld_flag (with proatoms and species) or isa_flag')
+        return kw
+
+    def igm_analysis(self):
+        """The independent gradient model on the charge density per atom (pybader_amd.igm) -- no counterpart in the reference.
+        The atomic densities are those of whichever of hirshfeld_analysis() and isa_analysis() ran; the region is delta-g_inter >=
+        igm_cut between the fragments igm_fragments, its classes by sign(lambda2) rho against igm_rho_split are attractive, van der
+        Waals and repulsive.  From atoms_volumes: atoms_igm_count [n, 3] (voxels), atoms_igm_volume [n, 3], atoms_igm_charge
+        [n, 3] (the integral of the density) and atoms_igm_integral [n, 3] (the integral of delta-g_inter)."""
+        from .igm import igm_regions
+        r = igm_regions(self.density, self.atoms_volumes, self.lattice, self.atoms - self.voxel_offset, self.igm_fragments,
+                        self.atoms.shape[0], self.voxel_volume, self.igm_cut, self.igm_rho_split, **self._igm_args('igm_analysis'))
+        self.atoms_igm_count, self.atoms_igm_volume, self.atoms_igm_charge, self.atoms_igm_integral = r.count, r.volume, r.charge, r.integral
+
+    def igm_domain_analysis(self):
+        """The connected domains of the IGM region (igm.igm_domains).  Sets igm_domains (an igm.IgmDomains) and, per domain,
+        igm_domain_count [m] (voxels), igm_domain_volume [m], igm_domain_charge [m] (the integral of the density),
+        igm_domain_integral [m] (the integral of delta-g_inter), igm_domain_kind [m] (the class of the domain's top voxel),
+        igm_domain_value [m] (delta-g_inter there), igm_domain_atoms [m, 2] (the two atoms of atoms_volumes that hold most of it,
+        -1 where fewer) and igm_domain_position [m, 3] (the Cartesian position of the top voxel, voxel_offset added)."""
+        from .critical import positions
+        from .igm import igm_domains
+        d = igm_domains(self.density, self.lattice, self.atoms - self.voxel_offset, self.igm_fragments, self.atoms_volumes,
+                        self.atoms.shape[0], self.voxel_volume, self.igm_cut, self.igm_rho_split, **self._igm_args('igm_domain_analysis'))
+        self.igm_domains = d
+        self.igm_domain_count, self.igm_domain_volume, self.igm_domain_charge = d.count, d.volume, d.charge
+        self.igm_domain_integral, self.igm_domain_kind, self.igm_domain_value = d.integral, d.kind, d.value
+        self.igm_domain_atoms = d.atoms
+        self.igm_domain_position = positions(d.top, d.shape, self.lattice) + self.voxel_offset
 
     mbis_flag = False    # True: _run runs mbis_analysis() before voronoi_partition() (no other step changes)
     mbis_shells = 1      # the Slater shells per atom: a number or one per atom, 1 .. 8
@@ -592,6 +644,10 @@ class Bader:
             self.hirshfeld_analysis()
         if self.isa_flag:   # (as hirshfeld_analysis)
             self.isa_analysis()
+        if self.igm_flag:   # (it reads the density, atoms_volumes and the tables of the analysis before it; it rewrites nothing)
+            self.igm_analysis()
+        if self.igm_domains_flag:
+            self.igm_domain_analysis()
         if self.mbis_flag:   # (as hirshfeld_analysis)
             self.mbis_analysis()
         if self.voronoi_flag:   # (last: it rewrites the device's label map)
