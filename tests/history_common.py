@@ -5,8 +5,10 @@ Every expectation comes from what the feature's own test file imports (the oracl
 comparison is the one that file makes: `==` (or equal bits) where it compares so, its rounding bound with its arguments elsewhere.
 Nothing is restated a second time and no tolerance is new.  Expectations are memoised on (kind, grid, the inputs the kind reads).
 The Hirshfeld, ISA, NCI, isosurface and regions kinds stand on tests/test_hirshfeld_cpu.py, test_isa_cpu.py, test_nci_cpu.py,
-test_isosurface_cpu.py and test_regions_cpu.py, which also hold the comparisons their GPU files make (check_s, check_sums,
-first_difference, sums_difference, ...): those files import tests/test_gpu_history.py, so the helpers cannot live there.
+test_isosurface_cpu.py and test_regions_cpu.py, the MBIS, stockholder-moments, DORI and IGM kinds on test_mbis_cpu.py,
+test_stockmom_cpu.py, test_dori_cpu.py and test_igm_cpu.py, which also hold the comparisons their GPU files make (check_s,
+check_sums, first_difference, sums_difference, same_rows, info_of, regions_difference, ...): those files import
+tests/test_gpu_history.py, so the helpers cannot live there.
 
     GRIDS, density(grid, name), labels(grid, name), n_of(grid, name)   the inputs
     KINDS                                                               call kind -> (reads the density, reads the map)
@@ -20,13 +22,18 @@ import random
 import numpy as np
 
 import oracle
+import test_dori_cpu as TD
 import test_hirshfeld_cpu as THS
+import test_igm_cpu as TI
 import test_isa_cpu as TISA
 import test_isosurface_cpu as TISO
+import test_mbis_cpu as TM
 import test_nci_cpu as TN
 import test_regions_cpu as TR
+import test_stockmom_cpu as TS
 from oracle_context import OracleContext
-from pybader_amd import isa, synth
+from pybader_amd import isa, mbis, synth
+from pybader_amd.hirshfeld import ProAtoms
 from pybader_amd.adjacency import active_directions
 from pybader_amd.interface import distance_matrix, gradient_transform
 from pybader_amd.weight import voronoi_weights
@@ -70,6 +77,14 @@ ISA = dict(r_cut=2.5, shells=8, tol=0.0, max_iter=5, check_every=2)        # thr
 NCI_CUTS, NCI_EDGES = TN.HISTORY_CUTS, TN.HISTORY_EDGES
 ISO_QUANTILE = 0.7
 FIELD_LEVEL = 0.0                                       # the *_of_field kinds: the zero envelope of the other density's Laplacian
+MBIS_SHELLS = np.array([1, 2, 1], np.int32)
+MBIS = dict(r_cut=2.5, tol=0.0, max_iter=5, check_every=2)                 # three library calls: 2 + 2 + 1 iterations
+MBIS_KNOTS, MBIS_X_MAX = 256, 48
+DORI_RHO_MIN = 1e-3                                     # dori_fields
+DORI_CUTS = TD.SUM_CUTS                                 # (d_cut, rho_min, rho_split) of dori_regions, dori_domains, dori_isosurface
+FRAGMENTS = np.array([0, 1, 0], np.int32)               # IGM: the second atom against the two others
+IGM_RHO_SPLIT = NCI_CUTS[2]
+IGM_QUANTILE = 0.25
 
 
 def shape_of(grid):
@@ -235,12 +250,24 @@ KINDS = {
     'nci_domains': (True, True),
     'isosurface': (True, True), 'isosurface_gather': (True, True), 'isosurface_of_field': (True, True),
     'regions': (True, True), 'regions_below': (True, True), 'regions_global': (True, True), 'regions_of_field': (True, True),
+    'mbis_charges': (True, False), 'mbis_charges_direct': (True, False), 'mbis_promolecule': (False, False), 'mbis_residual': (True, False),
+    'hirshfeld_moments': (True, False), 'hirshfeld_moments_direct': (True, False), 'isa_moments': (True, False),
+    'mbis_moments': (True, False),
+    'dori_fields': (True, False), 'dori_fields_gather': (True, False), 'dori_regions': (True, True), 'dori_domains': (True, True),
+    'dori_isosurface': (True, False),
+    'igm_fields': (True, False), 'igm_fields_pro': (True, False), 'igm_fields_isa': (True, False), 'igm_regions': (True, True),
+    'igm_domains': (True, True), 'igm_isosurface': (True, False),
 }
 # surface_distance takes the density and its result does not depend on it (the edge voxels are the map's).
 # voronoi_assign without a tolerance reads no density: its second input is the atom set, which goes with the density's name;
 # so do the atoms and pro-atoms of the Hirshfeld kinds and the atoms of the ISA kinds (promolecule reads nothing else).
 # The *_of_field kinds take the Laplacian of other(density name) as a host field beside the density: the mesh and the members
-# come from that field, the volumes' shares from the map, top and the sums from the density, which must stay the resident one
+# come from that field, the volumes' shares from the map, top and the sums from the density, which must stay the resident one.
+# The atoms of the MBIS, moments and IGM kinds go with the density's name as well; mbis_promolecule reads nothing else, and is
+# handed the restated shells of that name's own density.  mbis_residual, isa_moments, mbis_moments and igm_fields_isa are handed
+# results built from the restatement of the density they are called on (mbis_result, isa_result): no GPU run made them.
+# dori_isosurface and igm_isosurface take no label map (dori.dori_isosurface, igm.igm_isosurface have no such argument): their
+# meshes depend on the density alone, so they are (True, False)
 LABEL_WRITERS = ('voronoi', 'voronoi_full', 'voronoi_vacuum', 'voronoi_full_vacuum', 'volume_assign')
 
 
@@ -262,9 +289,9 @@ def maxima_for(grid, mname):
 def _key(kind, grid, dname, mname):
     reads_d, reads_m = KINDS[kind]
     mname = map_for(kind, mname)
-    if kind in ('voronoi', 'voronoi_full', 'promolecule'):
+    if kind in ('voronoi', 'voronoi_full', 'promolecule', 'mbis_promolecule'):
         dname = 'B' if dname.startswith('B') else 'A'
-    return kind, grid, dname if reads_d or kind == 'promolecule' else None, mname if reads_m else None
+    return kind, grid, dname if reads_d or kind in ('promolecule', 'mbis_promolecule') else None, mname if reads_m else None
 
 
 def expect(kind, grid, dname, mname):
@@ -340,6 +367,99 @@ def _components(mask, rho, lab, n):
     count, top, terms = TR.per_component(reg, seeds.size, rho)
     return {'reg': reg, 'seeds': seeds, 'count': count, 'top': top, 's1': TR.sums(terms)[0], 's2': TR.sums([t * t for t in terms])[0],
             'shares': TR.shares(reg, lab, n), 'rho': rho}
+
+
+@functools.lru_cache(maxsize=None)
+def _mbis_geometry(grid, which):
+    return TM.geometry(GRIDS[grid], LAT, SITES[which], MBIS['r_cut'])
+
+
+@functools.lru_cache(maxsize=None)
+def _mbis(grid, dname):
+    """the MBIS run of a density restated by tests/test_mbis_cpu.py from mbis.default_initial -> (g, e, the rows of the five
+    iterations, (N, sigma) after the last, max |rho|)"""
+    rho = density(grid, dname)
+    g = _mbis_geometry(grid, atoms_of(dname))
+    bound = float(np.max(np.abs(rho)))
+    e = TM.exponents(bound, g.count.max(), MBIS['r_cut'], g.N)
+    N0, s0 = mbis.default_initial(MBIS_SHELLS)
+    rows, pars = TM.run(g, TM.Table(TM.table(MBIS_KNOTS, MBIS_X_MAX), MBIS_KNOTS), MBIS_SHELLS, rho, N0, s0, bound, e, MBIS['max_iter'], VV)
+    for a in pars[-1]:
+        a.flags.writeable = False
+    return g, e, rows, pars[-1], bound
+
+
+def mbis_result(grid, dname):
+    """an MbisResult with the restated shells (no GPU run made it): what mbis_promolecule, mbis_residual and mbis_moments are handed"""
+    _, _, _, (N, sigma), bound = _mbis(grid, dname)
+    return mbis.MbisResult(populations=N, widths=sigma, shells=MBIS_SHELLS, r_cut=np.full(3, MBIS['r_cut']), rho_bound=bound,
+                           knots_per_unit=MBIS_KNOTS, x_max=MBIS_X_MAX, voxel_volume=VV)
+
+
+def _mbis_total(grid, dname):
+    g, _, _, (N, sigma), _ = _mbis(grid, dname)
+    return TM.total(g, TM.Table(TM.table(MBIS_KNOTS, MBIS_X_MAX), MBIS_KNOTS), MBIS_SHELLS, N, sigma)
+
+
+@functools.lru_cache(maxsize=None)
+def _stock_geometry(grid, which):
+    """the pairs of the three kinds of setup: one cutoff for every atom and a species per atom, so they are the same pairs"""
+    assert PRO_R_CUT == ISA['r_cut'] == MBIS['r_cut'] and (proatoms(which).r_cut == PRO_R_CUT).all()
+    return TS.geometry(GRIDS[grid], LAT, SITES[which], SPECIES, proatoms(which).r_cut)
+
+
+def _moments(kind, grid, dname):
+    """(bins, info, moments) of tests/test_stockmom_cpu.py's restatement at rho_bound = max |rho|, on the setup of the kind"""
+    rho, which = density(grid, dname), atoms_of(dname)
+    g = _stock_geometry(grid, which)
+    if kind.startswith('hirshfeld'):
+        term = TS.table_term(proatoms(which), SPECIES)
+    elif kind.startswith('isa'):
+        term = TS.isa_term(_isa(grid, dname)[3], np.full(3, ISA['r_cut']))
+    else:
+        term = TS.mbis_term(TM.Table(TM.table(MBIS_KNOTS, MBIS_X_MAX), MBIS_KNOTS), MBIS_SHELLS, *_mbis(grid, dname)[3])
+    bound = float(np.max(np.abs(rho)))
+    E = TS.exponents(bound, g.count.max(), PRO_R_CUT)
+    b, beyond, _, _ = TS.bins(g, term, rho, bound, E)
+    return b, TS.info_of(g, E, beyond), TS.moments(E, b, VV)
+
+
+@functools.lru_cache(maxsize=None)
+def _dori(grid, dname, rho_min):
+    return TD.restated(density(grid, dname), LAT, rho_min)
+
+
+@functools.lru_cache(maxsize=None)
+def _igm_sums(grid, which):
+    t = TI.table_sums(GRIDS[grid], LAT, SITES[which], SPECIES, proatoms(which))
+    for a in t.values():
+        a.flags.writeable = False
+    return t
+
+
+@functools.lru_cache(maxsize=None)
+def _igm(grid, dname, mode='stockholder', on_isa=False):
+    """the two fields of tests/test_igm_cpu.py's restatement for the fragments FRAGMENTS -> (dg, dgi), of the grid's shape"""
+    rho, which = density(grid, dname), atoms_of(dname)
+    if on_isa:          # (the ISA tables are piecewise constant: ProAtoms with a last column of zeros and flat=True, as test_gpu_igm.py)
+        tables = _isa(grid, dname)[3]
+        pro = ProAtoms(np.concatenate([tables, np.zeros((3, 1))], axis=1), np.full(3, ISA['r_cut']))
+        v = TI.restate(GRIDS[grid], LAT, SITES[which], SPECIES, pro, rho, FRAGMENTS, TI.MODES[mode], flat=True)
+    else:
+        v = TI.restate(GRIDS[grid], LAT, SITES[which], SPECIES, proatoms(which), rho, FRAGMENTS, TI.MODES[mode], sums=_igm_sums(grid, which))
+    out = v['dg'].reshape(GRIDS[grid]), v['dgi'].reshape(GRIDS[grid])
+    for a in out:
+        a.flags.writeable = False
+    return out
+
+
+def igm_cut(grid, dname):
+    """the bound of igm_regions, igm_domains and igm_isosurface, picked from the restated delta-g_inter as tests/test_gpu_igm.py's
+    igm_call picks its own (the field peaks near the cutoffs): a quantile of its positive values.  igm_call takes the median on
+    (A, atoms); on (G2, B, noise) the median leaves 42 voxels with a label the sums count, fewer than the 50 the comparison asks
+    for, so the lower quartile is taken here: tests/test_history_cpu.py asserts the 50 on every input a walk can draw"""
+    dgi = _igm(grid, dname)[1]
+    return float(np.quantile(dgi[dgi > 0], IGM_QUANTILE))
 
 
 @functools.lru_cache(maxsize=None)
@@ -440,6 +560,43 @@ def _expect(kind, grid, dname, mname):
         return _components(rho < TR.sum_level(rho), rho, lab, n)
     if kind == 'regions_of_field':
         return _components(field_of(grid, dname) >= FIELD_LEVEL, rho, lab, n)
+    if kind.startswith('mbis_charges'):
+        _, e, rows, (N, sigma), _ = _mbis(grid, dname)
+        return (np.array([TM.results(e, row, VV)[0] for row in rows]), N, sigma) + TM.results(e, rows[-1], VV)
+    if kind == 'mbis_promolecule':
+        return (_mbis_total(grid, dname).reshape(shape),)
+    if kind == 'mbis_residual':
+        return ((rho.reshape(-1) - _mbis_total(grid, dname)).reshape(shape),)
+    if kind.endswith(('_moments', '_moments_direct')):
+        return _moments(kind, grid, dname)
+    if kind.startswith('dori_fields'):
+        v = _dori(grid, dname, DORI_RHO_MIN)
+        return v['gamma'], v['x']
+    if kind == 'dori_regions':
+        return TD.sum_reference(_dori(grid, dname, DORI_CUTS[1]), lab, n, DORI_CUTS)
+    if kind == 'dori_domains':
+        v = _dori(grid, dname, DORI_CUTS[1])
+        out = _components(v['gamma'] >= DORI_CUTS[0], rho, lab, n)
+        out['value'] = v['gamma'].reshape(-1)[out['top']]
+        out['kind'] = TD.classes(v, DORI_CUTS[2]).reshape(-1)[out['top']].astype(np.int8)
+        return out
+    if kind == 'dori_isosurface':
+        v = _dori(grid, dname, DORI_CUTS[1])
+        return TISO.restate(v['gamma'], DORI_CUTS[0], LAT, v['x'])
+    if kind.startswith('igm_fields'):
+        return _igm(grid, dname, 'pro' if kind.endswith('pro') else 'stockholder', kind.endswith('isa')) + (_nci(grid, dname)['x'],)
+    if kind == 'igm_regions':
+        return TI.sum_reference(rho, _igm(grid, dname)[1], _nci(grid, dname)['x'], lab, n, igm_cut(grid, dname), IGM_RHO_SPLIT)
+    if kind == 'igm_domains':
+        val, x = _igm(grid, dname)[1], _nci(grid, dname)['x']
+        out = _components(val >= igm_cut(grid, dname), rho, lab, n)
+        out['value'] = val.reshape(-1)[out['top']]
+        xt = x.reshape(-1)[out['top']]
+        out['kind'] = np.where(xt < -IGM_RHO_SPLIT, 0, np.where(xt > IGM_RHO_SPLIT, 2, 1)).astype(np.int8)
+        out['integral'] = lap_grouped(val, out['reg'], out['seeds'].size)
+        return out
+    if kind == 'igm_isosurface':
+        return TISO.restate(_igm(grid, dname)[1], igm_cut(grid, dname), LAT, _nci(grid, dname)['x'])
     raise KeyError(kind)
 
 
@@ -586,6 +743,54 @@ def _compare(kind, got, want, grid, dname, mname):
         if np.shape(got[7]) != want.volume_by_label.shape:
             return f'volume_by_label of shape {np.shape(got[7])}, expected {want.volume_by_label.shape}'
         return TISO.first_difference(got, want, 'mesh') or TISO.sums_difference(got, want, 'mesh')
+    if kind.startswith('mbis_charges'):                           # test_gpu_mbis.test_a_device_density_equals_the_host_one: same_bits
+        for name, g, w in zip(('history', 'populations', 'widths', 'charge', 'volume', 'rest'), got, want):
+            msg = _first(name, g, w, bits=True)
+            if msg:
+                return msg
+        return None
+    if kind in ('mbis_promolecule', 'mbis_residual'):             # test_gpu_mbis.same_bits
+        return _first('field', got[0], want[0], bits=True)
+    if kind.endswith(('_moments', '_moments_direct')):            # test_gpu_stockmom: bins and info ==, the moments in equal bits
+        if got[1] != want[1]:
+            return f'info: got {got[1]}, expected {want[1]}'
+        return _first('bins', got[0], want[0]) or _first('moments', got[2], want[2], bits=True)
+    if kind.startswith('dori_fields'):                            # test_gpu_dori.same_bits
+        return _first('gamma', got[0], want[0], bits=True) or _first('x', got[1], want[1], bits=True)
+    if kind.startswith('igm_fields'):                             # test_gpu_igm.same_bits
+        return (_first('dg', got[0], want[0], bits=True) or _first('dg_inter', got[1], want[1], bits=True)
+                or _first('x', got[2], want[2], bits=True))
+    if kind == 'dori_regions':                                    # test_gpu_dori.dori_call (the NCI sums' comparison, key by key)
+        cnt = want[0][1]
+        if any(np.shape(a) != (cnt.size // 3, 3) for a in got):
+            return f'sums of shape {np.shape(got[0])}, expected {(cnt.size // 3, 3)}'
+        return TN.regions_difference(*got, want, 'regions')
+    if kind == 'igm_regions':                                     # test_gpu_igm.igm_call
+        cnt = want[0][1]
+        if any(np.shape(a) != (cnt.size // 3, 3) for a in got):
+            return f'sums of shape {np.shape(got[0])}, expected {(cnt.size // 3, 3)}'
+        return TI.regions_difference(*got, want, 'regions')
+    if kind in ('dori_domains', 'igm_domains'):                   # test_gpu_dori / test_gpu_igm: the domains against the components
+        m, reg, seed, count, top, s1, s2, shares, value, cls = got[:10]
+        if m != want['seeds'].size or want['seeds'].size < 1 or not np.array_equal(reg, want['reg']):
+            return 'the map differs'
+        if want['count'].sum() < 50:
+            return f'the restated region holds {int(want["count"].sum())} voxels, too few to say anything'
+        try:
+            TR.check_sums(kind, (seed, count, top, s1, s2), want['reg'], want['seeds'], want['rho'], VV)
+        except AssertionError as e:
+            return str(e)
+        if not all(np.array_equal(g, w) for g, w in zip(shares, want['shares'])):
+            return 'the shares differ'
+        msg = _first('value', value, want['value'], bits=True) or _first('kind', cls, want['kind'])
+        if msg is None and kind == 'igm_domains':                 # (three class sums added: three times the bound of one)
+            s, cnt, mag = want['integral']
+            msg = _within('integral', got[10], s * VV, 3 * lap_sum_bound(cnt, mag))
+        return msg
+    if kind in ('dori_isosurface', 'igm_isosurface'):             # the mesh of isosurface.isosurface on the restated fields
+        if want.triangles.shape[0] < 1:
+            return 'the restated mesh is empty'
+        return TISO.first_difference(got, want, 'mesh') or TISO.sums_difference(got, want, 'mesh')
     raise KeyError(kind)
 
 
@@ -630,18 +835,26 @@ def as_result(kind, want, grid):
     if kind == 'nci_domains' or kind.startswith('regions'):
         return ((want['seeds'].size, want['reg'], want['seeds'], want['count'], want['top'], want['s1'] * VV, want['s2'] * VV, want['shares'])
                 + ((want['class_count'], want['kind']) if kind == 'nci_domains' else ()))
-    if kind.startswith('isosurface'):
+    if kind.startswith('isosurface') or kind in ('dori_isosurface', 'igm_isosurface'):
         return want.vertices, want.colour, want.triangles, want.wrap, want.cells, want.area, want.volume, want.volume_by_label
+    if kind in ('dori_regions', 'igm_regions'):
+        (s1, cnt, _), (s2, _, _) = want
+        return cnt.reshape(-1, 3), (s1 * VV).reshape(-1, 3), (s2 * VV).reshape(-1, 3)
+    if kind in ('dori_domains', 'igm_domains'):
+        return ((want['seeds'].size, want['reg'], want['seeds'], want['count'], want['top'], want['s1'] * VV, want['s2'] * VV, want['shares'],
+                 want['value'], want['kind']) + ((want['integral'][0] * VV,) if kind == 'igm_domains' else ()))
     return want
 
 
 # ---- the seeded walks ------------------------------------------------------------------------------------------------------------
 EVENTS = ('shape', 'resident', 'mutate', 'fail')
 FAILURES = ('density of another shape', 'label map of another shape', 'n < 1', 'non-float device dtype',
-            'isa_iterate on a Hirshfeld setup', 'regions_shares without a labelling')
+            'isa_iterate on a Hirshfeld setup', 'regions_shares without a labelling',
+            'mbis_iterate on a Hirshfeld setup', 'stockholder_moments without a setup',
+            'stockholder_moments under a rho_bound below max |rho|', 'mbis_iterate under a rho_bound below max |rho|')
 
 
-def walk(seed, steps=140):
+def walk(seed, steps=180):
     """-> a list of steps, each a dict with 'op':
 
         call      kind, grid, dname, mname: one checked call
@@ -660,7 +873,10 @@ def walk(seed, steps=140):
     # volume_mask shows a density edit only where the map carries MASK_LABEL in the block (the noise map does not);
     # isosurface_of_field takes its mesh from the other density's Laplacian and its shares from the map: the density is only kept.
     # The 0.7 / 0.8 level sets of the density lie at the atoms: a relabelled block in the tails moves no share of theirs on most
-    # inputs (below the level, on the field and in the NCI region the block is inside: those kinds stay)
+    # inputs (below the level, on the field and in the NCI region the block is inside: those kinds stay).
+    # Every MBIS, moments, DORI and IGM kind shows both edits on every input (the block lies within the cutoffs of the atoms, in
+    # the DORI region and, at the lower quartile, in the IGM region; igm_fields_pro and igm_fields_isa, whose two fields hardly
+    # or not at all depend on the density, show it in x = sign(lambda2) rho): they all stay
     reads_d = [k for k in kinds if KINDS[k][0] and k not in ('voronoi', 'voronoi_full', 'adjacency', 'merge', 'critical_vacuum',
                                                              'critical_flood_vacuum', 'volume_mask', 'isosurface_of_field')]
     reads_m = [k for k in kinds if KINDS[k][1] and k not in ('surface_distance', 'merge', 'bond_graph', 'isosurface', 'isosurface_gather',

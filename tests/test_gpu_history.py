@@ -7,18 +7,29 @@ order, with and without utils.resident(), over host arrays and device tensors, a
 calls, and every result is compared with the expectation of tests/history_common.py (the feature's own restatement and bound).
 
 The kinds (history_common.KINDS): the calls of the reference's pipeline, the weight method, moments, adjacency, merge, Voronoi,
-critical points and bond graph, the Laplacian -- and the five newest analyses: Hirshfeld (hirshfeld_charges, _full, promolecule,
-deformation), ISA (isa_charges, _direct, isa_residual), NCI (nci_fields, _gather, nci_regions, nci_histogram, nci_domains),
-isosurfaces (isosurface, _gather, isosurface_of_field) and connected regions (regions, _below, _global, regions_of_field).  They
-bring the flags "the result is the resident density's" of the mesh and the labelling, the Hirshfeld setup that ISA replaces and
-hirshfeld._setup caches by key, and the calls whose field "becomes the resident density" unless `density=` names it.
+critical points and bond graph, the Laplacian; Hirshfeld (hirshfeld_charges, _full, promolecule, deformation), ISA (isa_charges,
+_direct, isa_residual), NCI (nci_fields, _gather, nci_regions, nci_histogram, nci_domains), isosurfaces (isosurface, _gather,
+isosurface_of_field) and connected regions (regions, _below, _global, regions_of_field), which bring the flags "the result is the
+resident density's" of the mesh and the labelling, the Hirshfeld setup that ISA replaces and hirshfeld._setup caches by key, and
+the calls whose field "becomes the resident density" unless `density=` names it -- and the four analyses that lean hardest on
+such state: MBIS (mbis_charges, _direct, mbis_promolecule, mbis_residual: a third kind of setup in the Hirshfeld block, a
+ping-pong index of its parameters on the host, a setup-only call), the stockholder moments (hirshfeld_moments, _direct,
+isa_moments, mbis_moments: "whichever setup is current", a counting pass once per Hirshfeld setup, bins in the block of
+moment_sum), DORI (dori_fields, _gather, dori_regions, dori_domains, dori_isosurface) and IGM (igm_fields, _pro, _isa,
+igm_regions, igm_domains, igm_isosurface), which write the block of the NCI sums and the shared scratch and hand their fields to
+the labelling and the mesh.
 
 test_every_call_after_every_other   every ordered pair (X, Y) of call kinds on G1, in five settings; one test id per X
-test_seeded_walks                   three seeded walks of about 140 steps over the three grids
+test_seeded_walks                   three seeded walks of about 180 steps over the three grids
 test_a_label_only_call_on_another_grid_inside_resident   the regression case of the defect these tests found
 test_a_hirshfeld_setup_replaced_by_isa_and_dropped_with_the_shape_inside_resident   the key of the cached setup across both events
+test_a_setup_only_mbis_call_on_another_grid_inside_resident   mbis_promolecule on another grid between calls on the pinned density
+test_hirshfeld_moments_across_a_shared_block_a_replaced_setup_and_a_change_of_shape   BLK_M, the counting pass, the key
 
 Wall time on an MI355X: MEASURED below."""
+import ctypes as C
+import warnings
+
 import numpy as np
 import pytest
 try:
@@ -27,20 +38,23 @@ except Exception:  # pragma: no cover
     torch = None
 
 import history_common as H
-from pybader_amd import (_lib, adjacency, critical, device, hirshfeld, isa, isosurface, laplacian, merge, multipole, nci, regions,
-                         thread_handlers, utils, voronoi, weight)
+from pybader_amd import (_lib, adjacency, critical, device, dori, hirshfeld, igm, isa, isosurface, laplacian, mbis, merge, multipole, nci,
+                         regions, stockholder, thread_handlers, utils, voronoi, weight)
 from test_isosurface_cpu import colour_field
 from test_merge_cpu import maxima_of
 from test_regions_cpu import sum_level
 
 pytestmark = pytest.mark.gpu
-MEASURED = ('this file alone in one process, 47 kinds, about 700 calls per id: test_every_call_after_every_other 0.31 s to 1.49 s per id '
-            '(vacuum_assign, the first id, 1.49 s with the shared restatements; isosurface_of_field 1.18 s, weight_other 0.99 s, weight_own '
-            '0.97 s, isosurface 0.95 s, isosurface_gather 0.86 s, regions_of_field 0.79 s, regions_below 0.75 s, nci_domains 0.74 s; the '
-            'ISA ids 0.32 s to 0.46 s, the Hirshfeld and NCI field ids 0.31 s to 0.33 s); test_seeded_walks 0.89 s, 0.65 s, 0.56 s for '
-            'the seeds 11, 23, 47; the three named cases 0.01 s or less each; 53 tests in 26.2 s (a second run: within 0.2 s per id).  '
-            'The slowest test of the five newer features\' own files in a run of theirs: '
-            'test_gpu_hirshfeld.py::test_sums_are_under_the_bound_through_both_routes[line_more], 1.46 s.')
+MEASURED = ('this file alone in one process, 66 kinds, about 1000 calls per id: test_every_call_after_every_other 0.43 s to 1.67 s per id '
+            '(vacuum_assign, the first id, 1.67 s with the shared restatements; isosurface_of_field 1.66 s, dori_isosurface 1.62 s, '
+            'weight_other 1.39 s, weight_own 1.36 s, isosurface 1.36 s, mbis_charges_direct 1.29 s, isosurface_gather 1.21 s, dori_domains '
+            '1.18 s, regions_of_field 1.15 s, regions_below 1.09 s, nci_domains 1.07 s; igm_isosurface 0.94 s, igm_domains 0.90 s, '
+            'hirshfeld_moments_direct 0.75 s, mbis_charges 0.69 s, the other MBIS, moments, DORI and IGM ids 0.45 s to 0.55 s); '
+            'test_seeded_walks 0.94 s, 0.62 s, 0.69 s for the seeds 11, 23, 47 (180 steps each); the five named cases 0.02 s or less '
+            'each; 74 tests in 49.7 s, where the 47 kinds before took 26.2 s.  No id is beyond a few seconds: the iteration counts of '
+            'the MBIS kinds are the ones asked for (5 iterations in calls of 2 + 2 + 1), nothing was lowered.  The '
+            'slowest test of the four newest features\' own files in a run of theirs: '
+            'test_gpu_mbis.py::test_iterates_equal_the_restatement[more_slots_m8-reduced], 1.57 s.')
 
 
 def have_torch():
@@ -199,6 +213,56 @@ class Runner:
                 r = regions.connected_regions(rho, sum_level(H.density(grid, dname)), below=kind.endswith('below'), voxel_volume=H.VV,
                                               volumes=lab, n=n, global_route=kind.endswith('global'))
             return r.m, host(r.labels), r.seed, r.count, r.top, r.charge, r.charge2, r.shares
+        if kind.startswith('mbis_'):
+            sites = H.sites_of(dname)
+            with warnings.catch_warnings():          # (r_cut = 2.5 truncates the model's tails: mbis_charges says so)
+                warnings.simplefilter('ignore', RuntimeWarning)
+                if kind.startswith('mbis_charges'):
+                    r = mbis.mbis_charges(rho, H.LAT, sites, H.VV, shells=H.MBIS_SHELLS, direct=kind.endswith('direct'), **H.MBIS)
+                    return r.history, r.populations, r.widths, r.charge, r.volume, r.rest
+                if kind == 'mbis_promolecule':       # (the shells of the atoms' own density; `rho` gives the shape and the side only)
+                    return (host(mbis.mbis_promolecule(rho, H.LAT, sites, H.mbis_result(grid, H.atoms_of(dname)))),)
+                if kind == 'mbis_residual':
+                    return (host(mbis.mbis_residual(rho, H.LAT, sites, H.mbis_result(grid, dname))),)
+                m = stockholder.mbis_moments(rho, H.LAT, sites, H.mbis_result(grid, dname))
+                return m.bins, m.info, m.moments
+        if kind.startswith('hirshfeld_moments'):
+            m = stockholder.hirshfeld_moments(rho, H.LAT, H.sites_of(dname), H.SPECIES, H.proatoms(H.atoms_of(dname)), H.VV,
+                                              direct=kind.endswith('direct'))
+            return m.bins, m.info, m.moments
+        if kind == 'isa_moments':
+            m = stockholder.isa_moments(rho, H.LAT, H.sites_of(dname), H.isa_result(grid, dname), H.VV)
+            return m.bins, m.info, m.moments
+        if kind.startswith('dori_'):
+            if kind.startswith('dori_fields'):
+                g, x = dori.dori_fields(rho, H.LAT, H.DORI_RHO_MIN, gather=kind.endswith('gather'))
+                return host(g), host(x)
+            if kind == 'dori_regions':
+                r = dori.dori_regions(rho, lab, H.LAT, n, H.VV, *H.DORI_CUTS)
+                return r.count, r.charge, r.charge2
+            if kind == 'dori_domains':
+                d = dori.dori_domains(rho, H.LAT, lab, n, H.VV, *H.DORI_CUTS)
+                return d.m, host(d.labels), d.seed, d.count, d.top, d.charge, d.charge2, d.shares, d.value, d.kind
+            m = dori.dori_isosurface(rho, H.LAT, *H.DORI_CUTS[:2])
+            return m.vertices, m.colour, m.triangles, m.wrap, m.cells, m.area, m.volume, m.volume_by_label
+        if kind.startswith('igm_'):
+            atoms = dict(species=H.SPECIES, proatoms=H.proatoms(H.atoms_of(dname)))
+            sites = H.sites_of(dname)
+            if kind.startswith('igm_fields'):
+                if kind.endswith('isa'):
+                    atoms = dict(isa=H.isa_result(grid, dname))
+                # (with x = sign(lambda2) rho: in mode 'pro' and on ISA tables it is the one output the density decides)
+                dg, dgi, x = igm.igm_fields(rho, H.LAT, sites, H.FRAGMENTS, mode='pro' if kind.endswith('pro') else 'stockholder', **atoms)
+                return host(dg), host(dgi), host(x)
+            cut = H.igm_cut(grid, dname)
+            if kind == 'igm_regions':
+                r = igm.igm_regions(rho, lab, H.LAT, sites, H.FRAGMENTS, n, H.VV, cut, H.IGM_RHO_SPLIT, **atoms)
+                return r.count, r.charge, r.integral
+            if kind == 'igm_domains':
+                d = igm.igm_domains(rho, H.LAT, sites, H.FRAGMENTS, lab, n, H.VV, cut, H.IGM_RHO_SPLIT, **atoms)
+                return d.m, host(d.labels), d.seed, d.count, d.top, d.charge, d.charge2, d.shares, d.value, d.kind, d.integral
+            m = igm.igm_isosurface(rho, H.LAT, sites, H.FRAGMENTS, cut, **atoms)
+            return m.vertices, m.colour, m.triangles, m.wrap, m.cells, m.area, m.volume, m.volume_by_label
         raise KeyError(kind)
 
     def checked(self, kind, grid, dname, mname, **kw):
@@ -253,10 +317,11 @@ def test_every_call_after_every_other(x):
     (A, bader) inside resident(A): B is uploaded over the pinned array and Y must see A again;  4 both on a float32 device tensor
     of A and an int32 device tensor of the map (expectations from A32.astype(float64));  4r the same inside resident(tensor).
 
-    X and Y run over every kind of history_common.KINDS, the Hirshfeld, ISA, NCI, isosurface and regions kinds included: a new
-    analysis after another new one, a Hirshfeld or ISA call next to calls that move the tokens, setting 3 for the calls whose
-    field becomes the resident density, and device tensors for all of them.  The *_of_field kinds hand their field over as a host
-    array in settings 4 and 4r too: it goes through the scratch upload beside the imported tensor."""
+    X and Y run over every kind of history_common.KINDS, the Hirshfeld, ISA, NCI, isosurface, regions, MBIS, moments, DORI and IGM
+    kinds included: a new analysis after another new one, a Hirshfeld, ISA or MBIS call next to calls that move the tokens, every
+    setup of one kind after every setup of another, setting 3 for the calls whose field becomes the resident density, and device
+    tensors for all of them.  The *_of_field kinds hand their field over as a host array in settings 4 and 4r too: it goes
+    through the scratch upload beside the imported tensor."""
     run = Runner()
     bad = pairs_of(x, run, '1 plain', ('A', 'bader'), ('A', 'bader'))
     bad += pairs_of(x, run, '2 resident(A)', ('A', 'bader'), ('A', 'bader'), pinned=H.density('G1', 'A'))
@@ -272,7 +337,9 @@ def test_every_call_after_every_other(x):
 
 # ---- the seeded walks ------------------------------------------------------------------------------------------------------------
 def refused(ctx, how, grid, run):
-    """one call that the host refuses (the refusals the features' own test_error_codes tests make: nothing reaches a kernel)"""
+    """one call that the host refuses (the refusals the features' own error tests make).  Nothing reaches a kernel, except in the
+    two refusals under a rho_bound below max |rho|: there the pass runs, finds voxels beyond the bound and the call returns
+    XB_E_ARG -- an error return, with BLK_M or the MBIS scratch written, which the checked call after it must survive"""
     rho, lab = H.density(grid, 'A'), H.labels(grid, 'atoms')
     small = np.zeros((3, 3, 3))
     if how == 'density of another shape':
@@ -307,6 +374,39 @@ def refused(ctx, how, grid, run):
         with pytest.raises(_lib.BaderHipError) as e:                # (connected_regions and nci_domains release theirs on return)
             ctx.regions_shares(H.n_of(grid, 'atoms'))
         assert e.value.code == _lib.XB_E_STATE
+    elif how == 'mbis_iterate on a Hirshfeld setup':
+        hirshfeld.promolecule(rho, H.LAT, H.SITES['A'], H.SPECIES, H.proatoms('A'))      # (a Hirshfeld setup is no MBIS setup)
+        with pytest.raises(_lib.BaderHipError) as e:
+            ctx.mbis_iterate(1)
+        assert e.value.code == _lib.XB_E_STATE
+    elif how == 'stockholder_moments without a setup':
+        ctx.hirshfeld_release()
+        with pytest.raises(_lib.BaderHipError) as e:
+            ctx.stockholder_moments(1.0)
+        assert e.value.code == _lib.XB_E_STATE
+    elif how == 'stockholder_moments under a rho_bound below max |rho|':
+        # (the kernel runs, counts the voxels beyond the bound and the call refuses: BLK_M is written, the output is not)
+        stockholder.hirshfeld_moments(rho, H.LAT, H.SITES['A'], H.SPECIES, H.proatoms('A'), H.VV)
+        low = 0.5 * float(np.abs(rho).max())
+        out = np.full((3, 12), -77, np.int64)
+        info, st = (C.c_int64 * 8)(), (C.c_int64 * 3)()
+        assert ctx.lib.xb_stockholder_moments(ctx.h, low, 0, out.ctypes.data_as(_lib._pi64), info, st) == _lib.XB_E_ARG
+        assert (out == -77).all() and info[7] == int((np.abs(rho) > low).sum()) > 0
+        with pytest.raises(_lib.BaderHipError) as e:
+            ctx.stockholder_moments(low)
+        assert e.value.code == _lib.XB_E_ARG
+    elif how == 'mbis_iterate under a rho_bound below max |rho|':
+        # (the pass runs into the MBIS scratch and the call refuses: the parameters stay)
+        utils.ensure_density(ctx, rho)
+        N0, s0 = mbis.default_initial(H.MBIS_SHELLS)
+        ctx.mbis_setup(H.LAT, H.SITES['A'], np.full(3, H.MBIS['r_cut']), H.MBIS_SHELLS, mbis.exp_table(H.MBIS_KNOTS, H.MBIS_X_MAX),
+                       H.MBIS_KNOTS, N0, s0, 0.5 * float(np.abs(rho).max()), H.VV)
+        for iters in (1, 2):
+            with pytest.raises(_lib.BaderHipError) as e:
+                ctx.mbis_iterate(iters)
+            assert e.value.code == _lib.XB_E_ARG
+            N, sg, _ = ctx.mbis_params()
+            assert np.array_equal(N.view(np.uint64), N0.view(np.uint64)) and np.array_equal(sg.view(np.uint64), s0.view(np.uint64))
     else:
         raise KeyError(how)
 
@@ -328,7 +428,7 @@ def test_seeded_walks(seed):
 
     Memory: a change to a grid of another voxel count frees everything the context holds for the grid, so right after set_grid
     memory_stats() must equal what it was after the first set_grid of that shape -- at every return to a shape, and at the end
-    after the seven release calls and a last return.  (Between those points the table, the edge buffers and the per-label sum
+    after the release calls and a last return.  (Between those points the table, the edge buffers and the per-label sum
     buffers grow with use and have no release call of their own: the releases can only be shown not to raise the figure.)"""
     ctx = _lib.default_context()
     run = Runner()
@@ -430,6 +530,47 @@ def test_a_hirshfeld_setup_replaced_by_isa_and_dropped_with_the_shape_inside_res
                            ('hirshfeld_charges', 'G1')):
             msg = run.checked(kind, grid, 'A', 'atoms')
             assert msg is None, msg
+
+
+def test_a_setup_only_mbis_call_on_another_grid_inside_resident():
+    """inside resident(A of G1): charge_sum on A, then mbis_promolecule on G2 -- it builds a setup and reads the grid's shape
+    without uploading a density, as the label-only calls above read no density --, then charge_sum on G1 again: the change of
+    shape dropped the device density, so A must be uploaded again.  The promolecule itself is checked too, and the same with a
+    call in between that leans on the setup (hirshfeld_moments) in the place of charge_sum."""
+    run = Runner()
+    _lib.default_context().set_grid(H.GRIDS['G1'], *H.geometry('G1'))
+    with utils.resident(H.density('G1', 'A')):          # (the setup-only call as the first call inside the block)
+        msg = run.checked('mbis_promolecule', 'G2', 'A', 'atoms') or run.checked('charge_sum', 'G1', 'A', 'bader')
+        assert msg is None, f'mbis_promolecule on G2, charge_sum: {msg}'
+    with utils.resident(H.density('G1', 'A')):
+        for kind in ('charge_sum', 'hirshfeld_moments', 'mbis_residual'):
+            assert run.checked(kind, 'G1', 'A', 'bader') is None
+            msg = run.checked('mbis_promolecule', 'G2', 'A', 'atoms')
+            assert msg is None, msg
+            msg = run.checked(kind, 'G1', 'A', 'bader')
+            assert msg is None, f'{kind}, mbis_promolecule on G2, {kind}: {msg}'
+
+
+def test_hirshfeld_moments_across_a_shared_block_a_replaced_setup_and_a_change_of_shape():
+    """hirshfeld_moments, moment_sum (the owner of BLK_M, where the moments' bins go), hirshfeld_moments (the counting pass ran
+    once for this setup: sm_cmax is kept), isa_charges (which replaces the setup: hirshfeld._setup's key and sm_cmax must go),
+    hirshfeld_moments, a change to G2 and back (the setup and the key go with the shape), hirshfeld_moments: every result
+    checked.  Outside resident() and inside it."""
+    run = Runner()
+    ctx = _lib.default_context()
+
+    def sequence(where):
+        for kind in ('hirshfeld_moments', 'moment_sum', 'hirshfeld_moments', 'isa_charges', 'hirshfeld_moments'):
+            msg = run.checked(kind, 'G1', 'A', 'atoms')
+            assert msg is None, f'{where}: {msg}'
+        ctx.set_grid(H.GRIDS['G2'], *H.geometry('G2'))
+        ctx.set_grid(H.GRIDS['G1'], *H.geometry('G1'))
+        msg = run.checked('hirshfeld_moments', 'G1', 'A', 'atoms')
+        assert msg is None, f'{where}, after G2 and back: {msg}'
+
+    sequence('plain')
+    with utils.resident(H.density('G1', 'A')):
+        sequence('resident(A)')
 
 
 # ---- the label token at the level of the Context -----------------------------------------------------------------------------------

@@ -25,7 +25,8 @@ from pybader_amd.hirshfeld import ProAtoms
 from pybader_amd.interface import Bader
 from pybader_amd.isa import IsaResult
 from test_gpu_history import Runner
-from test_igm_cpu import MODES, P_MIN, bits, fragments, reference, restate, sums, table_sums
+from test_igm_cpu import (MODES, P_MIN, bits, check_sums, fragments, keys_of, reference, regions_difference, restate, sum_reference,
+                          sums, table_sums)
 from test_laplacian_cpu import grouped, sum_bound
 from test_multipole_cpu import VV, label_map
 from test_regions_cpu import components, per_component
@@ -249,25 +250,6 @@ def sum_inputs():
     return c, val, x
 
 
-def keys_of(val, x, lab, n, cut, rho_split):
-    inside = (val >= cut) & (lab >= 0) & (lab < n)
-    cls = np.where(x < -rho_split, 0, np.where(x > rho_split, 2, 1))
-    return np.where(inside, 3 * lab.astype(np.int64) + cls, -1).reshape(-1)
-
-
-def check_sums(got, c, val, x, lab, n, cut, rho_split, what):
-    count, charge, integral = got
-    k = keys_of(val, x, lab, n, cut, rho_split)
-    s1, cnt, mag1 = grouped(np.asarray(c.rho, dtype=np.float64), k, 3 * n)
-    s2, _, mag2 = grouped(val, k, 3 * n)
-    print(what, 'voxels in the region', int(cnt.sum()), 'per class', [int(cnt[j::3].sum()) for j in range(3)])
-    assert count.shape == charge.shape == integral.shape == (n, 3) and count.dtype == np.int64
-    assert np.array_equal(count.reshape(-1), cnt), what + ': counts'
-    assert np.all(np.abs(charge.reshape(-1) - s1 * VV) <= sum_bound(cnt, mag1)), what + ': the sums of rho'
-    assert np.all(np.abs(integral.reshape(-1) - s2 * VV) <= sum_bound(cnt, mag2)), what + ': the sums of the field'
-    return cnt
-
-
 def test_sums_counts_are_exact_and_sums_are_under_the_bound(ctx):
     c, val, x = sum_inputs()
     rho_split = 0.5
@@ -487,18 +469,8 @@ def igm_call(kind, grid):
         return None
     cut = float(np.quantile(v['dgi'][v['dgi'] > 0], 0.5))      # (half of the voxels with a positive value: the field peaks near the cutoffs)
     r = igm.igm_regions(rho, lab, H.LAT, H.sites_of('A'), fr, n, VV, cut, 1e300, H.SPECIES, H.proatoms('A'))
-    k = keys_of(v['dgi'].reshape(rho.shape), np.zeros(rho.shape), lab, n, cut, 1e300)
-    s1, cnt, mag1 = grouped(rho, k, 3 * n)
-    s2, _, mag2 = grouped(v['dgi'], k, 3 * n)
-    if cnt.sum() < 50:
-        return f'igm_regions on {grid}: the restated region holds {int(cnt.sum())} voxels, too few to say anything'
-    if not np.array_equal(r.count.reshape(-1), cnt):
-        return f'igm_regions on {grid}: counts differ ({r.count.reshape(-1).tolist()} against {cnt.tolist()})'
-    if not np.all(np.abs(r.charge.reshape(-1) - s1 * VV) <= sum_bound(cnt, mag1)):
-        return f'igm_regions on {grid}: the sums of rho differ'
-    if not np.all(np.abs(r.integral.reshape(-1) - s2 * VV) <= sum_bound(cnt, mag2)):
-        return f'igm_regions on {grid}: the sums of the field differ'
-    return None
+    want = sum_reference(rho, v['dgi'].reshape(rho.shape), np.zeros(rho.shape), lab, n, cut, 1e300)
+    return regions_difference(r.count, r.charge, r.integral, want, f'igm_regions on {grid}')
 
 
 @pytest.mark.parametrize('other', ['hirshfeld_charges', 'isa_charges', 'nci_regions', 'basin_laplacian',

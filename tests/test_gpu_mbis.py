@@ -19,7 +19,7 @@ from pybader_amd import _lib, device, isa, mbis, synth
 from pybader_amd.interface import Bader
 from test_hirshfeld_cpu import n_tiles
 from test_hirshfeld_cpu import case as hs_case
-from test_mbis_cpu import CASES, VV, Table, case, exponents, geo, geometry, reference, results, run, table, total
+from test_mbis_cpu import CASES, VV, Table, case, exponents, geo, geometry, reference, results, run, same_rows, table, total
 
 pytestmark = pytest.mark.gpu
 PRO, DEF = _lib.XB_HIRSHFELD_PROMOLECULE, _lib.XB_HIRSHFELD_DEFORMATION
@@ -47,15 +47,6 @@ def setup(ctx, c, N=None, sigma=None, bound=None, density=True, vv=VV):
         ctx.upload_density(c.rho)
     return ctx.mbis_setup(c.lattice, c.atoms, c.r_cut, c.shells, table(), J, c.N0 if N is None else N, c.s0 if sigma is None else sigma,
                           c.bound if bound is None else bound, vv)
-
-
-def same_rows(got, want, what):
-    """(qsum, vsum, rest) of a call against the restated rows"""
-    q, v, r = got
-    assert q.dtype == v.dtype == r.dtype == np.int64 and q.shape[0] == len(want), what
-    assert np.array_equal(q, np.array([w[0] for w in want])), f'{what}: qsum'
-    assert np.array_equal(v, np.array([w[1] for w in want])), f'{what}: vsum'
-    assert np.array_equal(r, np.array([w[2] for w in want], np.int64)), f'{what}: rest'
 
 
 # ---- info, counts, rows, parameters, fields: every case through every route ------------------------------------------------------

@@ -20,7 +20,7 @@ from pybader_amd import _lib, device, isa, mbis, stockholder, synth
 from pybader_amd.interface import Bader
 from test_hirshfeld_cpu import candidate_counts, n_tiles
 from test_stockmom_cpu import (J, ROWS, SETUPS, VV, bins, exponents, geo, geometry, mbis_term, moments, reference, setup,
-                               table_term)
+                               table_term, want_info)
 
 pytestmark = pytest.mark.gpu
 PRO = _lib.XB_HIRSHFELD_PROMOLECULE
@@ -55,11 +55,6 @@ def install(ctx, s, density=True, grid=True):
         ctx.isa_setup(c.lattice, c.atoms, c.r_cut, c.K, s.bound, s.tables)
     else:
         ctx.mbis_setup(c.lattice, c.atoms, c.r_cut, c.shells, mb.table(), J, c.N0, c.s0, s.bound, VV)
-
-
-def want_info(name, E, beyond=0):
-    g = geo(name)
-    return {'E': tuple(E), 'cmax': int(g.count.max()), 'pairs': int(g.count.sum()), 'beyond_bound': beyond}
 
 
 # ---- bins, info and counts: every input through every route ----------------------------------------------------------------------

@@ -1,7 +1,8 @@
 """The check of the check for tests/test_gpu_history.py (no GPU): the inputs of tests/history_common.py tell a stale upload from a
-fresh one for every call kind -- the Hirshfeld, ISA, NCI, isosurface and regions kinds included --, the seeded walks reach every
-kind and every event, no generated step is left out, the oracle-built maps are converged, and the newer analyses' expectations
-are no empty sets on any grid (voxels no pro-atom reaches, no empty ISA shell, two components, two NCI domains, meshes, shares)."""
+fresh one for every call kind -- the Hirshfeld, ISA, NCI, isosurface, regions, MBIS, moments, DORI and IGM kinds included --, the
+seeded walks reach every kind and every event, no generated step is left out, the oracle-built maps are converged, and the newer
+analyses' expectations are no empty sets on any grid (voxels no pro-atom reaches, no empty ISA shell, two components, two NCI
+domains, meshes, shares, non-zero moments, DORI and IGM regions of 100 and 50 voxels with a component to label)."""
 import collections
 
 import numpy as np
@@ -39,10 +40,12 @@ def test_the_newer_kinds_accept_their_own_expectation_on_every_input_a_walk_can_
 def test_the_float32_density_is_told_from_the_float64_one():
     """setting 4 of the pair matrix computes its expectations from A32.astype(float64): they differ from A's wherever the kind
     returns a float, so a device import that is not the tensor's content cannot pass"""
-    # every new kind that returns a float: all but promolecule, which reads no density, and nci_histogram, which returns counts
-    new = [k for k in H.KINDS if k.startswith(('hirshfeld_charges', 'deformation', 'isa_', 'nci_', 'isosurface', 'regions'))
-           and k != 'nci_histogram']
-    assert len(new) == 17
+    # every new kind that returns a float: all but promolecule and mbis_promolecule, which read no density, and nci_histogram,
+    # which returns counts (the moments' integer bins differ as well; igm_fields_pro differs in x alone)
+    new = [k for k in H.KINDS if k.startswith(('hirshfeld_charges', 'deformation', 'isa_', 'nci_', 'isosurface', 'regions', 'mbis_',
+                                               'hirshfeld_moments', 'dori_', 'igm_'))
+           and k not in ('nci_histogram', 'mbis_promolecule')]
+    assert len(new) == 35
     for kind in ['charge_sum', 'volume_mask', 'weight_own', 'moment_sum', 'laplacian', 'basin_laplacian', 'point_properties'] + new:
         got = H.as_result(kind, H.expect(kind, 'G1', 'A32', 'bader'), 'G1')
         assert H.check(kind, got, ('G1', 'A', 'bader')) is not None, kind
@@ -53,7 +56,7 @@ def test_the_walks_reach_every_kind_and_every_event_and_leave_no_step_out():
     for seed in H.SEEDS:
         steps = H.walk(seed)
         assert steps == H.walk(seed), 'the walk is a function of its seed'
-        assert 135 <= len(steps) <= 150, len(steps)
+        assert 175 <= len(steps) <= 190, len(steps)
         grid, inside = 'G1', False
         for s in steps:
             total += 1
@@ -104,10 +107,39 @@ def test_the_edits_of_the_walks_show_in_the_expectation():
             assert H.check(kind, after, (grid, d, m)) is not None, s
             seen += 1
     assert seen >= 3
-    # ... and of the kinds added with the five newest analyses, at least 12 can be drawn for such a step
+    # ... and of the kinds added with the nine newest analyses, at least 30 can be drawn for such a step
     new = list(H.KINDS)[list(H.KINDS).index('hirshfeld_charges'):]
-    assert len(new) == 19 and sum(H.check(k, H.as_result(k, H.expect(k, 'G1', 'A+', 'bader'), 'G1'), ('G1', 'A', 'bader')) is not None
-                                  for k in new if H.KINDS[k][0] and k != 'isosurface_of_field') >= 12
+    assert len(new) == 38 and sum(H.check(k, H.as_result(k, H.expect(k, 'G1', 'A+', 'bader'), 'G1'), ('G1', 'A', 'bader')) is not None
+                                  for k in new if H.KINDS[k][0] and k != 'isosurface_of_field') >= 30
+
+
+NEWEST = list(H.KINDS)[list(H.KINDS).index('mbis_charges'):]      # the MBIS, moments, DORI and IGM kinds
+
+
+def edit_shows(kind, what, grid, d, m):
+    """the expectation after the edit of a 'mutate' step is its own, and is reported when taken for the result before the edit"""
+    d2, m2 = (d + '+', m) if what == 'density' else (d, m + '+')
+    after = H.as_result(kind, H.expect(kind, grid, d2, m2), grid)
+    assert H.check(kind, after, (grid, d2, m2)) is None, (kind, what, grid, d, m)
+    return H.check(kind, after, (grid, d, m)) is not None
+
+
+def test_the_newest_kinds_show_both_edits_on_every_input():
+    """walk() leaves no MBIS, moments, DORI or IGM kind out of either edit: the corner block's edit shows in the expectation of
+    every one of them on every (grid, density, map) a walk can draw"""
+    assert len(NEWEST) == 19
+    inputs = [(g, d, m) for g in H.GRIDS for d in H.densities(g) for m in H.maps(g)]
+    for kind in NEWEST:
+        reads_d, reads_m = H.KINDS[kind]
+        if reads_d:
+            assert all(edit_shows(kind, 'density', *i) for i in inputs), kind
+        if reads_m:
+            assert all(edit_shows(kind, 'labels', *i) for i in inputs), kind
+    drawn = {s['kind'] for seed in H.SEEDS for s in H.walk(seed) if s['op'] == 'mutate'}
+    assert drawn & set(NEWEST)
+    # (mode 'pro' takes the free atoms' own gradients: without x the density would not show in igm_fields_pro at all)
+    before, after = H.expect('igm_fields_pro', 'G1', 'A', 'atoms'), H.expect('igm_fields_pro', 'G1', 'A+', 'atoms')
+    assert np.array_equal(before[0], after[0]) and np.array_equal(before[1], after[1]) and not np.array_equal(before[2], after[2])
 
 
 def test_the_oracle_built_maps_are_converged():
@@ -153,3 +185,34 @@ def test_the_inputs_are_what_the_issue_asks_for():
             for kind in ('regions', 'regions_below', 'regions_of_field', 'nci_domains'):
                 assert H.expect(kind, grid, d, 'atoms')['shares'][2].sum() >= 50, (kind, grid, d)
             assert H.expect('nci_regions', grid, d, 'atoms')[0][1].sum() >= 100 and H.expect('nci_histogram', grid, d, 'atoms')[0].sum() > 100
+
+
+def test_the_mbis_moments_dori_and_igm_inputs_say_something_on_every_input_a_walk_can_draw():
+    """no voxel beyond the bound, every stockholder bin non-zero, every MBIS shell alive; the DORI and IGM regions hold the voxels
+    their comparisons ask for (100 and 50, with a label the sums count) and at least one component, the meshes are no empty sets;
+    stockholder IGM has voxels above 0.01 where pro-mode IGM is nearly zero, which is why the regions use it"""
+    for grid in H.GRIDS:
+        for d in H.densities(grid):
+            g, e, rows, (N, sigma), bound = H._mbis(grid, d)
+            assert (g.count > 0).all() and (N[H.MBIS_SHELLS[:, None] > np.arange(2)[None, :]] > 0).all(), (grid, d)
+            assert len(rows) == H.MBIS['max_iter'] == 5 and H.MBIS['check_every'] == 2 and bound == float(np.abs(H.density(grid, d)).max())
+            for kind in ('hirshfeld_moments', 'isa_moments', 'mbis_moments'):
+                bins, info, _ = H.expect(kind, grid, d, 'atoms')
+                assert (bins != 0).all() and info['beyond_bound'] == 0 and info['pairs'] > 1000, (kind, grid, d)
+            dgi = H.expect('igm_fields', grid, d, 'atoms')[1]
+            assert (dgi > 0.01).sum() >= (88 if d != 'B' else 25), (grid, d, int((dgi > 0.01).sum()))
+            assert H.expect('igm_fields_pro', grid, d, 'atoms')[1].max() < 6.5e-3
+            for kind in ('dori_isosurface', 'igm_isosurface'):
+                assert H.expect(kind, grid, d, 'atoms').triangles.shape[0] > 100, (kind, grid, d)
+            for m in H.maps(grid):
+                assert H.expect('dori_regions', grid, d, m)[0][1].sum() >= 100, (grid, d, m)
+                assert H.expect('igm_regions', grid, d, m)[0][1].sum() >= 50, (grid, d, m)
+                for kind in ('dori_domains', 'igm_domains'):
+                    want = H.expect(kind, grid, d, m)
+                    assert want['seeds'].size >= 1 and want['count'].sum() >= 50 and want['shares'][2].sum() >= 50, (kind, grid, d, m)
+    # both sides of the class bound occur in the DORI region of every grid, and in the IGM region of the noisy density
+    for grid in H.GRIDS:
+        cnt = H.expect('dori_regions', grid, 'A', 'atoms')[0][1]
+        assert cnt[0::3].sum() > 100 and cnt[1::3].sum() > 100, grid
+    cnt = H.expect('igm_regions', 'G1', 'N', 'atoms')[0][1]
+    assert cnt[0::3].sum() > 100 and cnt[1::3].sum() > 100

@@ -20,7 +20,8 @@ import test_hirshfeld_cpu as HS
 from pybader_amd import _lib, build, igm
 from pybader_amd.hirshfeld import ProAtoms
 from pybader_amd.interface import Bader
-from test_laplacian_cpu import restated_values
+from test_laplacian_cpu import grouped, restated_values, sum_bound
+from test_multipole_cpu import VV
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 U = 2.0 ** -53
@@ -222,6 +223,44 @@ def reference(name, F, loose, mode, p_min=P_MIN):
     for a in v.values():
         a.flags.writeable = False
     return v
+
+
+# ---- the comparisons of tests/test_gpu_igm.py (here, so that tests/history_common.py can make them too) ---------------------------
+def keys_of(val, x, lab, n, cut, rho_split):
+    inside = (val >= cut) & (lab >= 0) & (lab < n)
+    cls = np.where(x < -rho_split, 0, np.where(x > rho_split, 2, 1))
+    return np.where(inside, 3 * lab.astype(np.int64) + cls, -1).reshape(-1)
+
+
+def sum_reference(rho, val, x, lab, n, cut, rho_split):
+    """per key 3 a + class: ((fsum, count, fsum of magnitudes) of rho, the same of the field)"""
+    k = keys_of(val, x, lab, n, cut, rho_split)
+    return grouped(np.asarray(rho, dtype=np.float64), k, 3 * n), grouped(val, k, 3 * n)
+
+
+def check_sums(got, c, val, x, lab, n, cut, rho_split, what):
+    count, charge, integral = got
+    (s1, cnt, mag1), (s2, _, mag2) = sum_reference(c.rho, val, x, lab, n, cut, rho_split)
+    print(what, 'voxels in the region', int(cnt.sum()), 'per class', [int(cnt[j::3].sum()) for j in range(3)])
+    assert count.shape == charge.shape == integral.shape == (n, 3) and count.dtype == np.int64
+    assert np.array_equal(count.reshape(-1), cnt), what + ': counts'
+    assert np.all(np.abs(charge.reshape(-1) - s1 * VV) <= sum_bound(cnt, mag1)), what + ': the sums of rho'
+    assert np.all(np.abs(integral.reshape(-1) - s2 * VV) <= sum_bound(cnt, mag2)), what + ': the sums of the field'
+    return cnt
+
+
+def regions_difference(count, charge, integral, reference, what):
+    """None, or what of igm_regions differs from `reference` = sum_reference(...): the region must hold 50 voxels to say anything"""
+    (s1, cnt, mag1), (s2, _, mag2) = reference
+    if cnt.sum() < 50:
+        return f'{what}: the restated region holds {int(cnt.sum())} voxels, too few to say anything'
+    if not np.array_equal(count.reshape(-1), cnt):
+        return f'{what}: counts differ ({count.reshape(-1).tolist()} against {cnt.tolist()})'
+    if not np.all(np.abs(charge.reshape(-1) - s1 * VV) <= sum_bound(cnt, mag1)):
+        return f'{what}: the sums of rho differ'
+    if not np.all(np.abs(integral.reshape(-1) - s2 * VV) <= sum_bound(cnt, mag2)):
+        return f'{what}: the sums of the field differ'
+    return None
 
 
 def exact_case():

@@ -263,6 +263,16 @@ def results(e, row, vv=VV):
             np.array([vv * math.ldexp(float(rest[0]), -e[3]), vv * float(rest[1])]))
 
 
+# the comparison of tests/test_gpu_mbis.py (here, so that tests/history_common.py can make it too)
+def same_rows(got, want, what):
+    """(qsum, vsum, rest) of a call against the restated rows"""
+    q, v, r = got
+    assert q.dtype == v.dtype == r.dtype == np.int64 and q.shape[0] == len(want), what
+    assert np.array_equal(q, np.array([w[0] for w in want])), f'{what}: qsum'
+    assert np.array_equal(v, np.array([w[1] for w in want])), f'{what}: vsum'
+    assert np.array_equal(r, np.array([w[2] for w in want], np.int64)), f'{what}: rest'
+
+
 @functools.lru_cache(maxsize=None)
 def table(J=256, x_max=48):
     E = mbis.exp_table(J, x_max)

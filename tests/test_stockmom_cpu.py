@@ -336,6 +336,16 @@ def moments(E, b, vv=VV):
     return vv * np.ldexp(b.astype(np.float64), np.array([-E[k] for k in ORDER])[None, :])
 
 
+# the comparison of tests/test_gpu_stockmom.py (here, so that tests/history_common.py can make it too)
+def info_of(g, E, beyond=0):
+    """the info of a call on the geometry `g` with the exponents E"""
+    return {'E': tuple(E), 'cmax': int(g.count.max()), 'pairs': int(g.count.sum()), 'beyond_bound': beyond}
+
+
+def want_info(name, E, beyond=0):
+    return info_of(geo(name), E, beyond)
+
+
 CPU_NAMES = [n for n in SETUPS if n not in LONG]
 
 
